@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
 """Hybrid-retrieval benchmark: queries/sec on the 10M x 768 dense+BM25 workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one batch of B queries through the hot path with every input already
 resident in HBM: per-shard cosine top-100 (int8 MFMA candidate scan + exact fp32
 re-score, certified) and BM25 top-100 over the on-device inverted index, per-stage all-gather of
 the shards' lists over RCCL (N > 1), reciprocal-rank fusion, top-10.  The corpus is
 row-sharded over the N ranks (strong scaling: total work is fixed).  Rank 0 prints one
-JSON line; see DESIGN.md "Measurement" for every field."""
+JSON line; see DESIGN.md "Measurement" for every field.
+
+A plain run sets up, warms up, times the K steps and prints the headline fields (`value`,
+`ms_per_step`, `config`).  `--full` adds everything else the line can carry: the in-situ and
+one-kernel-at-a-time roofline, the host brute force of the timed step (`cpu_baseline`,
+`recall_at_10`) and the side measurements (`secondary`).  `--dump-outputs DIR` writes the lists
+of the last timed step as DIR/scores.npy, DIR/ids.npy and DIR/counts.npy."""
 from __future__ import annotations
 
 import argparse
@@ -56,7 +63,42 @@ def parse():
                          "whose per-kernel averages should hold the timed region's launches only")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the CPU baseline (0 = host cores / GPUs of the host: the box share of one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline (HIP-event profile of the timed steps + the same K steps with one kernel at a "
+                         "time), the CPU baseline and the side measurements; --no-* above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's lists (scores, ids, counts) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64_000_000     # every .npy of a dump together, headers included
+
+
+def dump_outputs(out_dir, res, eng):
+    """The caller's view of the last timed step: per query the fused list's fp32 scores and ids (float64: exact below 2**53)
+    and its length.  Entries past a query's count are not part of its list: written as score 0, id -1.  A batch whose
+    arrays would pass DUMP_MAX_BYTES is cut to a fixed, seeded sample of queries, listed in rows.npy."""
+    s, i = eng.unpack(res[0])
+    s, i, c = s.cpu().numpy(), i.cpu().numpy(), res[1].cpu().numpy().astype(np.int64)
+    B, L = s.shape
+    past = np.arange(L)[None, :] >= c[:, None]
+    s = np.where(past, np.float32(0), s).astype(np.float32)
+    i = np.where(past, -1, i).astype(np.float64)
+    arrays = dict(scores=s, ids=i, counts=c.astype(np.float64))
+    per_row = L * (4 + 8) + 8 + 8
+    if B * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, (DUMP_MAX_BYTES - 4096) // per_row, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:     # a dump inside a checkout stays out of git
+            f.write("*\n")
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
 
 
 CPU_BUILD = "gcc -O3 -mavx2 -fopenmp -ffp-contract=off (unfused fp32 mul + add: the arithmetic contract)"
@@ -634,7 +676,7 @@ def main():
     # ... and once more (hx_rebuild_sparse): the first build of a fresh process also pays for 32 GB of temporary device
     # allocations -- 45 ms or 1.2 s on two boxes of the pool for the same kernels; the second is the kernels' time
     k9_ms = k9_cold_ms
-    if rank == 0 and world == 1 and mode == "h1" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and mode == "h1" and not args.no_secondary:
         ev_a.record()
         ix.rebuild_sparse()
         ev_b.record()
@@ -713,8 +755,9 @@ def main():
         torch.cuda.synchronize()
         for _ in range(args.warmup):
             step()
-    ix.profile(True)
-    ix.profile_read()
+    if args.full:           # HIP events around the scan / select launches of the timed steps: the in-situ roofline
+        ix.profile(True)
+        ix.profile_read()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -727,13 +770,15 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    prof = ix.profile_read()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, eng)
+    prof = ix.profile_read()        # (a plain run has not profiled: every count is zero and `roofline` stays null)
     ix.profile(False)
     # The timed step runs its sparse stage on a second stream BESIDE the dense scans: a launch's duration above is what the
     # kernel took while it shared the chip.  The same K steps once more with every stage on one stream (hx_set_stream_overlap)
     # give each kernel's duration alone -- reported beside the in-situ figures as `roofline.alone`, never as `value`.
     alone = None
-    if world == 1 and mode == "h1" and not args.no_alone:
+    if args.full and world == 1 and mode == "h1" and not args.no_alone:
         ix.set_stream_overlap(False)
         step()
         torch.cuda.synchronize()
@@ -765,7 +810,7 @@ def main():
     # N > 1, side measurement (never part of `value`): the reference's own query -- the tree -- through the sharded
     # path: one all-gather per cascade level, the stages' flags deferred into one all-reduced word (distributed.py)
     tree_sharded = None
-    if world > 1 and mode == "h1" and not args.no_secondary:
+    if args.full and world > 1 and mode == "h1" and not args.no_secondary:
         Pt = dict(matryoshka_64_limit=100, matryoshka_128_limit=80, matryoshka_256_limit=60, dense_limit=40,
                   quantized_limit=40, sparse_limit=50, final_limit=30, hnsw_ef=128)
 
@@ -863,7 +908,7 @@ def main():
     cpu = None
     side = None
     st_main = ix.stats() if rank == 0 else None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         nq = max(1, min(args.cpu_queries, B))
         sel = np.arange(0, B, max(B // nq, 1))[:nq]
         if not args.no_cpu_baseline:      # (before the side measurements: they end with this index freed)
@@ -906,7 +951,7 @@ def main():
                       else f"queries/sec, {wl['desc']} [rows={rows}, batch={B}]",
             "value": B * args.steps / dt, "unit": "queries/sec", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "full": args.full,
             "data": "synthetic",
             "config": {"workload": wl["desc"], "rows": rows, "dim": dim, "batch": B, "top_k": 10,
                        "arithmetic": "dense: " + (DENSE_ARITH if st["cand8_queries"] else "fp16 MFMA candidate scan + exact fp32 "

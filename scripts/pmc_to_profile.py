@@ -1,7 +1,7 @@
 """Condense the rocprofv3 --pmc passes over bench.py (one directory per counter group, as written by
 scripts/final_prof.sh) into profiles/<name>.json: per scan launch of the last timed step, HBM traffic
 (FETCH_SIZE x 2 on gfx950), L2 hit rate, clock, MFMA busy fraction; the sparse select launch: TCC misses, wait split.
-    python scripts/pmc_to_profile.py gpurun_out/pmc_r02 profiles/r02_pmc_scan.json"""
+    python scripts/pmc_to_profile.py prof_out/pmc_r02 profiles/r02_pmc_scan.json"""
 import csv, collections, json, sys
 root, out_path = sys.argv[1], sys.argv[2]
 SP = "k_sparse_select"
