@@ -273,6 +273,30 @@ int hx_hybrid_query_dev(hx_index* h, const float* q_dense_dev,
                         const int64_t* q_indptr_dev, const int32_t* q_idx_dev,
                         const float* q_val_dev, int32_t B, const hx_params* p,
                         uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+/* Pre-filtered query (a payload filter evaluated by the caller, applied to EVERY stage -- the prefetches as well as
+ * the root): the two calls above restricted to the rows of a mask.  The lists are exactly those of the unmasked call
+ * on an index holding only the kept rows, added in the same order (same ids after the map back, same order, same
+ * fp32 score bits), in both modes.  mask = ceil(mask_rows / 32) uint32 words, bit r & 31 of word r >> 5 (LSB first)
+ * = local row r in insertion order; bits at or past mask_rows are ignored; mask_rows must equal hx_count (an error
+ * otherwise).  Every row kept: the unmasked call, the same keys.  No row kept: counts 0, empty slots.  Otherwise the
+ * whole-collection dense scans read copies of the kept rows, gathered on the caller's stream (only the copy a scan
+ * reads), and the sparse stage tests the mask inside its kernels over this index's inverted index (DESIGN.md section
+ * 13).  Synchronisation beyond the unmasked call: the device entry reads the number of kept rows back once (one
+ * synchronisation of `stream`; the host entry counts the host mask instead); a call that keeps more rows than any
+ * masked call before it synchronises `stream` once more and reallocates the copies' buffers (to the next power of two
+ * of the kept rows -- they stay allocated with the index until hx_release_mask_view or hx_destroy); a query no scan
+ * can serve (the exact fallback path) gathers its matrix once more.  The mask must stay valid until the call's work on
+ * `stream` is done.  Pre-filtered queries do not count toward the int8 guard window (hx_stats). */
+int hx_hybrid_query_host_masked(hx_index* h, const float* q_dense_host, const int64_t* q_indptr_host,
+                                const int32_t* q_idx_host, const float* q_val_host, int32_t B, const hx_params* p,
+                                const uint32_t* mask_host, int64_t mask_rows,
+                                float* scores_host, int64_t* ids_host, int32_t* counts_host);
+int hx_hybrid_query_dev_masked(hx_index* h, const float* q_dense_dev, const int64_t* q_indptr_dev,
+                               const int32_t* q_idx_dev, const float* q_val_dev, int32_t B, const hx_params* p,
+                               const uint32_t* mask_dev, int64_t mask_rows,
+                               uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+/* free the copies of kept rows the pre-filtered queries keep allocated between calls (synchronises the device) */
+int hx_release_mask_view(hx_index* h);
 
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
@@ -320,7 +344,8 @@ int hx_get_stats(hx_index* h, hx_stats* out);
 /* HIP-event profile of the hot kernels, measured on the stream they run on.
  * Index 0 = fp16 scan (k_scan<F16>), 1 = int8 scan of the "quantized" stage (k_scan<I8>), 3 = int8 candidate scan of
  * the dense stage (the same kernel over the per-row-scaled copy), 4 = the ingest kernel (K1/K2: k_prep_rows; bytes =
- * the raw row read once + every derived copy written once), 5 = spare, 2 = sparse scoring
+ * the raw row read once + every derived copy written once), 5 = the preparation of a masked query (hx_hybrid_query_*_masked:
+ * the list of kept rows and the gathers of the scanned copies), 2 = sparse scoring
  * (k_sparse_select: the pass over the inverted index; bytes = 8 per posting of the queries' terms).  flops/bytes are ALGORITHMIC: 2*B*rows*D and rows*row_bytes +
  * B*row_bytes per scan launch.  hx_profile_read drains what was recorded
  * since the last read (it synchronises the recorded events). */

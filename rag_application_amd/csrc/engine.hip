@@ -92,7 +92,8 @@ enum WsSlot {
   WS_F_DALL, WS_F_SALL, WS_F_D, WS_F_S, WS_F_DC, WS_F_SC,
   WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
-  WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE
+  WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
+  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB
 };
 
 template <typename T>
@@ -211,6 +212,26 @@ struct hx_index {
     int64_t next = -1;                // hx_set_next_id: global id of the next appended row (-1: continue)
     int64_t end = -1;                 // global id after the last row (-1: no row yet)
   } ids;
+
+  // Pre-filtered query (hx_hybrid_query_*_masked): while `on`, the whole-collection scans read
+  // these gathered copies of the kept rows (view row i = local row rows[i]) and map their candidates back to this index's
+  // rows before anything reads rows by id; the sparse stage tests `keep` at harvest.  A copy is gathered on first use in a
+  // call (bit of `have`); the buffers hold `cap` rows (a power of two), persist across calls and are freed by
+  // hx_release_mask_view or when a call needs more rows.
+  struct MaskView {
+    bool on = false;
+    int64_t n = 0, cap = 0;
+    const uint32_t* keep = nullptr;
+    const uint32_t* rows = nullptr;
+    unsigned have = 0;
+    int8_t* q8s = nullptr;
+    float* q8s_scale = nullptr;
+    _Float16* dense_h = nullptr;
+    _Float16* pre_h0 = nullptr;
+    int8_t* q8 = nullptr;
+    float* q8_rinv = nullptr;
+    TileMax tm_q8, tm_q8s;
+  } mv;
 
   void set_device() const { HX_HIP(hipSetDevice(device)); }
 };
@@ -656,23 +677,24 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
   a.overflow = ovf;
   a.cap = g.C;
   a.id_base = h->id_base;
+  const int64_t ns = h->mv.on ? h->mv.n : h->n;   // rows scanned: the kept rows of a pre-filtered query (A is their copy)
   if (kind == KIND_I8 && !rinv_x) {
-    rinv_x = h->q8_rinv;
-    tm = &h->tm_q8;
+    rinv_x = h->mv.on ? h->mv.q8_rinv : h->q8_rinv;
+    tm = h->mv.on ? &h->mv.tm_q8 : &h->tm_q8;
   }
   a.rinv_x = rinv_x;
   a.rinv_q = rinv_q;
   if (kind == KIND_I8) {
-    if (tm->rows != h->n) {   // rows were added since the last scan with these scales
-      const int64_t tiles = (h->cap + 255) / 256;
+    if (tm->rows != ns) {   // rows were added since the last scan with these scales
+      const int64_t tiles = ((h->mv.on ? h->mv.cap : h->cap) + 255) / 256;
       if (tiles > tm->cap) {
         if (tm->v) HX_HIP(hipFree(tm->v));
         tm->v = nullptr;
         HX_HIP(hipMalloc((void**)&tm->v, (size_t)tiles * 4));
         tm->cap = tiles;
       }
-      launch_tile_max(rinv_x, h->n, tm->v, st);
-      tm->rows = h->n;
+      launch_tile_max(rinv_x, ns, tm->v, st);
+      tm->rows = ns;
     }
     a.rinv_tile_max = tm->v;
   }
@@ -695,7 +717,7 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
     // a capacity planned for 2048 waves overflowed for half the queries).  Three times the mean, the largest launch.
     double want = 0.0;
     {
-      const std::vector<int64_t> plan = chunk_plan((h->n + 255) / 256 * 256, g);
+      const std::vector<int64_t> plan = chunk_plan((ns + 255) / 256 * 256, g);
       for (size_t i = 1; i < plan.size(); ++i) {
         const int64_t p1 = plan[i - 1], nx = plan[i];
         const double growth = (double)nx / (double)p1;
@@ -714,9 +736,9 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
   // Scan order (kernels.hpp): logical 256-row tile t is physical tile (t * mul) mod tiles, mul ~ 0.618 * tiles and
   // coprime to it, so every chunk samples the whole matrix evenly -- a topically clustered corpus stays
   // exchangeable for the predictive thresholds.  The logical range is [0, tiles * 256): rows past n count nothing.
-  const int64_t n_tiles = (h->n + 255) / 256;
+  const int64_t n_tiles = (ns + 255) / 256;
   const int64_t n_log = n_tiles * 256;
-  a.n_total = h->n;
+  a.n_total = ns;
   a.perm_n = 0;
   a.perm_mul = 1;
   if (n_tiles >= 8 && !getenv("HX_DEBUG_NO_PERM")) {
@@ -779,14 +801,24 @@ static void exact_range_fallback(hx_index* h, int kind, const void* M, int64_t r
   HX_HIP(hipMemsetAsync(buf, 0, (size_t)nsel * C * 8, st));
   RangeArgs ra{};
   ra.r.kind = kind;
-  ra.r.M = M;
   ra.r.row_stride = row_stride;
   ra.r.dim_pad = dim_pad;
   ra.r.Q = Qp;
   ra.r.q_stride = q_stride;
-  ra.r.rinv_x = h->q8_rinv;
+  int64_t nr = h->n;
+  const float* rinv_x = h->q8_rinv;
+  if (h->mv.on) {   // a pre-filtered query: the kept rows of M (rare: only queries no scan could serve come here)
+    const int64_t rb = row_stride * (kind == KIND_I8 ? 1 : kind == KIND_F32 ? 4 : 2);
+    void* g = h->ws.get(WS_M_FB, (size_t)std::max<int64_t>(h->mv.n * rb, 16));
+    launch_gather_rows16(M, g, rb, h->mv.rows, h->mv.n, st);
+    M = g;
+    nr = h->mv.n;
+    rinv_x = h->mv.q8_rinv;
+  }
+  ra.r.M = M;
+  ra.r.rinv_x = rinv_x;
   ra.r.rinv_q = rinv_q;
-  ra.r.n_rows = h->n;
+  ra.r.n_rows = nr;
   ra.r.id_base = h->id_base;
   ra.r.out = buf;
   ra.r.stride = C;
@@ -794,20 +826,64 @@ static void exact_range_fallback(hx_index* h, int kind, const void* M, int64_t r
   ra.nsel = nsel;
   ra.slot0 = L;
   const int64_t CH = C - L;
-  for (int64_t r0 = 0; r0 < h->n; r0 += CH) {
-    const int64_t r1 = std::min<int64_t>(h->n, r0 + CH);
+  for (int64_t r0 = 0; r0 < nr; r0 += CH) {
+    const int64_t r1 = std::min<int64_t>(nr, r0 + CH);
     ra.row_begin = r0;
     ra.row_end = r1;
     launch_rescore_range(ra, st);
     launch_fill_i32(incnt, nsel, (int)(L + (r1 - r0)), st);
     launch_compact(buf, C, incnt, nsel, L, 0, buf, C, cnt, nullptr, C, st);
   }
+  if (h->mv.on) launch_view_ids(buf, (int64_t)nsel * C, h->mv.rows, (uint32_t)h->mv.n, (uint32_t)h->id_base, st);
   // scatter rows back: out_keys[sel[f]] = buf[f][0..L)
   for (int f = 0; f < nsel; ++f) {
     HX_HIP(hipMemcpyAsync(out_keys + (int64_t)sel[f] * L, buf + (int64_t)f * C, (size_t)L * 8,
                           hipMemcpyDeviceToDevice, st));
     HX_HIP(hipMemcpyAsync(out_cnt + sel[f], cnt + f, 4, hipMemcpyDeviceToDevice, st));
   }
+}
+
+// ---- the gathered copies of a pre-filtered query (hx_index::MaskView) ----------------------------------------------
+enum { MV_Q8S = 1, MV_DENSE_H = 2, MV_PRE_H0 = 4, MV_Q8 = 8 };
+
+static void mv_release(hx_index* h) {
+  auto& v = h->mv;
+  void* ptrs[] = {v.q8s, v.q8s_scale, v.dense_h, v.pre_h0, v.q8, v.q8_rinv, v.tm_q8.v, v.tm_q8s.v};
+  for (void* p : ptrs)
+    if (p) HX_HIP(hipFree(p));
+  v.q8s = nullptr, v.q8s_scale = nullptr, v.dense_h = nullptr, v.pre_h0 = nullptr, v.q8 = nullptr, v.q8_rinv = nullptr;
+  v.tm_q8 = v.tm_q8s = hx_index::TileMax{};
+  v.cap = 0;
+  v.have = 0;
+}
+
+// the copy `what` of the kept rows, gathered on the first use in a call (on the stream of the scan that reads it)
+static void mv_need(hx_index* h, unsigned what, hipStream_t st) {
+  auto& v = h->mv;
+  if (v.have & what) return;
+  ProfScope ps(h, st, 5, 0.0, 0.0);   // hx_prof slot 5: the mask's list and the gathers
+  auto buf = [&](auto*& p, int64_t elems) {
+    if (!p) HX_HIP(hipMalloc((void**)&p, (size_t)std::max<int64_t>(elems, 1) * sizeof(*p)));
+  };
+  const int64_t c = v.cap, n = v.n;
+  if (what == MV_Q8S) {
+    buf(v.q8s, c * h->dim_pad8);
+    buf(v.q8s_scale, c + 256);
+    launch_gather_rows16(h->q8s, v.q8s, h->dim_pad8, v.rows, n, st);
+    launch_gather_u32(h->q8s_scale, v.q8s_scale, v.rows, n, st);
+  } else if (what == MV_DENSE_H) {
+    buf(v.dense_h, c * h->dim_pad);
+    launch_gather_rows16(h->dense_h, v.dense_h, (int64_t)h->dim_pad * 2, v.rows, n, st);
+  } else if (what == MV_PRE_H0) {
+    buf(v.pre_h0, c * h->psize[0]);
+    launch_gather_rows16(h->pre_h0, v.pre_h0, (int64_t)h->psize[0] * 2, v.rows, n, st);
+  } else if (what == MV_Q8) {
+    buf(v.q8, c * h->dim_pad8);
+    buf(v.q8_rinv, c + 256);
+    launch_gather_rows16(h->q8, v.q8, h->dim_pad8, v.rows, n, st);
+    launch_gather_u32(h->q8_rinv, v.q8_rinv, v.rows, n, st);
+  }
+  v.have |= what;
 }
 
 static int* host_pin(hx_index* h) {
@@ -900,7 +976,12 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
   // fp16) when the index holds the scaled int8 copy; a query it cannot certify is retried through the fp16 scan
   // (level 1) like any other flagged query.  Final scores are spec_dot on the fp32 rows either way.
   const bool use8 = h->cand8 && !h->cand8_off && h->q8s && prefix == 0 && level == 0;
-  if (m.m16 || use8) {
+  const _Float16* m16 = m.m16;   // the scanned fp16 copy (of the kept rows, for a pre-filtered query)
+  if (h->mv.on && m16 && !use8) {
+    mv_need(h, prefix == 0 ? MV_DENSE_H : MV_PRE_H0, st);
+    m16 = prefix == 0 ? h->mv.dense_h : h->mv.pre_h0;
+  }
+  if (m16 || use8) {
     const Geometry g = geometry(L, true, level > 0, use8, 0, B <= 32);
     uint64_t* cand = (uint64_t*)h->ws.get(WS_CAND + wo, (size_t)B * g.C * 8);
     uint64_t* cand2 = (uint64_t*)h->ws.get(WS_CAND2 + wo, (size_t)B * g.C * 8);
@@ -913,14 +994,23 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
       float* sq = (float*)h->ws.get(WS_SQ + wo, (size_t)Bpad * 4);
       float* eq = (float*)h->ws.get(WS_EPSQ + wo, (size_t)B * 4);
       launch_prep_queries_s8(qn, m.dpad, B, Bpad, h->dim_pad8, q8, sq, eq, h->s8_err, st);
-      chunked_scan(h, KIND_I8, (const uint8_t*)h->q8s, (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand, cnt, ovf, tau,
-                   sq, st, h->q8s_scale, &h->tm_q8s, 3);
+      if (h->mv.on) {
+        mv_need(h, MV_Q8S, st);
+        chunked_scan(h, KIND_I8, (const uint8_t*)h->mv.q8s, (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand, cnt, ovf, tau,
+                     sq, st, h->mv.q8s_scale, &h->mv.tm_q8s, 3);
+      } else {
+        chunked_scan(h, KIND_I8, (const uint8_t*)h->q8s, (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand, cnt, ovf, tau,
+                     sq, st, h->q8s_scale, &h->tm_q8s, 3);
+      }
       eps_q = eq;
       h->cand8_queries += B;
     } else {
-      chunked_scan(h, KIND_F16, (const uint8_t*)m.m16, (const uint8_t*)qh, (int64_t)m.dpad * 2, B, bn, g,
+      chunked_scan(h, KIND_F16, (const uint8_t*)m16, (const uint8_t*)qh, (int64_t)m.dpad * 2, B, bn, g,
                    cand, cnt, ovf, tau, nullptr, st);
     }
+    // candidates of a pre-filtered scan: view rows -> this index's rows, before the exact re-score reads rows by id
+    // (everything after it -- re-score, certificate, later stages -- reads this index's fp32 rows unchanged)
+    if (h->mv.on) launch_view_ids(cand, (int64_t)B * g.C, h->mv.rows, (uint32_t)h->mv.n, (uint32_t)h->id_base, st);
     if (after_scan) after_scan();
     RescoreArgs r{};
     r.kind = KIND_F32;
@@ -956,7 +1046,7 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
     if (between) between();
     if (defer) return false;
     sel = read_failures(h, fail, nfail, B, st);
-    if (use8) {
+    if (use8 && !h->mv.on) {   // (a pre-filtered query does not count toward the guard)
       h->cand8_failed += (int64_t)sel.size();
       // the guard: a collection whose rows the int8 grid resolves badly (one bad row widens the radius for every query)
       // would pay an fp16 scan on top of the int8 one for query after query
@@ -1014,14 +1104,17 @@ static void search_i8(hx_index* h, const float* q_dev, int B, int L, uint64_t* o
   float* tau = (float*)h->ws.get(WS_TAU + wo, (size_t)B * 4);
   int* fail = (int*)h->ws.get(WS_FAIL + wo, (size_t)B * 4);
   int* nfail = (int*)h->ws.get(WS_NFAIL + wo, 4);
-  chunked_scan(h, KIND_I8, (const uint8_t*)h->q8, (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand, cnt, ovf,
-               tau, rq, st);
+  if (h->mv.on) mv_need(h, MV_Q8, st);
+  chunked_scan(h, KIND_I8, (const uint8_t*)(h->mv.on ? h->mv.q8 : h->q8), (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand,
+               cnt, ovf, tau, rq, st);
   // the scan's scores are already exact: the list is final unless a buffer overflowed
   launch_compact(cand, g.C, cnt, B, L, 0, out_keys, L, out_cnt, nullptr, g.Lp, st);
   if (flag_acc) nfail = flag_acc;
   else HX_HIP(hipMemsetAsync(nfail, 0, 4, st));
   launch_certify(cand, g.C, cnt, std::numeric_limits<int>::max(), out_keys, L, out_cnt, L, ovf, 0.f, B,
                  fail, nfail, st);
+  // a pre-filtered scan's list (its scores are final): view rows -> this index's rows
+  if (h->mv.on) launch_view_ids(out_keys, (int64_t)B * L, h->mv.rows, (uint32_t)h->mv.n, (uint32_t)h->id_base, st);
   if (flag_acc) return;
   std::vector<int> sel = read_failures(h, fail, nfail, B, st);
   if (sel.empty()) return;
@@ -1150,6 +1243,8 @@ static SparseLists sparse_select_lists(hx_index* h, const int64_t* q_indptr, con
     for (int v = 0; v < 2; ++v) {
       if (!parts[v]) continue;
       SparseSelectArgs a{};
+      a.keep = h->mv.on ? h->mv.keep : nullptr;   // a pre-filtered query: the mask is tested at harvest
+      a.keep_base = (uint32_t)h->id_base;
       a.ix = pa.ix[v];
       a.q_indptr = q_indptr;
       a.q_ti = pa.q_ti[v];
@@ -1232,6 +1327,7 @@ static void sparse_exact_fallback(hx_index* h, const int64_t* q_indptr, const in
   const int C = CAND_CAP;
   SparseRangeArgs ra{};
   ra.d = csr_of(h);
+  ra.keep = h->mv.on ? h->mv.keep : nullptr;
   ra.q_indptr = q_indptr;
   ra.q_idx = q_idx;
   ra.q_val = q_val;
@@ -1600,6 +1696,76 @@ static void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
   }
 }
 
+// ---------------------------------------------------------------------------------
+// pre-filtered query (hx.h: hx_hybrid_query_*_masked)
+// ---------------------------------------------------------------------------------
+// The masked query is the unmasked query of THIS index with two stages restricted (hx_index::MaskView):
+//  - the whole-collection dense scans (k_scan8, k_scan, the first-chunk all-pass, exact_range_fallback) run unchanged on
+//    gathered copies of the kept rows -- only the copy a scan reads, on first use -- and their candidate keys are mapped
+//    back to this index's rows (k_view_ids) at the first point anything reads rows by id: before the exact re-score of
+//    search_dense, at the final list of search_i8 (its scores are final).  The re-score, the certificate, the cascade's
+//    later stages, the root and remap_out read this index's fp32 rows unchanged;
+//  - the sparse stage tests the mask at harvest (k_sparse_select<true>) and in the document-at-a-time kernel
+//    (k_sparse_range<true>), over this index's inverted index, base and tail alike.
+// The map from kept rows to rows is monotone, so the (score desc, id asc) order is kept.  The certificates hold on a subset:
+// the int8 copy's scales are per row and s8_err bounds every row; the integer BM25 scale is this index's.  Retries, the
+// tree's deferred path and its redo run inside the call, on the same copies.  A pre-filtered query does not count toward
+// the int8 guard window.
+
+// kept rows of the mask on the device -> rows (ascending), count written to *count_dev
+static void mask_rows_dev(hx_index* h, const uint32_t* mask_dev, uint32_t*& rows, uint32_t*& count_dev, hipStream_t st) {
+  const int64_t nw = (h->n + 31) / 32;
+  uint32_t* blk = (uint32_t*)h->ws.get(WS_M_BLK, (size_t)((nw + 255) / 256 + 1) * 4 + 4);
+  rows = (uint32_t*)h->ws.get(WS_M_ROWS, (size_t)std::max<int64_t>(h->n, 1) * 4);
+  count_dev = blk + (nw + 255) / 256 + 1;
+  launch_mask_rows(mask_dev, h->n, blk, rows, count_dev, st);
+}
+
+// hybrid_query_dev restricted to the rows of mask_dev.  count_known >= 0: the caller counted the kept rows (the host
+// entry, from the host mask); otherwise the count is read back once through the pinned buffer.  Keys leave with
+// internal ids, as those of hybrid_query_dev.
+static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
+                             const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
+                             int* out_cnt, hipStream_t st) {
+  if (count_known == h->n) return hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
+  if (count_known == 0) return zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
+  // (sparse vectors of rows whose dense rows have not arrived: the mask has no bit for them)
+  HX_CHECK(h->nnz == 0 || h->sp_rows <= h->n, "masked query: sparse vectors are pending for rows not added yet");
+  uint32_t *rows = nullptr, *count_dev = nullptr;
+  {
+    ProfScope ps(h, st, 5, 0.0, 0.0);   // hx_prof slot 5: the mask's list and the gathers
+    mask_rows_dev(h, mask_dev, rows, count_dev, st);
+  }
+  int64_t count = count_known;
+  if (count < 0) {
+    uint32_t* pin = (uint32_t*)host_pin(h) + 8;
+    HX_HIP(hipMemcpyAsync(pin, count_dev, 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    count = pin[0];
+    if (count == h->n) return hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
+    if (count == 0) return zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
+  }
+  auto& v = h->mv;
+  if (count > v.cap) {            // the copies' buffers: the next power of two of the kept rows, kept across calls
+    HX_HIP(hipStreamSynchronize(st));
+    mv_release(h);
+    int64_t c = 256;
+    while (c < count) c *= 2;
+    v.cap = c;
+  }
+  v.n = count;
+  v.keep = mask_dev;
+  v.rows = rows;
+  v.have = 0;
+  v.tm_q8.rows = v.tm_q8s.rows = -1;
+  struct Off {                    // (reset on every way out, exceptions included)
+    hx_index* h;
+    ~Off() { h->mv.on = false; }
+  } off{h};
+  v.on = true;
+  hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
+}
+
 static void check_params(const hx_params* p) {
   HX_CHECK(p != nullptr, "params is NULL");
   HX_CHECK(p->mode == HX_MODE_TREE || p->mode == HX_MODE_H1, "unknown mode");
@@ -1689,6 +1855,7 @@ int hx_destroy(hx_index* h) {
   if (!h) return 0;
   h->set_device();
   (void)hipDeviceSynchronize();
+  try { mv_release(h); } catch (...) {}
   free_sparse_index(h);
   void* ptrs[] = {h->dense, h->dense_h, h->q8, h->q8_rinv, h->pre[0], h->pre[1], h->pre[2], h->pre_h0,
                   h->sp_indptr, h->sp_idx, h->sp_val, h->sp_counter, h->q8s, h->q8s_scale, h->s8_err,
@@ -2507,14 +2674,24 @@ int hx_hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const 
   HX_CATCH
 }
 
-int hx_hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix,
-                         const float* qv, int32_t B, const hx_params* p, float* scores, int64_t* ids,
-                         int32_t* counts) {
-  HX_TRY
+// hx_hybrid_query_host and its masked form: mask_host NULL = every row
+static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                              int32_t B, const hx_params* p, const uint32_t* mask_host, float* scores, int64_t* ids,
+                              int32_t* counts) {
   HX_CHECK(h && qd && qip && scores && ids && counts && B > 0, "bad argument");
   check_params(p);
   h->set_device();
   hipStream_t st = nullptr;
+  int64_t kept = -1;
+  if (mask_host) {                      // the count from the host mask: no read-back
+    const int64_t nw = (h->n + 31) / 32;
+    kept = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+      uint32_t m = mask_host[w];
+      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
+      kept += __builtin_popcount(m);
+    }
+  }
   const int64_t nnz = qip[B];
   HX_CHECK(qip[0] == 0 && nnz >= 0, "bad query indptr");
   // sort each query's terms by id (the spec's summation order), reject duplicates
@@ -2549,13 +2726,59 @@ int hx_hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const
     HX_HIP(hipMemcpyAsync(dix, six.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, st));
     HX_HIP(hipMemcpyAsync(dv, sv.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, st));
   }
-  hybrid_query_dev(h, dq, dip, dix, dv, B, p, ok, oc, st);
+  if (kept < 0 || kept == h->n) {
+    hybrid_query_dev(h, dq, dip, dix, dv, B, p, ok, oc, st);
+  } else {
+    const int64_t nw = (h->n + 31) / 32;
+    uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+    if (nw) HX_HIP(hipMemcpyAsync(dm, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+    masked_query_dev(h, dq, dip, dix, dv, B, p, dm, kept, ok, oc, st);
+  }
   remap_out(h, ok, (int64_t)B * L, st);
   launch_unpack(ok, (int64_t)B * L, osc, oid, st);
   HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * L * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * L * 8, hipMemcpyDeviceToHost, st));
   HX_HIP(hipMemcpyAsync(counts, oc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipStreamSynchronize(st));
+}
+
+int hx_hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix,
+                         const float* qv, int32_t B, const hx_params* p, float* scores, int64_t* ids,
+                         int32_t* counts) {
+  HX_TRY
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, nullptr, scores, ids, counts);
+  HX_CATCH
+}
+
+int hx_hybrid_query_host_masked(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
+                                float* scores, int64_t* ids, int32_t* counts) {
+  HX_TRY
+  HX_CHECK(h && mask_host, "NULL argument");
+  HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, counts);
+  HX_CATCH
+}
+
+int hx_hybrid_query_dev_masked(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                               int32_t B, const hx_params* p, const uint32_t* mask_dev, int64_t mask_rows,
+                               uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && qd && qip && mask_dev && keys_dev && counts_dev, "NULL argument");
+  HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  check_params(p);
+  h->set_device();
+  masked_query_dev(h, qd, qip, qix, qv, B, p, mask_dev, -1, keys_dev, counts_dev, (hipStream_t)stream);
+  remap_out(h, keys_dev, (int64_t)B * p->final_limit, (hipStream_t)stream);
+  HX_CATCH
+}
+
+int hx_release_mask_view(hx_index* h) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  mv_release(h);
   HX_CATCH
 }
 

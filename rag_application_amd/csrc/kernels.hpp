@@ -278,6 +278,8 @@ struct SparseSelectArgs {
   uint64_t* cand;              // [B x parts x (seg_docs + seg_docs/8)] workgroup-private candidate buffers
   int* q_fail;                 // [B] set when a buffer overflowed: the query takes the exact path
   int cut_step;                // keys the buffer grows by between cuts (0: max(1024, 4 * limit))
+  const uint32_t* keep;        // row mask of a pre-filtered query (NULL: every row): bit r of keep = local row r
+  uint32_t keep_base;          // internal id of local row 0 (the index's id_base)
 };
 void launch_sparse_select(const SparseSelectArgs& a, hipStream_t st);   // dispatches on a.ix.seg_docs
 void launch_sparse_summary(const int* flag, const int* fail, int B, int* out, hipStream_t st);
@@ -334,6 +336,7 @@ struct SparseRangeArgs {
   const float* tau;
   int* cnt;
   int* ovf;
+  const uint32_t* keep;        // row mask of a pre-filtered query (NULL: every row): rows whose bit is clear score nothing
 };
 void launch_sparse_range(const SparseRangeArgs& a, hipStream_t st);
 // {min, max} of val[0, n) merged into mm[0], mm[1] (fp32, device); mm[2] counts non-finite values
@@ -348,6 +351,17 @@ void launch_csr_check(const int64_t* indptr_rows, const int32_t* idx, int64_t n_
 constexpr int CSR_UNIQUE_WAVE_MAX = 2048;
 void launch_csr_unique(const int64_t* indptr, const int32_t* idx, int64_t n_rows, int* bad, int64_t* long_rows,
                        int long_cap, int* n_long, hipStream_t st);
+
+// ---- mask.hip: row masks of the pre-filtered query (hx_hybrid_query_*_masked) ---------------------------------------
+// mask [ceil(n/32) words] -> rows[0, *count) = the kept local rows, ascending; blk = ceil(n/8192) words of scratch.
+// Everything enqueued: *count is on the device.
+void launch_mask_rows(const uint32_t* mask, int64_t n, uint32_t* blk, uint32_t* rows, uint32_t* count, hipStream_t st);
+// dst row i = src row rows[i] (row_bytes a multiple of 16), and the same for one 4-byte value per row
+void launch_gather_rows16(const void* src, void* dst, int64_t row_bytes, const uint32_t* rows, int64_t count,
+                          hipStream_t st);
+void launch_gather_u32(const void* src, void* dst, const uint32_t* rows, int64_t count, hipStream_t st);
+// keys of a scan of the view (internal ids id_base + view row) -> internal ids id_base + rows[view row], in place
+void launch_view_ids(uint64_t* keys, int64_t n, const uint32_t* rows, uint32_t count, uint32_t id_base, hipStream_t st);
 
 // ---- spbuild.hip -------------------------------------------------------------
 struct SparseBuildOut {

@@ -414,8 +414,22 @@ __device__ __forceinline__ uint32_t sp_take1(uint32_t e) {
   const uint32_t old = __hip_atomic_fetch_and(sp_word(e), ~(0xFFFFu << sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   return (old >> sh) & 0xFFFFu;
 }
+// Pre-filtered query (hx_hybrid_query_*_masked): a survivor (a >= tau) whose row's bit is clear in the row mask never enters
+// the buffer, so a_L and tau are taken over kept documents only and the superset argument above holds on the kept rows.
+// MASKED = false compiles to the code without the test.
+__device__ __forceinline__ bool sp_kept(const uint32_t* keep, uint32_t row) { return (keep[row >> 5] >> (row & 31)) & 1u; }
+template <bool MASKED>
+__device__ __forceinline__ void sp_append2_kept(uint64_t* cand, bool p0, uint32_t a0, uint32_t g0, bool p1, uint32_t a1,
+                                                uint32_t g1, const uint32_t* keep, uint32_t kbase) {
+  if (MASKED) {
+    if (p0) p0 = sp_kept(keep, g0 - kbase);
+    if (p1) p1 = sp_kept(keep, g1 - kbase);
+  }
+  sp_append2(cand, p0, a0, g0, p1, a1, g1);
+}
+template <bool MASKED>
 __device__ __forceinline__ void sp_harvest(const uint4& p, uint32_t m, uint64_t* cand, uint32_t tau, uint32_t gbase,
-                                           bool full) {
+                                           bool full, const uint32_t* keep, uint32_t kbase) {
   uint32_t a0 = 0, a1 = 0;
   if (full) {
     a0 = sp_take1(p.x);
@@ -424,15 +438,17 @@ __device__ __forceinline__ void sp_harvest(const uint4& p, uint32_t m, uint64_t*
     if (m & 1u) a0 = sp_take1(p.x);
     if (m & 2u) a1 = sp_take1(p.z);
   }
-  sp_append2(cand, a0 >= tau, a0, gbase + sp_doc(p.x), a1 >= tau, a1, gbase + sp_doc(p.z));   // tau >= 1: a cleared half never passes
+  sp_append2_kept<MASKED>(cand, a0 >= tau, a0, gbase + sp_doc(p.x), a1 >= tau, a1, gbase + sp_doc(p.z), keep,
+                          kbase);   // tau >= 1: a cleared half never passes
 }
 
 // The 2 * SP_K takes of SP_K chunks, issued back to back and waited for ONCE (sp_harvest under a per-posting
 // predicate put `s_waitcnt lgkmcnt(0)` behind every take: six LDS round trips per wave and round).  A posting that
 // does not count ANDs, with all ones, the lane's own word of the accumulator -- 64 idle lanes on ONE word would
 // serialise (measured: 2.06 -> 3.40 ms) -- and its result is dropped.
+template <bool MASKED>
 __device__ __forceinline__ void sp_harvest_batch(const uint4 (&p)[SP_K], const uint32_t (&m)[SP_K], int lane, uint64_t* cand,
-                                                 uint32_t tau, uint32_t gbase) {
+                                                 uint32_t tau, uint32_t gbase, const uint32_t* keep, uint32_t kbase) {
   uint32_t old[2 * SP_K];
   uint32_t* const idle = S.acc + lane;
 #pragma unroll
@@ -448,13 +464,15 @@ __device__ __forceinline__ void sp_harvest_batch(const uint4 (&p)[SP_K], const u
     const uint32_t e0 = p[k].x, e1 = p[k].z;
     const uint32_t a0 = (m[k] & 1u) ? (old[2 * k] >> (e0 >> 24)) & 0xFFFFu : 0u;
     const uint32_t a1 = (m[k] & 2u) ? (old[2 * k + 1] >> (e1 >> 24)) & 0xFFFFu : 0u;
-    sp_append2(cand, a0 >= tau, a0, gbase + sp_doc(e0), a1 >= tau, a1, gbase + sp_doc(e1));   // tau >= 1: a cleared half never passes
+    sp_append2_kept<MASKED>(cand, a0 >= tau, a0, gbase + sp_doc(e0), a1 >= tau, a1, gbase + sp_doc(e1), keep,
+                            kbase);   // tau >= 1: a cleared half never passes
   }
 }
 
 // ---------------------------------------------------------------------------------
 // kernel
 // ---------------------------------------------------------------------------------
+template <bool MASKED>
 __global__ __launch_bounds__(SP_THREADS, SEG_DOCS == 65536 ? SP_THREADS / 256 : SP_THREADS / 128) void k_sparse_select(SparseSelectArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -665,10 +683,10 @@ __global__ __launch_bounds__(SP_THREADS, SEG_DOCS == 65536 ? SP_THREADS / 256 : 
         uint32_t hm[SP_K];
 #pragma unroll
         for (int k = 0; k < SP_K; ++k) hm[k] = (mask >> (2 * k)) & 3u;
-        sp_harvest_batch(cur.p, hm, lane, cand, tau, gbase);
+        sp_harvest_batch<MASKED>(cur.p, hm, lane, cand, tau, gbase, a.keep, a.keep_base);
         if (c0 < nch) {
           while (c0 < nch) {
-            sp_harvest_batch(r, rm, lane, cand, tau, gbase);
+            sp_harvest_batch<MASKED>(r, rm, lane, cand, tau, gbase, a.keep, a.keep_base);
             c0 += SP_K * SP_WAVES;
             if (c0 < nch) load_round(c0);
           }
@@ -677,7 +695,8 @@ __global__ __launch_bounds__(SP_THREADS, SEG_DOCS == 65536 ? SP_THREADS / 256 : 
       }
 #else
 #pragma unroll
-      for (int k = 0; k < SP_K; ++k) sp_harvest(cur.p[k], (mask >> (2 * k)) & 3u, cand, tau, gbase, (tpack >> (24 + k)) & 1u);
+      for (int k = 0; k < SP_K; ++k) sp_harvest<MASKED>(cur.p[k], (mask >> (2 * k)) & 3u, cand, tau, gbase, (tpack >> (24 + k)) & 1u, a.keep,
+                                                 a.keep_base);
       for (uint32_t c0 = (uint32_t)(SP_K * SP_WAVES + wave); c0 < nch; c0 += SP_K * SP_WAVES) {
         uint4 r[SP_K];
         uint32_t rm[SP_K];
@@ -695,7 +714,7 @@ __global__ __launch_bounds__(SP_THREADS, SEG_DOCS == 65536 ? SP_THREADS / 256 : 
           }
         }
 #pragma unroll
-        for (int k = 0; k < SP_K; ++k) sp_harvest(r[k], rm[k], cand, tau, gbase, false);
+        for (int k = 0; k < SP_K; ++k) sp_harvest<MASKED>(r[k], rm[k], cand, tau, gbase, false, a.keep, a.keep_base);
       }
 #endif
       SP_STAMP(4)
@@ -804,7 +823,8 @@ void launch_sparse_select_variant(const SparseSelectArgs& a, hipStream_t st) {
   if (a.B <= 0 || a.parts <= 0) return;
   HX_CHECK(a.ix.seg_docs == SEG_DOCS, "sparse: index built for another segment size");
   HX_CHECK(a.limit >= 1 && a.limit <= a.lout && a.lout <= SP_CAP / 2, "sparse: limit too large");
-  hipLaunchKernelGGL(k_sparse_select, dim3(a.B * a.parts), dim3(SP_THREADS), 0, st, a);
+  if (a.keep) hipLaunchKernelGGL(k_sparse_select<true>, dim3(a.B * a.parts), dim3(SP_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(k_sparse_select<false>, dim3(a.B * a.parts), dim3(SP_THREADS), 0, st, a);
   HX_HIP(hipGetLastError());
 }
 

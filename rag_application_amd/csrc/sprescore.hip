@@ -330,11 +330,17 @@ void launch_sparse_pack(const uint64_t* parts, const int* pcnt, int B, int pt, i
 // Document-at-a-time path.  Rows [row_begin, row_end) against the listed queries: a document that shares a term
 // with the query and scores >= tau[f] appends its key to the query's buffer (slots [cnt0, cap)); a full
 // buffer sets ovf[f].  tau NULL: every row has its own slot (slot0 + row - row_begin), 0 when no term is shared.
+// MASKED (a pre-filtered query): a row whose bit is clear in a.keep is a document that shares no term.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void k_sparse_range(SparseRangeArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t row = a.row_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.row_end) return;
   const int f = blockIdx.y;
+  if (MASKED && !((a.keep[row >> 5] >> (row & 31)) & 1u)) {
+    if (!a.tau && lane == 0) a.out[(int64_t)f * a.stride + a.slot0 + (row - a.row_begin)] = 0ull;
+    return;
+  }
   const int b = a.qsel[f];
   const int64_t qb = a.q_indptr[b];
   bool any;
@@ -352,7 +358,8 @@ __global__ __launch_bounds__(256) void k_sparse_range(SparseRangeArgs a) {
 void launch_sparse_range(const SparseRangeArgs& a, hipStream_t st) {
   const int64_t n = a.row_end - a.row_begin;
   if (n <= 0 || a.nsel <= 0) return;
-  hipLaunchKernelGGL(k_sparse_range, dim3((unsigned)((n + 3) / 4), a.nsel), dim3(256), 0, st, a);
+  if (a.keep) hipLaunchKernelGGL(k_sparse_range<true>, dim3((unsigned)((n + 3) / 4), a.nsel), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_sparse_range<false>, dim3((unsigned)((n + 3) / 4), a.nsel), dim3(256), 0, st, a);
   HX_HIP(hipGetLastError());
 }
 

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import HX_MODE_H1, HX_MODE_TREE, HxError, HxParams, HxProf, HxStats, check
+from .filters import pack_rows
 
 SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_256_limit",
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
@@ -332,20 +333,54 @@ class HxIndex:
                                     _ptr(cand_counts), limit, _ptr(keys), _ptr(cnt), _stream()))
         return keys, cnt
 
+    def _mask(self, mask):
+        """(packed uint32 words, mask_rows) of a row mask: a bool array of one entry per row, or the packed words
+        themselves (ceil(count / 32) of them, bit r & 31 of word r >> 5 = row r)."""
+        m = np.asarray(mask)
+        if m.dtype == np.bool_:
+            return pack_rows(m), int(m.shape[0])
+        if m.dtype != np.uint32:
+            raise TypeError("mask: a bool array (one entry per row) or packed np.uint32 words")
+        n = self.count()
+        if m.shape[0] != (n + 31) // 32:
+            raise ValueError(f"mask: {m.shape[0]} words for {n} rows (want {(n + 31) // 32})")
+        return np.ascontiguousarray(m), n
+
     def hybrid_query(self, q: torch.Tensor, q_indptr: torch.Tensor, q_idx: torch.Tensor,
-                     q_val: torch.Tensor, params: HxParams):
+                     q_val: torch.Tensor, params: HxParams, mask=None):
+        """mask: None = every row; else a packed uint32 tensor / array or a bool array (hx_hybrid_query_dev_masked)."""
         q = _need_cuda(q, torch.float32, "q")
         q_indptr = _need_cuda(q_indptr, torch.int64, "q_indptr")
         q_idx = _need_cuda(q_idx, torch.int32, "q_idx")
         q_val = _need_cuda(q_val, torch.float32, "q_val")
         B = q.shape[0]
         keys, cnt = self._out(B, params.final_limit)
-        check(_lib.lib().hx_hybrid_query_dev(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
-                                             C.byref(params), _ptr(keys), _ptr(cnt), _stream()))
+        if mask is None:
+            check(_lib.lib().hx_hybrid_query_dev(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                 C.byref(params), _ptr(keys), _ptr(cnt), _stream()))
+            return keys, cnt
+        if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
+            if mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not mask.is_contiguous():
+                raise TypeError("device mask: a contiguous int32 / uint32 tensor holding the packed words, or a bool tensor")
+            words, rows = mask, self.count()
+            if words.shape[0] != (rows + 31) // 32:
+                raise ValueError(f"mask: {words.shape[0]} words for {rows} rows")
+        else:   # a bool mask (host or device) or host words: packed on the host
+            packed, rows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
+            words = torch.from_numpy(packed.view(np.int32)).to(q.device)
+        check(_lib.lib().hx_hybrid_query_dev_masked(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                    C.byref(params), _ptr(words), rows, _ptr(keys), _ptr(cnt),
+                                                    _stream()))
         return keys, cnt
 
+    def release_mask_view(self):
+        """Free the gathered copies pre-filtered queries keep between calls (hx_release_mask_view)."""
+        check(_lib.lib().hx_release_mask_view(self._h))
+
     def hybrid_query_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
-                          params: HxParams):
+                          params: HxParams, mask=None):
+        """mask: None = every row; else a bool array (one entry per row) or packed np.uint32 words
+        (hx_hybrid_query_host_masked: the lists of the same query on an index of the kept rows only)."""
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
         q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
         q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
@@ -354,8 +389,14 @@ class HxIndex:
         scores = np.empty((B, L), dtype=np.float32)
         ids = np.empty((B, L), dtype=np.int64)
         counts = np.empty((B,), dtype=np.int32)
-        check(_lib.lib().hx_hybrid_query_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
-                                              C.byref(params), _ptr(scores), _ptr(ids), _ptr(counts)))
+        if mask is None:
+            check(_lib.lib().hx_hybrid_query_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                  C.byref(params), _ptr(scores), _ptr(ids), _ptr(counts)))
+            return scores, ids, counts
+        words, rows = self._mask(mask)
+        check(_lib.lib().hx_hybrid_query_host_masked(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                     C.byref(params), _ptr(words), rows, _ptr(scores), _ptr(ids),
+                                                     _ptr(counts)))
         return scores, ids, counts
 
 

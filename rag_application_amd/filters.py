@@ -17,10 +17,17 @@ Qdrant is absent from the image, so the condition semantics are restated from it
   {"is_empty": {"key": k}}               k missing, None or []
   {"is_null": {"key": k}}                k present with value None
   {"has_id": [ids]}                      the point id is listed
-Keys may be dotted paths ("chunk_metadata.page")."""
+Keys may be dotted paths ("chunk_metadata.page").
+
+`row_mask` evaluates a filter over every stored row at once, as the packed row mask of the engine's
+pre-filtered query (include/hx.h: hx_hybrid_query_*_masked): the filter then applies to every stage,
+not to the root alone (QdrantHandler.hybrid_search(..., filter_stages="all"))."""
 from __future__ import annotations
 
-from typing import Any, Dict, Iterable, Optional
+import json
+from typing import Any, Dict, Iterable, Optional, Sequence
+
+import numpy as np
 
 _MISSING = object()
 
@@ -104,3 +111,31 @@ def matches(payload: Dict[str, Any], flt: Optional[Dict[str, Any]], point_id=Non
     if should and not any(_condition(c, payload, point_id) for c in should):
         return False
     return True
+
+
+def pack_rows(keep) -> np.ndarray:
+    """bool per row -> the engine's row mask: ceil(n / 32) uint32 words, bit r & 31 of word r >> 5 (LSB first) = row r."""
+    keep = np.asarray(keep, dtype=bool).ravel()
+    nw = (keep.shape[0] + 31) // 32
+    b = np.packbits(keep, bitorder="little")
+    b = np.concatenate([b, np.zeros(nw * 4 - b.shape[0], np.uint8)])
+    return b.view("<u4").astype(np.uint32)
+
+
+def row_mask(ids: Sequence[Any], payloads: Sequence[Dict[str, Any]], flt: Optional[Dict[str, Any]],
+             start: int = 0, prev: Optional[np.ndarray] = None) -> np.ndarray:
+    """The packed row mask of `flt` over the rows (ids[r], payloads[r]): bit r set when `matches` holds for row r.
+    start / prev: the rows before `start` are already evaluated in the packed mask `prev` (rows appended since),
+    only rows [start, n) are evaluated."""
+    n = len(ids)
+    keep = np.zeros(n, dtype=bool)
+    if prev is not None and start > 0:
+        keep[:start] = np.unpackbits(np.asarray(prev, np.uint32).view(np.uint8), bitorder="little")[:start].astype(bool)
+    for r in range(start, n):
+        keep[r] = matches(payloads[r], flt, ids[r])
+    return pack_rows(keep)
+
+
+def filter_key(flt: Optional[Dict[str, Any]]) -> str:
+    """Canonical JSON of a filter: the key of a collection's mask cache."""
+    return json.dumps(flt, sort_keys=True, separators=(",", ":"), default=str)

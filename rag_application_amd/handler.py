@@ -73,6 +73,22 @@ class _Collection:
         self.ids: List[str] = []
         self.payloads: List[Dict[str, Any]] = []
         self.sparse_enabled = True
+        self._masks: Dict[str, Any] = {}
+
+    MASK_CACHE = 64   # filters whose row masks a collection keeps (least recently used first out): n / 8 bytes each
+
+    def row_mask(self, flt) -> np.ndarray:
+        """The packed row mask of `flt` (filters.row_mask), cached by the filter's canonical JSON: rows appended since
+        the last evaluation are the only rows evaluated again.  The cache holds the MASK_CACHE most recent filters."""
+        key = _filters.filter_key(flt)
+        n = len(self.ids)
+        done, prev = self._masks.pop(key, (0, None))
+        if done != n:
+            prev = _filters.row_mask(self.ids, self.payloads, flt, start=done, prev=prev)
+        self._masks[key] = (n, prev)                      # (dicts keep insertion order: the last used is last)
+        while len(self._masks) > self.MASK_CACHE:
+            del self._masks[next(iter(self._masks))]
+        return prev
 
     def close(self):
         self.index.close()
@@ -97,11 +113,18 @@ class _Collection:
         self.ids = list(meta["ids"])
         self.payloads = list(meta["payloads"])
         self.sparse_enabled = bool(meta["sparse_enabled"])
+        self._masks = {}
         return self
+
+
+FILTER_STAGES = ("root", "all")
 
 
 class QdrantHandler:
     """Handles vector operations for hybrid search with dense and sparse vectors."""
+
+    # filter_stages="all" (the engine's pre-filtered query) needs one engine index per collection
+    _masked_search = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -266,7 +289,12 @@ class QdrantHandler:
             raise
 
     # ---------------------------------------------------------------------------- search
-    def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree"):
+    def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree",
+                     filter_stages="root"):
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if filter_stages == "all" and not self._masked_search:
+            raise ValueError("filter_stages='all' is not supported on a sharded collection: use filter_stages='root'")
         col = self._collections[str(user_id)]
         q = np.asarray(dense_vectors, dtype=np.float32).reshape(len(sparse_vectors), -1)
         if q.shape[1] != col.dim:
@@ -286,8 +314,17 @@ class QdrantHandler:
         # KeyError/TypeError like the reference when search_params lacks a key / is None
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
         final_limit = int(hp.final_limit)
+        if filters and filter_stages == "all":
+            # the filter applies to every stage: the engine searches the kept rows only, the root included
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            scores, ids, counts = col.index.hybrid_query_host(q, indptr, idx.astype(np.int32), val.astype(np.float32),
+                                                              hp, mask=col.row_mask(filters))
+            cids, cpay = col.ids, col.payloads
+            return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+                    for sc, rw, n in zip(scores.tolist(), ids.tolist(), counts.tolist())]
         if filters and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree'")
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
         if filters:
             # query_filter belongs to the ROOT query only (:297, :371): the union of the branches'
             # candidates (<= dense_limit + the fusion's 10) is re-scored, filtered, cut to final_limit.
@@ -307,12 +344,14 @@ class QdrantHandler:
     async def hybrid_search(self, user_id: str, query_text: str, dense_vector: List[float],
                             sparse_vector: Dict[str, List[float]], image_embedding: Optional[List[float]] = None,
                             top_k: int = 10, search_params: Optional[Dict[str, Any]] = None,
-                            filters: Optional[Dict] = None) -> List[Dict]:
+                            filters: Optional[Dict] = None, filter_stages: str = "root") -> List[Dict]:
         """Matryoshka cascade, quantized + dense refinement, sparse, RRF, dense root
-        re-score, reranking hook (qdrant_handler.py:269-386)."""
+        re-score, reranking hook (qdrant_handler.py:269-386).  filter_stages (additive): "root" = the
+        filter on the root query only, as the reference passes it (:297, :371); "all" = every stage
+        searches only the rows the filter keeps (the engine's pre-filtered query)."""
         try:
             results = (await self._run(self._search_sync, user_id, [dense_vector], [sparse_vector],
-                                       search_params, filters))[0]
+                                       search_params, filters, "tree", filter_stages))[0]
             max_tokens_per_doc = 8000 // top_k
             documents = [res.payload["content"] for res in results
                          if hasattr(res, "payload") and res.payload and "content" in res.payload]
@@ -324,12 +363,14 @@ class QdrantHandler:
 
     async def hybrid_search_batch(self, user_id: str, dense_vectors, sparse_vectors, top_k: int = 10,
                                   search_params: Optional[Dict[str, Any]] = None,
-                                  filters: Optional[Dict] = None, mode: str = "tree") -> List[List[ScoredPoint]]:
+                                  filters: Optional[Dict] = None, mode: str = "tree",
+                                  filter_stages: str = "root") -> List[List[ScoredPoint]]:
         """B queries in one engine call (additive; no reranking hook).  mode "tree" = the reference query
-        (:305-372), "h1" = dense top-dense_limit (+) sparse top-sparse_limit -> RRF -> final_limit."""
+        (:305-372), "h1" = dense top-dense_limit (+) sparse top-sparse_limit -> RRF -> final_limit.
+        filter_stages as in hybrid_search; mode "h1" takes filters with filter_stages="all" only."""
         try:
             res = await self._run(self._search_sync, user_id, dense_vectors, sparse_vectors, search_params, filters,
-                                  mode)
+                                  mode, filter_stages)
             return [r[:top_k] for r in res]
         except Exception as e:
             logging.error("hybrid search for %s failed: %s", user_id, e)
@@ -373,9 +414,8 @@ class QdrantHandler:
                 logging.warning("get_collection_chunk_count: no collection for %s", user_id)
                 return 0
             col = self._collections[str(user_id)]
-            if filters:   # :464-470: count the points the filter keeps
-                return await self._run(lambda: sum(1 for i, p in zip(col.ids, col.payloads)
-                                                   if _filters.matches(p, filters, i)))
+            if filters:   # :464-470: count the points the filter keeps (the popcount of its cached row mask)
+                return await self._run(lambda: int(np.unpackbits(col.row_mask(filters).view(np.uint8)).sum()))
             return await self._run(col.index.count)
         except Exception as e:
             logging.error("get_collection_chunk_count(%s) failed: %s", user_id, e)
