@@ -241,7 +241,17 @@ int hx_h1_fuse(int32_t device, const uint64_t* gathered_dev, int32_t world, int3
  *                        hold): the caller then redoes the batch through hx_h1_local, as after hx_h1_local_async.
  * The integer BM25 scores of different shards are comparable only under one scale: hx_set_sparse_wmax gives every shard
  * the largest document weight of ANY shard (hx_sparse_wmax reads the shard's own; also whether it holds a non-positive
- * weight).  Needs the int8 candidate copy (the default). */
+ * weight).  Needs the int8 candidate copy (the default, hx_dense_candidates): a shard whose int8 pass is off does not
+ * fail in hx_h1_nominate_async (its peers are already on their way into the all-gather); it sends an empty dense list
+ * flagged as overflowed, so every rank sees a flagged batch and redoes it per shard.
+ * hx_h1_plan fails (and the caller uses the per-shard exchange, hx_h1_local_async + hx_h1_fuse) when
+ *  - dense_limit, rounded up to a multiple of 32, exceeds 8192 / world (also rounded down to 32): a shard's dense list
+ *    must hold dense_limit rows, and world x k1 keys are merged in one 8192-key buffer;
+ *  - a shard's share of sparse_limit (mean + 10 sigma, to 32) exceeds 256, the most exact sparse keys per query and
+ *    shard hx_h1_rescore_async takes (sparse_limit from 257 at world 1, 331 at world 2, 1151 at world 8);
+ *  - the arguments are out of range (limits in [1, 2048], world in [1, 64]).
+ * Every plan it returns meets the checks of hx_h1_nominate_async, hx_h1_rescore_async and hx_h1_finish: dense_limit <=
+ * k1, k1 a share of lp and k2 = k3 a share of sparse_limit (all multiples of 32), world x k <= 8192, k3 <= 256. */
 int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t* k1, int32_t* k2, int32_t* lp,
                int32_t* k3, int32_t* lout);
 int hx_sparse_wmax(hx_index* h, float* wmax, int32_t* nonpos);
@@ -360,6 +370,10 @@ typedef struct hx_prof {
  * default; a query its certificate does not cover is re-run on the fp16 copy), 0 = the fp16 copy.  The lists are the
  * same either way (final scores are exact fp32): this is a measurement and test switch. */
 int hx_set_dense_candidates(hx_index* h, int32_t kind);
+/* *kind = 1 when the int8 copy nominates this index's dense candidates now, 0 when the fp16 copy does (switched by
+ * hx_set_dense_candidates(h, 0), by the guard that turns the int8 pass off for rows it resolves badly, or an index
+ * created without the int8 copy).  The candidates-first sharded H1 exchange needs 1 on every shard. */
+int hx_dense_candidates(hx_index* h, int32_t* kind);
 /* Where the sparse stage of a hybrid call runs: 1 (the default) = on the index's second stream, beside the dense scans;
  * 0 = every stage on the caller's stream, one kernel at a time -- a measurement switch: a kernel's duration (hx_profile)
  * is its own only when nothing runs beside it.  The lists do not depend on it. */

@@ -2415,6 +2415,8 @@ int hx_h1_fuse(int32_t device, const uint64_t* gathered, int32_t world, int32_t 
 // Workspace slots of the rescore step: it runs on the exchange stream BESIDE the next batch's nominate step on the same
 // index, so it shares no buffer with any other entry.
 enum { WSX = 3000 };
+// Largest k3 (exact sparse keys a shard returns per query) hx_h1_rescore_async takes
+constexpr int H1X_K3_MAX = 256;
 
 int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t* k1, int32_t* k2, int32_t* lp,
                int32_t* k3, int32_t* lout) {
@@ -2433,10 +2435,15 @@ int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t
   HX_CHECK(cap >= 32, "world too large for the candidates-first exchange");
   const int Lp = cand8_lprime(dense_limit);
   HX_CHECK(Lp <= MAX_LIMIT, "dense_limit too large for the candidates-first exchange");
+  // a shard's dense list must hold dense_limit rows whatever its share (the nomination's geometry keeps exactly k1)
+  const int k1min = (int)round_up(dense_limit, 32);
+  HX_CHECK(k1min <= cap, "dense_limit too large for the candidates-first exchange at this world size");
+  const int ks = std::min(share(sparse_limit), cap);
+  HX_CHECK(ks <= H1X_K3_MAX, "sparse_limit too large for the candidates-first exchange at this world size");
   *lp = Lp;
-  *k1 = std::min(share(Lp), cap);
-  *k2 = std::min(share(sparse_limit), cap);         // integer scores: enough to fix the value of the global L-th
-  *k3 = std::min(share(sparse_limit), cap);         // exact sparse keys a shard returns
+  *k1 = std::max(std::min(share(Lp), cap), k1min);
+  *k2 = ks;                                         // integer scores: enough to fix the value of the global L-th
+  *k3 = ks;                                         // exact sparse keys a shard returns
   *lout = sparse_lout(sparse_limit);
   HX_CATCH
 }
@@ -2465,13 +2472,32 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
   HX_CHECK(dense_limit >= 1 && dense_limit <= MAX_LIMIT && sparse_limit >= 1 && sparse_limit <= MAX_LIMIT, "limit out of range [1, 2048]");
   const int lout = sparse_lout(sparse_limit);
   HX_CHECK(k1 >= 1 && k1 <= CAND_CAP / 4 && k2 >= 1 && k2 <= lout, "k1 / k2 out of range");
+  HX_CHECK(k1 >= dense_limit, "k1 < dense_limit (hx_h1_plan)");
   h->set_device();
   hipStream_t st = (hipStream_t)stream;
   Workspace& w = h->ws;
+  // The int8 candidate pass nominates the dense rows.  A shard whose pass is off (hx_set_dense_candidates(h, 0), the
+  // guard in search_dense, an index created without the copy) must not raise here: its peers are about to enter the
+  // all-gather.  It sends an empty dense list flagged as not trustworthy (dflag bit 0), every rank sees the flag in the
+  // gathered words, and the batch is redone per shard on all of them.
+  const bool use8 = h->cand8 && !h->cand8_off && h->q8s;
+  Geometry g{};
+  if (h->n > 0 && use8) g = geometry(dense_limit, true, false, true, k1);   // (its checks throw before the fork)
   // ---- sparse: the shard's integer-score list (the select pass only; ids stay internal: only the scores travel, the
   // list itself is consumed by this rank's own rescore step) -- on the second stream, beside the dense scan
-  bool forked = false;
   hipStream_t sst = st;
+  // Once forked, the caller's stream waits for the select pass however the call ends: on an error the second stream
+  // would otherwise go on writing buffers that the next call on `st` reuses unordered.
+  struct Beside {
+    hx_index* h;
+    hipStream_t st;
+    bool pending;
+    ~Beside() {
+      h->beside = false;
+      if (pending && hipEventRecord(h->ev_join, h->st2) == hipSuccess) (void)hipStreamWaitEvent(st, h->ev_join, 0);
+    }
+  } beside_guard{h, st, false};
+  bool forked = false;
   // Only for LARGE shards: alone the call is shorter with it at every size (1.34 -> 1.27 ms at 1.25M rows, B = 1024), but in
   // H1Pipeline the re-score + exchange of the previous batch already run beside it on the pipeline's side stream, and a third
   // stream in the mix made the pipelined step LONGER at the 8- and 4-GPU shard sizes (1.49 -> 1.55 ms at 1.25M rows, 2.68 ->
@@ -2485,11 +2511,8 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
     HX_HIP(hipStreamWaitEvent(h->st2, h->ev_fork, 0));
     sst = h->st2;
     forked = true;
+    beside_guard.pending = true;
   }
-  struct Beside {
-    hx_index* h;
-    ~Beside() { h->beside = false; }
-  } beside_guard{h};
   h->beside = forked;
   const SparseLists sl = sparse_select_lists(h, qip, qix, qv, B, sparse_limit, sst);
   h->sp_sum_pending = false;                         // nobody will call sparse_resolve for this batch
@@ -2500,14 +2523,12 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
   int *cnt = nullptr, *ovf = nullptr;
   float* eq = nullptr;
   int cstride = 0;
-  if (h->n > 0) {
-    HX_CHECK(h->cand8 && !h->cand8_off && h->q8s, "the candidates-first exchange needs the int8 candidate copy");
+  if (h->n > 0 && use8) {
     const MatrixRef m = pick_matrix(h, 0);
     const int bn = scan_bn(h, B);
     const int Bpad = (int)round_up(B, bn);
     float* qn = (float*)w.get(WS_QN, (size_t)B * m.dpad * 4);
     launch_prep_queries_f(qd, h->dim, B, B, m.d, m.dpad, qn, nullptr, st);
-    const Geometry g = geometry(dense_limit, true, false, true, k1);
     cand = (uint64_t*)w.get(WS_CAND, (size_t)B * g.C * 8);
     cnt = (int*)w.get(WS_CNT, (size_t)B * 4);
     ovf = (int*)w.get(WS_OVF, (size_t)B * 4);
@@ -2521,12 +2542,22 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
     cstride = g.C;
     h->cand8_queries += B;
     remap_out(h, cand, (int64_t)B * g.C, st);        // (identity for a shard filled in one block: skipped)
+  } else if (h->n > 0) {                             // int8 pass off: no rows, and every query's dense list overflowed
+    cand = (uint64_t*)w.get(WS_CAND, 8);              // (never read: the count is 0)
+    cnt = (int*)w.get(WS_CNT, (size_t)B * 4);
+    ovf = (int*)w.get(WS_OVF, (size_t)B * 4);
+    eq = (float*)w.get(WS_EPSQ, (size_t)B * 4);
+    HX_HIP(hipMemsetAsync(cnt, 0, (size_t)B * 4, st));
+    HX_HIP(hipMemsetAsync(ovf, 0xFF, (size_t)B * 4, st));
+    HX_HIP(hipMemsetAsync(eq, 0, (size_t)B * 4, st));
   }
   h->beside = false;
   if (forked) HX_HIP(hipStreamWaitEvent(st, h->ev_join, 0));
+  beside_guard.pending = false;
   HX_CHECK(!sl.list || sl.lout == lout, "sparse list stride");
-  launch_h1x_pack(cand, cstride, cnt, ovf, eq, h->n <= k1 ? 1 : 0, k1, sl.list, sl.lout, sl.lcnt, sl.flag, sl.fail, k2,
-                  lout, std::max(h->sp_wmax, h->sp_wmax_shared), B, nom_dev, st);
+  const int complete = (h->n == 0 || (use8 && h->n <= k1)) ? 1 : 0;   // the list holds every row the shard has
+  launch_h1x_pack(cand, cstride, cnt, ovf, eq, complete, k1, sl.list, sl.lout, sl.lcnt, sl.flag, sl.fail, k2, lout,
+                  std::max(h->sp_wmax, h->sp_wmax_shared), B, nom_dev, st);
   HX_CATCH
 }
 
@@ -2538,7 +2569,7 @@ int hx_h1_rescore_async(hx_index* h, const float* qd, const int64_t* qip, const 
   HX_CHECK(h && qd && qip && nom_dev && gathered_dev && res_dev && B > 0 && world >= 1 && rank >= 0 && rank < world, "bad argument");
   HX_CHECK(dense_limit >= 1 && dense_limit <= lp && lp <= MAX_LIMIT && sparse_limit >= 1 && sparse_limit <= MAX_LIMIT, "limits out of range");
   HX_CHECK((int64_t)world * k1 <= CAND_CAP && (int64_t)world * k2 <= CAND_CAP && (int64_t)world * k3 <= CAND_CAP && k1 >= 1 &&
-               k2 >= 1 && k3 >= 1 && k3 <= 256,
+               k2 >= 1 && k3 >= 1 && k3 <= H1X_K3_MAX,
            "world x k out of range");
   h->set_device();
   hipStream_t st = (hipStream_t)stream;
@@ -2822,6 +2853,13 @@ int hx_set_stream_overlap(hx_index* h, int32_t on) {
   HX_TRY
   HX_CHECK(h, "index is NULL");
   h->overlap_tail = on != 0;
+  HX_CATCH
+}
+
+int hx_dense_candidates(hx_index* h, int32_t* kind) {
+  HX_TRY
+  HX_CHECK(h && kind, "NULL argument");
+  *kind = (h->cand8 && !h->cand8_off && (h->q8s || h->n == 0)) ? 1 : 0;
   HX_CATCH
 }
 

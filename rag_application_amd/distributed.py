@@ -103,6 +103,20 @@ class ShardedIndex:
                 t = d.cpu()
         self.local.set_sparse_wmax(float(t.item()))
 
+    def all_min(self, v: int) -> int:
+        """Collective: the smallest `v` of any rank (a decision every rank must take alike).  Nothing to exchange at
+        world 1."""
+        if self.world == 1:
+            return int(v)
+        t = torch.tensor([int(v)], dtype=torch.int64)
+        if dist.get_backend(self.group) == "gloo":
+            dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
+        else:
+            d = t.cuda()
+            dist.all_reduce(d, op=dist.ReduceOp.MIN, group=self.group)
+            t = d.cpu()
+        return int(t.item())
+
     def _global(self, keys, limit, dedupe=False):
         if self.world == 1:
             return keys, None
@@ -221,6 +235,11 @@ class H1Pipeline:
         self.sh = sh
         self.args = (dense_limit, sparse_limit, limit, rrf_k, rank_base)
         fast = hasattr(sh.local, "h1_local") and hasattr(sh.ops, "h1_fuse")
+        if fast and max(sh.world, 1) * max(dense_limit, sparse_limit) > 8192:
+            # the per-shard exchange merges world x limit keys in one 8192-key buffer (hx_h1_fuse), and it is also what
+            # redoes a flagged batch of the candidates-first one: neither serves these limits
+            raise ValueError(f"H1Pipeline: world {sh.world} x max(dense_limit {dense_limit}, sparse_limit {sparse_limit}) "
+                             f"exceeds 8192")
         self.deferred = fast and hasattr(sh.local, "h1_local_async") and (sh.world > 1 or force_side_stream)
         self.side = torch.cuda.Stream() if (self.deferred and torch.cuda.is_available()) else None
         self.depth = max(1, depth)
@@ -234,18 +253,24 @@ class H1Pipeline:
         # next batch's local stage; what a shard pays per query whatever its row count falls by about the number of
         # shards.  A batch that a check flags -- a shard's list cut above the global cut (topically clustered rows), an
         # overflow, a certificate that does not hold -- is redone through the per-shard path, and the lists are widened.
+        # Every step of this decision comes out the same on every rank: the plan is arithmetic on the limits, and
+        # whether each shard's int8 candidate pass is on is exchanged (a shard without it could not nominate).
         cf_ok = (self.deferred and hasattr(sh.local, "h1_nominate_async") and hasattr(sh.ops, "h1_finish")
                  and hasattr(sh.ops, "h1_plan"))
         self.cf = cf_ok if candidates_first is None else bool(candidates_first and cf_ok)
         if self.cf:
             try:
                 self.k1, self.k2, self.lp, self.k3, self.lout = sh.ops.h1_plan(dense_limit, sparse_limit, max(sh.world, 1))
-                cap = 8192 // max(sh.world, 1) // 32 * 32       # world x k keys are merged in one 8192-key buffer
-                L32 = (sparse_limit + 31) // 32 * 32
-                self.k1max = min(max((self.lp + 31) // 32 * 32, self.k1), cap)
-                self.k2max, self.k3max = min(max(L32, self.k2), cap), min(max(L32, self.k3), cap, 256)
-                sh.sync_sparse_scale()
-            except Exception:          # limits the plan does not take: the per-shard exchange serves them
+                dc = getattr(sh.local, "dense_candidates", None)
+                mine = 1 if dc is None or dc() == "i8" else 0      # (a stand-in without the query nominates as it likes)
+                self.cf = sh.all_min(mine) == 1
+                if self.cf:
+                    cap = 8192 // max(sh.world, 1) // 32 * 32       # world x k keys are merged in one 8192-key buffer
+                    L32 = (sparse_limit + 31) // 32 * 32
+                    self.k1max = min(max((self.lp + 31) // 32 * 32, self.k1), cap)
+                    self.k2max, self.k3max = min(max(L32, self.k2), cap), min(max(L32, self.k3), cap, 256)
+                    sh.sync_sparse_scale()
+            except Exception:   # limits the plan does not take (hx.h: hx_h1_plan): the per-shard exchange serves them
                 self.cf = False
 
     def _exchange_and_fuse(self, mine, B):

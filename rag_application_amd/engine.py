@@ -175,6 +175,12 @@ class HxIndex:
         """'i8' (default) or 'f16': which copy nominates the dense stage's candidates (hx_set_dense_candidates)."""
         check(_lib.lib().hx_set_dense_candidates(self._h, {"f16": 0, "i8": 1}[kind]))
 
+    def dense_candidates(self) -> str:
+        """'i8' when the int8 copy nominates the dense candidates now, else 'f16' (hx_dense_candidates)."""
+        k = C.c_int32()
+        check(_lib.lib().hx_dense_candidates(self._h, C.byref(k)))
+        return "i8" if k.value else "f16"
+
     def set_stream_overlap(self, on: bool):
         """False: every stage of a hybrid call on the caller's stream (a kernel's profiled duration is then its own)."""
         check(_lib.lib().hx_set_stream_overlap(self._h, 1 if on else 0))

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.test_gpu_shard_exchange import _cf_exchange
 
 pytestmark = pytest.mark.gpu
 
@@ -510,19 +511,6 @@ def test_two_shards_one_gpu_merge_equals_unsharded(eng, torch_mod, synth_tables)
     one.close()
     for s in shards:
         s.close()
-
-
-def _cf_exchange(eng, torch_mod, shards, Qd, tq, dl, sl, limit, k1, k2, lp, k3, lout):
-    """The candidates-first H1 exchange by hand on one GPU: nominate on every shard, the all-gather = cat of the public
-    parts, rescore on every shard, the integer-sum all-reduce = sum, finish.  Returns (keys, counts, failed queries)."""
-    W, B = len(shards), Qd.shape[0]
-    noms = [s.h1_nominate_async(Qd, *tq, dl, sl, k1, k2, lout) for s in shards]
-    pub = B * (k1 + k2 + 2)
-    g = torch_mod.cat([x[:pub] for x in noms])
-    res = [s.h1_rescore_async(Qd, *tq, noms[r], g, W, r, dl, sl, k1, k2, lp, k3) for r, s in enumerate(shards)]
-    red = torch_mod.stack(res).sum(dim=0)
-    k, c, nf = eng.h1_finish(red, W, B, lp, k3, dl, sl, limit)
-    return k, c, int(nf.item())
 
 
 @pytest.mark.parametrize("fork", ["select pass on the caller's stream", "select pass on the second stream"])
