@@ -156,6 +156,10 @@ class World:
                                   mode=self.eng.HX_MODE_H1)
         return self.one.hybrid_query(*q, hp)
 
+    def expected(self, b0, b1, dl, sl):
+        """(keys, counts) the pipeline must return for queries [b0, b1): the one index's"""
+        return self.one_index(self.batch(b0, b1), dl, sl)
+
     def oracle(self, b, dl, sl):
         if self._ora is None:
             d = self.d
@@ -245,7 +249,8 @@ def rank0(shards):
 
 
 def run_pipeline(eng, torch_mod, w, dl, sl, batches, force=False, before_submit=None):
-    """H1Pipeline over rank 0 of `w`'s shards: every batch's lists must equal the one index's.  Returns the pipeline."""
+    """H1Pipeline over rank 0 of `w`'s shards: every batch's lists must equal `w.expected` (the one index's).  Returns
+    the pipeline."""
     from rag_application_amd.distributed import H1Pipeline
     pipe = H1Pipeline(rank0(w.shards), dl, sl, LIMIT, force_side_stream=force)
     outs = []
@@ -256,7 +261,7 @@ def run_pipeline(eng, torch_mod, w, dl, sl, batches, force=False, before_submit=
     pipe.wait()
     torch_mod.cuda.synchronize()
     for (b0, b1), (k, c) in zip(batches, outs):
-        k1, c1 = w.one_index(w.batch(b0, b1), dl, sl)
+        k1, c1 = w.expected(b0, b1, dl, sl)
         assert torch_mod.equal(c, c1) and torch_mod.equal(k, k1), f"pipeline ({dl}, {sl}) batch {b0}:{b1}"
     return pipe
 
