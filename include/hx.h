@@ -43,6 +43,10 @@ typedef struct hx_index hx_index;
  * (app/services/agents/hybrid_search_workflow.py:8-19,
  *  app/api/v1/endpoints/mcp/qdrant_search_mcp_endpoint.py:19-28) plus the
  * switches for semantics inherited from Qdrant (oracle/oracle.py names them). */
+/* The hybrid entries refuse (before any device work) rrf_k that is non-finite, <= 0 or so small that 2 / rrf_k
+ * overflows, and rrf_rank_base outside [0, 2^30]: a document's fused score, the sum of its two contributions
+ * 1 / (f32(rank + rrf_rank_base) + rrf_k), then stays finite and positive.  hx_rrf, hx_h1_fuse and
+ * hx_h1_finish take the two settings directly and apply the same rule. */
 typedef struct hx_params {
   int32_t matryoshka_64_limit;   /* limit of the innermost prefix stage (first matryoshka size)   */
   int32_t matryoshka_128_limit;  /* second prefix stage                                           */
@@ -52,8 +56,8 @@ typedef struct hx_params {
   int32_t sparse_limit;
   int32_t final_limit;
   int32_t hnsw_ef;               /* accepted, unused: every stage is exact (qdrant_handler.py:369) */
-  float   rrf_k;                 /* 2.0  : Qdrant RRF constant                                      */
-  int32_t rrf_rank_base;         /* 0    : 0-based ranks                                            */
+  float   rrf_k;                 /* 2.0  : Qdrant RRF constant; finite, > 0, with 2 / rrf_k finite    */
+  int32_t rrf_rank_base;         /* 0    : 0-based ranks; in [0, 2^30]                              */
   int32_t rrf_limit;             /* 10   : default limit of a Prefetch without `limit`              */
   int32_t mode;                  /* HX_MODE_TREE or HX_MODE_H1                                      */
 } hx_params;
@@ -82,7 +86,11 @@ int hx_abi_version(void);
 int hx_reserve(hx_index* h, int64_t n_rows, int64_t nnz);
 /* append n raw dense rows [n x dim] (host fp32).  Derives on device, per row:
  * the L2-normalised "dense" vector, the normalised prefixes, the int8
- * "quantized" copy trunc(127*x) (qdrant_handler.py:144-150) and its norm. */
+ * "quantized" copy trunc(127*x) (qdrant_handler.py:144-150) and its norm.
+ * Every element must be finite: a batch with a NaN or +-Inf element anywhere is refused whole ("finite" in the
+ * message), the index stays as it was (count, stored rows, the int8 copy's error bound); the call may consume its ids.
+ * A finite row whose squared length overflows to +Inf is valid: it is stored as a zero row.  The same holds for
+ * hx_add_dense_dev, hx_add_rows and hx_add_rows_dev (checked on the device while the rows are derived). */
 int hx_add_dense(hx_index* h, const float* rows_host, int64_t n);
 /* the same for rows already on the device -- the output of an encoder on PyTorch-ROCm
  * (embedding_handler.py:64-99 produces them; qdrant_handler.py:120-198 stores them): read in place,
@@ -140,7 +148,11 @@ int hx_synth_queries_dense(int32_t dim, int64_t q0, int32_t B, uint32_t seed,
 
 /* Prefetch(query=dense_vector[:prefix], using="matryoshka_<prefix>"|"dense", limit)
  * (qdrant_handler.py:311-315, 327-329, 366-368).  q_dev: B raw (un-normalised)
- * query rows [B x dim] fp32.  prefix = 0 searches the full vector.  Output: keys
+ * query rows [B x dim] fp32.  Every element of every query must be finite (all dim of them, whatever the prefix): the
+ * call fails for a batch holding a NaN or +-Inf ("finite" in the message), reported at the stage's one host round trip.
+ * The same holds for hx_search_i8, hx_h1_local and the hybrid entries; the _async entries and hx_h1_local_async count
+ * such a batch's queries as not final (the caller's redo through the synchronous entry then fails), and
+ * hx_h1_nominate_async sends the batch flagged.  prefix = 0 searches the full vector.  Output: keys
  * [B x limit] + counts[B].  Synchronises `stream` (exactness certificate). */
 int hx_search_dense(hx_index* h, const float* q_dev, int32_t B, int32_t prefix, int32_t limit,
                     uint64_t* keys_dev, int32_t* counts_dev, void* stream);

@@ -356,10 +356,11 @@ SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
 
 
-def hybrid_tree(ix: OracleIndex, q_raw, q_sp_idx, q_sp_val, params: dict):
+def hybrid_tree(ix: OracleIndex, q_raw, q_sp_idx, q_sp_val, params: dict, rrf_k=None, rank_base=None, rrf_limit=None):
     """The reference query (qdrant_handler.py:305-372), every stage exhaustive
     ("exact" mode).  Returns (scores, ids): <= final_limit points scored by the
-    root stage's full-D dense cosine."""
+    root stage's full-D dense cosine.  rrf_k / rank_base / rrf_limit: the fusion
+    settings of hx_params (None = RRF_K, RRF_RANK_BASE, PREFETCH_DEFAULT_LIMIT)."""
     m = sorted(ix.msizes)
     limits = [params[f"matryoshka_{d}_limit"] for d in m]
     # matryoshka cascade :305-330
@@ -373,17 +374,18 @@ def hybrid_tree(ix: OracleIndex, q_raw, q_sp_idx, q_sp_val, params: dict):
     # sparse :347-354
     _, cand_s = ix.search_sparse(q_sp_idx, q_sp_val, params["sparse_limit"])
     # RRF :357-360 (no limit => PREFETCH_DEFAULT_LIMIT)
-    _, cand_r = rrf([cand_q, cand_s])
+    _, cand_r = rrf([cand_q, cand_s], limit=rrf_limit, k=rrf_k, rank_base=rank_base)
     # root :363-372 -- union re-scored by dense cosine
     return ix.rescore(q_raw, np.concatenate([cand_a, cand_r]), params["final_limit"])
 
 
-def hybrid_h1(ix: OracleIndex, q_raw, q_sp_idx, q_sp_val, dense_limit=100, sparse_limit=100, limit=10):
+def hybrid_h1(ix: OracleIndex, q_raw, q_sp_idx, q_sp_val, dense_limit=100, sparse_limit=100, limit=10, rrf_k=None,
+              rank_base=None):
     """H1 "simple hybrid" (SURVEY.md §8d): dense top-L (+) sparse top-L -> RRF -> top-10.
     Returned scores are RRF scores."""
     _, cd = ix.search_dense(q_raw, dense_limit)
     _, cs = ix.search_sparse(q_sp_idx, q_sp_val, sparse_limit)
-    return rrf([cd, cs], limit=limit)
+    return rrf([cd, cs], limit=limit, k=rrf_k, rank_base=rank_base)
 
 
 # ----------------------------------------------------------------------------

@@ -93,7 +93,7 @@ enum WsSlot {
   WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
-  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB
+  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD
 };
 
 template <typename T>
@@ -319,9 +319,11 @@ struct ProfScope {
   }
 };
 
-static void prep_rows_device(hx_index* h, const float* raw_dev, int64_t n, hipStream_t st) {
+// nonfinite (optional, device): set to 1 when a row holds a NaN or +-Inf element (rows_check_begin / rows_check_end)
+static void prep_rows_device(hx_index* h, const float* raw_dev, int64_t n, hipStream_t st, int* nonfinite = nullptr) {
   PrepRowsArgs a{};
   a.raw = raw_dev;
+  a.nonfinite = nonfinite;
   a.dim = h->dim;
   a.dim_pad = h->dim_pad;
   a.n = n;
@@ -891,19 +893,30 @@ static int* host_pin(hx_index* h) {
   return h->pin;
 }
 
+// A dense query with a NaN or +-Inf element is an error.  The stage's query preparation counts such
+// queries in nfail[1]; the host reads that word with the failure count, at the stage's one round trip.
+static void refuse_nonfinite_queries(hx_index* h, int nbad) {
+  if (nbad == 0) return;
+  h->sp_sum_pending = false;            // the batch is abandoned: a sparse summary read along belongs to nobody
+  h->sp_sum_fetched = false;
+  throw Error("dense query values must be finite");
+}
+
+// nfail: [0] queries to redo, [1] queries with a non-finite element (refused)
 static std::vector<int> read_failures(hx_index* h, int* fail, int* nfail, int B, hipStream_t st) {
   int* pin = host_pin(h);
-  HX_HIP(hipMemcpyAsync(pin, nfail, 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(pin + 4, nfail, 8, hipMemcpyDeviceToHost, st));
   // a sparse stage enqueued before this point (search_dense's `between`): its summary rides along
   const bool take_sparse = h->sp_sum_pending && !h->sp_sum_fetched;
   if (take_sparse) HX_HIP(hipMemcpyAsync(pin + 1, h->ws.get(WS_SP_SUM, 8), 8, hipMemcpyDeviceToHost, st));
   HX_HIP(hipStreamSynchronize(st));
-  const int nf = pin[0];
+  const int nf = pin[4];
   if (take_sparse) {
     h->sp_sum[0] = pin[1];
     h->sp_sum[1] = pin[2];
     h->sp_sum_fetched = true;
   }
+  refuse_nonfinite_queries(h, pin[5]);
   std::vector<int> sel;
   if (nf > 0) {
     std::vector<int> f((size_t)B);
@@ -968,9 +981,16 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
   const int Bpad = (int)round_up(B, bn);
   float* qn = (float*)h->ws.get(WS_QN + wo, (size_t)B * m.dpad * 4);
   _Float16* qh = (_Float16*)h->ws.get(WS_QH + wo, (size_t)Bpad * m.dpad * 2);
-  launch_prep_queries_f(q_dev, h->dim, B, Bpad, m.d, m.dpad, qn, qh, st);
   int* fail = (int*)h->ws.get(WS_FAIL + wo, (size_t)B * 4);
-  int* nfail = (int*)h->ws.get(WS_NFAIL + wo, 4);
+  int* nfail = (int*)h->ws.get(WS_NFAIL + wo, 8);   // read_failures: [0] queries to redo, [1] non-finite queries
+  // the preparation counts queries with a non-finite element: into nfail[1] (refused at the round trip), or -- deferred --
+  // into the word of queries whose lists are not final (the caller redoes the batch synchronously, and it is refused there)
+  int* qbad = flag_acc;
+  if (!(defer && flag_acc)) {
+    HX_HIP(hipMemsetAsync(nfail, 0, 8, st));
+    qbad = defer ? nfail : nfail + 1;
+  }
+  launch_prep_queries_f(q_dev, h->dim, B, Bpad, m.d, m.dpad, qn, qh, st, level == 0 ? qbad : nullptr);
   std::vector<int> sel;
   // The candidate pass of the full-vector stage runs on the int8 matrix pipe (half the bytes, twice the rate of
   // fp16) when the index holds the scaled int8 copy; a query it cannot certify is retried through the fp16 scan
@@ -1027,8 +1047,7 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
     r.max_cnt = g.Lp;       // chunked_scan's last compaction keeps at most L' keys
     r.B = B;
     r.out = cand2;
-    if (defer && flag_acc) nfail = flag_acc;
-    else HX_HIP(hipMemsetAsync(nfail, 0, 4, st));
+    if (defer && flag_acc) nfail = flag_acc;   // (otherwise zeroed before the preparation)
     // re-score + top-L + certificate in one launch (select.hip: k_dense_finish) when the lists fit a wave's registers
     unsigned int* done = (unsigned int*)h->ws.get(WS_DONE + wo, (size_t)B * 4);
     if (h->done_zeroed[level > 0] < B) {              // the kernel leaves its counters at zero: cleared once per growth
@@ -1076,6 +1095,10 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
       launch_fill_i32(flag_acc ? flag_acc : nfail, 1, B, st);
       return false;
     }
+    int* pin = host_pin(h);              // (the exact path synchronises anyway)
+    HX_HIP(hipMemcpyAsync(pin + 5, nfail + 1, 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    refuse_nonfinite_queries(h, pin[5]);
   }
   if (!sel.empty()) {
     h->dense_fallbacks += (int64_t)sel.size();
@@ -1096,21 +1119,22 @@ static void search_i8(hx_index* h, const float* q_dev, int B, int L, uint64_t* o
   const int Bpad = (int)round_up(B, bn);
   int8_t* q8 = (int8_t*)h->ws.get(WS_Q8 + wo, (size_t)Bpad * h->dim_pad8);
   float* rq = (float*)h->ws.get(WS_RINVQ + wo, (size_t)Bpad * 4);
-  launch_prep_queries_i8(q_dev, h->dim, B, Bpad, h->dim_pad8, q8, rq, st);
+  int* fail = (int*)h->ws.get(WS_FAIL + wo, (size_t)B * 4);
+  int* nfail = (int*)h->ws.get(WS_NFAIL + wo, 8);   // as search_dense: [0] queries to redo, [1] non-finite queries
+  if (!flag_acc) HX_HIP(hipMemsetAsync(nfail, 0, 8, st));
+  launch_prep_queries_i8(q_dev, h->dim, B, Bpad, h->dim_pad8, q8, rq, st,
+                         level > 0 ? nullptr : (flag_acc ? flag_acc : nfail + 1));
   const Geometry g = geometry(L, false, level > 0, false, 0, B <= 32);
   uint64_t* cand = (uint64_t*)h->ws.get(WS_CAND + wo, (size_t)B * g.C * 8);
   int* cnt = (int*)h->ws.get(WS_CNT + wo, (size_t)B * 4);
   int* ovf = (int*)h->ws.get(WS_OVF + wo, (size_t)B * 4);
   float* tau = (float*)h->ws.get(WS_TAU + wo, (size_t)B * 4);
-  int* fail = (int*)h->ws.get(WS_FAIL + wo, (size_t)B * 4);
-  int* nfail = (int*)h->ws.get(WS_NFAIL + wo, 4);
   if (h->mv.on) mv_need(h, MV_Q8, st);
   chunked_scan(h, KIND_I8, (const uint8_t*)(h->mv.on ? h->mv.q8 : h->q8), (const uint8_t*)q8, h->dim_pad8, B, bn, g, cand,
                cnt, ovf, tau, rq, st);
   // the scan's scores are already exact: the list is final unless a buffer overflowed
   launch_compact(cand, g.C, cnt, B, L, 0, out_keys, L, out_cnt, nullptr, g.Lp, st);
-  if (flag_acc) nfail = flag_acc;
-  else HX_HIP(hipMemsetAsync(nfail, 0, 4, st));
+  if (flag_acc) nfail = flag_acc;   // (otherwise zeroed before the preparation)
   launch_certify(cand, g.C, cnt, std::numeric_limits<int>::max(), out_keys, L, out_cnt, L, ovf, 0.f, B,
                  fail, nfail, st);
   // a pre-filtered scan's list (its scores are final): view rows -> this index's rows
@@ -1684,15 +1708,15 @@ static void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
       HX_HIP(hipMemcpyAsync(pin + 1, w.get(WS_SP_SUM, 8), 8, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     const bool redo = (pin[0] | pin[1] | pin[2]) != 0;
+    // some list is not final: the batch again, every stage resolving its own flags.  A batch the synchronous stages
+    // refuse (a non-finite query value) throws here, before the guard below counts it: it says nothing of the collection
+    if (redo) hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st, true);
     // the guard: 4 redone batches within a window of 16 and the tree stops speculating on this collection
     h->tree_win_n += 1;
     h->tree_win_redone += redo ? 1 : 0;
     if (h->tree_win_redone >= 4) h->tree_spec_off = true;
     if (h->tree_win_n >= 16) h->tree_win_n = h->tree_win_redone = 0;
-    if (redo) {      // some list is not final: the batch again, every stage resolving its own flags
-      h->tree_redone += 1;
-      hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st, true);
-    }
+    h->tree_redone += redo ? 1 : 0;
   }
 }
 
@@ -1766,9 +1790,20 @@ static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
   hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
 }
 
+// RRF settings: k finite and positive with 2 / k finite -- a document's two contributions
+// 1 / (f32(rank + rank_base) + k), each at most 1 / k, then sum to a finite positive score -- and 0 <= rank_base <= 2^30,
+// so that rank + rank_base (rank < CAND_CAP) stays far inside int32.
+constexpr int RRF_RANK_BASE_MAX = 1 << 30;
+static void check_rrf(float k, int rank_base) {
+  HX_CHECK(std::isfinite(k) && k > 0.0f && std::isfinite((float)(2.0 / (double)k)),
+           "rrf_k must be finite and positive, with 2 / rrf_k finite");
+  HX_CHECK(rank_base >= 0 && rank_base <= RRF_RANK_BASE_MAX, "rrf_rank_base must be in [0, 2^30]");
+}
+
 static void check_params(const hx_params* p) {
   HX_CHECK(p != nullptr, "params is NULL");
   HX_CHECK(p->mode == HX_MODE_TREE || p->mode == HX_MODE_H1, "unknown mode");
+  check_rrf(p->rrf_k, p->rrf_rank_base);
   auto ok = [](int v) { return v >= 1 && v <= MAX_LIMIT; };
   HX_CHECK(ok(p->dense_limit) && ok(p->sparse_limit) && ok(p->final_limit), "limit out of range [1, 2048]");
   if (p->mode == HX_MODE_TREE) {
@@ -1882,6 +1917,28 @@ int hx_reserve(hx_index* h, int64_t n_rows, int64_t nnz) {
 }
 
 // ---- ingest (store_document_vectors -> upsert, qdrant_handler.py:120-198) -----------------------------
+// Dense rows must be finite.  Word [0] of WS_ROWS_CHECK is the batch's flag (k_prep_rows raises it
+// for a row with a NaN or +-Inf element), word [1] the largest row quantisation error before the batch: a refused batch
+// restores it, so that it leaves the certificates of later queries as they were.  The flag reaches the host in pin[12],
+// copied behind the batch's last launch and read after the synchronisation the ingest makes anyway.
+static int* rows_check_begin(hx_index* h, hipStream_t st) {
+  int* w = (int*)h->ws.get(WS_ROWS_CHECK, 8);
+  HX_HIP(hipMemsetAsync(w, 0, 4, st));
+  if (h->s8_err) HX_HIP(hipMemcpyAsync(w + 1, h->s8_err, 4, hipMemcpyDeviceToDevice, st));
+  return w;
+}
+static void rows_check_fetch(hx_index* h, int* w, hipStream_t st) {
+  HX_HIP(hipMemcpyAsync(host_pin(h) + 12, w, 4, hipMemcpyDeviceToHost, st));
+}
+static void rows_check_end(hx_index* h, int* w, hipStream_t st) {   // (after the stream is synchronised)
+  if (host_pin(h)[12] == 0) return;
+  if (h->s8_err) {
+    HX_HIP(hipMemcpyAsync(h->s8_err, w + 1, 4, hipMemcpyDeviceToDevice, st));
+    HX_HIP(hipStreamSynchronize(st));
+  }
+  throw Error("dense values must be finite: a row holds a NaN or an infinity");
+}
+
 static void add_dense_host(hx_index* h, const float* rows_host, int64_t n) {
   HX_CHECK(n >= 0, "n < 0");
   if (n == 0) return;
@@ -1894,13 +1951,16 @@ static void add_dense_host(hx_index* h, const float* rows_host, int64_t n) {
   float* raw = (float*)h->ws.get(WS_RAW, (size_t)std::min(n, CH) * h->dim * 4);
   const int64_t n_before = h->n;
   try {
+    int* chk = rows_check_begin(h, nullptr);
     for (int64_t r0 = 0; r0 < n; r0 += CH) {
       const int64_t m = std::min(CH, n - r0);
       HX_HIP(hipMemcpy(raw, rows_host + r0 * h->dim, (size_t)m * h->dim * 4, hipMemcpyHostToDevice));
-      prep_rows_device(h, raw, m, nullptr);
+      prep_rows_device(h, raw, m, nullptr, chk);
+      if (r0 + m >= n) rows_check_fetch(h, chk, nullptr);
       HX_HIP(hipStreamSynchronize(nullptr));
       h->n += m;
     }
+    rows_check_end(h, chk, nullptr);
   } catch (...) {
     h->n = n_before;   // all or nothing
     throw;
@@ -1921,12 +1981,15 @@ static void add_dense_dev(hx_index* h, const float* rows_dev, int64_t n, hipStre
   const int64_t CH = 65536;
   const int64_t n_before = h->n;
   try {
+    int* chk = rows_check_begin(h, st);
     for (int64_t r0 = 0; r0 < n; r0 += CH) {
       const int64_t m = std::min(CH, n - r0);
-      prep_rows_device(h, rows_dev + r0 * h->dim, m, st);
+      prep_rows_device(h, rows_dev + r0 * h->dim, m, st, chk);
       h->n += m;
     }
+    rows_check_fetch(h, chk, st);
     HX_HIP(hipStreamSynchronize(st));
+    rows_check_end(h, chk, st);
   } catch (...) {
     h->n = n_before;   // all or nothing
     throw;
@@ -2310,6 +2373,7 @@ int hx_rrf(int32_t device, const uint64_t* a, int32_t as, const int32_t* ac, con
            int32_t* counts_dev, void* stream) {
   HX_TRY
   HX_CHECK(a && ac && b && bc && keys_dev && counts_dev && B > 0, "bad argument");
+  check_rrf(rrf_k, rank_base);
   HX_HIP(hipSetDevice(device));
   rrf(nullptr, a, as, ac, b, bs, bc, B, rrf_k, rank_base, limit, keys_dev, counts_dev, (hipStream_t)stream,
       static_ws(device));
@@ -2394,6 +2458,7 @@ int hx_h1_fuse(int32_t device, const uint64_t* gathered, int32_t world, int32_t 
   HX_CHECK(dense_limit >= 1 && sparse_limit >= 1 && (int64_t)world * std::max(dense_limit, sparse_limit) <= CAND_CAP,
            "h1_fuse: world x limit out of range [1, 8192]");
   HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "limit out of range [1, 2048]");
+  check_rrf(rrf_k, rank_base);
   HX_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   Workspace& w = static_ws(device);
@@ -2520,7 +2585,7 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
   if (forked) HX_HIP(hipEventRecord(h->ev_join, h->st2));
   // ---- dense: the shard's best k1 rows by the int8 candidate score (no exact score here)
   uint64_t* cand = nullptr;
-  int *cnt = nullptr, *ovf = nullptr;
+  int *cnt = nullptr, *ovf = nullptr, *qbad = nullptr;
   float* eq = nullptr;
   int cstride = 0;
   if (h->n > 0 && use8) {
@@ -2528,7 +2593,9 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
     const int bn = scan_bn(h, B);
     const int Bpad = (int)round_up(B, bn);
     float* qn = (float*)w.get(WS_QN, (size_t)B * m.dpad * 4);
-    launch_prep_queries_f(qd, h->dim, B, B, m.d, m.dpad, qn, nullptr, st);
+    qbad = (int*)w.get(WS_NOM_QBAD, 4);              // queries with a non-finite element: the batch goes out flagged
+    HX_HIP(hipMemsetAsync(qbad, 0, 4, st));
+    launch_prep_queries_f(qd, h->dim, B, B, m.d, m.dpad, qn, nullptr, st, qbad);
     cand = (uint64_t*)w.get(WS_CAND, (size_t)B * g.C * 8);
     cnt = (int*)w.get(WS_CNT, (size_t)B * 4);
     ovf = (int*)w.get(WS_OVF, (size_t)B * 4);
@@ -2557,7 +2624,7 @@ int hx_h1_nominate_async(hx_index* h, const float* qd, const int64_t* qip, const
   HX_CHECK(!sl.list || sl.lout == lout, "sparse list stride");
   const int complete = (h->n == 0 || (use8 && h->n <= k1)) ? 1 : 0;   // the list holds every row the shard has
   launch_h1x_pack(cand, cstride, cnt, ovf, eq, complete, k1, sl.list, sl.lout, sl.lcnt, sl.flag, sl.fail, k2, lout,
-                  std::max(h->sp_wmax, h->sp_wmax_shared), B, nom_dev, st);
+                  std::max(h->sp_wmax, h->sp_wmax_shared), B, nom_dev, st, qbad);
   HX_CATCH
 }
 
@@ -2666,6 +2733,7 @@ int hx_h1_finish(int32_t device, const uint64_t* reduced_dev, int32_t world, int
                (int64_t)world * k3 <= CAND_CAP,
            "limits out of range");
   HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "limit out of range [1, 2048]");
+  check_rrf(rrf_k, rank_base);
   HX_HIP(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   Workspace& w = static_ws(device);

@@ -162,7 +162,7 @@ void launch_remap_ids(const uint64_t* in, uint64_t* out, int64_t n, const uint32
 // ---- shardx.hip: row-sharded H1, candidates exchanged before the exact scores ----------------
 void launch_h1x_pack(const uint64_t* cand, int cstride, const int* cnt, const int* ovf, const float* eps, int complete,
                      int k1, const uint64_t* list, int lstride, const int* lcnt, const int* sflag, const int* sfail, int k2,
-                     int lout, float wmax, int B, uint64_t* nom, hipStream_t st);
+                     int lout, float wmax, int B, uint64_t* nom, hipStream_t st, const int* qbad = nullptr);
 void launch_h1x_union(const uint64_t* g, int world, int B, int k1, int k2, uint64_t* du, uint64_t* su, hipStream_t st);
 void launch_h1x_cuts(const uint64_t* g, int world, int B, int k1, int k2, const uint64_t* G, const int* gc, int lp,
                      const uint64_t* ST, const int* sc, int L_s, const int64_t* q_indptr, uint64_t* meta, uint32_t* thr_out,
@@ -193,6 +193,7 @@ struct PrepRowsArgs {
   int8_t* q8s;             // [n x dim_pad8]
   float* q8s_scale;        // [n]
   uint32_t* err_max;       // one device word
+  int* nonfinite;          // one device word (may be NULL): set to 1 when a row holds a NaN or +-Inf element
 };
 void launch_prep_rows(const PrepRowsArgs& a, hipStream_t st);
 void launch_requant_rows(const float* dense, int dim_pad, int dim_pad8, int64_t n, int8_t* q8s, float* scale,
@@ -207,10 +208,11 @@ void launch_synth_dense(float* raw, int64_t row0_global, int64_t n, int dim, uin
 
 // Prepare a query batch for one named vector: normalised fp32 [B x dpad] (+ fp16
 // zero-padded to Bpad rows) from raw q[:, :d]; or the int8 copy + rinv.
+// bad (optional, device): += the number of queries with a NaN or +-Inf among their q_dim raw elements.
 void launch_prep_queries_f(const float* q_raw, int q_dim, int B, int Bpad, int d, int dpad,
-                           float* qn, _Float16* qh, hipStream_t st);
+                           float* qn, _Float16* qh, hipStream_t st, int* bad = nullptr);
 void launch_prep_queries_i8(const float* q_raw, int q_dim, int B, int Bpad, int dpad8, int8_t* q8,
-                            float* rinv_q, hipStream_t st);
+                            float* rinv_q, hipStream_t st, int* bad = nullptr);
 
 // ---- sparse2.hip / sprescore.hip ------------------------------------------------
 // K7 in two passes (DESIGN.md "sparse stage"):

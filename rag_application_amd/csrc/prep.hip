@@ -110,6 +110,11 @@ __global__ __launch_bounds__(256) void k_prep_rows(PrepRowsArgs a) {
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) vmax = __builtin_fmaxf(vmax, __shfl_xor(vmax, off, 64));
+  // A row with a NaN or +-Inf element is refused: the batch's word is raised, the host reads it
+  // once the batch is derived and rolls the batch back (every row stores the same value: no atomic).  The two sums
+  // tell: a NaN element makes len^2 NaN (fmaxf drops it from vmax), an infinite one makes vmax Inf; a finite row's
+  // len^2 is a sum of non-negative squares -- never NaN, +Inf when it overflows (such a row is valid: a zero row).
+  if (lane == 0 && a.nonfinite && (!(len2[0] == len2[0]) || !(vmax <= 3.40282347e38f))) *a.nonfinite = 1;
   bool keep[4];
   float ln[4];
 #pragma unroll
@@ -271,8 +276,15 @@ void launch_synth_dense(float* raw, int64_t row0_global, int64_t n, int dim, uin
 }
 
 // queries: normalised first d elements of each raw query -> fp32 [B x dpad], fp16 [Bpad x dpad]
+// raw query `src` has a NaN or +-Inf element among its q_dim: one more query counted in *bad (one wave per query)
+__device__ __forceinline__ void count_nonfinite_query(const float* src, int q_dim, int lane, int* bad) {
+  bool nf = false;
+  for (int c = lane; c < q_dim; c += 64) nf = nf || !(__builtin_fabsf(src[c]) <= 3.40282347e38f);
+  if (__ballot(nf) != 0 && lane == 0) atomicAdd(bad, 1);
+}
+
 __global__ __launch_bounds__(256) void k_prep_queries_f(const float* q_raw, int q_dim, int B, int Bpad,
-                                                        int d, int dpad, float* qn, _Float16* qh) {
+                                                        int d, int dpad, float* qn, _Float16* qh, int* bad) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= Bpad) return;
@@ -286,6 +298,7 @@ __global__ __launch_bounds__(256) void k_prep_queries_f(const float* q_raw, int 
   // run-time chunk count, which hipcc kept in scratch (272 B per lane; the same pattern k_prep_rows lost in round 3).
   // Lane l accumulates the squares of elements 64 j + l for ascending j: spec_dot's order.
   const float* src = q_raw + (int64_t)b * q_dim;
+  if (bad) count_nonfinite_query(src, q_dim, lane, bad);   // (every element, also those past a prefix stage's d)
   float p = 0.0f;
   for (int j = 0; j < nch; ++j) {
     const int c = (j << 6) + lane;
@@ -307,19 +320,20 @@ __global__ __launch_bounds__(256) void k_prep_queries_f(const float* q_raw, int 
   }
 }
 void launch_prep_queries_f(const float* q_raw, int q_dim, int B, int Bpad, int d, int dpad, float* qn,
-                           _Float16* qh, hipStream_t st) {
+                           _Float16* qh, hipStream_t st, int* bad) {
   if (Bpad <= 0) return;
   HX_CHECK(dpad <= MAXCH * 64, "dim > 4096 unsupported");
   hipLaunchKernelGGL(k_prep_queries_f, dim3((Bpad + 3) / 4), dim3(256), 0, st, q_raw, q_dim, B, Bpad, d,
-                     dpad, qn, qh);
+                     dpad, qn, qh, bad);
   HX_HIP(hipGetLastError());
 }
 
 __global__ __launch_bounds__(256) void k_prep_queries_i8(const float* q_raw, int q_dim, int B, int Bpad,
-                                                         int dpad8, int8_t* q8, float* rinv_q) {
+                                                         int dpad8, int8_t* q8, float* rinv_q, int* bad) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= Bpad) return;
+  if (bad && b < B) count_nonfinite_query(q_raw + (int64_t)b * q_dim, q_dim, lane, bad);
   int n2 = 0;
   for (int c = lane; c < dpad8; c += 64) {
     const int8_t t = (b < B && c < q_dim) ? quant_i8(q_raw[(int64_t)b * q_dim + c]) : (int8_t)0;
@@ -331,10 +345,10 @@ __global__ __launch_bounds__(256) void k_prep_queries_i8(const float* q_raw, int
   if (lane == 0) rinv_q[b] = n2 > 0 ? (float)(1.0 / sqrt((double)n2)) : 0.0f;
 }
 void launch_prep_queries_i8(const float* q_raw, int q_dim, int B, int Bpad, int dpad8, int8_t* q8,
-                            float* rinv_q, hipStream_t st) {
+                            float* rinv_q, hipStream_t st, int* bad) {
   if (Bpad <= 0) return;
   hipLaunchKernelGGL(k_prep_queries_i8, dim3((Bpad + 3) / 4), dim3(256), 0, st, q_raw, q_dim, B, Bpad,
-                     dpad8, q8, rinv_q);
+                     dpad8, q8, rinv_q, bad);
   HX_HIP(hipGetLastError());
 }
 

@@ -35,7 +35,7 @@ namespace hx {
 __global__ __launch_bounds__(256) void k_h1x_pack(const uint64_t* cand, int cstride, const int* cnt, const int* ovf,
                                                   const float* eps, int complete, int k1, const uint64_t* list,
                                                   int lstride, const int* lcnt, const int* sflag, const int* sfail, int k2,
-                                                  int lout, float wmax, int B, uint64_t* nom) {
+                                                  int lout, float wmax, int B, uint64_t* nom, const int* qbad) {
   const int b = blockIdx.x;
   uint64_t* d = nom + (int64_t)b * k1;
   uint64_t* s = nom + (int64_t)B * k1 + (int64_t)b * k2;
@@ -52,7 +52,9 @@ __global__ __launch_bounds__(256) void k_h1x_pack(const uint64_t* cand, int cstr
   const int npl = ns < lout ? ns : lout;
   for (int j = threadIdx.x; j < npl; j += 256) pl[j] = list[(int64_t)b * lstride + j];
   if (threadIdx.x == 0) {
-    const uint32_t df = ((cand && ovf[b]) ? 1u : 0u) | (complete ? 2u : 0u);
+    // a batch holding a non-finite dense query (counted in *qbad by the preparation) is flagged as a whole: every rank then
+    // redoes it through hx_h1_local, which refuses it
+    const uint32_t df = (((cand && ovf[b]) || (qbad && *qbad != 0)) ? 1u : 0u) | (complete ? 2u : 0u);
     m[0] = (uint64_t)(cand ? __builtin_bit_cast(uint32_t, eps[b]) : 0u) | ((uint64_t)df << 32);
     const uint32_t sf = (list && (sflag[b] != 0 || sfail[b] != 0 || ns > lout)) ? 1u : 0u;
     m[1] = (uint64_t)((uint32_t)ns & 0x7FFFFFFFu) | ((uint64_t)sf << 31) | ((uint64_t)__builtin_bit_cast(uint32_t, wmax) << 32);
@@ -61,10 +63,10 @@ __global__ __launch_bounds__(256) void k_h1x_pack(const uint64_t* cand, int cstr
 }
 void launch_h1x_pack(const uint64_t* cand, int cstride, const int* cnt, const int* ovf, const float* eps, int complete,
                      int k1, const uint64_t* list, int lstride, const int* lcnt, const int* sflag, const int* sfail, int k2,
-                     int lout, float wmax, int B, uint64_t* nom, hipStream_t st) {
+                     int lout, float wmax, int B, uint64_t* nom, hipStream_t st, const int* qbad) {
   if (B <= 0) return;
   hipLaunchKernelGGL(k_h1x_pack, dim3(B), dim3(256), 0, st, cand, cstride, cnt, ovf, eps, complete, k1, list, lstride,
-                     lcnt, sflag, sfail, k2, lout, wmax, B, nom);
+                     lcnt, sflag, sfail, k2, lout, wmax, B, nom, qbad);
   HX_HIP(hipGetLastError());
 }
 

@@ -355,7 +355,10 @@ class H1Pipeline:
             self.redone += 1
             # (the same decision on every rank: the flag words are the same.)  Only a batch that went out with the shares
             # in force NOW says anything about them: batches verified late had the narrower ones of before
-            if self.cf and shares is not None and shares[:2] + shares[3:] == (self.k1, self.k2, self.k3):
+            # A batch holding a non-finite dense query (flagged by the nomination, refused by the redo) says nothing about
+            # them either -- decided from the query batch, which every rank holds alike (a rank's own error is not).
+            valid = bool(torch.isfinite(inputs[0]).all())
+            if self.cf and valid and shares is not None and shares[:2] + shares[3:] == (self.k1, self.k2, self.k3):
                 if self.k1 >= self.k1max and self.k2 >= self.k2max and self.k3 >= self.k3max:
                     self.cf = False     # full-length lists were still not enough: the per-shard exchange from here on
                 self.k1, self.k2 = min(2 * self.k1, self.k1max), min(2 * self.k2, self.k2max)

@@ -96,6 +96,25 @@ def check_sparse_rows(indptr: np.ndarray, idx: np.ndarray, val: np.ndarray) -> N
         raise ValueError("sparse indices must be unique within a vector")
 
 
+def check_dense_rows(dense) -> None:
+    """What hx_add_rows checks of the dense rows (engine.hip: k_prep_rows), on the front rank BEFORE a batch is
+    announced: every element finite (a row holding a NaN or an infinity is refused)."""
+    if not np.isfinite(np.asarray(dense, np.float32)).all():
+        raise ValueError("dense values must be finite: a row holds a NaN or an infinity")
+
+
+def check_rrf(rrf_k: float, rank_base: int) -> None:
+    """What check_params (engine.hip) accepts of the RRF settings, on the front rank: rrf_k finite and positive with
+    2 / rrf_k finite in fp32, 0 <= rrf_rank_base <= 2^30."""
+    k = np.float32(rrf_k)
+    with np.errstate(divide="ignore", over="ignore"):
+        two_over_k = np.float32(2.0 / np.float64(k)) if k > 0 else np.float32(np.inf)
+    if not (np.isfinite(k) and k > 0 and np.isfinite(two_over_k)):
+        raise ValueError("rrf_k must be finite and positive, with 2 / rrf_k finite")
+    if not 0 <= int(rank_base) <= 2 ** 30:
+        raise ValueError("rrf_rank_base must be in [0, 2^30]")
+
+
 def bcast_queries(q, q_indptr, q_idx, q_val, src: int = 0, group=None, device: Optional[torch.device] = None,
                   header_group=None):
     """C2: the query batch from `src` to every rank.  A 3-word header (B, D, nnz), then ONE broadcast of a packed
@@ -206,6 +225,8 @@ class ShardedCollection:
                 n = len(texts) if texts is not None else int(np.asarray(dense).shape[0])
                 if texts is None and np.asarray(dense).shape[1:] != (self.dim,):
                     raise ValueError(f"Dense vector dimension mismatch. Expected {self.dim}, got {np.asarray(dense).shape[-1]}")
+                if texts is None:
+                    check_dense_rows(dense)
                 if sp_indptr is not None:
                     check_sparse_rows(sp_indptr, sp_idx, sp_val)
                     if len(sp_indptr) != n + 1:
@@ -323,6 +344,9 @@ class ShardedCollection:
                     int(params[k])
                 if mode not in ("tree", "h1"):
                     raise ValueError("mode must be 'tree' or 'h1'")
+                if not torch.isfinite(q).all():
+                    raise ValueError("dense query values must be finite")
+                check_rrf(float(rrf_k), int(rank_base))
                 head = (params, mode, rrf_k, rank_base, rrf_limit)
             except Exception as e:
                 head = ("refused", f"{type(e).__name__}: {e}")
@@ -395,6 +419,7 @@ class _ShardedBackend:
         dense = np.ascontiguousarray(dense, np.float32)
         if dense.ndim != 2 or dense.shape[1] != self.col.dim:
             raise ValueError(f"Dense vector dimension mismatch. Expected {self.col.dim}, got {dense.shape[-1]}")
+        check_dense_rows(dense)
         if sp_indptr is not None:
             check_sparse_rows(sp_indptr, sp_idx, sp_val)
         self.h._command("store", self.user)
@@ -407,6 +432,9 @@ class _ShardedBackend:
         q_idx, q_val = np.asarray(q_idx, np.int64), np.asarray(q_val, np.float32)
         if (q_idx < 0).any() or (q_idx >= 2 ** 31).any() or not np.isfinite(q_val).all():
             raise ValueError("sparse query: indices in [0, 2^31), finite values")
+        if not np.isfinite(q).all():
+            raise ValueError("dense query values must be finite")
+        check_rrf(float(hp.rrf_k), int(hp.rrf_rank_base))
         rows = np.repeat(np.arange(q_indptr.size - 1), np.diff(q_indptr))
         o = np.lexsort((q_idx, rows))
         q_idx, q_val = q_idx[o], q_val[o]

@@ -309,3 +309,93 @@ def test_scout_post_filter_and_stable_merge():
     got1 = O.scout_search(spaces, q, 1, "u", "o")
     assert [(s, r) for s, r, _ in got1] == [("relationship", 0)]
     assert O.scout_search(spaces, q, 0, "u", "o") == got1          # limit = max(1, top_k)
+
+
+# ---------------------------------------------------------------------------- RRF settings
+RRF_KS = (0.25, 1.0, 2.0, 60.0)
+RANK_BASES = (0, 1, 7)
+
+
+def _rrf_term(r, k, base):
+    return np.float32(1.0) / (np.float32(r + base) + np.float32(k))
+
+
+@pytest.mark.parametrize("k", RRF_KS)
+@pytest.mark.parametrize("base", RANK_BASES)
+def test_rrf_settings_numpy_equals_c(k, base):
+    """oracle.rrf and the C restatement ho_rrf agree bit for bit at every rrf_k and rank base the GPU tests use, over
+    random lists that overlap (ids in both lists, in one list only, at every rank) and at every limit."""
+    rng = np.random.default_rng(int(k * 4) * 10 + base)
+    for trial in range(40):
+        na, nb = int(rng.integers(0, 300)), int(rng.integers(0, 300))
+        pool = rng.permutation(700)[:max(na + nb, 1)]
+        a = pool[:na]
+        shared = rng.random(nb) < 0.5                     # about half of b also ranks in a
+        b = np.where(shared & (na > 0), rng.choice(a, nb) if na else 0, pool[na:na + nb])
+        b = np.asarray(list(dict.fromkeys(b.tolist())), np.int64)
+        for limit in (1, 10, 600):
+            s, i = O.rrf([a, b], limit=limit, k=k, rank_base=base)
+            cs, ci = CO.rrf(a, b, k, base, limit)
+            assert i.tolist() == ci.tolist(), (trial, limit)
+            np.testing.assert_array_equal(bits(cs), bits(s))
+            assert len(i) == min(limit, len(set(a.tolist()) | set(b.tolist())))
+
+
+def test_rrf_unrelated_rank_pairs_tie_at_k60():
+    """At k = 60 the sums of two UNRELATED rank pairs (not one pair swapped) round to the same fp32 value: the ids then
+    rank by the tie rule, id ascending.  The pairs are found by search over ranks below 200."""
+    k = 60.0
+    r = np.arange(200)
+    t = np.array([_rrf_term(x, k, 0) for x in r], np.float32)
+    s = (np.float32(0.0) + t[:, None]).astype(np.float32) + t[None, :]          # s[i, j]: rank i in a, rank j in b
+    found = None
+    seen = {}
+    for i in range(200):
+        for j in range(200):
+            key = s[i, j].view(np.uint32).item()
+            for (i2, j2) in seen.get(key, ()):
+                if {i, j} != {i2, j2} and len({i, i2}) == 2 and len({j, j2}) == 2:
+                    found = (i2, j2, i, j)
+                    break
+            if found:
+                break
+            seen.setdefault(key, []).append((i, j))
+        if found:
+            break
+    assert found is not None, "no unrelated rank pairs tie at k = 60"
+    i1, j1, i2, j2 = found
+    # id 900 at (i1, j1), id 100 at (i2, j2): equal scores, id 100 first; fillers take the other ranks
+    n = max(i1, i2, j1, j2) + 1
+    a = np.arange(1000, 1000 + n, dtype=np.int64)
+    b = np.arange(2000, 2000 + n, dtype=np.int64)
+    a[i1], b[j1] = 900, 900
+    a[i2], b[j2] = 100, 100
+    for sc, ids in (O.rrf([a, b], limit=4 * n, k=k), CO.rrf(a, b, k, 0, 4 * n)):
+        p900, p100 = ids.tolist().index(900), ids.tolist().index(100)
+        assert sc[p900].view(np.uint32) == sc[p100].view(np.uint32)
+        assert p100 == p900 - 1, (found, p100, p900)
+
+
+def test_hybrid_oracles_take_the_fusion_settings(synth_tables):
+    """hybrid_tree / hybrid_h1 pass rrf_k, rank_base and rrf_limit through; the defaults are today's (2.0, 0, 10)."""
+    n, dim = 1200, 256
+    X = O.synth_dense(O.SEED_CORPUS, 0, n, dim)
+    ip, si, sv = O.synth_sparse_docs(O.SEED_SPDOC, 0, n, synth_tables)
+    ora = O.OracleIndex(dim, (64, 128, 256))
+    ora.add(X, ip, si, sv)
+    ora.finalize()
+    q = O.synth_dense(O.SEED_QUERY, 0, 1, dim)[0]
+    qip, qsi, qsv = O.synth_sparse_queries(O.SEED_SPQUERY, 0, 1, synth_tables)
+    P = dict(P_MCP, final_limit=60)
+    base = O.hybrid_tree(ora, q, qsi, qsv, P)
+    same = O.hybrid_tree(ora, q, qsi, qsv, P, rrf_k=2.0, rank_base=0, rrf_limit=10)
+    assert base[1].tolist() == same[1].tolist()
+    wide = O.hybrid_tree(ora, q, qsi, qsv, P, rrf_k=60.0, rank_base=7, rrf_limit=80)
+    assert len(wide[1]) == 60 and set(base[1].tolist()) != set(wide[1].tolist())
+    h = O.hybrid_h1(ora, q, qsi, qsv, 50, 50, 30)
+    h2 = O.hybrid_h1(ora, q, qsi, qsv, 50, 50, 30, rrf_k=60.0, rank_base=1)
+    _, cd = ora.search_dense(q, 50)
+    _, cs = ora.search_sparse(qsi, qsv, 50)
+    e2 = O.rrf([cd, cs], limit=30, k=60.0, rank_base=1)
+    assert h2[1].tolist() == e2[1].tolist() and bits(h2[0]).tolist() == bits(e2[0]).tolist()
+    assert bits(h[0]).tolist() != bits(h2[0]).tolist()
