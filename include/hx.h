@@ -125,6 +125,24 @@ int hx_set_next_id(hx_index* h, int64_t first_id);
 /* Roll the collection back to its first n_rows rows (dense and sparse): how the shards that stored their slice of
  * a batch undo it when another shard could not (one upsert = one request in the reference, :190-193). */
 int hx_truncate(hx_index* h, int64_t n_rows);
+/* Per-point delete (the reference deletes a file's chunks when its user deletes or re-uploads the file,
+ * IndexerAPI/src/api/v1/endpoints/delete.py): keep only the rows of a mask (same layout as hx_hybrid_query_*_masked: bit
+ * r = local row r, set = kept; mask_rows must equal hx_count).  *n_removed = rows dropped (n_removed may be NULL).
+ * After the call the index is the index one gets by creating a new one and adding the kept rows in their order: row i
+ * is the i-th kept row, its id id_base + i; hx_count / hx_nnz are those of the kept rows; every search entry returns
+ * (ids and fp32 score bits) what that index returns; later hx_add_* calls continue as on it; hx_save / hx_load round-trip
+ * it.  Equivalently: an unmasked call afterwards returns what the masked call with the same mask returned before, ids
+ * mapped to their rank among the kept rows.  Every stored copy and the sparse CSR are compacted on the device, in
+ * place; the inverted index is dropped and rebuilt by the next search or hx_finalize; the sparse
+ * weight range (hx_sparse_wmax) is that of the surviving weights.  Capacities stay as they are.  One figure may differ
+ * from the fresh index's: cand8_row_error_max (hx_stats) keeps covering the removed rows -- an upper bound is all the
+ * certificate needs, as after hx_truncate.
+ * Every row kept: returns 0 with *n_removed = 0, nothing is touched or invalidated, no device work.  No row kept: an
+ * empty index that accepts adds.  Refused before anything moves (the index stays as it was): a NULL index, a NULL mask
+ * with mask_rows > 0, mask_rows != hx_count, sparse vectors pending for rows not added yet, and an index whose ids
+ * were named with hx_set_next_id (a shard of a sharded collection: renumbering is a collective matter).  Synchronises
+ * the device (as hx_truncate) and returns when the compaction is done. */
+int hx_retain_rows(hx_index* h, const uint32_t* keep_host, int64_t mask_rows, int64_t* n_removed);
 /* build the on-device inverted index over everything added so far; searches
  * call it implicitly when the index is stale. */
 int hx_finalize(hx_index* h);

@@ -62,6 +62,7 @@ _SIGS = {
     "hx_add_rows_dev": [_P, _P, _P, _P, _P, C.c_int64, _P],
     "hx_set_next_id": [_P, C.c_int64],
     "hx_truncate": [_P, C.c_int64],
+    "hx_retain_rows": [_P, _P, C.c_int64, C.POINTER(C.c_int64)],
     "hx_finalize": [_P],
     "hx_count": [_P, C.POINTER(C.c_int64)],
     "hx_nnz": [_P, C.POINTER(C.c_int64)],

@@ -93,7 +93,7 @@ enum WsSlot {
   WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
-  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD
+  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN
 };
 
 template <typename T>
@@ -172,6 +172,7 @@ struct hx_index {
   int seg_docs_force = 0;             // HX_DEBUG_SEG_DOCS (tests): 32768 / 65536, 0 = by size
   int sp_cut_step = 0;                // HX_DEBUG_SP_CUTSTEP (diagnostics): keys between cuts of the select pass, 0 = default
   int64_t tail_min_force = -1;        // HX_DEBUG_TAIL_MIN (tests): documents a tail may hold before the base is rebuilt
+  int64_t compact_chunk = 0;          // HX_DEBUG_COMPACT_CHUNK (tests): rows per chunk of hx_retain_rows, 0 = by the bounce buffer's size
   float sp_wmin = 0.f, sp_wmax = 0.f; // range of the document weights (all finite: checked at ingest)
   float sp_wmax_shared = 0.f;         // hx_set_sparse_wmax: the largest weight of any shard of the collection (0: unset)
   bool sp_have_w = false;
@@ -1876,6 +1877,7 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
     if (v == SEG_DOCS_SMALL || v == SEG_DOCS_LARGE) h->seg_docs_force = v;
   }
   if (const char* e = getenv("HX_DEBUG_TAIL_MIN")) h->tail_min_force = atoll(e);   // tests: force / forbid a tail index
+  if (const char* e = getenv("HX_DEBUG_COMPACT_CHUNK")) h->compact_chunk = std::max<int64_t>(0, atoll(e));   // tests: many chunks
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);
     if (v >= 1 && v <= SCAN8_LOGCAP) h->scan_logcap = v;
@@ -2178,6 +2180,229 @@ int hx_truncate(hx_index* h, int64_t n_rows) {
   }
   b.end = b.row0.empty() ? -1 : (int64_t)b.gid0.back() + (n_rows - (int64_t)b.row0.back());
   b.dirty = true;
+  HX_CATCH
+}
+
+// ---- per-point deletes ----------------------------------------------------------------------
+namespace hx {
+
+// The kept rows of a host mask, for the chunk plan: rank -> row without the list itself (that one is built on the device).
+struct KeepIndex {
+  const uint32_t* m;
+  int64_t n, nw;
+  std::vector<int64_t> cum;          // set bits in front of word w; cum[nw] = the kept rows
+  uint32_t word(int64_t w) const {
+    uint32_t v = m[w];
+    const int tail = (int)(n & 31);
+    if (w == nw - 1 && tail) v &= (1u << tail) - 1u;
+    return v;
+  }
+  KeepIndex(const uint32_t* mask, int64_t n_) : m(mask), n(n_), nw((n_ + 31) / 32), cum((size_t)((n_ + 31) / 32) + 1, 0) {
+    for (int64_t w = 0; w < nw; ++w) cum[(size_t)w + 1] = cum[(size_t)w] + __builtin_popcount(word(w));
+  }
+  int64_t kept() const { return cum[(size_t)nw]; }
+  int64_t kept_below(int64_t r) const {          // kept rows in [0, r), r <= n
+    if (r >= n) return kept();
+    const int64_t w = r >> 5;
+    return cum[(size_t)w] + __builtin_popcount(word(w) & ((1u << (r & 31)) - 1u));
+  }
+  int64_t row_of(int64_t i) const {              // the i-th kept row, i < kept()
+    const int64_t w = (std::upper_bound(cum.begin(), cum.end(), i) - cum.begin()) - 1;
+    uint32_t v = word(w);
+    for (int64_t k = i - cum[(size_t)w]; k > 0; --k) v &= v - 1u;
+    return w * 32 + (__builtin_ffs((int)v) - 1);
+  }
+  int64_t first_removed() const {                // rows in front of it do not move
+    for (int64_t w = 0; w < nw; ++w) {
+      const uint32_t full = (w == nw - 1 && (n & 31)) ? (1u << (n & 31)) - 1u : 0xFFFFFFFFu;
+      const uint32_t gone = ~word(w) & full;
+      if (gone) return w * 32 + (__builtin_ffs((int)gone) - 1);
+    }
+    return n;
+  }
+};
+
+// Bytes of the bounce buffer of a bounced chunk: the chunk is written there, read back and written into place while
+// its source rows stream past -- three times its size between the two uses of a line, inside the 256 MiB Infinity Cache.
+constexpr int64_t COMPACT_BOUNCE_BYTES = 32ll << 20;
+
+struct CompactChunk {
+  int64_t d0, d1;
+  bool direct;
+};
+// Destination rows [first, count) in stream-ordered chunks (compact.hip): a chunk whose first source row lies at or
+// past its end is gathered in place, any other goes through the bounce buffer, `chunk` rows at a time.
+static std::vector<CompactChunk> compact_plan(const KeepIndex& k, int64_t first, int64_t count, int64_t chunk) {
+  std::vector<CompactChunk> plan;
+  for (int64_t d = first; d < count;) {
+    const int64_t shift = k.row_of(d) - d;       // >= 1 from the first removed row on
+    const bool direct = shift >= chunk;
+    const int64_t e = std::min(count, d + (direct ? shift : chunk));
+    plan.push_back({d, e, direct});
+    d = e;
+  }
+  return plan;
+}
+
+struct DevTmp {                      // a temporary of one call
+  void* p = nullptr;
+  void alloc(size_t bytes) { HX_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
+  ~DevTmp() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
+  const int64_t n = h->n;
+  const KeepIndex k(keep, n);
+  const int64_t count = k.kept();
+  if (n_removed) *n_removed = n - count;
+  if (count == n) return;                          // nothing to do: nothing touched, nothing invalidated
+  HX_CHECK(h->sp_rows <= n, "hx_retain_rows: sparse vectors are pending for rows not added yet");
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  hipStream_t st = nullptr;
+  const int64_t first = k.first_removed();
+  const bool sparse = h->sp_rows > 0 && h->sp_indptr != nullptr;
+  const int64_t kept_sp = sparse ? k.kept_below(h->sp_rows) : 0;   // kept documents that have a sparse row
+
+  // ---- everything that can fail comes first: the row list, the plans, the temporaries, the CSR offsets ----
+  struct Arr {
+    void* p;
+    int64_t rb;                      // row bytes; 4 = one scale per row
+    std::vector<CompactChunk> plan;
+  };
+  std::vector<Arr> arrs;
+  if (count > 0) {
+    auto add = [&](void* p, int64_t rb) {
+      if (p) arrs.push_back({p, rb, {}});
+    };
+    add(h->dense, (int64_t)h->dim_pad * 4);
+    add(h->dense_h, (int64_t)h->dim_pad * 2);
+    add(h->q8, h->dim_pad8);
+    add(h->q8_rinv, 4);
+    add(h->q8s, h->dim_pad8);
+    add(h->q8s_scale, 4);
+    for (int p = 0; p < h->n_pre; ++p) add(h->pre[p], (int64_t)h->psize[p] * 4);
+    if (h->n_pre > 0) add(h->pre_h0, (int64_t)h->psize[0] * 2);
+  }
+  int64_t bounce_bytes = 0;
+  for (auto& a : arrs) {
+    const int64_t chunk = h->compact_chunk > 0 ? h->compact_chunk : std::max<int64_t>(COMPACT_BOUNCE_BYTES / a.rb, 1);
+    a.plan = compact_plan(k, first, count, chunk);
+    for (const auto& c : a.plan)
+      if (!c.direct) bounce_bytes = std::max(bounce_bytes, (c.d1 - c.d0) * a.rb);
+  }
+  uint32_t* rows = nullptr;
+  if (count > 0) {
+    const int64_t nw = (n + 31) / 32;
+    uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)nw * 4);
+    HX_HIP(hipMemcpyAsync(dm, keep, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+    uint32_t* count_dev = nullptr;
+    mask_rows_dev(h, dm, rows, count_dev, st);
+  }
+  DevTmp bounce, sp_idx2, sp_val2;
+  if (bounce_bytes > 0) bounce.alloc((size_t)bounce_bytes);
+  // CSR: the documents [0, first) stay; kept documents [first, kept_sp) move to the offsets base + off[j]
+  const int64_t m = std::max<int64_t>(kept_sp - first, 0);
+  int64_t base = 0, moved = 0, new_nnz = 0;
+  int64_t* off = nullptr;
+  uint32_t* mm = nullptr;
+  if (sparse && kept_sp > 0) {
+    mm = (uint32_t*)h->ws.get(WS_SP_MM, 16);
+    HX_HIP(hipMemcpy(&base, h->sp_indptr + std::min(first, kept_sp), 8, hipMemcpyDeviceToHost));
+    if (m > 0) {
+      int64_t* len = (int64_t*)h->ws.get(WS_C_LEN, (size_t)(m + 1) * 8 * 2);
+      off = len + (m + 1);
+      HX_HIP(hipMemsetAsync(len + m, 0, 8, st));
+      launch_csr_keep_len(h->sp_indptr, rows + first, m, len, st);
+      exclusive_scan_i64(len, off, m, st);
+      HX_HIP(hipMemcpy(&moved, off + m, 8, hipMemcpyDeviceToHost));
+      if (moved > 0) {
+        sp_idx2.alloc((size_t)moved * 4);
+        sp_val2.alloc((size_t)moved * 4);
+      }
+    }
+    new_nnz = base + moved;
+  }
+
+  // ---- the rows move ----
+  for (const auto& a : arrs) {
+    uint8_t* p = (uint8_t*)a.p;
+    for (const auto& c : a.plan) {
+      const int64_t cnt = c.d1 - c.d0;
+      void* dst = c.direct ? (void*)(p + c.d0 * a.rb) : bounce.p;
+      if (a.rb == 4) launch_compact_u32(p, dst, rows + c.d0, cnt, st);
+      else launch_compact_rows16(p, dst, a.rb, rows + c.d0, cnt, st);
+      if (c.direct) continue;
+      if (a.rb == 4) launch_copy_u32(bounce.p, p + c.d0 * 4, cnt, st);
+      else launch_copy16(bounce.p, p + c.d0 * a.rb, cnt * a.rb, st);
+    }
+  }
+  // (the per-row scales behind the last row are zero in a freshly grown buffer)
+  if (h->q8_rinv) HX_HIP(hipMemsetAsync(h->q8_rinv + count, 0, (size_t)(n - count) * 4, st));
+  if (h->q8s_scale) HX_HIP(hipMemsetAsync(h->q8s_scale + count, 0, (size_t)(n - count) * 4, st));
+  uint32_t got[3] = {0xFFFFFFFFu, 0u, 0u};
+  if (mm && new_nnz > 0) {
+    HX_HIP(hipMemcpyAsync(mm, got, 12, hipMemcpyHostToDevice, st));
+    launch_minmax_f32(h->sp_val, base, (float*)mm, st);           // the documents that stay where they are
+    if (moved > 0) {
+      launch_csr_compact(h->sp_indptr, rows + first, off, m, h->sp_idx, h->sp_val, (int32_t*)sp_idx2.p, (float*)sp_val2.p,
+                         mm, st);
+      // (4-byte words: base need not be a multiple of 4 postings)
+      launch_copy_u32(sp_idx2.p, h->sp_idx + base, moved, st);
+      launch_copy_u32(sp_val2.p, h->sp_val + base, moved, st);
+    }
+    HX_HIP(hipMemcpyAsync(got, mm, 12, hipMemcpyDeviceToHost, st));
+  }
+  if (m > 0) launch_csr_new_indptr(h->sp_indptr + first, off, m, base, st);
+  HX_HIP(hipDeviceSynchronize());
+
+  // ---- the index of the kept rows ----
+  h->n = count;
+  h->tm_q8.rows = h->tm_q8s.rows = -1;
+  if (sparse) {
+    h->sp_rows = kept_sp;
+    h->nnz = new_nnz;
+    if (new_nnz > 0 && got[0] <= got[1]) {
+      h->sp_wmin = orderable_f32(got[0]);
+      h->sp_wmax = orderable_f32(got[1]);
+      h->sp_have_w = true;
+    } else {
+      h->sp_wmin = h->sp_wmax = 0.f;
+      h->sp_have_w = false;
+    }
+  }
+  free_sparse_index(h);
+  h->sparse_stale = true;
+  auto& b = h->ids;
+  b.row0.clear();
+  b.gid0.clear();
+  if (count > 0) {
+    b.row0.push_back(0u);
+    b.gid0.push_back((uint32_t)h->id_base);
+  }
+  b.end = count > 0 ? h->id_base + count : -1;
+  b.next = -1;
+  b.dirty = true;
+}
+
+}  // namespace hx
+
+int hx_retain_rows(hx_index* h, const uint32_t* keep_host, int64_t mask_rows, int64_t* n_removed) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  HX_CHECK(mask_rows >= 0, "hx_retain_rows: mask_rows < 0");
+  HX_CHECK(keep_host || mask_rows == 0, "hx_retain_rows: mask is NULL");
+  HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  HX_CHECK(ids_identity(h) && h->ids.next < 0,
+           "hx_retain_rows: the ids of this index were named with hx_set_next_id (a shard of a sharded collection): "
+           "renumbering them is not supported");
+  if (mask_rows == 0) {
+    if (n_removed) *n_removed = 0;
+    return 0;
+  }
+  retain_rows(h, keep_host, n_removed);
   HX_CATCH
 }
 

@@ -365,6 +365,23 @@ void launch_gather_u32(const void* src, void* dst, const uint32_t* rows, int64_t
 // keys of a scan of the view (internal ids id_base + view row) -> internal ids id_base + rows[view row], in place
 void launch_view_ids(uint64_t* keys, int64_t n, const uint32_t* rows, uint32_t count, uint32_t id_base, hipStream_t st);
 
+// ---- compact.hip: per-point deletes (hx_retain_rows) ------------------------------------------------------------------
+// dst row i = src row rows[i], i < count (row_bytes a multiple of 16; one 4-byte value per row for _u32).  src and dst
+// may be one allocation as long as the launch reads no byte it writes (engine.hip cuts the rows into such chunks).
+void launch_compact_rows16(const void* src, void* dst, int64_t row_bytes, const uint32_t* rows, int64_t count,
+                           hipStream_t st);
+void launch_compact_u32(const void* src, void* dst, const uint32_t* rows, int64_t count, hipStream_t st);
+// plain copies between disjoint buffers (bytes a multiple of 16 / n 4-byte words)
+void launch_copy16(const void* src, void* dst, int64_t bytes, hipStream_t st);
+void launch_copy_u32(const void* src, void* dst, int64_t n, hipStream_t st);
+// document-major CSR: len[j] = postings of document rows[j] (j < m); the segmented copy of those documents' postings
+// to idx2 / val2 at off[j] (off = exclusive prefix of len, off[m] = total) with the min / max of the copied weights
+// merged into mm[0] / mm[1] (orderable u32, as launch_minmax_f32); indptr[j] = base + off[j] for j <= m
+void launch_csr_keep_len(const int64_t* indptr, const uint32_t* rows, int64_t m, int64_t* len, hipStream_t st);
+void launch_csr_compact(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const int32_t* idx,
+                        const float* val, int32_t* idx2, float* val2, uint32_t* mm, hipStream_t st);
+void launch_csr_new_indptr(int64_t* indptr, const int64_t* off, int64_t m, int64_t base, hipStream_t st);
+
 // ---- spbuild.hip -------------------------------------------------------------
 struct SparseBuildOut {
   uint2* post;

@@ -145,6 +145,14 @@ class HxIndex:
         """Roll back to the first n_rows rows (hx_truncate)."""
         check(_lib.lib().hx_truncate(self._h, int(n_rows)))
 
+    def retain(self, keep) -> int:
+        """Per-point delete (hx_retain_rows): keep only the rows of `keep` -- a bool array of length count() or packed
+        uint32 words, as `_mask` takes them -- and compact the index on the device.  Returns the rows removed."""
+        words, rows = self._mask(keep)
+        removed = C.c_int64()
+        check(_lib.lib().hx_retain_rows(self._h, _ptr(words), rows, C.byref(removed)))
+        return removed.value
+
     def synth_fill(self, n: int, seed_dense: int, seed_sparse: int = 0, tables=None):
         if tables is not None:
             cdf = np.ascontiguousarray(tables[0], dtype=np.uint32)

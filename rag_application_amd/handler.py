@@ -125,6 +125,8 @@ class QdrantHandler:
 
     # filter_stages="all" (the engine's pre-filtered query) needs one engine index per collection
     _masked_search = True
+    # delete_points renumbers the rows of ONE engine index (hx_retain_rows)
+    _point_deletes = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -406,6 +408,52 @@ class QdrantHandler:
             logging.info("delete_collection: %s dropped", user_id)
         except Exception as e:
             logging.error("delete_collection(%s) failed: %s", user_id, e)
+            raise
+
+    def _delete_sync(self, user_id, filters, point_ids) -> int:
+        col = self._collections[str(user_id)]              # KeyError if absent: re-raised
+        n = len(col.ids)
+        gone = np.zeros(n, dtype=bool)
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before anything moves
+            hit = np.unpackbits(col.row_mask(filters).view(np.uint8), bitorder="little")[:n].astype(bool)
+            gone |= hit
+        if point_ids:
+            listed = {str(p) for p in point_ids}
+            gone |= np.fromiter((i in listed for i in col.ids), dtype=bool, count=n)
+        keep = ~gone
+        removed = int(gone.sum())
+        if removed == 0:
+            return 0
+        # the engine first (it refuses before it moves anything), then the ids and payloads the same way
+        col.index.retain(_filters.pack_rows(keep))
+        col.ids = [i for i, k in zip(col.ids, keep) if k]
+        col.payloads = [p for p, k in zip(col.payloads, keep) if k]
+        # the cached row masks speak of the old rows: dropped, not patched (a delete of k rows followed by an add of k
+        # rows would pass the cache's `done != n` test with a stale mask)
+        col._masks.clear()
+        return removed
+
+    async def delete_points(self, user_id: str, filters: Optional[Dict] = None,
+                            point_ids: Optional[List[str]] = None) -> int:
+        """Delete the points the payload filter matches and / or the points with the listed ids (additive: the
+        reference's handler has no delete, the application around it deletes a file's chunks when the file is deleted
+        or uploaded again).  Returns the number of points deleted.  The engine index is compacted on the GPU
+        (hx_retain_rows): later searches run the ordinary path on an index that holds only the survivors.  Both
+        selectors None or empty raises ValueError (dropping everything is delete_collection's job); an unknown
+        collection raises KeyError.  Nothing is saved: call save_collection."""
+        try:
+            if not self._point_deletes:
+                raise ValueError("delete_points is not supported on a sharded collection")
+            if not filters and not point_ids:
+                raise ValueError("delete_points needs a filter or point ids (delete_collection drops a whole collection)")
+            if str(user_id) not in self._collections:
+                raise KeyError(str(user_id))
+            n = await self._run(self._delete_sync, user_id, filters, point_ids)
+            logging.info("delete_points: %d points deleted for %s", n, user_id)
+            return n
+        except Exception as e:
+            logging.error("delete_points(%s) failed: %s", user_id, e)
             raise
 
     async def get_collection_chunk_count(self, user_id: str, filters: Optional[Dict] = None) -> int:
