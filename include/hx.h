@@ -338,6 +338,81 @@ int hx_hybrid_query_dev_masked(hx_index* h, const float* q_dense_dev, const int6
 /* free the copies of kept rows the pre-filtered queries keep allocated between calls (synchronises the device) */
 int hx_release_mask_view(hx_index* h);
 
+/* ---- payload index -------------------------------------
+ * Qdrant's create_payload_index, the engine's way: indexed payload fields live as columns beside the vectors, a filter
+ * arrives as a small postfix program, and one kernel evaluates it over every row and writes the packed row mask of
+ * hx_hybrid_query_*_masked / hx_retain_rows.  The engine never sees strings: the caller keeps the dictionaries.
+ * A column holds one cell per row, for rows [0, filled), filled <= hx_count:
+ *   HX_PAY_U32  a 32-bit code (a keyword's dictionary code, 0 / 1 of a bool); HX_PAY_U32_MISSING / _NULL say so;
+ *   HX_PAY_F64  an IEEE double; the two NaN bit patterns HX_PAY_F64_MISSING / _NULL say so (every other NaN must be
+ *               kept out by the caller: a NaN cell is equal to nothing and ordered against nothing).
+ * Adds leave columns alone: the caller appends the cells of new rows after a successful add.  hx_truncate(n) cuts every
+ * column to min(filled, n).  hx_retain_rows compacts every column that is filled to hx_count with the rows (same chunk
+ * plan, same hazard rule) and DROPS a column that lags (the caller rebuilds it).  hx_save / hx_load do not store
+ * columns (a loaded index has none: they are derived from the payloads); hx_destroy frees them. */
+#define HX_PAY_U32 1
+#define HX_PAY_F64 2
+#define HX_PAY_U32_MISSING 0xFFFFFFFFu
+#define HX_PAY_U32_NULL    0xFFFFFFFEu
+#define HX_PAY_F64_MISSING 0x7FF80000FFFFFFFFull
+#define HX_PAY_F64_NULL    0x7FF80000FFFFFFFEull
+#define HX_PAY_MAX_COLUMNS 64
+#define HX_PAY_MAX_STACK   32
+#define HX_PAY_MAX_OPS     4096
+/* a new empty column; *col = its id (ids are never reused).  Refused when the index holds HX_PAY_MAX_COLUMNS columns. */
+int hx_payload_create(hx_index* h, int32_t kind, int32_t* col);
+/* an unknown or dropped column is an error, here and in every entry below */
+int hx_payload_drop(hx_index* h, int32_t col);
+/* the cells of rows [filled, filled + n): n uint32 (HX_PAY_U32) or n doubles (HX_PAY_F64) on the host.  Refused, with
+ * the column unchanged, when filled + n > hx_count.  Returns when the cells are stored. */
+int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t n);
+int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled);
+/* The program: postfix over a per-row boolean stack (at most HX_PAY_MAX_STACK deep, exactly one entry at the end).
+ *   HX_PAY_TRUE / _FALSE                 push a constant
+ *   HX_PAY_IS_MISSING / _IS_NULL / _PRESENT  col   push the cell's state (PRESENT = neither missing nor null)
+ *   HX_PAY_EQ  col imm                    cell == imm (U32: the code in the low word; F64: the double's bits, IEEE ==)
+ *   HX_PAY_IN  col imm = set index        cell is in the set
+ *   HX_PAY_LT / _LE / _GT / _GE  col imm  F64 columns only, IEEE comparison with the double in imm
+ *   HX_PAY_ROW_IN  imm = set index        the local row number is in the set (uint32 rows)
+ *   HX_PAY_AND / _OR / _NOT               pop two (one), push the result
+ * EQ, IN and the comparisons are false on a missing or null cell.  A set is `n` values on the host, ascending (equal
+ * neighbours allowed): uint32 for a U32 column and ROW_IN, doubles (no NaN) for an F64 column. */
+#define HX_PAY_TRUE 0
+#define HX_PAY_FALSE 1
+#define HX_PAY_IS_MISSING 2
+#define HX_PAY_IS_NULL 3
+#define HX_PAY_PRESENT 4
+#define HX_PAY_EQ 5
+#define HX_PAY_IN 6
+#define HX_PAY_LT 7
+#define HX_PAY_LE 8
+#define HX_PAY_GT 9
+#define HX_PAY_GE 10
+#define HX_PAY_ROW_IN 11
+#define HX_PAY_AND 12
+#define HX_PAY_OR 13
+#define HX_PAY_NOT 14
+typedef struct hx_pay_op {
+  int32_t op;
+  int32_t col;
+  uint64_t imm;
+} hx_pay_op;
+typedef struct hx_pay_set {
+  const void* vals;
+  int64_t n;
+} hx_pay_set;
+/* Evaluate a program over rows [0, hx_count): mask_dev receives ceil(hx_count / 32) words in the layout of
+ * hx_hybrid_query_*_masked, bits at or past hx_count zero.  n_kept (may be NULL) receives the number of set bits: the
+ * call then synchronises `stream` once; with NULL nothing is read back and the call only enqueues work (the host
+ * arguments are copied before it returns).  Refused before any device work: a referenced column that is unknown or not
+ * filled to hx_count, a comparison on a U32 column, a set index out of range, a set that is not ascending, more than
+ * HX_PAY_MAX_OPS ops, a stack that would exceed HX_PAY_MAX_STACK entries or underflow or does not end with exactly one
+ * entry. */
+int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets_host, int32_t n_sets,
+                    uint32_t* mask_dev, int64_t* n_kept, void* stream);
+/* copy one cell to the host (4 bytes of a U32 column, 8 of an F64 column), as hx_debug_row does for vectors */
+int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host);
+
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
  * Qdrant/bm25 :41, :123), batched (the reference's TODO :100): n texts -> CSR of (term id, weight)

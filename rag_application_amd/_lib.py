@@ -49,6 +49,14 @@ class HxProf(C.Structure):
                 ("bytes", C.c_double * 6)]
 
 
+class HxPayOp(C.Structure):
+    _fields_ = [("op", C.c_int32), ("col", C.c_int32), ("imm", C.c_uint64)]
+
+
+class HxPaySet(C.Structure):
+    _fields_ = [("vals", C.c_void_p), ("n", C.c_int64)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "hx_create": [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.POINTER(_P)],
@@ -97,6 +105,12 @@ _SIGS = {
     "hx_hybrid_query_host_masked": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, _P, _P, _P],
     "hx_hybrid_query_dev_masked": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, _P, _P, _P],
     "hx_release_mask_view": [_P],
+    "hx_payload_create": [_P, C.c_int32, C.POINTER(C.c_int32)],
+    "hx_payload_drop": [_P, C.c_int32],
+    "hx_payload_append": [_P, C.c_int32, _P, C.c_int64],
+    "hx_payload_rows": [_P, C.c_int32, C.POINTER(C.c_int64)],
+    "hx_payload_mask": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int64), _P],
+    "hx_payload_debug_cell": [_P, C.c_int32, C.c_int64, _P],
     "hx_bm25_embed_batch": [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, C.c_int64, _P],
     "hx_save": [_P, C.c_char_p],
     "hx_load": [C.c_char_p, C.c_int32, C.POINTER(_P)],

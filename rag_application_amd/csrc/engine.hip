@@ -93,7 +93,7 @@ enum WsSlot {
   WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
-  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN
+  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT
 };
 
 template <typename T>
@@ -234,6 +234,22 @@ struct hx_index {
     TileMax tm_q8, tm_q8s;
   } mv;
 
+  // Payload index (hx_payload_*): columns of one (U32) or two (F64: low word, high word) planes of
+  // uint32 per row, filled for rows [0, filled), filled <= n.  Ids are never reused.  A program and its sets travel
+  // through one pinned staging buffer; pay_ev says when the device has taken the last one.
+  struct PayCol {
+    int id = 0, kind = 0;
+    uint32_t* p0 = nullptr;
+    uint32_t* p1 = nullptr;
+    int64_t filled = 0, cap = 0;
+  };
+  std::vector<PayCol> pay;
+  int pay_next_id = 0;
+  uint8_t* pay_pin = nullptr;
+  size_t pay_pin_cap = 0;
+  hipEvent_t pay_ev = nullptr;
+  bool pay_ev_pending = false;
+
   void set_device() const { HX_HIP(hipSetDevice(device)); }
 };
 
@@ -247,6 +263,13 @@ void launch_sparse_select(const SparseSelectArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------------------------
 // storage
 // ---------------------------------------------------------------------------------
+static void pay_free(hx_index::PayCol& c) {
+  if (c.p0) (void)hipFree(c.p0);
+  if (c.p1) (void)hipFree(c.p1);
+  c.p0 = c.p1 = nullptr;
+  c.filled = c.cap = 0;
+}
+
 static void reserve_rows(hx_index* h, int64_t want) {
   if (want <= h->cap) return;
   int64_t nc = std::max<int64_t>(want, h->cap * 2);
@@ -1904,6 +1927,9 @@ int hx_destroy(hx_index* h) {
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->st2) (void)hipStreamDestroy(h->st2);
   if (h->ids.dev) (void)hipFree(h->ids.dev);
+  for (auto& c : h->pay) pay_free(c);
+  if (h->pay_pin) (void)hipHostFree(h->pay_pin);
+  if (h->pay_ev) (void)hipEventDestroy(h->pay_ev);
   h->ws.release();
   delete h;
   HX_CATCH
@@ -2159,6 +2185,7 @@ int hx_truncate(hx_index* h, int64_t n_rows) {
   h->set_device();
   HX_HIP(hipDeviceSynchronize());
   h->ids.next = -1;
+  for (auto& c : h->pay) c.filled = std::min(c.filled, n_rows);
   if (n_rows == h->n && h->sp_rows <= n_rows) return 0;
   h->n = n_rows;
   h->tm_q8.rows = h->tm_q8s.rows = -1;
@@ -2285,6 +2312,11 @@ static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
     add(h->q8s_scale, 4);
     for (int p = 0; p < h->n_pre; ++p) add(h->pre[p], (int64_t)h->psize[p] * 4);
     if (h->n_pre > 0) add(h->pre_h0, (int64_t)h->psize[0] * 2);
+    for (auto& c : h->pay)           // the payload columns that cover every row move with the rows; a lagging one is dropped
+      if (c.filled == n) {
+        add(c.p0, 4);
+        add(c.p1, 4);
+      }
   }
   int64_t bounce_bytes = 0;
   for (auto& a : arrs) {
@@ -2360,6 +2392,14 @@ static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
 
   // ---- the index of the kept rows ----
   h->n = count;
+  for (size_t i = h->pay.size(); i-- > 0;) {
+    if (h->pay[i].filled == n) {
+      h->pay[i].filled = count;
+      continue;
+    }
+    pay_free(h->pay[i]);
+    h->pay.erase(h->pay.begin() + (long)i);
+  }
   h->tm_q8.rows = h->tm_q8s.rows = -1;
   if (sparse) {
     h->sp_rows = kept_sp;
@@ -3103,6 +3143,225 @@ int hx_release_mask_view(hx_index* h) {
   h->set_device();
   HX_HIP(hipDeviceSynchronize());
   mv_release(h);
+  HX_CATCH
+}
+
+// ---- payload index ---------------------------------------------------------------------------
+static hx_index::PayCol& pay_col(hx_index* h, int32_t col) {
+  for (auto& c : h->pay)
+    if (c.id == col) return c;
+  throw Error("payload: unknown column " + std::to_string(col));
+}
+
+int hx_payload_create(hx_index* h, int32_t kind, int32_t* col) {
+  HX_TRY
+  HX_CHECK(h && col, "NULL argument");
+  HX_CHECK(kind == HX_PAY_U32 || kind == HX_PAY_F64, "payload: kind must be HX_PAY_U32 or HX_PAY_F64");
+  HX_CHECK((int)h->pay.size() < HX_PAY_MAX_COLUMNS, "payload: an index holds at most 64 columns");
+  hx_index::PayCol c;
+  c.id = h->pay_next_id++;
+  c.kind = kind;
+  h->pay.push_back(c);
+  *col = c.id;
+  HX_CATCH
+}
+
+int hx_payload_drop(hx_index* h, int32_t col) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  pay_free(c);
+  h->pay.erase(h->pay.begin() + (&c - h->pay.data()));
+  HX_CATCH
+}
+
+int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled) {
+  HX_TRY
+  HX_CHECK(h && filled, "NULL argument");
+  *filled = pay_col(h, col).filled;
+  HX_CATCH
+}
+
+int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t n) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(n >= 0, "payload: n < 0");
+  HX_CHECK(cells_host || n == 0, "payload: cells are NULL");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  if (n == 0) return 0;
+  h->set_device();
+  const bool f64 = c.kind == HX_PAY_F64;
+  const int64_t want = c.filled + n;
+  if (want > c.cap) {                  // (everything that can fail comes before the column changes)
+    const int64_t nc = round_up(std::max<int64_t>(std::max(want, c.cap * 2), h->cap), 256);
+    HX_HIP(hipDeviceSynchronize());
+    uint32_t *a = nullptr, *b = nullptr;
+    HX_HIP(hipMalloc((void**)&a, (size_t)nc * 4));
+    if (f64 && hipMalloc((void**)&b, (size_t)nc * 4) != hipSuccess) {
+      (void)hipFree(a);
+      throw Error("payload: out of device memory");
+    }
+    if (c.filled > 0) {
+      HX_HIP(hipMemcpy(a, c.p0, (size_t)c.filled * 4, hipMemcpyDeviceToDevice));
+      if (f64) HX_HIP(hipMemcpy(b, c.p1, (size_t)c.filled * 4, hipMemcpyDeviceToDevice));
+    }
+    if (c.p0) (void)hipFree(c.p0);
+    if (c.p1) (void)hipFree(c.p1);
+    c.p0 = a;
+    c.p1 = b;
+    c.cap = nc;
+  }
+  if (!f64) {
+    HX_HIP(hipMemcpy(c.p0 + c.filled, cells_host, (size_t)n * 4, hipMemcpyHostToDevice));
+  } else {
+    const uint64_t* v = (const uint64_t*)cells_host;
+    std::vector<uint32_t> lo((size_t)n), hi((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      lo[(size_t)i] = (uint32_t)v[i];
+      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
+    }
+    HX_HIP(hipMemcpy(c.p0 + c.filled, lo.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HX_HIP(hipMemcpy(c.p1 + c.filled, hi.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  c.filled = want;
+  HX_CATCH
+}
+
+int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host) {
+  HX_TRY
+  HX_CHECK(h && out_host, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
+  h->set_device();
+  HX_HIP(hipMemcpy(out_host, c.p0 + row, 4, hipMemcpyDeviceToHost));
+  if (c.kind == HX_PAY_F64) HX_HIP(hipMemcpy((uint8_t*)out_host + 4, c.p1 + row, 4, hipMemcpyDeviceToHost));
+  HX_CATCH
+}
+
+int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets, int32_t n_sets,
+                    uint32_t* mask_dev, int64_t* n_kept, void* stream) {
+  HX_TRY
+  HX_CHECK(h && ops && (mask_dev || h->n == 0), "NULL argument");
+  HX_CHECK(n_ops >= 1 && n_ops <= HX_PAY_MAX_OPS, "payload: a program holds 1 to 4096 ops");
+  HX_CHECK(n_sets >= 0 && (sets || n_sets == 0), "payload: bad sets");
+  // ---- every refusal, before any device work ----
+  std::vector<PayOpDev> prog((size_t)n_ops);
+  std::vector<int8_t> set_kind((size_t)n_sets, 0);        // 0 = unused, 1 = uint32, 2 = double
+  int depth = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    const hx_pay_op& o = ops[i];
+    PayOpDev d{0u, 0u, o.imm, nullptr, nullptr};
+    int pops = 0;
+    const hx_index::PayCol* c = nullptr;
+    const bool reads_col = o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_GE;
+    if (reads_col) {
+      c = &pay_col(h, o.col);
+      HX_CHECK(c->filled == h->n, "payload: column " + std::to_string(o.col) + " is not filled to the index's row count");
+      d.p0 = c->p0;
+      d.p1 = c->kind == HX_PAY_F64 ? c->p1 : nullptr;
+    }
+    const bool f64 = c && c->kind == HX_PAY_F64;
+    switch (o.op) {
+      case HX_PAY_TRUE: d.op = PAY_D_TRUE; break;
+      case HX_PAY_FALSE: d.op = PAY_D_FALSE; break;
+      case HX_PAY_IS_MISSING: d.op = PAY_D_IS_MISSING; break;
+      case HX_PAY_IS_NULL: d.op = PAY_D_IS_NULL; break;
+      case HX_PAY_PRESENT: d.op = PAY_D_PRESENT; break;
+      case HX_PAY_EQ: d.op = f64 ? PAY_D_EQ_F64 : PAY_D_EQ_U32; break;
+      case HX_PAY_IN: d.op = f64 ? PAY_D_IN_F64 : PAY_D_IN_U32; break;
+      case HX_PAY_LT: d.op = PAY_D_LT; break;
+      case HX_PAY_LE: d.op = PAY_D_LE; break;
+      case HX_PAY_GT: d.op = PAY_D_GT; break;
+      case HX_PAY_GE: d.op = PAY_D_GE; break;
+      case HX_PAY_ROW_IN: d.op = PAY_D_ROW_IN; break;
+      case HX_PAY_AND: d.op = PAY_D_AND; pops = 2; break;
+      case HX_PAY_OR: d.op = PAY_D_OR; pops = 2; break;
+      case HX_PAY_NOT: d.op = PAY_D_NOT; pops = 1; break;
+      default: throw Error("payload: unknown op " + std::to_string(o.op));
+    }
+    if (o.op >= HX_PAY_LT && o.op <= HX_PAY_GE) HX_CHECK(f64, "payload: LT / LE / GT / GE need an F64 column");
+    if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN) {
+      HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
+      const int8_t kind = f64 ? 2 : 1;
+      HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == kind, "payload: one set used as uint32 and as double");
+      set_kind[(size_t)o.imm] = kind;
+    }
+    HX_CHECK(depth >= pops, "payload: stack underflow at op " + std::to_string(i));
+    depth += 1 - pops;
+    HX_CHECK(depth <= HX_PAY_MAX_STACK, "payload: the stack exceeds 32 entries at op " + std::to_string(i));
+    prog[(size_t)i] = d;
+  }
+  HX_CHECK(depth == 1, "payload: the program must leave exactly one entry on the stack");
+  const size_t prog_bytes = (size_t)n_ops * sizeof(PayOpDev);
+  std::vector<size_t> set_off((size_t)n_sets, 0);
+  size_t bytes = prog_bytes;
+  for (int s = 0; s < n_sets; ++s) {
+    if (!set_kind[(size_t)s]) continue;
+    const int64_t m = sets[s].n;
+    HX_CHECK(m >= 0 && m <= 0xFFFFFFFFll && (sets[s].vals || m == 0), "payload: bad set");
+    bool ok = true;
+    if (set_kind[(size_t)s] == 1) {
+      const uint32_t* v = (const uint32_t*)sets[s].vals;
+      for (int64_t i = 1; i < m; ++i) ok &= v[i - 1] <= v[i];
+    } else {
+      const double* v = (const double*)sets[s].vals;
+      for (int64_t i = 0; i < m; ++i) ok &= v[i] == v[i] && (i == 0 || v[i - 1] <= v[i]);
+    }
+    HX_CHECK(ok, "payload: set " + std::to_string(s) + " is not sorted ascending");
+    set_off[(size_t)s] = bytes;
+    bytes += (size_t)round_up(std::max<int64_t>(m, 1) * (set_kind[(size_t)s] == 1 ? 4 : 8), 8);
+  }
+  const int64_t n = h->n;
+  if (n == 0) {
+    if (n_kept) *n_kept = 0;
+    return 0;
+  }
+  // ---- the program and its sets: one pinned staging buffer, one copy ----
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  if (h->pay_ev_pending) {              // the device has taken the previous call's program
+    HX_HIP(hipEventSynchronize(h->pay_ev));
+    h->pay_ev_pending = false;
+  }
+  if (bytes > h->pay_pin_cap) {
+    if (h->pay_pin) HX_HIP(hipHostFree(h->pay_pin));
+    h->pay_pin = nullptr;
+    h->pay_pin_cap = 0;
+    const size_t want = (size_t)round_up((int64_t)bytes * 2, 4096);
+    HX_HIP(hipHostMalloc((void**)&h->pay_pin, want, hipHostMallocDefault));
+    h->pay_pin_cap = want;
+  }
+  if (!h->pay_ev) HX_HIP(hipEventCreateWithFlags(&h->pay_ev, hipEventDisableTiming));
+  uint8_t* dev = (uint8_t*)h->ws.get(WS_PAY_PROG, bytes);
+  for (int i = 0; i < n_ops; ++i) {
+    PayOpDev& d = prog[(size_t)i];
+    if (d.op != PAY_D_ROW_IN && d.op != PAY_D_IN_U32 && d.op != PAY_D_IN_F64) continue;
+    const size_t s = (size_t)d.imm;
+    d.cnt = (uint32_t)sets[s].n;
+    d.imm = (uint64_t)(uintptr_t)(dev + set_off[s]);
+  }
+  std::memcpy(h->pay_pin, prog.data(), prog_bytes);
+  for (int s = 0; s < n_sets; ++s)
+    if (set_kind[(size_t)s] && sets[s].n > 0)
+      std::memcpy(h->pay_pin + set_off[(size_t)s], sets[s].vals, (size_t)sets[s].n * (set_kind[(size_t)s] == 1 ? 4 : 8));
+  HX_HIP(hipMemcpyAsync(dev, h->pay_pin, bytes, hipMemcpyHostToDevice, st));
+  HX_HIP(hipEventRecord(h->pay_ev, st));
+  h->pay_ev_pending = true;
+  uint32_t* kept = nullptr;
+  if (n_kept) {
+    kept = (uint32_t*)h->ws.get(WS_PAY_KEPT, 4);
+    HX_HIP(hipMemsetAsync(kept, 0, 4, st));
+  }
+  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, st);
+  if (n_kept) {
+    uint32_t* pin = (uint32_t*)host_pin(h) + 14;
+    HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    *n_kept = pin[0];
+  }
   HX_CATCH
 }
 

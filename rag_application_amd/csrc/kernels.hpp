@@ -402,4 +402,24 @@ void synth_sparse_fill(int64_t doc0_global, int64_t n, uint32_t seed, const uint
                        hipStream_t st);
 void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t st);  // out[n] = total
 
+// ---- payload.hip: the payload index (hx_payload_mask) ----------------------------------------------
+// One op of a program as the kernel reads it: engine.hip resolves the columns of hx_pay_op to their planes (p0 = the
+// cell of a U32 column or the low word of an F64 cell, p1 = its high word or NULL) and the sets to device pointers
+// (imm; cnt = entries).  Codes from PAY_D_FIRST_COL on read a column.
+enum PayDevOp : uint32_t {
+  PAY_D_TRUE = 0, PAY_D_FALSE, PAY_D_AND, PAY_D_OR, PAY_D_NOT, PAY_D_ROW_IN,
+  PAY_D_FIRST_COL, PAY_D_IS_MISSING = PAY_D_FIRST_COL, PAY_D_IS_NULL, PAY_D_PRESENT, PAY_D_EQ_U32, PAY_D_IN_U32,
+  PAY_D_EQ_F64, PAY_D_IN_F64, PAY_D_LT, PAY_D_LE, PAY_D_GT, PAY_D_GE
+};
+struct PayOpDev {
+  uint32_t op, cnt;
+  uint64_t imm;
+  const uint32_t* p0;
+  const uint32_t* p1;
+};
+constexpr int PAY_INLINE_SET = 8;   // sets up to here are compared entry by entry, larger ones searched
+// mask[ceil(n / 32)] = the verdicts of the program over rows [0, n) (bits at or past n zero); *kept += their number
+// when kept is not NULL (the caller zeroes it)
+void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, hipStream_t st);
+
 }  // namespace hx

@@ -15,6 +15,9 @@ from . import _lib
 from ._lib import HX_MODE_H1, HX_MODE_TREE, HxError, HxParams, HxProf, HxStats, check
 from .filters import pack_rows
 
+# payload index (hx.h): the column kinds; the cell codes and the ops of a program are in payload_index.py
+PAY_U32, PAY_F64 = 1, 2
+
 SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_256_limit",
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
 
@@ -390,6 +393,63 @@ class HxIndex:
     def release_mask_view(self):
         """Free the gathered copies pre-filtered queries keep between calls (hx_release_mask_view)."""
         check(_lib.lib().hx_release_mask_view(self._h))
+
+    # -- payload index (hx.h: hx_payload_*; payload_index.py compiles filters to the programs) ----------------------
+    def payload_create(self, kind: int) -> int:
+        """A new empty column of `kind` (PAY_U32 / PAY_F64); returns its id (hx_payload_create)."""
+        col = C.c_int32()
+        check(_lib.lib().hx_payload_create(self._h, int(kind), C.byref(col)))
+        return col.value
+
+    def payload_drop(self, col: int) -> None:
+        check(_lib.lib().hx_payload_drop(self._h, int(col)))
+
+    def payload_append(self, col: int, cells: np.ndarray) -> None:
+        """The cells of the next len(cells) rows of the column: np.uint32 codes (a U32 column) or np.uint64 bit patterns
+        of doubles (an F64 column; np.float64 is taken as it is).  Refused past count() (hx_payload_append)."""
+        cells = np.ascontiguousarray(cells)
+        if cells.dtype not in (np.uint32, np.uint64, np.float64) or cells.ndim != 1:
+            raise TypeError("payload cells: a 1-d np.uint32 (U32 column) or np.uint64 / np.float64 (F64 column) array")
+        check(_lib.lib().hx_payload_append(self._h, int(col), _ptr(cells), cells.shape[0]))
+
+    def payload_rows(self, col: int) -> int:
+        n = C.c_int64()
+        check(_lib.lib().hx_payload_rows(self._h, int(col), C.byref(n)))
+        return n.value
+
+    def payload_cell(self, col: int, row: int, kind: int) -> int:
+        """The stored bits of one cell (hx_payload_debug_cell): a code, or the bit pattern of a double."""
+        out = np.zeros(1, dtype=np.uint64)
+        check(_lib.lib().hx_payload_debug_cell(self._h, int(col), int(row), _ptr(out)))
+        return int(out[0]) & (0xFFFFFFFF if kind == PAY_U32 else 0xFFFFFFFFFFFFFFFF)
+
+    def payload_mask(self, ops, sets=(), want_count: bool = True):
+        """Evaluate a program (hx_payload_mask).  ops: (op, col, imm) triples, imm an int (a code, the bits of a double, a
+        set index); sets: sorted 1-d arrays, np.uint32 or np.float64.  Returns (mask, n_kept): the packed words as an int32
+        device tensor of ceil(count() / 32) entries -- what hybrid_query takes as `mask` -- and the number of set bits
+        (None when want_count is False: the call then only enqueues work).  mask_host(mask) gives the numpy form."""
+        arr = (_lib.HxPayOp * max(len(ops), 1))()
+        for k, (op, col, imm) in enumerate(ops):
+            arr[k].op, arr[k].col, arr[k].imm = int(op), int(col), int(imm) & 0xFFFFFFFFFFFFFFFF
+        keep = []
+        sarr = (_lib.HxPaySet * max(len(sets), 1))()
+        for k, s in enumerate(sets):
+            s = np.ascontiguousarray(s)
+            if s.dtype not in (np.uint32, np.float64) or s.ndim != 1:
+                raise TypeError("payload set: a 1-d np.uint32 or np.float64 array")
+            keep.append(s)
+            sarr[k].vals, sarr[k].n = s.ctypes.data, s.shape[0]
+        nw = (self.count() + 31) // 32
+        mask = torch.empty((max(nw, 1),), dtype=torch.int32, device=self._tdev)   # (an empty index: still a valid pointer)
+        kept = C.c_int64()
+        check(_lib.lib().hx_payload_mask(self._h, arr, len(ops), sarr, len(sets), _ptr(mask),
+                                         C.byref(kept) if want_count else None, _stream()))
+        return mask[:nw], (kept.value if want_count else None)
+
+    @staticmethod
+    def mask_host(mask: torch.Tensor) -> np.ndarray:
+        """A device mask of payload_mask as packed np.uint32 words (what filters.row_mask returns)."""
+        return mask.cpu().numpy().view(np.uint32).copy()
 
     def hybrid_query_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
                           params: HxParams, mask=None):

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import engine as _engine
 from . import filters as _filters
+from . import payload_index as _pindex
 from ._lib import HX_MODE_H1, HX_MODE_TREE
 
 
@@ -74,6 +75,7 @@ class _Collection:
         self.payloads: List[Dict[str, Any]] = []
         self.sparse_enabled = True
         self._masks: Dict[str, Any] = {}
+        self.pindex: Optional[_pindex.PayloadIndex] = None
 
     MASK_CACHE = 64   # filters whose row masks a collection keeps (least recently used first out): n / 8 bytes each
 
@@ -84,11 +86,103 @@ class _Collection:
         n = len(self.ids)
         done, prev = self._masks.pop(key, (0, None))
         if done != n:
-            prev = _filters.row_mask(self.ids, self.payloads, flt, start=done, prev=prev)
+            dev = self._device_mask(flt, n)               # a payload index and a filter that compiles: one kernel
+            prev = dev if dev is not None else _filters.row_mask(self.ids, self.payloads, flt, start=done, prev=prev)
         self._masks[key] = (n, prev)                      # (dicts keep insertion order: the last used is last)
         while len(self._masks) > self.MASK_CACHE:
             del self._masks[next(iter(self._masks))]
         return prev
+
+    # -- payload index (payload_index.py) ---------------------------------------------------------
+    def _id_rows(self) -> Optional[Dict[str, int]]:
+        """id -> row, built lazily, extended by the rows appended since, discarded by a delete; None when two rows
+        share an id (has_id then goes the Python way)."""
+        m = getattr(self, "_idrows", None)
+        if m is None:
+            m = self._idrows = {}
+            self._idrows_n = 0
+        for r in range(self._idrows_n, len(self.ids)):
+            m[self.ids[r]] = r
+        self._idrows_n = len(self.ids)
+        return m if len(m) == len(self.ids) else None
+
+    def _device_mask(self, flt, n: int) -> Optional[np.ndarray]:
+        """The packed row mask of `flt` from hx_payload_mask, or None: no payload index, or the filter is declined."""
+        pi = getattr(self, "pindex", None)
+        if pi is None:
+            return None
+        prog = pi.compile(flt, self._id_rows)
+        if prog is not None:
+            try:
+                if self.index.count() != n:
+                    raise RuntimeError("the engine's row count differs from the payloads'")
+                mask, _ = self.index.payload_mask(prog[0], prog[1], want_count=False)
+                words = self.index.mask_host(mask)
+                pi.device_evals += 1
+                return words
+            except Exception as e:                        # never a wrong mask: the Python loop is always right
+                logging.warning("payload index: device evaluation failed, Python path taken: %s", e)
+                pi.declined["engine refused"] = pi.declined.get("engine refused", 0) + 1
+        pi.python_evals += 1
+        return None
+
+    def _poison(self, key: str) -> None:
+        k = self.pindex.keys[key]
+        if k.col is not None:
+            try:
+                self.index.payload_drop(k.col)
+            except Exception as e:
+                logging.warning("payload index: dropping the column of %r failed: %s", key, e)
+        k.col = None
+
+    def create_payload_index(self, key: str, schema: str) -> bool:
+        """Index `key` (again): encode every stored row in one pass and append the cells to a new column.  True when
+        the key is live, False when a stored value poisoned it."""
+        if not hasattr(self.index, "payload_create"):
+            raise ValueError("this collection's engine index has no payload columns")
+        if getattr(self, "pindex", None) is None:
+            self.pindex = _pindex.PayloadIndex()
+        pi = self.pindex
+        if key in pi.keys:
+            self._poison(key)
+        elif len(pi.keys) >= _pindex.MAX_COLUMNS:
+            raise ValueError(f"a collection takes at most {_pindex.MAX_COLUMNS} payload indexes")
+        k = pi.keys[key] = _pindex._Key(schema)
+        cells = pi.encode(key, self.payloads)
+        if cells is None:
+            return False
+        col = self.index.payload_create(k.kind)
+        try:
+            self.index.payload_append(col, cells)
+        except Exception:
+            self.index.payload_drop(col)
+            raise
+        k.col = col
+        return True
+
+    def delete_payload_index(self, key: str) -> bool:
+        pi = getattr(self, "pindex", None)
+        if pi is None or key not in pi.keys:
+            return False
+        self._poison(key)
+        del pi.keys[key]
+        return True
+
+    def append_payload_cells(self, payloads) -> None:
+        """The cells of rows just added, for every live key.  A value that poisons a key, or an engine failure, drops
+        that key's column; the upsert stands."""
+        pi = getattr(self, "pindex", None)
+        if pi is None:
+            return
+        for key in pi.live_keys():
+            try:
+                cells = pi.encode(key, payloads)
+                if cells is not None:
+                    self.index.payload_append(pi.keys[key].col, cells)
+                    continue
+            except Exception as e:
+                logging.warning("payload index: appending to %r failed, the key is dropped: %s", key, e)
+            self._poison(key)
 
     def close(self):
         self.index.close()
@@ -99,7 +193,8 @@ class _Collection:
         self.index.save(base + ".hx")
         with open(base + ".json", "w") as f:
             json.dump({"dim": self.dim, "msizes": list(self.msizes), "sparse_enabled": self.sparse_enabled,
-                       "ids": self.ids, "payloads": self.payloads}, f)
+                       "ids": self.ids, "payloads": self.payloads,
+                       "payload_indexes": self.pindex.definitions() if getattr(self, "pindex", None) else {}}, f)
 
     @classmethod
     def load(cls, base: str, device: int, index_loader=None):
@@ -114,6 +209,11 @@ class _Collection:
         self.payloads = list(meta["payloads"])
         self.sparse_enabled = bool(meta["sparse_enabled"])
         self._masks = {}
+        self.pindex = None
+        # the payload indexes are derived data: the sidecar names them (old files have none), the payloads rebuild them
+        if hasattr(self.index, "payload_create"):
+            for key, schema in (meta.get("payload_indexes") or {}).items():
+                self.create_payload_index(str(key), _pindex.schema_of(schema))
         return self
 
 
@@ -127,6 +227,8 @@ class QdrantHandler:
     _masked_search = True
     # delete_points renumbers the rows of ONE engine index (hx_retain_rows)
     _point_deletes = True
+    # payload columns live in ONE engine index, beside the rows whose payloads this process holds
+    _payload_indexes = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -208,6 +310,36 @@ class QdrantHandler:
         os.makedirs(self.persist_dir, exist_ok=True)
         await self._run(col.save, self._base(user_id))
 
+    # ------------------------------------------------------------------- payload indexes
+    async def create_payload_index(self, user_id: str, field_name: str, field_schema: str = "keyword") -> bool:
+        """Qdrant's create_payload_index (additive: the reference creates none): index the payload field `field_name` (a
+        dotted path) as "keyword" | "number" ("integer" / "float" mean the same) | "bool".  Filters on indexed fields are
+        then evaluated by one kernel over the collection's columns instead of a Python loop over its payloads
+        (payload_index.py); the results are the same.  Returns True when the field is live, False when a stored value is
+        not of the schema (a list, a dict, another type, NaN, an int beyond 2^53): such a field stays on the Python path.
+        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload columns; KeyError for
+        an unknown collection."""
+        try:
+            if not self._payload_indexes:
+                raise ValueError("create_payload_index is not supported on a sharded collection")
+            schema = _pindex.schema_of(field_schema)
+            if not isinstance(field_name, str) or not field_name:
+                raise ValueError("field_name must be a non-empty string")
+            col = self._collections[str(user_id)]          # KeyError if absent: re-raised
+            return bool(await self._run(col.create_payload_index, field_name, schema))
+        except Exception as e:
+            logging.error("create_payload_index(%s, %s) failed: %s", user_id, field_name, e)
+            raise
+
+    async def delete_payload_index(self, user_id: str, field_name: str) -> bool:
+        """Drop the index on `field_name`; True when there was one.  Filters on the field go the Python way again."""
+        try:
+            col = self._collections[str(user_id)]
+            return bool(await self._run(col.delete_payload_index, field_name))
+        except Exception as e:
+            logging.error("delete_payload_index(%s, %s) failed: %s", user_id, field_name, e)
+            raise
+
     # --------------------------------------------------------------------------- upserts
     async def _store(self, user_id, items, emb_key_payload):
         if str(user_id) not in self._collections:
@@ -233,6 +365,7 @@ class QdrantHandler:
                           np.asarray(val, np.float32))
             col.ids.extend(ids)
             col.payloads.extend(payloads)
+            col.append_payload_cells(payloads)
         await self._run(add)
         return len(dense)
 
@@ -432,6 +565,7 @@ class QdrantHandler:
         # the cached row masks speak of the old rows: dropped, not patched (a delete of k rows followed by an add of k
         # rows would pass the cache's `done != n` test with a stale mask)
         col._masks.clear()
+        col._idrows = None                                 # (the payload columns were compacted with the rows: the keys stay live)
         return removed
 
     async def delete_points(self, user_id: str, filters: Optional[Dict] = None,

@@ -1,0 +1,349 @@
+"""Payload index: indexed payload fields as engine columns, filters as predicate programs.
+
+Qdrant's `create_payload_index(collection, field_name, field_schema)`, the engine's way.  A `PayloadIndex` belongs to
+one collection.  It knows the indexed keys (dotted paths as `filters._get` reads them), each key's schema
+("keyword" | "number" | "bool"), the keyword dictionaries (str -> code) and the ids of the engine columns
+(hx.h: hx_payload_*).  It does two things:
+
+  encode(key, payloads)   the cells of some rows of one key -- or None when a value POISONS the key;
+  compile(filter)         the postfix program hx_payload_mask evaluates -- or None when the filter is DECLINED.
+
+The oracle is `filters.matches`: whatever compiles gives exactly its mask; everything else goes the Python way
+(`filters.row_mask`), which is always right and only slow.
+
+A row's value: missing -> MISSING, None -> NULL, a value of the key's schema -> its cell.  Values of the schema are a
+`str` (keyword), a `bool` (bool), an `int` / `float` that is not a bool, not a NaN and -- an int -- at most 2^53 in
+magnitude (number: every stored number is then an exact double, and Python's exact int / float comparison is IEEE's).
+Anything else (a list, a dict, a value of another type, NaN, an oversized int) poisons the key: its column is
+dropped and every filter that mentions the key is declined until the index on it is created again."""
+from __future__ import annotations
+
+import struct
+from typing import Any, Callable, Dict, List, Optional, Tuple
+
+import numpy as np
+
+from . import filters as _filters
+
+# hx.h
+PAY_U32, PAY_F64 = 1, 2
+U32_MISSING, U32_NULL = 0xFFFFFFFF, 0xFFFFFFFE
+F64_MISSING, F64_NULL = 0x7FF80000FFFFFFFF, 0x7FF80000FFFFFFFE
+MAX_STACK, MAX_OPS, MAX_COLUMNS = 32, 4096, 64
+(TRUE, FALSE, IS_MISSING, IS_NULL, PRESENT, EQ, IN, LT, LE, GT, GE, ROW_IN, AND, OR, NOT) = range(15)
+
+SCHEMAS = {"keyword": "keyword", "number": "number", "integer": "number", "float": "number", "bool": "bool"}
+_CLAUSES = ("must", "should", "must_not")
+_MAX_KEYWORDS = U32_NULL            # codes 0 .. 0xFFFFFFFD
+
+
+def schema_of(field_schema) -> str:
+    s = SCHEMAS.get(str(field_schema).lower()) if isinstance(field_schema, str) else None
+    if s is None:
+        raise ValueError(f"field_schema must be one of {sorted(SCHEMAS)}, got {field_schema!r}")
+    return s
+
+
+def f64_bits(x: float) -> int:
+    return struct.unpack("<Q", struct.pack("<d", x))[0]
+
+
+def exact_double(v) -> Optional[float]:
+    """The double equal to the int / float v (Python compares the two kinds exactly), None when there is none: a
+    bool, another type, a NaN, an int no double holds."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        return None
+    if isinstance(v, float):
+        return None if v != v else v
+    try:
+        f = float(v)
+    except OverflowError:
+        return None
+    return f if f == v else None
+
+
+class _Decline(Exception):
+    pass
+
+
+class _Key:
+    def __init__(self, schema: str):
+        self.schema = schema
+        self.col: Optional[int] = None     # the engine column; None = not live (poisoned, or its column was lost)
+        self.codes: Dict[str, int] = {}    # keyword -> code
+
+    @property
+    def kind(self) -> int:
+        return PAY_F64 if self.schema == "number" else PAY_U32
+
+
+class PayloadIndex:
+    def __init__(self):
+        self.keys: Dict[str, _Key] = {}
+        self.device_evals = 0              # masks evaluated by hx_payload_mask
+        self.python_evals = 0              # masks evaluated by the Python loop
+        self.declined: Dict[str, int] = {}  # reason -> filters that did not compile
+
+    # -- definitions -----------------------------------------------------------------------------------------------
+    def definitions(self) -> Dict[str, str]:
+        return {k: v.schema for k, v in self.keys.items()}
+
+    def live(self, key: str) -> bool:
+        return key in self.keys and self.keys[key].col is not None
+
+    def live_keys(self) -> List[str]:
+        return [k for k, v in self.keys.items() if v.col is not None]
+
+    # -- encoder ---------------------------------------------------------------------------------------------------
+    def encode(self, key: str, payloads) -> Optional[np.ndarray]:
+        """The cells of `payloads` for `key` (np.uint32 codes or np.uint64 bit patterns of doubles), or None when a
+        value poisons the key.  Keywords met for the first time get the next code; a poisoned call leaves the
+        dictionary with codes no row uses, which is harmless."""
+        k = self.keys[key]
+        get, missing = _filters._get, _filters._MISSING
+        n = len(payloads)
+        if k.schema == "number":
+            vals = np.zeros(n, np.float64)
+            special: List[Tuple[int, int]] = []
+            for r, p in enumerate(payloads):
+                v = get(p, key)
+                if v is missing:
+                    special.append((r, F64_MISSING))
+                elif v is None:
+                    special.append((r, F64_NULL))
+                elif isinstance(v, bool) or not isinstance(v, (int, float)):
+                    return None
+                elif isinstance(v, float):
+                    if v != v:
+                        return None
+                    vals[r] = v
+                else:
+                    if abs(v) > 2 ** 53:
+                        return None
+                    vals[r] = float(v)
+            cells = vals.view(np.uint64).copy()
+            for r, bits in special:
+                cells[r] = bits
+            return cells
+        cells = np.empty(n, np.uint32)
+        if k.schema == "bool":
+            for r, p in enumerate(payloads):
+                v = get(p, key)
+                if v is missing:
+                    cells[r] = U32_MISSING
+                elif v is None:
+                    cells[r] = U32_NULL
+                elif isinstance(v, bool):
+                    cells[r] = 1 if v else 0
+                else:
+                    return None
+            return cells
+        codes = k.codes
+        for r, p in enumerate(payloads):
+            v = get(p, key)
+            if v is missing:
+                cells[r] = U32_MISSING
+            elif v is None:
+                cells[r] = U32_NULL
+            elif type(v) is str:
+                c = codes.get(v)
+                if c is None:
+                    if len(codes) >= _MAX_KEYWORDS:
+                        return None
+                    c = codes[v] = len(codes)
+                cells[r] = c
+            else:
+                return None
+        return cells
+
+    # -- compiler --------------------------------------------------------------------------------------------------
+    def compile(self, flt, id_rows: Optional[Callable[[], Dict[Any, int]]] = None):
+        """(ops, sets) for hx_payload_mask -- ops: (op, column, imm) triples, sets: sorted np.uint32 / np.float64
+        arrays -- or None when the filter is declined (the reason is counted in `declined`).  Unknown clause names of
+        the filter itself raise ValueError, as filters.matches does.  id_rows: gives the collection's id -> row
+        dictionary (for has_id)."""
+        if flt and isinstance(flt, dict):
+            unknown = set(flt) - set(_CLAUSES)
+            if unknown:
+                raise ValueError(f"unsupported filter clause(s): {sorted(unknown, key=str)}")
+        ops: List[Tuple[int, int, int]] = []
+        sets: List[np.ndarray] = []
+        try:
+            self._filter(flt, ops, sets, id_rows)
+            if len(ops) > MAX_OPS:
+                raise _Decline("program too long")
+            depth = 0
+            for op, _, _ in ops:
+                depth += -1 if op in (AND, OR) else 0 if op == NOT else 1
+                if depth > MAX_STACK:
+                    raise _Decline("stack deeper than 32")
+        except _Decline as d:
+            reason = str(d)
+            self.declined[reason] = self.declined.get(reason, 0) + 1
+            return None
+        return ops, sets
+
+    def _filter(self, flt, ops, sets, id_rows):
+        if not flt:
+            ops.append((TRUE, 0, 0))
+            return
+        if not isinstance(flt, dict):
+            raise _Decline("filter is not a dict")
+        if set(flt) - set(_CLAUSES):
+            raise _Decline("unknown clause in a nested filter")      # (matches raises only where evaluation reaches it)
+        terms = 0
+        for c in _filters._as_list(flt.get("must")):
+            self._condition(c, ops, sets, id_rows)
+            if terms:
+                ops.append((AND, 0, 0))
+            terms += 1
+        for c in _filters._as_list(flt.get("must_not")):
+            self._condition(c, ops, sets, id_rows)
+            ops.append((NOT, 0, 0))
+            if terms:
+                ops.append((AND, 0, 0))
+            terms += 1
+        should = _filters._as_list(flt.get("should"))
+        for i, c in enumerate(should):
+            self._condition(c, ops, sets, id_rows)
+            if i:
+                ops.append((OR, 0, 0))
+        if should:
+            if terms:
+                ops.append((AND, 0, 0))
+            terms += 1
+        if not terms:
+            ops.append((TRUE, 0, 0))
+
+    def _key(self, key) -> _Key:
+        if not isinstance(key, str):
+            raise _Decline("key is not a string")
+        k = self.keys.get(key)
+        if k is None:
+            raise _Decline("unindexed key")
+        if k.col is None:
+            raise _Decline("poisoned key")
+        return k
+
+    def _condition(self, c, ops, sets, id_rows):
+        if not isinstance(c, dict):
+            raise _Decline("condition is not a dict")
+        if any(k in c for k in _CLAUSES):
+            return self._filter(c, ops, sets, id_rows)
+        if "has_id" in c:
+            listed = c["has_id"]
+            if not isinstance(listed, (list, tuple)) or id_rows is None:
+                raise _Decline("has_id form")
+            rows = id_rows()
+            if rows is None:
+                raise _Decline("has_id over duplicate ids")
+            found = set()
+            for i in listed:
+                try:
+                    r = rows.get(i)
+                except TypeError:                     # unhashable: equal to no id
+                    r = None
+                if r is not None and type(i) is str:
+                    found.add(r)
+            sets.append(np.array(sorted(found), np.uint32))
+            ops.append((ROW_IN, 0, len(sets) - 1))
+            return
+        if "is_empty" in c or "is_null" in c:
+            what = "is_empty" if "is_empty" in c else "is_null"
+            if not isinstance(c[what], dict) or "key" not in c[what]:
+                raise _Decline(what + " form")
+            k = self._key(c[what]["key"])
+            if what == "is_empty":
+                ops.extend([(IS_MISSING, k.col, 0), (IS_NULL, k.col, 0), (OR, 0, 0)])
+            else:
+                ops.append((IS_NULL, k.col, 0))
+            return
+        if "key" in c:
+            if "match" in c:
+                return self._match(self._key(c["key"]), c["match"], ops, sets)
+            if "range" in c:
+                return self._range(self._key(c["key"]), c["range"], ops)
+        raise _Decline("unsupported condition")
+
+    @staticmethod
+    def _cell_of(k: _Key, v) -> Optional[int]:
+        """The cell a stored value equal to the constant v has (filters._match's rule for `value`: equal, and of the
+        same type or neither a bool), None when no stored value of the key's schema can equal it."""
+        if k.schema == "keyword":
+            return k.codes.get(v) if isinstance(v, str) else None
+        if k.schema == "bool":
+            return (1 if v else 0) if isinstance(v, bool) else None
+        d = exact_double(v)
+        return None if d is None else f64_bits(d)
+
+    def _set_of(self, k: _Key, listed) -> np.ndarray:
+        """The cells equal (Python's ==, as `in` compares) to an entry of the list."""
+        if not isinstance(listed, (list, tuple)):
+            raise _Decline("match list is not a list")
+        has_bool = any(isinstance(e, bool) for e in listed)
+        has_num = any(isinstance(e, (int, float)) and not isinstance(e, bool) for e in listed)
+        if has_bool and has_num:
+            raise _Decline("list mixes bools and numbers")
+        out = set()
+        for e in listed:
+            if k.schema == "keyword":
+                if isinstance(e, str) and e in k.codes:
+                    out.add(k.codes[e])
+            elif k.schema == "bool":                  # True == 1 and False == 0 under `in`
+                if isinstance(e, (bool, int, float)) and e == 0:
+                    out.add(0)
+                elif isinstance(e, (bool, int, float)) and e == 1:
+                    out.add(1)
+            else:
+                d = float(e) if isinstance(e, bool) else exact_double(e)
+                if d is not None:
+                    out.add(d + 0.0)                  # (-0.0 and 0.0 are one entry: -0.0 + 0.0 = 0.0)
+        if k.schema == "number":
+            return np.array(sorted(out), np.float64)
+        return np.array(sorted(out), np.uint32)
+
+    def _match(self, k: _Key, m, ops, sets):
+        if not isinstance(m, dict):
+            raise _Decline("match is not a dict")
+        if "value" in m:
+            v = m["value"]
+            if v is not None and not isinstance(v, (str, bool, int, float)):
+                raise _Decline("match value of an unsupported type")
+            cell = self._cell_of(k, v)
+            ops.append((FALSE, 0, 0) if cell is None else (EQ, k.col, cell))
+        elif "any" in m:
+            sets.append(self._set_of(k, m["any"]))
+            ops.append((IN, k.col, len(sets) - 1))
+        elif "except" in m:
+            sets.append(self._set_of(k, m["except"]))
+            ops.extend([(PRESENT, k.col, 0), (IN, k.col, len(sets) - 1), (NOT, 0, 0), (AND, 0, 0)])
+        elif "text" in m:
+            raise _Decline("match text")
+        else:
+            raise _Decline("unsupported match")
+
+    def _range(self, k: _Key, r, ops):
+        if not isinstance(r, dict):
+            raise _Decline("range is not a dict")
+        if k.schema != "number":                      # (filters._range: only numbers that are not bools are in a range)
+            ops.append((FALSE, 0, 0))
+            return
+        terms = 0
+        for name, op in (("gt", GT), ("gte", GE), ("lt", LT), ("lte", LE)):
+            b = r.get(name)
+            if b is None:
+                continue
+            if isinstance(b, bool) or not isinstance(b, (int, float)):
+                raise _Decline("range bound is not a number")
+            if b != b:
+                ops.append((FALSE, 0, 0))             # nothing is ordered against a NaN
+            else:
+                d = exact_double(b)
+                if d is None:
+                    raise _Decline("range bound is not an exact double")
+                ops.append((op, k.col, f64_bits(d)))
+            if terms:
+                ops.append((AND, 0, 0))
+            terms += 1
+        if not terms:
+            ops.append((PRESENT, k.col, 0))

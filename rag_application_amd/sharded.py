@@ -470,6 +470,7 @@ class ShardedHandler(QdrantHandler):
 
     _masked_search = False
     _point_deletes = False           # delete_points raises ValueError: nothing is sent to the ranks
+    _payload_indexes = False         # create_payload_index raises ValueError: payloads live on the front rank only
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
