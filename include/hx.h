@@ -352,6 +352,8 @@ int hx_release_mask_view(hx_index* h);
  * columns (a loaded index has none: they are derived from the payloads); hx_destroy frees them. */
 #define HX_PAY_U32 1
 #define HX_PAY_F64 2
+#define HX_PAY_LIST_U32 3   /* list-valued fields: one state per row -- missing, null, or a list of */
+#define HX_PAY_LIST_F64 4   /* k >= 0 elements: U32 codes below HX_PAY_U32_NULL, or doubles that are not NaN              */
 #define HX_PAY_U32_MISSING 0xFFFFFFFFu
 #define HX_PAY_U32_NULL    0xFFFFFFFEu
 #define HX_PAY_F64_MISSING 0x7FF80000FFFFFFFFull
@@ -367,6 +369,17 @@ int hx_payload_drop(hx_index* h, int32_t col);
  * the column unchanged, when filled + n > hx_count.  Returns when the cells are stored. */
 int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t n);
 int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled);
+/* The cells of rows [filled, filled + n) of a LIST column.  heads_host[i] = HX_PAY_U32_MISSING, HX_PAY_U32_NULL or the
+ * row's element count (0 = the empty list); values_host = the elements of the rows one after another: n_values uint32
+ * (HX_PAY_LIST_U32) or doubles (HX_PAY_LIST_F64).  On the device the column is a head plane (uint32 per row: missing,
+ * null, 0 = a list), int64 offsets [filled + 1] and one element plane (two for doubles: low words, high words).
+ * Refused, with the column unchanged: filled + n > hx_count, counts that do not sum to n_values, an element that is a
+ * reserved code (>= HX_PAY_U32_NULL) or a NaN, a column that is not a list column ("kind" in the message; likewise
+ * hx_payload_append on a list column), a column that would hold 2^31 elements or more.  hx_truncate cuts heads and
+ * offsets (the elements behind them are dead); hx_retain_rows compacts a list column that is filled to hx_count -- the
+ * heads with the rows, offsets and elements as the sparse CSR -- and drops one that lags. */
+int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* values_host,
+                            int64_t n_values);
 /* The program: postfix over a per-row boolean stack (at most HX_PAY_MAX_STACK deep, exactly one entry at the end).
  *   HX_PAY_TRUE / _FALSE                 push a constant
  *   HX_PAY_IS_MISSING / _IS_NULL / _PRESENT  col   push the cell's state (PRESENT = neither missing nor null)
@@ -375,6 +388,14 @@ int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled);
  *   HX_PAY_LT / _LE / _GT / _GE  col imm  F64 columns only, IEEE comparison with the double in imm
  *   HX_PAY_ROW_IN  imm = set index        the local row number is in the set (uint32 rows)
  *   HX_PAY_AND / _OR / _NOT               pop two (one), push the result
+ * List columns take IS_MISSING / IS_NULL / PRESENT (the row's state) and
+ *   HX_PAY_ANY_EQ  col imm                some element equals imm (as EQ compares)
+ *   HX_PAY_ANY_IN  col imm = set index    some element is in the set
+ *   HX_PAY_ANY_RANGE  col imm = set index HX_PAY_LIST_F64 only; the set is exactly two doubles lo <= hi: some element x
+ *                                         has lo <= x <= hi -- ONE element meets both bounds ([1, 10] is not in [4, 6])
+ *   HX_PAY_IS_EMPTY_LIST  col             the row holds a list with no element
+ * The ANY ops are false on a missing, null or empty row.  EQ / IN / LT / LE / GT / GE are refused on a list column, the
+ * four list ops on a scalar column.
  * EQ, IN and the comparisons are false on a missing or null cell.  A set is `n` values on the host, ascending (equal
  * neighbours allowed): uint32 for a U32 column and ROW_IN, doubles (no NaN) for an F64 column. */
 #define HX_PAY_TRUE 0
@@ -392,6 +413,10 @@ int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled);
 #define HX_PAY_AND 12
 #define HX_PAY_OR 13
 #define HX_PAY_NOT 14
+#define HX_PAY_ANY_EQ 15
+#define HX_PAY_ANY_IN 16
+#define HX_PAY_ANY_RANGE 17
+#define HX_PAY_IS_EMPTY_LIST 18
 typedef struct hx_pay_op {
   int32_t op;
   int32_t col;
@@ -405,13 +430,19 @@ typedef struct hx_pay_set {
  * hx_hybrid_query_*_masked, bits at or past hx_count zero.  n_kept (may be NULL) receives the number of set bits: the
  * call then synchronises `stream` once; with NULL nothing is read back and the call only enqueues work (the host
  * arguments are copied before it returns).  Refused before any device work: a referenced column that is unknown or not
- * filled to hx_count, a comparison on a U32 column, a set index out of range, a set that is not ascending, more than
+ * filled to hx_count, a comparison on a U32 column, a list op on a scalar column or a scalar op on a list column,
+ * ANY_RANGE on a U32 list column or with a set of other than two entries, a set index out of range, a set that is not ascending, more than
  * HX_PAY_MAX_OPS ops, a stack that would exceed HX_PAY_MAX_STACK entries or underflow or does not end with exactly one
  * entry. */
 int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets_host, int32_t n_sets,
                     uint32_t* mask_dev, int64_t* n_kept, void* stream);
-/* copy one cell to the host (4 bytes of a U32 column, 8 of an F64 column), as hx_debug_row does for vectors */
+/* copy one cell to the host (4 bytes of a U32 column, 8 of an F64 column), as hx_debug_row does for vectors; refused on
+ * a list column */
 int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host);
+/* copy one row of a list column to the host: *head = what hx_payload_append_lists took for it (missing, null or the
+ * element count), *count = its elements, of which the first min(count, cap) go to values_out (uint32 or doubles) */
+int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,
+                          int64_t* count);
 
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed

@@ -13,6 +13,7 @@
 //   k_csr_keep_len / k_csr_compact / k_csr_new_indptr   the document-major CSR: lengths of the kept documents, the
 //            segmented copy of their postings (coalesced over postings, min / max of the surviving weights fused in),
 //            the new offsets
+//   k_csr_compact_u32                  the same segmented copy for one 4-byte element plane of a payload list column
 #include "hx_common.hpp"
 #include "kernels.hpp"
 
@@ -191,6 +192,43 @@ void launch_csr_compact(const int64_t* indptr, const uint32_t* rows, const int64
   if (m <= 0) return;
   hipLaunchKernelGGL(k_csr_compact, dim3((unsigned)((m + CP_WG - 1) / CP_WG)), dim3(CP_WG), 0, st, indptr, rows, off, m, idx,
                      val, idx2, val2, mm);
+  HX_HIP(hipGetLastError());
+}
+
+// k_csr_compact for one 4-byte plane without weights: the elements of a payload list column (a
+// column of doubles calls it once per plane).  Same walk: 256 kept rows per workgroup, destination order.
+__global__ void __launch_bounds__(CP_WG) k_csr_compact_u32(const int64_t* __restrict__ indptr,
+                                                           const uint32_t* __restrict__ rows,
+                                                           const int64_t* __restrict__ off, int64_t m,
+                                                           const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
+  __shared__ int64_t s_src[CP_WG];
+  __shared__ int64_t s_dst[CP_WG + 1];
+  const int64_t j0 = (int64_t)blockIdx.x * CP_WG;
+  const int nd = (int)std::min<int64_t>(CP_WG, m - j0);
+  const int64_t o0 = off[j0];
+  if ((int)threadIdx.x < nd) {
+    s_src[threadIdx.x] = indptr[rows[j0 + threadIdx.x]];
+    s_dst[threadIdx.x] = off[j0 + threadIdx.x] - o0;
+  }
+  if (threadIdx.x == 0) s_dst[nd] = off[j0 + nd] - o0;
+  __syncthreads();
+  const int64_t total = s_dst[nd];
+  for (int64_t p = threadIdx.x; p < total; p += CP_WG) {
+    int a = 0, b = nd;               // the last row d with s_dst[d] <= p (empty rows share an offset)
+    while (b - a > 1) {
+      const int c = (a + b) >> 1;
+      if (s_dst[c] <= p) a = c;
+      else b = c;
+    }
+    dst[o0 + p] = src[s_src[a] + (p - s_dst[a])];
+  }
+}
+
+void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
+                            uint32_t* dst, hipStream_t st) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_csr_compact_u32, dim3((unsigned)((m + CP_WG - 1) / CP_WG)), dim3(CP_WG), 0, st, indptr, rows, off, m,
+                     src, dst);
   HX_HIP(hipGetLastError());
 }
 

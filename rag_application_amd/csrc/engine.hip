@@ -15,6 +15,7 @@
 #include <limits>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
 #include <cmath>
@@ -237,13 +238,21 @@ struct hx_index {
   // Payload index (hx_payload_*): columns of one (U32) or two (F64: low word, high word) planes of
   // uint32 per row, filled for rows [0, filled), filled <= n.  Ids are never reused.  A program and its sets travel
   // through one pinned staging buffer; pay_ev says when the device has taken the last one.
+  // A list column (HX_PAY_LIST_*): p0 = the head plane (missing / null / 0 = a list), off = int64
+  // offsets [filled + 1] into the element planes e0 (codes, or the low words of doubles) and e1 (the high words).
   struct PayCol {
     int id = 0, kind = 0;
     uint32_t* p0 = nullptr;
     uint32_t* p1 = nullptr;
     int64_t filled = 0, cap = 0;
+    int64_t* off = nullptr;
+    uint32_t* e0 = nullptr;
+    uint32_t* e1 = nullptr;
+    int64_t n_el = 0, el_cap = 0;
+    bool list() const { return kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64; }
   };
   std::vector<PayCol> pay;
+  int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap
   int pay_next_id = 0;
   uint8_t* pay_pin = nullptr;
   size_t pay_pin_cap = 0;
@@ -266,8 +275,12 @@ void launch_sparse_select(const SparseSelectArgs& a, hipStream_t st) {
 static void pay_free(hx_index::PayCol& c) {
   if (c.p0) (void)hipFree(c.p0);
   if (c.p1) (void)hipFree(c.p1);
-  c.p0 = c.p1 = nullptr;
-  c.filled = c.cap = 0;
+  if (c.off) (void)hipFree(c.off);
+  if (c.e0) (void)hipFree(c.e0);
+  if (c.e1) (void)hipFree(c.e1);
+  c.p0 = c.p1 = c.e0 = c.e1 = nullptr;
+  c.off = nullptr;
+  c.filled = c.cap = c.n_el = c.el_cap = 0;
 }
 
 static void reserve_rows(hx_index* h, int64_t want) {
@@ -1901,6 +1914,7 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   }
   if (const char* e = getenv("HX_DEBUG_TAIL_MIN")) h->tail_min_force = atoll(e);   // tests: force / forbid a tail index
   if (const char* e = getenv("HX_DEBUG_COMPACT_CHUNK")) h->compact_chunk = std::max<int64_t>(0, atoll(e));   // tests: many chunks
+  if (const char* e = getenv("HX_DEBUG_PAY_GRID")) h->pay_grid = (int)std::clamp<long long>(atoll(e), 0, 1 << 20);   // tests: the grid-stride loop
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);
     if (v >= 1 && v <= SCAN8_LOGCAP) h->scan_logcap = v;
@@ -2185,7 +2199,11 @@ int hx_truncate(hx_index* h, int64_t n_rows) {
   h->set_device();
   HX_HIP(hipDeviceSynchronize());
   h->ids.next = -1;
-  for (auto& c : h->pay) c.filled = std::min(c.filled, n_rows);
+  for (auto& c : h->pay) {
+    if (c.list() && c.filled > n_rows)     // (the elements past off[n_rows] are dead)
+      HX_HIP(hipMemcpy(&c.n_el, c.off + n_rows, 8, hipMemcpyDeviceToHost));
+    c.filled = std::min(c.filled, n_rows);
+  }
   if (n_rows == h->n && h->sp_rows <= n_rows) return 0;
   h->n = n_rows;
   h->tm_q8.rows = h->tm_q8s.rows = -1;
@@ -2335,6 +2353,36 @@ static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
   }
   DevTmp bounce, sp_idx2, sp_val2;
   if (bounce_bytes > 0) bounce.alloc((size_t)bounce_bytes);
+  // the list columns that cover every row (section 17): the head plane is in `arrs`; offsets and elements go the sparse
+  // CSR's way -- rows [0, first) stay, the kept rows behind them move to lbase + loff[j]
+  struct ListPlan {
+    hx_index::PayCol* c;
+    int64_t lbase = 0, moved = 0;
+    DevTmp lenoff, t0, t1;
+    int64_t* loff = nullptr;
+  };
+  std::vector<std::unique_ptr<ListPlan>> lists;
+  const int64_t lm = count - std::min(first, count);     // kept rows at or behind the first removed one
+  for (auto& c : h->pay) {
+    if (!c.list() || c.filled != n) continue;
+    auto lp = std::make_unique<ListPlan>();
+    lp->c = &c;
+    HX_HIP(hipMemcpy(&lp->lbase, c.off + std::min(first, count), 8, hipMemcpyDeviceToHost));
+    if (lm > 0) {
+      lp->lenoff.alloc((size_t)(lm + 1) * 8 * 2);
+      int64_t* len = (int64_t*)lp->lenoff.p;
+      lp->loff = len + (lm + 1);
+      HX_HIP(hipMemsetAsync(len + lm, 0, 8, st));
+      launch_csr_keep_len(c.off, rows + first, lm, len, st);
+      exclusive_scan_i64(len, lp->loff, lm, st);
+      HX_HIP(hipMemcpy(&lp->moved, lp->loff + lm, 8, hipMemcpyDeviceToHost));
+      if (lp->moved > 0) {
+        lp->t0.alloc((size_t)lp->moved * 4);
+        if (c.e1) lp->t1.alloc((size_t)lp->moved * 4);
+      }
+    }
+    lists.push_back(std::move(lp));
+  }
   // CSR: the documents [0, first) stay; kept documents [first, kept_sp) move to the offsets base + off[j]
   const int64_t m = std::max<int64_t>(kept_sp - first, 0);
   int64_t base = 0, moved = 0, new_nnz = 0;
@@ -2388,6 +2436,17 @@ static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
     HX_HIP(hipMemcpyAsync(got, mm, 12, hipMemcpyDeviceToHost, st));
   }
   if (m > 0) launch_csr_new_indptr(h->sp_indptr + first, off, m, base, st);
+  for (auto& lp : lists) {
+    hx_index::PayCol& c = *lp->c;
+    if (lp->moved > 0) {
+      launch_csr_compact_u32(c.off, rows + first, lp->loff, lm, c.e0, (uint32_t*)lp->t0.p, st);
+      if (c.e1) launch_csr_compact_u32(c.off, rows + first, lp->loff, lm, c.e1, (uint32_t*)lp->t1.p, st);
+      launch_copy_u32(lp->t0.p, c.e0 + lp->lbase, lp->moved, st);
+      if (c.e1) launch_copy_u32(lp->t1.p, c.e1 + lp->lbase, lp->moved, st);
+    }
+    if (lm > 0) launch_csr_new_indptr(c.off + first, lp->loff, lm, lp->lbase, st);
+    c.n_el = lp->lbase + lp->moved;
+  }
   HX_HIP(hipDeviceSynchronize());
 
   // ---- the index of the kept rows ----
@@ -3156,7 +3215,8 @@ static hx_index::PayCol& pay_col(hx_index* h, int32_t col) {
 int hx_payload_create(hx_index* h, int32_t kind, int32_t* col) {
   HX_TRY
   HX_CHECK(h && col, "NULL argument");
-  HX_CHECK(kind == HX_PAY_U32 || kind == HX_PAY_F64, "payload: kind must be HX_PAY_U32 or HX_PAY_F64");
+  HX_CHECK(kind == HX_PAY_U32 || kind == HX_PAY_F64 || kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64,
+           "payload: kind must be HX_PAY_U32, HX_PAY_F64, HX_PAY_LIST_U32 or HX_PAY_LIST_F64");
   HX_CHECK((int)h->pay.size() < HX_PAY_MAX_COLUMNS, "payload: an index holds at most 64 columns");
   hx_index::PayCol c;
   c.id = h->pay_next_id++;
@@ -3190,6 +3250,7 @@ int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t 
   auto& c = pay_col(h, col);
   HX_CHECK(n >= 0, "payload: n < 0");
   HX_CHECK(cells_host || n == 0, "payload: cells are NULL");
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_append_lists (column kind)");
   HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
   if (n == 0) return 0;
   h->set_device();
@@ -3230,10 +3291,144 @@ int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t 
   HX_CATCH
 }
 
+// grow a device array to `want` entries keeping the first `keep` (the new one is made before the old one goes)
+extern "C++" template <typename T>
+static T* pay_grown(const T* old, int64_t keep, int64_t want) {
+  T* a = nullptr;
+  if (hipMalloc((void**)&a, (size_t)want * sizeof(T)) != hipSuccess) throw Error("payload: out of device memory");
+  if (keep > 0 && hipMemcpy(a, old, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+    (void)hipFree(a);
+    throw Error("payload: device copy failed");
+  }
+  return a;
+}
+
+int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* values_host,
+                            int64_t n_values) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_append_lists needs a list column (column kind)");
+  HX_CHECK(n >= 0 && n_values >= 0, "payload: n < 0");
+  HX_CHECK((heads_host || n == 0) && (values_host || n_values == 0), "payload: cells are NULL");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  // ---- every refusal and every allocation before the column changes ----
+  std::vector<uint32_t> heads((size_t)n);
+  std::vector<int64_t> off((size_t)n + 1);
+  int64_t total = 0;
+  off[0] = c.n_el;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    const bool is_list = hd < HX_PAY_U32_NULL;
+    heads[(size_t)i] = is_list ? 0u : hd;
+    if (is_list) total += hd;
+    HX_CHECK(total <= n_values, "payload: the element counts of the heads do not sum to n_values");
+    off[(size_t)i + 1] = c.n_el + total;
+  }
+  HX_CHECK(total == n_values, "payload: the element counts of the heads do not sum to n_values");
+  HX_CHECK(c.n_el + total <= 0x7FFFFFFFll, "payload: a list column holds fewer than 2^31 elements");
+  std::vector<uint32_t> lo, hi;
+  if (f64) {
+    const uint64_t* v = (const uint64_t*)values_host;
+    const double* d = (const double*)values_host;
+    lo.resize((size_t)total);
+    hi.resize((size_t)total);
+    for (int64_t i = 0; i < total; ++i) {
+      HX_CHECK(d[i] == d[i], "payload: a list element is a NaN");
+      lo[(size_t)i] = (uint32_t)v[i];
+      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
+    }
+  } else {
+    const uint32_t* v = (const uint32_t*)values_host;
+    for (int64_t i = 0; i < total; ++i) HX_CHECK(v[i] < HX_PAY_U32_NULL, "payload: a list element is a reserved code");
+  }
+  if (n == 0) return 0;
+  h->set_device();
+  const int64_t want = c.filled + n, want_el = c.n_el + total;
+  uint32_t *np0 = nullptr, *ne0 = nullptr, *ne1 = nullptr;
+  int64_t* noff = nullptr;
+  int64_t nc = c.cap, nec = c.el_cap;
+  try {
+    if (want > c.cap || !c.off) {
+      nc = round_up(std::max<int64_t>(std::max(want, c.cap * 2), h->cap), 256);
+      HX_HIP(hipDeviceSynchronize());
+      np0 = pay_grown(c.p0, c.filled, nc);
+      noff = pay_grown(c.off, c.off ? c.filled + 1 : 0, nc + 1);
+    }
+    if (want_el > c.el_cap) {
+      nec = round_up(std::max<int64_t>(want_el, c.el_cap * 2), 256);
+      HX_HIP(hipDeviceSynchronize());
+      ne0 = pay_grown(c.e0, c.n_el, nec);
+      if (f64) ne1 = pay_grown(c.e1, c.n_el, nec);
+    }
+  } catch (...) {
+    for (void* q : {(void*)np0, (void*)noff, (void*)ne0, (void*)ne1})
+      if (q) (void)hipFree(q);
+    throw;
+  }
+  if (np0) {
+    if (c.p0) (void)hipFree(c.p0);
+    if (c.off) (void)hipFree(c.off);
+    c.p0 = np0;
+    c.off = noff;
+    c.cap = nc;
+  }
+  if (ne0) {
+    if (c.e0) (void)hipFree(c.e0);
+    if (c.e1) (void)hipFree(c.e1);
+    c.e0 = ne0;
+    c.e1 = ne1;
+    c.el_cap = nec;
+  }
+  // (the cells behind `filled` and the elements behind n_el are dead until `filled` moves: a failed copy changes nothing)
+  HX_HIP(hipMemcpy(c.p0 + c.filled, heads.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(c.off + c.filled, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+  if (total > 0) {
+    HX_HIP(hipMemcpy(c.e0 + c.n_el, f64 ? (const void*)lo.data() : values_host, (size_t)total * 4, hipMemcpyHostToDevice));
+    if (f64) HX_HIP(hipMemcpy(c.e1 + c.n_el, hi.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+  }
+  c.filled = want;
+  c.n_el = want_el;
+  HX_CATCH
+}
+
+int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,
+                          int64_t* count) {
+  HX_TRY
+  HX_CHECK(h && head && count, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_debug_list needs a list column (column kind)");
+  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
+  HX_CHECK(cap >= 0 && (values_out || cap == 0), "payload: bad output buffer");
+  h->set_device();
+  uint32_t hd = 0;
+  int64_t o[2] = {0, 0};
+  HX_HIP(hipMemcpy(&hd, c.p0 + row, 4, hipMemcpyDeviceToHost));
+  HX_HIP(hipMemcpy(o, c.off + row, 16, hipMemcpyDeviceToHost));
+  const int64_t len = o[1] - o[0];
+  HX_CHECK(len >= 0 && o[0] >= 0 && o[1] <= c.n_el, "payload: corrupt list offsets");
+  *count = len;
+  *head = hd >= HX_PAY_U32_NULL ? hd : (uint32_t)len;
+  const int64_t k = std::min(len, cap);
+  if (k <= 0) return 0;
+  if (c.kind == HX_PAY_LIST_U32) {
+    HX_HIP(hipMemcpy(values_out, c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<uint32_t> lo((size_t)k), hi((size_t)k);
+    HX_HIP(hipMemcpy(lo.data(), c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+    HX_HIP(hipMemcpy(hi.data(), c.e1 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+    uint64_t* out = (uint64_t*)values_out;
+    for (int64_t i = 0; i < k; ++i) out[i] = ((uint64_t)hi[(size_t)i] << 32) | lo[(size_t)i];
+  }
+  HX_CATCH
+}
+
 int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host) {
   HX_TRY
   HX_CHECK(h && out_host, "NULL argument");
   auto& c = pay_col(h, col);
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_debug_list (column kind)");
   HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
   h->set_device();
   HX_HIP(hipMemcpy(out_host, c.p0 + row, 4, hipMemcpyDeviceToHost));
@@ -3253,17 +3448,26 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
   int depth = 0;
   for (int i = 0; i < n_ops; ++i) {
     const hx_pay_op& o = ops[i];
-    PayOpDev d{0u, 0u, o.imm, nullptr, nullptr};
+    PayOpDev d{0u, 0u, o.imm, nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
     int pops = 0;
     const hx_index::PayCol* c = nullptr;
-    const bool reads_col = o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_GE;
+    const bool list_op = o.op >= HX_PAY_ANY_EQ && o.op <= HX_PAY_IS_EMPTY_LIST;
+    const bool reads_col = (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_GE) || list_op;
     if (reads_col) {
       c = &pay_col(h, o.col);
       HX_CHECK(c->filled == h->n, "payload: column " + std::to_string(o.col) + " is not filled to the index's row count");
       d.p0 = c->p0;
       d.p1 = c->kind == HX_PAY_F64 ? c->p1 : nullptr;
+      if (c->list()) {                 // (filled == hx_count > 0 below: off is allocated; no element = never read)
+        d.off = c->off;
+        d.e0 = c->e0;
+        d.e1 = c->kind == HX_PAY_LIST_F64 ? c->e1 : nullptr;
+      }
+      HX_CHECK(!list_op || c->list(), "payload: ANY_EQ / ANY_IN / ANY_RANGE / IS_EMPTY_LIST need a list column");
+      HX_CHECK(!(o.op >= HX_PAY_EQ && o.op <= HX_PAY_GE) || !c->list(),
+               "payload: EQ / IN / LT / LE / GT / GE need a scalar column (a list column takes the ANY ops)");
     }
-    const bool f64 = c && c->kind == HX_PAY_F64;
+    const bool f64 = c && (c->kind == HX_PAY_F64 || c->kind == HX_PAY_LIST_F64);
     switch (o.op) {
       case HX_PAY_TRUE: d.op = PAY_D_TRUE; break;
       case HX_PAY_FALSE: d.op = PAY_D_FALSE; break;
@@ -3280,11 +3484,17 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
       case HX_PAY_AND: d.op = PAY_D_AND; pops = 2; break;
       case HX_PAY_OR: d.op = PAY_D_OR; pops = 2; break;
       case HX_PAY_NOT: d.op = PAY_D_NOT; pops = 1; break;
+      case HX_PAY_ANY_EQ: d.op = f64 ? PAY_D_ANY_EQ_F64 : PAY_D_ANY_EQ_U32; break;
+      case HX_PAY_ANY_IN: d.op = f64 ? PAY_D_ANY_IN_F64 : PAY_D_ANY_IN_U32; break;
+      case HX_PAY_ANY_RANGE: d.op = PAY_D_ANY_RANGE; break;
+      case HX_PAY_IS_EMPTY_LIST: d.op = PAY_D_IS_EMPTY_LIST; break;
       default: throw Error("payload: unknown op " + std::to_string(o.op));
     }
     if (o.op >= HX_PAY_LT && o.op <= HX_PAY_GE) HX_CHECK(f64, "payload: LT / LE / GT / GE need an F64 column");
-    if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN) {
+    if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(f64, "payload: ANY_RANGE needs an F64 list column");
+    if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN || o.op == HX_PAY_ANY_IN || o.op == HX_PAY_ANY_RANGE) {
       HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
+      if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(sets[o.imm].n == 2, "payload: the set of ANY_RANGE holds exactly two doubles, lo <= hi");
       const int8_t kind = f64 ? 2 : 1;
       HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == kind, "payload: one set used as uint32 and as double");
       set_kind[(size_t)o.imm] = kind;
@@ -3338,7 +3548,15 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
   uint8_t* dev = (uint8_t*)h->ws.get(WS_PAY_PROG, bytes);
   for (int i = 0; i < n_ops; ++i) {
     PayOpDev& d = prog[(size_t)i];
-    if (d.op != PAY_D_ROW_IN && d.op != PAY_D_IN_U32 && d.op != PAY_D_IN_F64) continue;
+    if (d.op == PAY_D_ANY_RANGE) {     // (two doubles, checked above: the closed interval travels in the op itself)
+      const uint64_t* v = (const uint64_t*)sets[(size_t)d.imm].vals;
+      d.imm = v[0];
+      d.imm2 = v[1];
+      continue;
+    }
+    if (d.op != PAY_D_ROW_IN && d.op != PAY_D_IN_U32 && d.op != PAY_D_IN_F64 && d.op != PAY_D_ANY_IN_U32 &&
+        d.op != PAY_D_ANY_IN_F64)
+      continue;
     const size_t s = (size_t)d.imm;
     d.cnt = (uint32_t)sets[s].n;
     d.imm = (uint64_t)(uintptr_t)(dev + set_off[s]);
@@ -3355,7 +3573,7 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
     kept = (uint32_t*)h->ws.get(WS_PAY_KEPT, 4);
     HX_HIP(hipMemsetAsync(kept, 0, 4, st));
   }
-  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, st);
+  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, h->pay_grid, st);
   if (n_kept) {
     uint32_t* pin = (uint32_t*)host_pin(h) + 14;
     HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));

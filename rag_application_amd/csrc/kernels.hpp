@@ -406,20 +406,33 @@ void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t 
 // One op of a program as the kernel reads it: engine.hip resolves the columns of hx_pay_op to their planes (p0 = the
 // cell of a U32 column or the low word of an F64 cell, p1 = its high word or NULL) and the sets to device pointers
 // (imm; cnt = entries).  Codes from PAY_D_FIRST_COL on read a column.
+// A list column gives p0 = its head plane (p1 = NULL: the head reads as a U32 cell), off = its
+// int64 offsets [n + 1] and e0 / e1 = its element planes (e1 = the high words of doubles or NULL).  Codes from
+// PAY_D_FIRST_LIST on walk the elements; ANY_RANGE carries its closed interval in imm / imm2 (the bits of two doubles).
 enum PayDevOp : uint32_t {
   PAY_D_TRUE = 0, PAY_D_FALSE, PAY_D_AND, PAY_D_OR, PAY_D_NOT, PAY_D_ROW_IN,
   PAY_D_FIRST_COL, PAY_D_IS_MISSING = PAY_D_FIRST_COL, PAY_D_IS_NULL, PAY_D_PRESENT, PAY_D_EQ_U32, PAY_D_IN_U32,
-  PAY_D_EQ_F64, PAY_D_IN_F64, PAY_D_LT, PAY_D_LE, PAY_D_GT, PAY_D_GE
+  PAY_D_EQ_F64, PAY_D_IN_F64, PAY_D_LT, PAY_D_LE, PAY_D_GT, PAY_D_GE,
+  PAY_D_FIRST_LIST, PAY_D_IS_EMPTY_LIST = PAY_D_FIRST_LIST, PAY_D_ANY_EQ_U32, PAY_D_ANY_IN_U32, PAY_D_ANY_EQ_F64,
+  PAY_D_ANY_IN_F64, PAY_D_ANY_RANGE
 };
 struct PayOpDev {
   uint32_t op, cnt;
   uint64_t imm;
   const uint32_t* p0;
   const uint32_t* p1;
+  const int64_t* off;
+  const uint32_t* e0;
+  const uint32_t* e1;
+  uint64_t imm2;
 };
 constexpr int PAY_INLINE_SET = 8;   // sets up to here are compared entry by entry, larger ones searched
 // mask[ceil(n / 32)] = the verdicts of the program over rows [0, n) (bits at or past n zero); *kept += their number
-// when kept is not NULL (the caller zeroes it)
-void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, hipStream_t st);
+// when kept is not NULL (the caller zeroes it).  grid_cap > 0 caps the grid (HX_DEBUG_PAY_GRID: tests).
+void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, int grid_cap,
+                         hipStream_t st);
+// compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
+void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
+                            uint32_t* dst, hipStream_t st);
 
 }  // namespace hx

@@ -11,6 +11,9 @@
 //                    binary search of a large set, whose trip count is uniform too.  A plane is loaded once per pass:
 //                    consecutive ops on the same column reuse the registers.  The wave's 64 verdicts of a row group are
 //                    combined with a ballot and written by lane 0 as two ordinary 4-byte stores.
+//                    A list column (a head plane, int64 offsets, element planes) is matched by
+//                    the ANY_* ops: the wave walks the contiguous element run of its rows in chunks of 64, one element
+//                    per lane, and each row lane picks the bits of its own segment out of the chunk's ballot.
 #include "hx_common.hpp"
 #include "kernels.hpp"
 
@@ -45,6 +48,11 @@ __device__ __forceinline__ bool pay_in_set(const T* __restrict__ s, uint32_t cnt
   return *b == v;
 }
 
+// bits [0, k) of a ballot, k in [0, 64]
+__device__ __forceinline__ unsigned long long pay_low_bits(uint32_t k) {
+  return k >= 64u ? ~0ull : (1ull << k) - 1ull;
+}
+
 __global__ void __launch_bounds__(PAY_WG) k_payload_mask(const PayOpDev* __restrict__ prog, int n_ops, int64_t n,
                                                          uint32_t* __restrict__ mask, uint32_t* __restrict__ kept) {
   const int lane = threadIdx.x & (WAVE - 1);
@@ -76,6 +84,52 @@ __global__ void __launch_bounds__(PAY_WG) k_payload_mask(const PayOpDev* __restr
           hi[u] = (op.p1 && in[u]) ? op.p1[row[u]] : PAY_NAN_HI;
         }
       }
+      // A list op: the rows of the pass own ONE contiguous element run [S, E) of the column (both
+      // offsets are uniform: scalar loads).  The wave walks it 64 elements at a time -- lane j tests element base + j,
+      // the 64 verdicts are balloted -- and every row lane ORs the bits of its own segment [rs, re) (relative to S; the
+      // engine keeps a column below 2^31 elements) into its verdict.  The trip count is the wave's, not the lane's: a
+      // long row costs the wave its length / 64 steps, nothing waits for one lane.  Rows at or past n own no element.
+      uint32_t lhit = 0u;                 // bit u = the verdict of row group u
+      if (code >= PAY_D_FIRST_LIST) {
+        const int64_t r0 = (int64_t)__builtin_amdgcn_readfirstlane((int)g0) * WAVE;
+        const int64_t S = op.off[r0], E = op.off[std::min<int64_t>(r0 + PAY_U * WAVE, n)];
+        uint32_t rs[PAY_U], re[PAY_U];
+#pragma unroll
+        for (int u = 0; u < PAY_U; ++u) {
+          rs[u] = in[u] ? (uint32_t)(op.off[row[u]] - S) : 0u;
+          re[u] = in[u] ? (uint32_t)(op.off[row[u] + 1] - S) : 0u;
+        }
+        if (code == PAY_D_IS_EMPTY_LIST) {
+#pragma unroll
+          for (int u = 0; u < PAY_U; ++u) lhit |= (lo[u] == 0u && rs[u] == re[u] ? 1u : 0u) << u;
+        } else {
+          const double c = __longlong_as_double((long long)op.imm), c2 = __longlong_as_double((long long)op.imm2);
+          for (int64_t base = S; base < E; base += WAVE) {
+            const int64_t e = base + lane;
+            const bool ok = e < E;
+            const uint32_t vl = ok ? op.e0[e] : 0u;
+            const uint32_t vh = (ok && op.e1) ? op.e1[e] : 0u;
+            const double x = pay_f64(vl, vh);
+            bool p = false;
+            switch (code) {
+              case PAY_D_ANY_EQ_U32: p = vl == (uint32_t)op.imm; break;
+              case PAY_D_ANY_IN_U32: p = pay_in_set<uint32_t>((const uint32_t*)op.imm, op.cnt, vl); break;
+              case PAY_D_ANY_EQ_F64: p = x == c; break;
+              case PAY_D_ANY_IN_F64: p = pay_in_set<double>((const double*)op.imm, op.cnt, x); break;
+              case PAY_D_ANY_RANGE: p = c <= x && x <= c2; break;
+              default: break;
+            }
+            const unsigned long long hits = __ballot(ok && p);
+            const uint32_t rel = (uint32_t)(base - S);
+#pragma unroll
+            for (int u = 0; u < PAY_U; ++u) {
+              const uint32_t a = rs[u] > rel ? std::min(rs[u] - rel, (uint32_t)WAVE) : 0u;
+              const uint32_t b = re[u] > rel ? std::min(re[u] - rel, (uint32_t)WAVE) : 0u;
+              lhit |= ((hits & pay_low_bits(b) & ~pay_low_bits(a)) != 0ull ? 1u : 0u) << u;
+            }
+          }
+        }
+      }
 #pragma unroll
       for (int u = 0; u < PAY_U; ++u) {
         const bool missing = hi[u] == PAY_NAN_HI && lo[u] == 0xFFFFFFFFu;
@@ -101,6 +155,8 @@ __global__ void __launch_bounds__(PAY_WG) k_payload_mask(const PayOpDev* __restr
           case PAY_D_LE: b = x <= c; break;
           case PAY_D_GT: b = x > c; break;
           case PAY_D_GE: b = x >= c; break;
+          case PAY_D_IS_EMPTY_LIST: case PAY_D_ANY_EQ_U32: case PAY_D_ANY_IN_U32: case PAY_D_ANY_EQ_F64:
+          case PAY_D_ANY_IN_F64: case PAY_D_ANY_RANGE: b = (lhit >> u) & 1u; break;
           default: break;
         }
         stack[u] = (s << 1) | (b ? 1u : 0u);
@@ -120,10 +176,12 @@ __global__ void __launch_bounds__(PAY_WG) k_payload_mask(const PayOpDev* __restr
   if (kept && lane == 0 && total) atomicAdd(kept, total);
 }
 
-void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, hipStream_t st) {
+void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, int grid_cap,
+                         hipStream_t st) {
   if (n <= 0) return;
   const int64_t rows_per_wg = (int64_t)PAY_WG * PAY_U;
-  const unsigned grid = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, PAY_GRID_MAX);
+  unsigned grid = (unsigned)std::min<int64_t>((n + rows_per_wg - 1) / rows_per_wg, PAY_GRID_MAX);
+  if (grid_cap > 0) grid = std::min(grid, (unsigned)grid_cap);
   hipLaunchKernelGGL(k_payload_mask, dim3(grid), dim3(PAY_WG), 0, st, prog, n_ops, n, mask, kept);
   HX_HIP(hipGetLastError());
 }

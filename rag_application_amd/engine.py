@@ -16,7 +16,7 @@ from ._lib import HX_MODE_H1, HX_MODE_TREE, HxError, HxParams, HxProf, HxStats, 
 from .filters import pack_rows
 
 # payload index (hx.h): the column kinds; the cell codes and the ops of a program are in payload_index.py
-PAY_U32, PAY_F64 = 1, 2
+PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64 = 1, 2, 3, 4
 
 SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_256_limit",
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
@@ -396,7 +396,8 @@ class HxIndex:
 
     # -- payload index (hx.h: hx_payload_*; payload_index.py compiles filters to the programs) ----------------------
     def payload_create(self, kind: int) -> int:
-        """A new empty column of `kind` (PAY_U32 / PAY_F64); returns its id (hx_payload_create)."""
+        """A new empty column of `kind` (PAY_U32 / PAY_F64 / PAY_LIST_U32 / PAY_LIST_F64); returns its id
+        (hx_payload_create)."""
         col = C.c_int32()
         check(_lib.lib().hx_payload_create(self._h, int(kind), C.byref(col)))
         return col.value
@@ -411,6 +412,26 @@ class HxIndex:
         if cells.dtype not in (np.uint32, np.uint64, np.float64) or cells.ndim != 1:
             raise TypeError("payload cells: a 1-d np.uint32 (U32 column) or np.uint64 / np.float64 (F64 column) array")
         check(_lib.lib().hx_payload_append(self._h, int(col), _ptr(cells), cells.shape[0]))
+
+    def payload_append_lists(self, col: int, heads: np.ndarray, values: np.ndarray) -> None:
+        """The cells of the next len(heads) rows of a list column (hx_payload_append_lists): heads np.uint32 -- MISSING,
+        NULL or the row's element count --, values the rows' elements one after another, np.uint32 codes (PAY_LIST_U32)
+        or np.float64 (PAY_LIST_F64)."""
+        heads, values = np.ascontiguousarray(heads), np.ascontiguousarray(values)
+        if heads.dtype != np.uint32 or heads.ndim != 1 or values.dtype not in (np.uint32, np.float64) or values.ndim != 1:
+            raise TypeError("payload lists: 1-d np.uint32 heads and 1-d np.uint32 / np.float64 values")
+        check(_lib.lib().hx_payload_append_lists(self._h, int(col), _ptr(heads), heads.shape[0], _ptr(values),
+                                                 values.shape[0]))
+
+    def payload_list(self, col: int, row: int, kind: int):
+        """One row of a list column (hx_payload_debug_list): (head, elements) -- head = MISSING, NULL or the element
+        count; elements np.uint32 codes or np.float64."""
+        head, count = C.c_uint32(), C.c_int64()
+        check(_lib.lib().hx_payload_debug_list(self._h, int(col), int(row), C.byref(head), None, 0, C.byref(count)))
+        out = np.zeros(max(count.value, 1), dtype=np.uint32 if kind == PAY_LIST_U32 else np.float64)
+        check(_lib.lib().hx_payload_debug_list(self._h, int(col), int(row), C.byref(head), _ptr(out), count.value,
+                                               C.byref(count)))
+        return head.value, out[:count.value]
 
     def payload_rows(self, col: int) -> int:
         n = C.c_int64()

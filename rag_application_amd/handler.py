@@ -147,18 +147,27 @@ class _Collection:
             self._poison(key)
         elif len(pi.keys) >= _pindex.MAX_COLUMNS:
             raise ValueError(f"a collection takes at most {_pindex.MAX_COLUMNS} payload indexes")
-        k = pi.keys[key] = _pindex._Key(schema)
+        k = _pindex._Key(schema)
+        if k.is_list and not hasattr(self.index, "payload_append_lists"):
+            raise ValueError("this collection's engine index has no list columns")
+        pi.keys[key] = k
         cells = pi.encode(key, self.payloads)
         if cells is None:
             return False
         col = self.index.payload_create(k.kind)
         try:
-            self.index.payload_append(col, cells)
+            self._append_cells(k, col, cells)
         except Exception:
             self.index.payload_drop(col)
             raise
         k.col = col
         return True
+
+    def _append_cells(self, k, col: int, cells) -> None:
+        if k.is_list:                                     # (heads, values): hx_payload_append_lists
+            self.index.payload_append_lists(col, cells[0], cells[1])
+        else:
+            self.index.payload_append(col, cells)
 
     def delete_payload_index(self, key: str) -> bool:
         pi = getattr(self, "pindex", None)
@@ -178,7 +187,7 @@ class _Collection:
             try:
                 cells = pi.encode(key, payloads)
                 if cells is not None:
-                    self.index.payload_append(pi.keys[key].col, cells)
+                    self._append_cells(pi.keys[key], pi.keys[key].col, cells)
                     continue
             except Exception as e:
                 logging.warning("payload index: appending to %r failed, the key is dropped: %s", key, e)
@@ -317,8 +326,12 @@ class QdrantHandler:
         then evaluated by one kernel over the collection's columns instead of a Python loop over its payloads
         (payload_index.py); the results are the same.  Returns True when the field is live, False when a stored value is
         not of the schema (a list, a dict, another type, NaN, an int beyond 2^53): such a field stays on the Python path.
-        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload columns; KeyError for
-        an unknown collection."""
+        List-valued fields (the reference's `languages`, `entities`, `relationships`) take the opt-in schemas
+        "keyword_list" | "number_list" ("integer_list" / "float_list") | "bool_list": a value is then None, a list of
+        values of the element schema or one such value (the one-element list); a tuple, a nested list or dict, a None
+        element or an element of another type makes the field stay on the Python path.
+        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload (or list) columns;
+        KeyError for an unknown collection."""
         try:
             if not self._payload_indexes:
                 raise ValueError("create_payload_index is not supported on a sharded collection")

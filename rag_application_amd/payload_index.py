@@ -15,9 +15,16 @@ A row's value: missing -> MISSING, None -> NULL, a value of the key's schema -> 
 `str` (keyword), a `bool` (bool), an `int` / `float` that is not a bool, not a NaN and -- an int -- at most 2^53 in
 magnitude (number: every stored number is then an exact double, and Python's exact int / float comparison is IEEE's).
 Anything else (a list, a dict, a value of another type, NaN, an oversized int) poisons the key: its column is
-dropped and every filter that mentions the key is declined until the index on it is created again."""
+dropped and every filter that mentions the key is declined until the index on it is created again.
+
+List schemas ("keyword_list" | "number_list" | "bool_list") are opt-in: a row's value is then
+missing, None, or a `list` of values of the element schema ([] included); a bare scalar of the element schema is stored
+as the one-element list (filters._values makes the two equivalent in every clause).  A tuple (() is not [] to
+is_empty), a nested list or dict, a None element, a NaN, an oversized int or an element of another type poisons the
+key.  The clauses compile to the list ops: one element has to meet a whole `range`, as filters._range asks."""
 from __future__ import annotations
 
+import math
 import struct
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -26,13 +33,16 @@ import numpy as np
 from . import filters as _filters
 
 # hx.h
-PAY_U32, PAY_F64 = 1, 2
+PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64 = 1, 2, 3, 4
 U32_MISSING, U32_NULL = 0xFFFFFFFF, 0xFFFFFFFE
 F64_MISSING, F64_NULL = 0x7FF80000FFFFFFFF, 0x7FF80000FFFFFFFE
 MAX_STACK, MAX_OPS, MAX_COLUMNS = 32, 4096, 64
-(TRUE, FALSE, IS_MISSING, IS_NULL, PRESENT, EQ, IN, LT, LE, GT, GE, ROW_IN, AND, OR, NOT) = range(15)
+(TRUE, FALSE, IS_MISSING, IS_NULL, PRESENT, EQ, IN, LT, LE, GT, GE, ROW_IN, AND, OR, NOT, ANY_EQ, ANY_IN, ANY_RANGE,
+ IS_EMPTY_LIST) = range(19)
 
-SCHEMAS = {"keyword": "keyword", "number": "number", "integer": "number", "float": "number", "bool": "bool"}
+SCHEMAS = {"keyword": "keyword", "number": "number", "integer": "number", "float": "number", "bool": "bool",
+           "keyword_list": "keyword_list", "number_list": "number_list", "integer_list": "number_list",
+           "float_list": "number_list", "bool_list": "bool_list"}
 _CLAUSES = ("must", "should", "must_not")
 _MAX_KEYWORDS = U32_NULL            # codes 0 .. 0xFFFFFFFD
 
@@ -73,7 +83,17 @@ class _Key:
         self.codes: Dict[str, int] = {}    # keyword -> code
 
     @property
+    def is_list(self) -> bool:
+        return self.schema.endswith("_list")
+
+    @property
+    def elem(self) -> str:             # the schema of a cell, or of a list's elements
+        return self.schema[:-5] if self.is_list else self.schema
+
+    @property
     def kind(self) -> int:
+        if self.is_list:
+            return PAY_LIST_F64 if self.elem == "number" else PAY_LIST_U32
         return PAY_F64 if self.schema == "number" else PAY_U32
 
 
@@ -102,6 +122,8 @@ class PayloadIndex:
         k = self.keys[key]
         get, missing = _filters._get, _filters._MISSING
         n = len(payloads)
+        if k.is_list:
+            return self._encode_lists(k, key, payloads)
         if k.schema == "number":
             vals = np.zeros(n, np.float64)
             special: List[Tuple[int, int]] = []
@@ -155,6 +177,46 @@ class PayloadIndex:
             else:
                 return None
         return cells
+
+    def _encode_lists(self, k: _Key, key: str, payloads):
+        """(heads, values) of a list key for hx_payload_append_lists -- heads: np.uint32, MISSING / NULL / the row's
+        element count; values: the rows' elements one after another, np.uint32 codes or np.float64 -- or None when a
+        value poisons the key.  The element rules are the scalar encoder's."""
+        get, missing = _filters._get, _filters._MISSING
+        elem, codes = k.elem, k.codes
+        heads = np.empty(len(payloads), np.uint32)
+        vals: List[Any] = []
+        for r, p in enumerate(payloads):
+            v = get(p, key)
+            if v is missing:
+                heads[r] = U32_MISSING
+                continue
+            if v is None:
+                heads[r] = U32_NULL
+                continue
+            row = v if type(v) is list else (v,)          # (a tuple inside the 1-tuple fails the element test below)
+            for x in row:
+                if elem == "keyword":
+                    if type(x) is not str:
+                        return None
+                    c = codes.get(x)
+                    if c is None:
+                        if len(codes) >= _MAX_KEYWORDS:
+                            return None
+                        c = codes[x] = len(codes)
+                    vals.append(c)
+                elif elem == "bool":
+                    if not isinstance(x, bool):
+                        return None
+                    vals.append(1 if x else 0)
+                else:
+                    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x:
+                        return None
+                    if isinstance(x, int) and abs(x) > 2 ** 53:
+                        return None
+                    vals.append(float(x))
+            heads[r] = len(row)
+        return heads, np.array(vals, np.float64 if elem == "number" else np.uint32)
 
     # -- compiler --------------------------------------------------------------------------------------------------
     def compile(self, flt, id_rows: Optional[Callable[[], Dict[Any, int]]] = None):
@@ -255,6 +317,8 @@ class PayloadIndex:
             k = self._key(c[what]["key"])
             if what == "is_empty":
                 ops.extend([(IS_MISSING, k.col, 0), (IS_NULL, k.col, 0), (OR, 0, 0)])
+                if k.is_list:
+                    ops.extend([(IS_EMPTY_LIST, k.col, 0), (OR, 0, 0)])
             else:
                 ops.append((IS_NULL, k.col, 0))
             return
@@ -262,16 +326,16 @@ class PayloadIndex:
             if "match" in c:
                 return self._match(self._key(c["key"]), c["match"], ops, sets)
             if "range" in c:
-                return self._range(self._key(c["key"]), c["range"], ops)
+                return self._range(self._key(c["key"]), c["range"], ops, sets)
         raise _Decline("unsupported condition")
 
     @staticmethod
     def _cell_of(k: _Key, v) -> Optional[int]:
         """The cell a stored value equal to the constant v has (filters._match's rule for `value`: equal, and of the
         same type or neither a bool), None when no stored value of the key's schema can equal it."""
-        if k.schema == "keyword":
+        if k.elem == "keyword":
             return k.codes.get(v) if isinstance(v, str) else None
-        if k.schema == "bool":
+        if k.elem == "bool":
             return (1 if v else 0) if isinstance(v, bool) else None
         d = exact_double(v)
         return None if d is None else f64_bits(d)
@@ -286,10 +350,10 @@ class PayloadIndex:
             raise _Decline("list mixes bools and numbers")
         out = set()
         for e in listed:
-            if k.schema == "keyword":
+            if k.elem == "keyword":
                 if isinstance(e, str) and e in k.codes:
                     out.add(k.codes[e])
-            elif k.schema == "bool":                  # True == 1 and False == 0 under `in`
+            elif k.elem == "bool":                  # True == 1 and False == 0 under `in`
                 if isinstance(e, (bool, int, float)) and e == 0:
                     out.add(0)
                 elif isinstance(e, (bool, int, float)) and e == 1:
@@ -298,7 +362,7 @@ class PayloadIndex:
                 d = float(e) if isinstance(e, bool) else exact_double(e)
                 if d is not None:
                     out.add(d + 0.0)                  # (-0.0 and 0.0 are one entry: -0.0 + 0.0 = 0.0)
-        if k.schema == "number":
+        if k.elem == "number":
             return np.array(sorted(out), np.float64)
         return np.array(sorted(out), np.uint32)
 
@@ -310,24 +374,26 @@ class PayloadIndex:
             if v is not None and not isinstance(v, (str, bool, int, float)):
                 raise _Decline("match value of an unsupported type")
             cell = self._cell_of(k, v)
-            ops.append((FALSE, 0, 0) if cell is None else (EQ, k.col, cell))
+            ops.append((FALSE, 0, 0) if cell is None else (ANY_EQ if k.is_list else EQ, k.col, cell))
         elif "any" in m:
             sets.append(self._set_of(k, m["any"]))
-            ops.append((IN, k.col, len(sets) - 1))
-        elif "except" in m:
+            ops.append((ANY_IN if k.is_list else IN, k.col, len(sets) - 1))
+        elif "except" in m:                           # (a list: no element is listed -- [] passes, as all() of nothing)
             sets.append(self._set_of(k, m["except"]))
-            ops.extend([(PRESENT, k.col, 0), (IN, k.col, len(sets) - 1), (NOT, 0, 0), (AND, 0, 0)])
+            ops.extend([(PRESENT, k.col, 0), (ANY_IN if k.is_list else IN, k.col, len(sets) - 1), (NOT, 0, 0), (AND, 0, 0)])
         elif "text" in m:
             raise _Decline("match text")
         else:
             raise _Decline("unsupported match")
 
-    def _range(self, k: _Key, r, ops):
+    def _range(self, k: _Key, r, ops, sets):
         if not isinstance(r, dict):
             raise _Decline("range is not a dict")
-        if k.schema != "number":                      # (filters._range: only numbers that are not bools are in a range)
+        if k.elem != "number":                        # (filters._range: only numbers that are not bools are in a range)
             ops.append((FALSE, 0, 0))
             return
+        if k.is_list:
+            return self._range_any(k, r, ops, sets)
         terms = 0
         for name, op in (("gt", GT), ("gte", GE), ("lt", LT), ("lte", LE)):
             b = r.get(name)
@@ -347,3 +413,40 @@ class PayloadIndex:
             terms += 1
         if not terms:
             ops.append((PRESENT, k.col, 0))
+
+    def _range_any(self, k: _Key, r, ops, sets):
+        """filters._range over a list: ONE element meets every bound, so the bounds become one closed interval [lo, hi]
+        and one ANY_RANGE op.  A strict bound moves to the neighbouring double (every stored number is a double, so
+        x > b is x >= nextafter(b, +inf) exactly; +-0 and the subnormals included)."""
+        lo, hi = -math.inf, math.inf
+        for name in ("gt", "gte", "lt", "lte"):
+            b = r.get(name)
+            if b is None:
+                continue
+            if isinstance(b, bool) or not isinstance(b, (int, float)):
+                raise _Decline("range bound is not a number")
+            if b != b:
+                ops.append((FALSE, 0, 0))             # nothing is ordered against a NaN
+                return
+            d = exact_double(b)
+            if d is None:
+                raise _Decline("range bound is not an exact double")
+            if name == "gt":
+                if d == math.inf:
+                    ops.append((FALSE, 0, 0))
+                    return
+                d = math.nextafter(d, math.inf)
+            elif name == "lt":
+                if d == -math.inf:
+                    ops.append((FALSE, 0, 0))
+                    return
+                d = math.nextafter(d, -math.inf)
+            if name in ("gt", "gte"):
+                lo = max(lo, d)
+            else:
+                hi = min(hi, d)
+        if lo > hi:
+            ops.append((FALSE, 0, 0))
+            return
+        sets.append(np.array([lo, hi], np.float64))
+        ops.append((ANY_RANGE, k.col, len(sets) - 1))
