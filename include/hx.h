@@ -284,6 +284,23 @@ int hx_h1_fuse(int32_t device, const uint64_t* gathered_dev, int32_t world, int3
  * k1, k1 a share of lp and k2 = k3 a share of sparse_limit (all multiples of 32), world x k <= 8192, k3 <= 256. */
 int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t* k1, int32_t* k2, int32_t* lp,
                int32_t* k3, int32_t* lout);
+/* Which kernels serve the tail of hx_search_dense's full-vector stage for a batch of B queries and limit L (host
+ * arithmetic only: no index, no device; the dense stage and its launchers decide by the same functions, so the report
+ * cannot differ from what runs).  cand_kind: 1 = int8 candidates, 0 = fp16 candidates (also the first prefix stage, an
+ * index without the int8 copy or with it switched off); retry_level: 0 = the first pass, 1 = the re-run of a query the
+ * first pass could not certify (always fp16 candidates: cand_kind is ignored there).
+ *  lp, cap               L' = candidates kept per query, C = keys of a query's candidate buffer (L <= L', 2 L' <= C);
+ *  finish_e              0: exact re-score, top-L and certificate are three launches (k_rescore_list, k_compact_top,
+ *                        k_certify); 2 | 4 | 8: one launch, k_dense_finish with that many keys per lane -- B <= 64 and
+ *                        L' <= 512; the smallest of 2, 4, 8 with L <= 64 x finish_e;
+ *  compact_nw, compact_e the compaction behind every launch of the candidate scan (keep = L' of C keys):
+ *                        k_compact_top<compact_nw, compact_e>, or 0, 0 = the sort in LDS (k_compact).
+ * It reports the default routing: HX_DEBUG_NO_FINISH_FUSE and HX_DEBUG_FINISH_NB (tests; read by hx_create, per index)
+ * force the three launches / a block count for one index and do not change this answer.
+ * Fails when B < 1, L is outside [1, 2048], or cand_kind / retry_level is neither 0 nor 1. */
+int hx_dense_route(int32_t B, int32_t L, int32_t cand_kind /* 1 int8, 0 fp16 */, int32_t retry_level /* 0 | 1 */,
+                   int32_t* lp, int32_t* cap, int32_t* finish_e /* 0 = three launches, else 2 | 4 | 8 */,
+                   int32_t* compact_nw, int32_t* compact_e /* 0, 0 = the LDS sort */);
 int hx_sparse_wmax(hx_index* h, float* wmax, int32_t* nonpos);
 int hx_set_sparse_wmax(hx_index* h, float wmax);
 int hx_h1_nominate_async(hx_index* h, const float* q_dev, const int64_t* q_indptr_dev, const int32_t* q_idx_dev,

@@ -92,6 +92,7 @@ _SIGS = {
                    _P, _P, _P],
     "hx_h1_plan": [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "hx_dense_route": [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 5,
     "hx_sparse_wmax": [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
     "hx_set_sparse_wmax": [_P, C.c_float],
     "hx_h1_nominate_async": [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P],

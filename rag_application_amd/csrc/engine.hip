@@ -139,6 +139,8 @@ struct hx_index {
   int tree_win_n = 0, tree_win_redone = 0;
   bool tree_spec_off = false;
   int done_zeroed[2] = {0, 0};        // entries of the finish kernel's per-query counters known to be zero (level 0 / retry level)
+  bool no_finish_fuse = false;        // HX_DEBUG_NO_FINISH_FUSE (tests): the dense stage's tail always as three launches
+  int finish_nb = 0;                  // HX_DEBUG_FINISH_NB (tests): blocks per query of k_dense_finish, 0 = one per four candidates
   // query-tile routing of the scans (read from the environment at hx_create: tests and diagnostics):
   //   B <= 32: k_scan 128 x 32; <= bn64_max: k_scan 128 x 64; <= bn128_max: 128 queries per tile -- the staggered kernel's
   //   256 x 128 form (scan8.hip, HQ) unless no_hq, then k_scan 128 x 128; above: the staggered 256 x 256 kernel
@@ -585,6 +587,21 @@ static int cand8_lprime(int L) {
   static const int add = getenv("HX_DEBUG_CAND8_ADD") ? std::max(0, atoi(getenv("HX_DEBUG_CAND8_ADD"))) : 288;
   return std::min(std::max(mul2 * L / 2, L + add), std::max(L, CAND_CAP / 4));
 }
+// L' and C of geometry() below, alone (what hx_dense_route reports): no growth search, no cache
+static void geometry_sizes(int L, bool approx, bool safe, bool cand8, int lp_force, int* Lp, int* C) {
+  int lp = approx ? L + std::max(32, L / 2) : L;
+  if (cand8) lp = lp_force > 0 ? lp_force : cand8_lprime(L);
+  if (safe) lp = std::min(std::max(2 * lp, lp + 256), CAND_CAP / 4);
+  int c = next_pow2(std::max(8 * lp, 1024));
+  if (cand8) {
+    static const int cmin = getenv("HX_DEBUG_CAND8_C") ? atoi(getenv("HX_DEBUG_CAND8_C")) : 4096;
+    static const int cmin_n = getenv("HX_DEBUG_NOM_C") ? atoi(getenv("HX_DEBUG_NOM_C")) : 1024;   // (8 x 1.25M rows: 1.585 ms per step at 1024, 1.605 at 2048, 1.81 at 4096)
+    c = std::max(c, lp_force > 0 ? cmin_n : cmin);
+  }
+  *Lp = lp;
+  *C = safe ? CAND_CAP : std::min(c, CAND_CAP);
+  HX_CHECK(*Lp * 2 <= *C && *Lp >= L, "limit too large");
+}
 // lp_force > 0 (with cand8): keep exactly that many candidates -- a shard of the candidates-first H1 exchange nominates
 // its share of the global L', not L' of its own (hx_h1_nominate_async)
 // few_queries (B <= 32): the scan is bandwidth-bound and what a launch costs is the compaction of ONE list per query
@@ -595,17 +612,7 @@ static Geometry geometry(int L, bool approx, bool safe, bool cand8 = false, int 
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
   Geometry g;
-  g.Lp = approx ? L + std::max(32, L / 2) : L;
-  if (cand8) g.Lp = lp_force > 0 ? lp_force : cand8_lprime(L);
-  if (safe) g.Lp = std::min(std::max(2 * g.Lp, g.Lp + 256), CAND_CAP / 4);
-  int c = next_pow2(std::max(8 * g.Lp, 1024));
-  if (cand8) {
-    static const int cmin = getenv("HX_DEBUG_CAND8_C") ? atoi(getenv("HX_DEBUG_CAND8_C")) : 4096;
-    static const int cmin_n = getenv("HX_DEBUG_NOM_C") ? atoi(getenv("HX_DEBUG_NOM_C")) : 1024;   // (8 x 1.25M rows: 1.585 ms per step at 1024, 1.605 at 2048, 1.81 at 4096)
-    c = std::max(c, lp_force > 0 ? cmin_n : cmin);
-  }
-  g.C = safe ? CAND_CAP : std::min(c, CAND_CAP);
-  HX_CHECK(g.Lp * 2 <= g.C && g.Lp >= L, "limit too large");
+  geometry_sizes(L, approx, safe, cand8, lp_force, &g.Lp, &g.C);
   g.predictive = false;
   g.grow = 2;
   g.grow_max = 2;
@@ -1091,10 +1098,8 @@ static bool search_dense(hx_index* h, const float* q_dev, int B, int prefix, int
       HX_HIP(hipMemsetAsync(done, 0, (size_t)B * 4, st));
       h->done_zeroed[level > 0] = B;
     }
-    static const bool no_fuse = getenv("HX_DEBUG_NO_FINISH_FUSE") != nullptr;
-    // (a small batch only: at B = 1024 the three kernels take 0.74 ms of a dense search against 0.83 through the fused one
-    // -- a wave per candidate over 113 blocks per query beats the last block's fold, and three launches are nothing there)
-    if (no_fuse || B > 64 || !launch_dense_finish(r, g.Lp, L, out_keys, out_cnt, ovf, HX_EPS_F16, eps_q, fail, nfail, done, st)) {
+    const int fe = h->no_finish_fuse ? 0 : dense_finish_e(B, g.Lp, L);   // (select.hip: a small batch, lists of at most 512)
+    if (!fe || !launch_dense_finish(r, g.Lp, L, out_keys, out_cnt, ovf, HX_EPS_F16, eps_q, fail, nfail, done, st, h->finish_nb)) {
       launch_rescore_list(r, st);
       launch_compact(cand2, g.C, cnt, B, L, 0, out_keys, L, out_cnt, nullptr, g.Lp, st);
       launch_certify(cand, g.C, cnt, g.Lp, out_keys, L, out_cnt, L, ovf, HX_EPS_F16, B, fail, nfail, st, eps_q);
@@ -1904,6 +1909,8 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_BN64_MAX")) h->bn64_max = std::max(0, atoi(e));
   if (const char* e = getenv("HX_DEBUG_BN128_MAX")) h->bn128_max = std::max(32, atoi(e));
   h->no_hq = getenv("HX_DEBUG_NO_HQ") != nullptr;
+  h->no_finish_fuse = getenv("HX_DEBUG_NO_FINISH_FUSE") != nullptr;                            // tests: the dense stage's tail
+  if (const char* e = getenv("HX_DEBUG_FINISH_NB")) h->finish_nb = std::clamp(atoi(e), 0, 65535);
   h->overlap_tail = getenv("HX_DEBUG_NO_OVERLAP") == nullptr;
   if (const char* e = getenv("HX_DEBUG_FORK_EARLY_MAX")) h->fork_early_max = atoi(e);
   if (const char* e = getenv("HX_DEBUG_SCAN_OVERSUB")) h->scan_oversub = atoi(e);
@@ -2834,6 +2841,25 @@ int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t
   *k2 = ks;                                         // integer scores: enough to fix the value of the global L-th
   *k3 = ks;                                         // exact sparse keys a shard returns
   *lout = sparse_lout(sparse_limit);
+  HX_CATCH
+}
+
+int hx_dense_route(int32_t B, int32_t L, int32_t cand_kind, int32_t retry_level, int32_t* lp, int32_t* cap,
+                   int32_t* finish_e, int32_t* compact_nw, int32_t* compact_e) {
+  HX_TRY
+  HX_CHECK(lp && cap && finish_e && compact_nw && compact_e, "NULL argument");
+  HX_CHECK(B >= 1, "B must be positive");
+  HX_CHECK(L >= 1 && L <= MAX_LIMIT, "limit out of range [1, 2048]");
+  HX_CHECK((cand_kind == 0 || cand_kind == 1) && (retry_level == 0 || retry_level == 1), "cand_kind / retry_level must be 0 or 1");
+  // as search_dense: geometry(L, approx, safe = the retry level, int8 candidates at level 0 only)
+  int Lp = 0, C = 0;
+  geometry_sizes(L, true, retry_level > 0, cand_kind == 1 && retry_level == 0, 0, &Lp, &C);
+  *lp = Lp;
+  *cap = C;
+  *finish_e = dense_finish_e(B, Lp, L);
+  const CompactForm cf = compact_form(C, Lp, 0);   // chunked_scan: launch_compact(cand, C, ..., keep = L', no dedupe, hint = C)
+  *compact_nw = cf.nw;
+  *compact_e = cf.e;
   HX_CATCH
 }
 

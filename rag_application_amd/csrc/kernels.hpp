@@ -90,6 +90,12 @@ void launch_compact(uint64_t* keys, int stride, const int* in_cnt, int B, int ke
                     uint64_t* out_keys, int out_stride, int* out_cnt, float* tau,
                     int max_cnt_hint, hipStream_t st, int tau_rank = 0, int chk_rank = 0,
                     int* kept_io = nullptr, int* underflow = nullptr);
+// The kernel launch_compact picks for lists of at most list_len (= min(max_cnt_hint, stride)) keys: k_compact_top<nw, e>
+// (a wave sorts 64 e keys in registers, nw waves fold), or {0, 0} = k_compact, the LDS sort.  No device, no launch.
+struct CompactForm {
+  int nw, e;
+};
+CompactForm compact_form(int list_len, int keep, int dedupe);
 
 // Exact spec score of listed candidates: out_keys[b*stride + i] = key(spec_dot(row, q_b), id)
 // for i < min(cnt[b], stride); ids outside [id_base, id_base+n) give key 0.
@@ -115,10 +121,15 @@ void launch_rescore_list(const RescoreArgs& a, hipStream_t st);
 // as launch_rescore_list for a list that is mostly OTHER shards' rows: only this shard's slots are scored and written
 void launch_rescore_own(const RescoreArgs& a, hipStream_t st);
 // exact re-score of the (<= 512) candidates of every query + top-L + the certificate of launch_certify, one launch
-// (r.out = scratch [B x stride]; done = [B] zeroed counters, left zero).  Returns false when the sizes do not fit
-// (lprime or L above 512): use launch_rescore_list + launch_compact + launch_certify.
+// (r.out = scratch [B x stride]; done = [B] zeroed counters, left zero).  Returns false when dense_finish_e says the
+// sizes do not fit (more than 64 queries, lprime or L above 512): use launch_rescore_list + launch_compact +
+// launch_certify.  nb_force > 0: that many blocks per query instead of one per four candidates (tests).
 bool launch_dense_finish(const RescoreArgs& r, int lprime, int L, uint64_t* out_keys, int* out_cnt, const int* overflow,
-                         float eps, const float* eps_q, int* fail, int* nfail, unsigned int* done, hipStream_t st);
+                         float eps, const float* eps_q, int* fail, int* nfail, unsigned int* done, hipStream_t st,
+                         int nb_force = 0);
+// Keys per lane (2 | 4 | 8) of the k_dense_finish instantiation that serves B queries with lprime candidates and limit
+// L, 0 when the three launches serve them.  No device, no launch.
+int dense_finish_e(int B, int lprime, int L);
 
 // Exact scores of ALL rows [row_begin,row_end) for the listed queries (fallback path):
 // out[qsel[f]*stride + slot0 + (row-row_begin)] = key.

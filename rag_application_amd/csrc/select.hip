@@ -192,6 +192,16 @@ __global__ __launch_bounds__(NW * 64) void k_compact_top(const uint64_t* __restr
   }
 }
 
+// Which kernel compacts a list of at most `list_len` keys down to `keep` (host arithmetic only: launch_compact below
+// launches exactly this form, and hx_dense_route reports it): k_compact_top<nw, e>, or {0, 0} = k_compact, the LDS sort.
+CompactForm compact_form(int list_len, int keep, int dedupe) {
+  const int P = next_pow2(list_len < 256 ? 256 : list_len);
+  if (dedupe || keep < 1) return {0, 0};
+  if (keep <= 256 && P <= 2048) return {P / 256, 4};          // short form, 4 keys per lane
+  if (keep > 256 && keep <= 512 && P <= 8192) return {P <= 512 ? 1 : P / 512, 8};   // ... with 8 keys per lane: the int8 candidate pass
+  return {0, 0};
+}
+
 void launch_compact(uint64_t* keys, int stride, const int* in_cnt, int B, int keep, int dedupe,
                     uint64_t* out_keys, int out_stride, int* out_cnt, float* tau, int max_cnt_hint,
                     hipStream_t st, int tau_rank, int chk_rank, int* kept_io, int* underflow) {
@@ -203,24 +213,22 @@ void launch_compact(uint64_t* keys, int stride, const int* in_cnt, int B, int ke
 #define HX_TOP(NW, E)                                                                                            \
   hipLaunchKernelGGL((k_compact_top<NW, E>), dim3(B), dim3(NW * 64), 0, st, keys, stride, in_cnt, keep, out_keys, \
                      out_stride, out_cnt, tau, tau_rank, chk_rank, kept_io, underflow)
-  if (!dedupe && keep >= 1 && keep <= 256 && P <= 2048) {   // short form; the tau rank is <= keep
+  const CompactForm form = compact_form(m, keep, dedupe);
+  if (form.e != 0) {   // the register forms; the tau rank is <= keep
     if (tau_rank <= 0 || tau_rank > keep) tau_rank = keep;
     HX_CHECK(!kept_io || underflow, "compact: kept_io without an underflow flag array");
-    if (P <= 256) HX_TOP(1, 4);
-    else if (P <= 512) HX_TOP(2, 4);
-    else if (P <= 1024) HX_TOP(4, 4);
-    else HX_TOP(8, 4);
-    HX_HIP(hipGetLastError());
-    return;
-  }
-  if (!dedupe && keep > 256 && keep <= 512 && P <= 8192) {  // ... with 8 keys per lane: the int8 candidate pass
-    if (tau_rank <= 0 || tau_rank > keep) tau_rank = keep;
-    HX_CHECK(!kept_io || underflow, "compact: kept_io without an underflow flag array");
-    if (P <= 512) HX_TOP(1, 8);
-    else if (P <= 1024) HX_TOP(2, 8);
-    else if (P <= 2048) HX_TOP(4, 8);
-    else if (P <= 4096) HX_TOP(8, 8);
-    else HX_TOP(16, 8);
+    switch (form.e * 100 + form.nw) {
+      case 401: HX_TOP(1, 4); break;
+      case 402: HX_TOP(2, 4); break;
+      case 404: HX_TOP(4, 4); break;
+      case 408: HX_TOP(8, 4); break;
+      case 801: HX_TOP(1, 8); break;
+      case 802: HX_TOP(2, 8); break;
+      case 804: HX_TOP(4, 8); break;
+      case 808: HX_TOP(8, 8); break;
+      case 816: HX_TOP(16, 8); break;
+      default: HX_CHECK(false, "compact: no kernel of this form");
+    }
     HX_HIP(hipGetLastError());
     return;
   }
@@ -444,9 +452,21 @@ __global__ __launch_bounds__(256) void k_dense_finish(FinishArgs f) {
     f.done[b] = 0u;                                  // for the next launch
   }
 }
+// Whether a batch of B queries with lprime candidates each finishes in the one launch above, and with how many keys per
+// lane (host arithmetic only: search_dense and launch_dense_finish decide by it, hx_dense_route reports it): 0 = the
+// three launches.  A small batch only: at B = 1024 the three kernels take 0.74 ms of a dense search against 0.83 through
+// the fused one -- a wave per candidate over 113 blocks per query beats the last block's fold, and three launches are
+// nothing there.  E keys per lane: the top 64 E end in wave 0 (L <= 64 E), 4 x 64 E keys fit the fold (>= 512 from E = 2).
+int dense_finish_e(int B, int lprime, int L) {
+  if (B > 64 || lprime > 512 || L > 512 || L < 1) return 0;
+  return L <= 128 ? 2 : (L <= 256 ? 4 : 8);
+}
+
 bool launch_dense_finish(const RescoreArgs& r, int lprime, int L, uint64_t* out_keys, int* out_cnt, const int* overflow,
-                         float eps, const float* eps_q, int* fail, int* nfail, unsigned int* done, hipStream_t st) {
-  if (lprime > 512 || L > 512 || L < 1 || r.stride < lprime) return false;
+                         float eps, const float* eps_q, int* fail, int* nfail, unsigned int* done, hipStream_t st,
+                         int nb_force) {
+  const int e = dense_finish_e(r.B, lprime, L);
+  if (e == 0 || r.stride < lprime) return false;
   if (r.B <= 0) return true;
   FinishArgs f{};
   f.r = r;
@@ -460,13 +480,10 @@ bool launch_dense_finish(const RescoreArgs& r, int lprime, int L, uint64_t* out_
   f.fail = fail;
   f.nfail = nfail;
   f.done = done;
-  // a small batch gets a wave per candidate (the chip is otherwise idle), a large one has blocks enough
-  static const int nb_env = getenv("HX_DEBUG_FINISH_NB") ? atoi(getenv("HX_DEBUG_FINISH_NB")) : 0;
-  int nb = r.B <= 64 ? (lprime + 3) / 4 : 16;
-  if (nb_env > 0) nb = nb_env;
-  // E keys per lane: the top 64 E end in wave 0 (L <= 64 E), 4 x 64 E keys fit the fold (>= 512 from E = 2)
-  if (L <= 128) hipLaunchKernelGGL(k_dense_finish<2>, dim3(nb, r.B), dim3(256), 0, st, f);
-  else if (L <= 256) hipLaunchKernelGGL(k_dense_finish<4>, dim3(nb, r.B), dim3(256), 0, st, f);
+  // a wave per candidate: the chip is otherwise idle behind a small batch's scan (a larger batch is never fused)
+  const int nb = nb_force > 0 ? nb_force : (lprime + 3) / 4;
+  if (e == 2) hipLaunchKernelGGL(k_dense_finish<2>, dim3(nb, r.B), dim3(256), 0, st, f);
+  else if (e == 4) hipLaunchKernelGGL(k_dense_finish<4>, dim3(nb, r.B), dim3(256), 0, st, f);
   else hipLaunchKernelGGL(k_dense_finish<8>, dim3(nb, r.B), dim3(256), 0, st, f);
   HX_HIP(hipGetLastError());
   return true;

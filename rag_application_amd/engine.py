@@ -529,6 +529,17 @@ def h1_plan(dense_limit: int, sparse_limit: int, world: int):
     return tuple(int(x.value) for x in v)
 
 
+def dense_route(B: int, L: int, cand: str = "i8", retry_level: int = 0):
+    """(lp, cap, finish_e, compact_nw, compact_e) of search_dense's full-vector stage for B queries and limit L
+    (hx_dense_route; cand "i8" | "f16"): finish_e 0 = three launches, else k_dense_finish's keys per lane; compact
+    (0, 0) = the LDS sort.  No index and no device are involved."""
+    if cand not in ("i8", "f16"):
+        raise ValueError("cand must be 'i8' or 'f16'")
+    v = [C.c_int32() for _ in range(5)]
+    check(_lib.lib().hx_dense_route(B, L, 1 if cand == "i8" else 0, retry_level, *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
 def h1_finish(reduced: torch.Tensor, world: int, B: int, lp: int, k3: int, dense_limit: int, sparse_limit: int,
               limit: int = 10, k: float = 2.0, rank_base: int = 0, nfail: Optional[torch.Tensor] = None):
     """reduced: the all-reduced (integer sum over the `world` ranks) result of h1_rescore_async.  Returns (keys [B, limit],
