@@ -301,6 +301,18 @@ int hx_h1_plan(int32_t dense_limit, int32_t sparse_limit, int32_t world, int32_t
 int hx_dense_route(int32_t B, int32_t L, int32_t cand_kind /* 1 int8, 0 fp16 */, int32_t retry_level /* 0 | 1 */,
                    int32_t* lp, int32_t* cap, int32_t* finish_e /* 0 = three launches, else 2 | 4 | 8 */,
                    int32_t* compact_nw, int32_t* compact_e /* 0, 0 = the LDS sort */);
+/* Which kernel the whole-collection candidate scan launches for a batch of B queries over rows of row_bytes bytes
+ * (kind: 0 fp16, 1 int8), by the default routing; no index and no device are involved.
+ *  form  0: k_scan (batches of at most 32 queries, or more than 4096);
+ *        1: k_scan8, the staggered 256 x 256 tile;
+ *        2: k_scan8 in its 256-row x 128-query form (33..128 queries);
+ *        3: k_scan8q, the query-stationary form: int8 rows of 768 bytes and ceil(B / 256) in {1, 2, 4, 8, 16}.
+ * HX_DEBUG_NO_QS (read by hx_create, per index) sends form 3 to form 1 for one index and does not change this answer;
+ * the first chunk of every scan (the candidate buffer's capacity, a few thousand rows) goes through k_scan whatever B. */
+int hx_scan8_form(int32_t B, int64_t row_bytes, int32_t kind, int32_t* form);
+/* Waves that share the log appends of one scan launch over `tiles` 256-row tiles and nq_tiles query tiles (qs: the
+ * query-stationary form): what the per-wave log capacity is planned by.  Host arithmetic only. */
+int hx_scan8_log_waves(int64_t tiles, int32_t nq_tiles, int32_t qs, double* waves);
 int hx_sparse_wmax(hx_index* h, float* wmax, int32_t* nonpos);
 int hx_set_sparse_wmax(hx_index* h, float wmax);
 int hx_h1_nominate_async(hx_index* h, const float* q_dev, const int64_t* q_indptr_dev, const int32_t* q_idx_dev,

@@ -155,6 +155,7 @@ struct hx_index {
   int fork_early_max = 1 << 30;       // batches of at most this many queries start the sparse stage beside the dense SCAN
                                       // (HX_DEBUG_FORK_EARLY_MAX=0: beside the stage's tail only, as round 4 began)
   bool no_hq = false;
+  bool no_qs = false;                 // HX_DEBUG_NO_QS (tests): never the query-stationary form of the staggered kernel (k_scan8q)
   // doc-major sparse staging (device)
   int64_t* sp_indptr = nullptr;  // [sp_rows_cap + 1]
   int32_t* sp_idx = nullptr;
@@ -651,9 +652,10 @@ static Geometry geometry(int L, bool approx, bool safe, bool cand8 = false, int 
 // of HBM peak (profiles/r04_mid_batch.txt): the 256 x 128 form of the staggered kernel 1.53-1.59 / 0.69-0.72 over B = 48..128
 // (k_scan's 128 x 64 tile 1.71-1.77 / 0.60-0.62 at 48-64, its 128 x 128 tile 1.94-2.04 / 0.51-0.54 at 65-128, the 256-wide
 // staggered kernel 2.03-2.13 / 0.59 at 96-128); two 128-query tiles for 129..256 lose to the 256-wide form (2.46-2.93 / 1.9-2.2).
-static int scan_bn(const hx_index* h, int B) {
-  return B <= h->bn32_max ? 32 : (B <= h->bn64_max ? 64 : (B <= h->bn128_max ? 128 : 256));
+static int scan_bn(int B, int bn32_max, int bn64_max, int bn128_max) {
+  return B <= bn32_max ? 32 : (B <= bn64_max ? 64 : (B <= bn128_max ? 128 : 256));
 }
+static int scan_bn(const hx_index* h, int B) { return scan_bn(B, h->bn32_max, h->bn64_max, h->bn128_max); }
 
 struct MatrixRef {
   const float* m32;
@@ -752,6 +754,7 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
   // k_scan streams at half of HBM peak there, the 256-wide form of scan8 spends half its MFMAs on padding columns
   const bool hq = bn == 128 && !h->no_hq;
   a.half_q = hq ? 1 : 0;
+  a.no_qs = h->no_qs ? 1 : 0;
   static const int os_always = getenv("HX_DEBUG_SCAN_OVERSUB_ALWAYS") ? atoi(getenv("HX_DEBUG_SCAN_OVERSUB_ALWAYS")) : 0;   // diagnostics
   a.oversub = h->beside ? h->scan_oversub : os_always;
   if (bn == 256 || hq) {   // per-wave append logs of the staggered kernel (scan8.hip)
@@ -761,6 +764,10 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
     // score is its threshold) and its items run on min(SCAN8_WAVES, 8 waves per 256 x 256 tile) waves -- a SMALL
     // collection has few tiles, so few waves share the same number of appends (15000 rows, B = 130: 43 tiles, and
     // a capacity planned for 2048 waves overflowed for half the queries).  Three times the mean, the largest launch.
+    // The query-stationary form (k_scan8q) deals 128-row halves to 8 query columns of 32: a wave owns half the queries
+    // of a k_scan8 wave and a query is logged by half as many waves, so a full grid has the same mean per wave, and a
+    // small launch spreads over twice the workgroups (scan8_log_waves).
+    const bool qs = !hq && !h->no_qs && scan8_qs_form(kind, 0, row_bytes, a.nq_tiles);
     double want = 0.0;
     {
       const std::vector<int64_t> plan = chunk_plan((ns + 255) / 256 * 256, g);
@@ -768,7 +775,7 @@ static void chunked_scan(hx_index* h, int kind, const uint8_t* A, const uint8_t*
         const int64_t p1 = plan[i - 1], nx = plan[i];
         const double growth = (double)nx / (double)p1;
         const double rank = g.predictive ? predict_rank(g.Lp, growth) : g.Lp;
-        const double waves = std::min<double>(SCAN8_WAVES, 8.0 * (double)((nx - p1 + 255) / 256) * (double)(round_up(B, bn) / bn));
+        const double waves = scan8_log_waves((nx - p1 + 255) / 256, a.nq_tiles, qs);
         want = std::max(want, 3.0 * rank * (growth - 1.0) * (double)B / waves + 64.0);
       }
     }
@@ -1909,6 +1916,7 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_BN64_MAX")) h->bn64_max = std::max(0, atoi(e));
   if (const char* e = getenv("HX_DEBUG_BN128_MAX")) h->bn128_max = std::max(32, atoi(e));
   h->no_hq = getenv("HX_DEBUG_NO_HQ") != nullptr;
+  h->no_qs = getenv("HX_DEBUG_NO_QS") != nullptr;
   h->no_finish_fuse = getenv("HX_DEBUG_NO_FINISH_FUSE") != nullptr;                            // tests: the dense stage's tail
   if (const char* e = getenv("HX_DEBUG_FINISH_NB")) h->finish_nb = std::clamp(atoi(e), 0, 65535);
   h->overlap_tail = getenv("HX_DEBUG_NO_OVERLAP") == nullptr;
@@ -2860,6 +2868,30 @@ int hx_dense_route(int32_t B, int32_t L, int32_t cand_kind, int32_t retry_level,
   const CompactForm cf = compact_form(C, Lp, 0);   // chunked_scan: launch_compact(cand, C, ..., keep = L', no dedupe, hint = C)
   *compact_nw = cf.nw;
   *compact_e = cf.e;
+  HX_CATCH
+}
+
+int hx_scan8_form(int32_t B, int64_t row_bytes, int32_t kind, int32_t* form) {
+  HX_TRY
+  HX_CHECK(form, "NULL argument");
+  HX_CHECK(B >= 1 && row_bytes >= 128 && (row_bytes & 127) == 0, "B must be positive, row_bytes a positive multiple of 128");
+  HX_CHECK(kind == KIND_F16 || kind == KIND_I8, "kind must be 0 (fp16) or 1 (int8)");
+  const int bn = scan_bn(B, 32, 32, 128);   // hx_index's default thresholds
+  ScanArgs a{};
+  a.B = B;
+  a.row_bytes = row_bytes;
+  a.half_q = bn == 128 ? 1 : 0;
+  a.hitlog = (uint4*)(uintptr_t)16;     // (only compared with NULL)
+  if (!scan8_usable(a, bn)) *form = 0;
+  else if (a.half_q) *form = 2;
+  else *form = scan8_qs_form(kind, 0, row_bytes, (int)(round_up(B, 256) / 256)) ? 3 : 1;
+  HX_CATCH
+}
+
+int hx_scan8_log_waves(int64_t tiles, int32_t nq_tiles, int32_t qs, double* waves) {
+  HX_TRY
+  HX_CHECK(waves && tiles >= 1 && nq_tiles >= 1, "bad argument");
+  *waves = scan8_log_waves(tiles, nq_tiles, qs != 0);
   HX_CATCH
 }
 

@@ -41,6 +41,8 @@ struct ScanArgs {
   int all_pass;
   // scan8 only: the 256-row x 128-query form (65..128 queries; Q holds 128-row query tiles)
   int half_q;
+  // scan8 only: never the query-stationary form (k_scan8q), whatever the shape (HX_DEBUG_NO_QS: tests)
+  int no_qs;
   int oversub;             // k_scan only: k > 1 = k x the resident grid (less 32 workgroups), each with 1 / k of the static share --
                            // for a scan that runs BESIDE another stream's kernels: its two workgroups per CU take the whole LDS, so
                            // a workgroup of the other stream in the way at launch leaves a scan workgroup waiting for a whole
@@ -77,6 +79,10 @@ void launch_scan(const ScanArgs& a, int kind, int bn, hipStream_t st, hipEvent_t
 // scan8.hip: the 256 x 256 staggered-phase kernel behind launch_scan for large batches
 bool scan8_usable(const ScanArgs& a, int bn);
 void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_kernel = nullptr);   // includes the log scatter
+// whether launch_scan8 takes the query-stationary form k_scan8q for this shape (host arithmetic; ScanArgs.no_qs aside)
+bool scan8_qs_form(int kind, int half_q, int64_t row_bytes, int nq_tiles);
+// waves that share the appends of a launch over `tiles` 256-row tiles, by form
+double scan8_log_waves(int64_t tiles, int nq_tiles, bool qs);
 
 // ---- select.hip --------------------------------------------------------------
 // Sort each query's buffer (first min(cnt, stride) keys) best-first, optionally drop

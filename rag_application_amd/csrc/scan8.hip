@@ -516,6 +516,8 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
 #ifndef HX_S8_LDMA
 #define HX_S8_LDMA 1   // where the four global_load_lds of a phase are issued: 0 between the MFMAs of its M segment (round 1),
 #endif                 // 1 in its L segment -- by the wave that is NOT on the matrix pipe -- 2 half and half
+  // (the explicit filter calls of the other placements name the hb = 1 quadrants, which the HQ form never computes)
+  static_assert(!HQ || (HX_S8_FILTER_IN_M == 1 && HX_S8_FILTER_SPLIT == 0), "the 256 x 128 form filters behind each quadrant's MFMAs only");
 
 #define S8_QUAD(ACC, BF, HA, HB, BASE, KOFF, OFF, SLOT, INM)                    \
   mma(ACC, BF, FIRST, 0, KS / 2);                                               \
@@ -659,6 +661,259 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
 #undef S8_WAIT
 }
 
+// The query-stationary form (int8, 16x16x64 MFMA, rows of KT x 128 bytes; shipped for KT = 6, dim 768).
+//
+// k_scan8's tile walk gives a workgroup ONE query tile for the whole launch (qt = i0 mod nq_tiles), and its 256 queries
+// x 768 B are exactly the register file of 8 waves at 96 VGPRs a lane.  Here every wave loads the B fragments of its 32
+// queries (2 tiles x KT k-tiles x 2 k-steps x 4 registers) once, before any LDS-DMA is in flight, and only corpus rows
+// travel through LDS: half the global_load_lds pieces per MAC of the 256 x 256 form, and no L2 reads of queries at all.
+//
+// Geometry.  8 waves as 1 (rows) x 8 (32 queries each).  Workgroup (xcd, i0): query tile qt = i0 mod nq, stream
+// i0 / nq of per_xcd / nq; the streams of an XCD deal out the 128-row halves of the XCD's 256-row tiles (same tile
+// order and physical-tile permutation as k_scan8), so the nq workgroups of a stream walk the same rows at the same
+// time, one per query tile, and share them in L2.  A half is scanned as two ITEMS of 64 rows; an item is KT SLABS of
+// 64 rows x 128 B = 8 KiB (one 1-KiB piece per wave, same swizzled lane-linear image as above).
+//
+// Schedule.  One phase = KP slabs (KP consecutive k-tiles of the item; shipped: 2), 16 KP MFMAs (4 row tiles x 2 query
+// tiles x 2 k-steps per slab) into 32 accumulator registers.
+//     L segment : ds_read the 8 KP A fragments of the phase's slabs, stage the same k-tiles of the NEXT item (KP pieces),
+//                 counted wait
+//     barrier
+//     M segment : the 16 KP MFMAs; behind the last phase of an item its threshold filter
+//     barrier
+// Phase shapes measured on the 10M x 768 step, one box, six alternations (profiles/scan8_qs.txt; HX_DEBUG_S8Q_KP picks
+// one for diagnostics): one slab per phase 9.03 ms -- twice k_scan8's barriers per MAC, and a 256-cycle M segment is too
+// short a cover for its partner's L segment: the kernel alone took what k_scan8 takes; two slabs 8.86 ms (k_scan8's 32
+// MFMAs per phase and barriers per MAC, 218 VGPRs); three slabs 8.88 ms at 250 VGPRs -- no better, no headroom.
+// (128 ROWS per phase would need 64 accumulator + 64 fragment registers beside the 96 of the queries.)
+// The ring is 2 KT slots, slot = (item & 1) * KT + kt.  RAW: the wait of a phase leaves KT - KP pieces in flight (the
+// slabs behind those of the NEXT phase), so the next phase's slabs are in LDS, for every wave of the group, before the
+// barrier that precedes their reads; the other group's pieces of them were retired one barrier earlier or are retired
+// at the barrier between.  WAR: the slots staged in a phase last held the same k-tiles of the PREVIOUS item, whose reads
+// every wave retired (lgkmcnt(0) ahead of its barrier) KT / KP >= 2 phases ago.  Waves 4..7 run one barrier behind
+// waves 0..3, as in k_scan8.
+// The thresholds of a lane's two query columns are constants of the launch and live in two registers; the row-scale
+// bound of an item is the one of its parent 256-row tile (still an upper bound of the half's rows).
+// Log entries are k_scan8's: {query, first row} + MT words, one entry per passing column of a 64-row item;
+// k_scatter_log<.., QS> maps wave w of workgroup (xcd, i0) to queries qt * 256 + 32 w .. + 31.
+// DBG 2 (timing build, wrong results): no global_load_lds in the loop.
+constexpr int S8Q_SLAB = 8192;
+template <int KT, int DBG, int KP>
+__global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
+  constexpr int MT = 4, NT = 2, KS = 2;
+  static_assert(KT % KP == 0 && KT / KP >= 2, "a phase is KP slabs of one item");
+  constexpr bool NO_GLDS = DBG == 2;
+  __shared__ __attribute__((aligned(1024))) uint8_t lds[2 * KT * S8Q_SLAB];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2;                  // stagger group
+  const int r = lane & 15, hh = lane >> 4;    // row/column inside a tile, k-group
+
+  typedef __attribute__((address_space(1))) const float GF;
+  GF* g_tau = (GF*)a.tau;
+  GF* g_rinv_q = (GF*)a.rinv_q;
+  auto* g_ovf = (__attribute__((address_space(1))) int*)a.overflow;
+
+  const int64_t n_rows = a.row_end - a.row_begin;
+  const int n_row_tiles = (int)((n_rows + 255) >> 8);
+  const int nq = a.nq_tiles;
+  const int xcd = blockIdx.x & 7;
+  const int per_xcd = gridDim.x >> 3;
+  const int i0 = blockIdx.x >> 3;
+  const int qt = i0 % nq, stream = i0 / nq, nstreams = per_xcd / nq;
+  const int halves_x = 2 * ((n_row_tiles - xcd + 7) >> 3);   // 128-row halves of this XCD's tiles
+  if (stream >= halves_x) {
+    if (lane == 0) a.hitcnt[blockIdx.x * 8 + wave] = 0;
+    return;
+  }
+  const int n_items = 2 * ((halves_x - stream + nstreams - 1) / nstreams);   // 64-row items of this workgroup
+
+  // ---- the wave's query fragments and thresholds: plain loads, nothing else in flight ----------------------
+  i32x4 qf[NT][KT][KS];
+  {
+    const uint8_t* qb = a.Q + (int64_t)(qt * 256 + wave * 32 + r) * a.row_bytes + hh * 16;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          qf[nt][kt][ks] = *(const i32x4*)(qb + (int64_t)nt * 16 * a.row_bytes + kt * 128 + ks * 64);
+  }
+  // threshold of f32(max dot) * max row scale, as k_scan8's table: tau / rinv_q pushed down by 2^-20; +inf for padding
+  float tau_r[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int q = qt * 256 + wave * 32 + nt * 16 + r;
+    float t = q < a.B ? g_tau[q] : __builtin_inff();
+    const float rq = q < a.B ? g_rinv_q[q] : 0.f;
+    if (t <= 0.f) t = -__builtin_inff();
+    else if (!(rq > 0.f)) t = __builtin_inff();
+    else t = (t / rq) * 0.99999905f;
+    tau_r[nt] = t;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[nt][kt][ks]));
+
+  // ---- per-lane constants -------------------------------------------------------------------------------
+  // source byte offset of this lane's 16-byte slot of the wave's piece (rows 8 wave .. 8 wave + 7 of the slab)
+  const int rr = wave * 8 + (lane >> 3);
+  const uint32_t off_a = (uint32_t)rr * (uint32_t)a.row_bytes + (uint32_t)(((lane & 7) ^ ((rr >> 1) & 7)) << 4);
+  const int swz = (r >> 1) & 7;
+  uint32_t rd[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) rd[ks] = (uint32_t)r * 128 + (uint32_t)(((ks * 4 + hh) ^ swz) << 4);   // + mt * 2048
+
+  // ---- item cursor (scalar): item k = 64-row part (k & 1) of half u = stream + (k >> 1) * nstreams ------
+  struct Item {
+    const uint8_t* p;   // first row of the item
+    int64_t row0;       // its physical row
+    int rt;             // its physical 256-row tile
+  };
+  auto item_at = [&](int k) __attribute__((always_inline)) {
+    const int u = stream + (k >> 1) * nstreams;
+    const int rt = (int)__builtin_amdgcn_readfirstlane(
+        (int)scan_phys_tile((uint32_t)((a.row_begin >> 8) + (u >> 1) * 8 + xcd), a.perm_mul, a.perm_n, a.perm_inv));
+    Item it;
+    it.rt = rt;
+    it.row0 = (int64_t)rt * 256 + (u & 1) * 128 + (k & 1) * 64;
+    it.p = a.A + it.row0 * a.row_bytes;
+    return it;
+  };
+  auto stage = [&](const uint8_t* base, int kt, int slot) __attribute__((always_inline)) {
+    // (the empty asm keeps `scalar base + zext(32-bit lane offset)` visible to instruction selection: see k_scan8)
+    // (and the one on the base keeps the k-tile's 128 bytes a SCALAR add: folded into the lane offset it costs two 64-bit
+    // VALU adds per piece)
+    uint32_t o = off_a;
+    asm volatile("" : "+v"(o));
+    const uint8_t* bk = base + kt * 128;
+    asm volatile("" : "+s"(bk));
+    __builtin_amdgcn_global_load_lds(GLB_PTR(bk + o), LDS_PTR(lds + slot * S8Q_SLAB + wave * 1024), 16, 0, 0);
+  };
+
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  constexpr int S8_ENTRY = 1 + MT;   // 16-byte words per log entry (TS = 16: one word per row tile)
+  auto* g_log = (__attribute__((address_space(1))) u32x4*)a.hitlog + (int64_t)(blockIdx.x * 8 + wave) * a.logcap * S8_ENTRY;
+  int wpos = 0;   // entries this wave has logged (scalar)
+
+  i32x4 acc[MT][NT];
+  half8 af[KP][MT][KS];
+  float rxm = 0.f;
+
+  // lane owns query column r of each of the NT tiles and rows 4 hh + e of each of the MT row tiles
+  auto filter = [&](int64_t row0) __attribute__((always_inline)) {
+    auto imax3 = [](int x, int y, int z) __attribute__((always_inline)) {
+      const int t = x > y ? x : y;
+      return t > z ? t : z;
+    };
+    float m[NT];
+    bool any = false;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      int im = acc[0][nt][0];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) im = imax3(imax3(im, acc[mt][nt][0], acc[mt][nt][1]), acc[mt][nt][2], acc[mt][nt][3]);
+      m[nt] = im > 0 ? (float)im * rxm : 0.f;    // (k_scan8's bound: f32(max dot) * max row scale of the parent tile)
+      any |= (m[nt] >= tau_r[nt]);
+    }
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(any) == 0ull, 1)) return;
+    const int64_t rowq = row0 + 4 * hh;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const bool hit = m[nt] >= tau_r[nt];
+      const uint64_t mask = __builtin_amdgcn_ballot_w64(hit);
+      if (mask == 0ull) continue;
+      const int idx = wpos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                            __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+      if (hit) {
+        const int q = qt * 256 + wave * 32 + nt * 16 + r;
+        if (idx < a.logcap) {
+          auto* e = g_log + (int64_t)idx * S8_ENTRY;
+          e[0] = u32x4{(uint32_t)q, (uint32_t)rowq, (uint32_t)((uint64_t)rowq >> 32), 0u};
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const int x0 = acc[mt][nt][0], x1 = acc[mt][nt][1], x2 = acc[mt][nt][2], x3 = acc[mt][nt][3];
+            e[1 + mt] = u32x4{(uint32_t)x0, (uint32_t)x1, (uint32_t)x2, (uint32_t)x3};
+          }
+        } else {
+          g_ovf[q] = 1;
+        }
+      }
+      wpos += __builtin_popcountll(mask);
+    }
+  };
+
+  // ---- prologue: the KT slabs of item 0 ---------------------------------------------------------------------
+  Item cur = item_at(0);
+#pragma unroll
+  for (int kt = 0; kt < KT; ++kt) stage(cur.p, kt, kt);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (grp == 1) __builtin_amdgcn_s_barrier();   // the stagger
+
+  for (int k = 0; k < n_items; ++k) {
+    const Item nxt = item_at(k + 1 < n_items ? k + 1 : k);   // past the last item: re-load it (never read)
+    const int s_cur = (k & 1) * KT, s_nxt = KT - s_cur;
+    {
+      typedef __attribute__((address_space(4))) const float CF;   // constant address space + uniform index = s_load_dword
+      rxm = ((CF*)a.rinv_tile_max)[cur.rt];
+    }
+#pragma unroll
+    for (int kt = 0; kt < KT; kt += KP) {
+      // L segment
+#pragma unroll
+      for (int kp = 0; kp < KP; ++kp) {
+        const uint8_t* s = lds + (s_cur + kt + kp) * S8Q_SLAB;
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) af[kp][mt][ks] = *(const half8*)(s + rd[ks] + mt * 2048);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (!NO_GLDS) {
+#pragma unroll
+        for (int kp = 0; kp < KP; ++kp) stage(nxt.p, kt + kp, s_nxt + kt + kp);
+      }
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(KT - KP) : "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      // M segment
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int kp = 0; kp < KP; ++kp)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+              const i32x4 z = i32x4{};
+              const i32x4 cin = (kt + kp == 0 && ks == 0) ? z : acc[mt][nt];
+              acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[kp][mt][ks]), qf[nt][kt + kp][ks],
+                                                                  cin, 0, 0, 0);
+            }
+      if (kt + KP == KT) filter(cur.row0);
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    cur = nxt;
+  }
+
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the never-read tail loads
+  if (grp == 0) __builtin_amdgcn_s_barrier();
+  if (lane == 0) a.hitcnt[blockIdx.x * 8 + wave] = wpos;
+}
+
 // Logs -> per-query candidate buffers.  Every entry is a lane's column of one quadrant (see the
 // filter); rows whose score reaches the query's threshold are appended (order is irrelevant,
 // k_compact sorts).  tau is what the scan used: nothing updates it in between.
@@ -675,7 +930,9 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
                         // everything of a dense search but its scan kernels, B = 1024, L = 100: 0.857 / 0.75 / 0.747 ms at 1 / 2 / 4)
 constexpr int S8_WPL = HX_S8_WPL;
 constexpr int S8_SB = 8 / S8_WPL;
-template <int KIND, int TS, bool HQ = false>
+// QS: the logs of k_scan8q.  Wave w of scan workgroup (xcd, i0) owns queries qt * 256 + 32 w .. + 31, qt = i0 mod nq_tiles:
+// a workgroup takes the eight logs of ONE scan workgroup, i.e. the 256 queries of its query tile.
+template <int KIND, int TS, bool HQ = false, bool QS = false>
 __global__ __launch_bounds__(1024) void k_scatter_log(uint4* log, const int* __restrict__ hitcnt,
                                                       int logcap, int n_scan_blocks, int nq_tiles,
                                                       const float* __restrict__ tau, int64_t row_end, int64_t id_base,
@@ -686,17 +943,20 @@ __global__ __launch_bounds__(1024) void k_scatter_log(uint4* log, const int* __r
   static_assert(MT * NG * 4 <= 32, "one mask bit per logged score");
   __shared__ int lcnt[S8_MAXQ / 4];    // per query of the column group: candidates, then next slot
   const int tid = threadIdx.x;
-  const int wn = blockIdx.x & 3;                      // query column group
-  const int sb0 = (blockIdx.x >> 2) * S8_SB;          // first scan workgroup
+  static_assert(!QS || (!HQ && KIND == KIND_I8 && S8_WPL == 2), "k_scan8q: int8, eight logs per scatter workgroup");
+  const int wn = QS ? 0 : blockIdx.x & 3;             // query column group
+  const int sb0 = QS ? blockIdx.x : (blockIdx.x >> 2) * S8_SB;   // first scan workgroup
   constexpr int QT = HQ ? 128 : 256, QW = HQ ? 32 : 64, QTS = HQ ? 7 : 8;   // (k_scan8: queries per tile / per wave column)
-  const int nloc = nq_tiles * QW;                     // queries of the group: q = qt*QT + wn*QW + j
+  const int qs_q0 = QS ? (((int)blockIdx.x >> 3) % nq_tiles) * 256 : 0;    // QS: first query of the scan workgroup's tile
+  const int nloc = QS ? 256 : nq_tiles * QW;          // queries of the group: q = qt*QT + wn*QW + j (QS: qs_q0 + j)
+  auto lidx = [](int q) __attribute__((always_inline)) { return QS ? (q & 255) : (q >> QTS) * QW + (q & (QW - 1)); };
   for (int i = tid; i < nloc; i += 1024) lcnt[i] = 0;
   __syncthreads();
   static_assert(2 * S8_SB * S8_WPL == 1024 / 64, "S8_WPL waves of the workgroup per log");
   const int l = (tid >> 6) / S8_WPL, lane = tid & 63; // waves l * S8_WPL ... walk log l: the logs advance together
   const int sub = (tid >> 6) % S8_WPL;
-  const int sb = sb0 + (l >> 1);
-  const int w = sb * 8 + (l & 1) * 4 + wn;            // waves wn and wn + 4 of the scan workgroup
+  const int sb = QS ? sb0 : sb0 + (l >> 1);
+  const int w = QS ? sb * 8 + l : sb * 8 + (l & 1) * 4 + wn;   // waves wn and wn + 4 of the scan workgroup (QS: all eight)
   int n = sb < n_scan_blocks ? hitcnt[w] : 0;
   n = n < logcap ? n : logcap;
   uint4* base = log + (int64_t)w * logcap * ENTRY;
@@ -733,12 +993,12 @@ __global__ __launch_bounds__(1024) void k_scatter_log(uint4* log, const int* __r
         }
       }
     ((uint32_t*)e)[3] = mask;
-    if (mask) atomicAdd(&lcnt[(q >> QTS) * QW + (q & (QW - 1))], __builtin_popcount(mask));
+    if (mask) atomicAdd(&lcnt[lidx(q)], __builtin_popcount(mask));
   }
   __syncthreads();
   for (int i = tid; i < nloc; i += 1024) {
     const int c = lcnt[i];
-    const int q = (i / QW) * QT + wn * QW + (i & (QW - 1));
+    const int q = QS ? qs_q0 + i : (i / QW) * QT + wn * QW + (i & (QW - 1));
     lcnt[i] = c > 0 ? atomicAdd(cnt + q, c) : 0;   // first slot of this workgroup's range
   }
   __syncthreads();
@@ -751,7 +1011,7 @@ __global__ __launch_bounds__(1024) void k_scatter_log(uint4* log, const int* __r
     const int64_t row0 = (int64_t)(((uint64_t)h.z << 32) | h.y);
     float rq = 0.f;
     if constexpr (KIND == KIND_I8) rq = rinv_q[q];
-    int pos = atomicAdd(&lcnt[(q >> QTS) * QW + (q & (QW - 1))], __builtin_popcount(mask));
+    int pos = atomicAdd(&lcnt[lidx(q)], __builtin_popcount(mask));
     while (mask) {
       const int bit = __builtin_ctz(mask);
       mask &= mask - 1;
@@ -773,6 +1033,23 @@ bool scan8_usable(const ScanArgs& a, int bn) {
          a.row_bytes * 256 < (1ll << 31);
 }
 
+// The query-stationary form serves int8 rows of 768 bytes whose query tiles divide the 32 workgroups of an XCD evenly
+// (every workgroup then keeps one query tile for the whole launch).  Its grid is always the full 256: the streams of an
+// XCD are 32 / nq_tiles whatever the launch, and a workgroup whose stream has no rows leaves at once.
+bool scan8_qs_form(int kind, int half_q, int64_t row_bytes, int nq_tiles) {
+  return HX_S8_TS == 16 && kind == KIND_I8 && !half_q && row_bytes == 768 && nq_tiles >= 1 && nq_tiles <= 32 &&
+         32 % nq_tiles == 0;
+}
+
+// Waves that share the appends of a launch over `tiles` 256-row tiles (chunked_scan sizes the per-wave logs by it).
+// 256 x 256 / 256 x 128 form: 8 waves per (row tile, query tile) item, at most the 256 workgroups of the grid.
+// Query-stationary form: the 2 x tiles halves go to the 32 / nq_tiles streams of their XCD, every stream is nq_tiles
+// workgroups of 8 waves: min(256, 2 x tiles x nq_tiles) workgroups -- never fewer waves than the other form has.
+double scan8_log_waves(int64_t tiles, int nq_tiles, bool qs) {
+  const double items = (qs ? 2.0 : 1.0) * (double)tiles * (double)nq_tiles;
+  return 8.0 * (items < 256.0 ? items : 256.0);
+}
+
 void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_kernel) {
   const int64_t n_rows = a.row_end - a.row_begin;
   if (n_rows <= 0 || a.B <= 0) return;
@@ -786,6 +1063,28 @@ void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_
   g = (g + 7) / 8 * 8;
 #ifdef HX_SCAN_DBG
   static const int dbg = getenv("HX_SCAN_DBG") ? atoi(getenv("HX_SCAN_DBG")) : 0;
+#else
+  constexpr int dbg = 0;
+#endif
+  // HX_SCAN_DBG 12 (timing build): the query-stationary form without its global_load_lds; every other value times k_scan8
+  static const int qs_kp = getenv("HX_DEBUG_S8Q_KP") ? atoi(getenv("HX_DEBUG_S8Q_KP")) : 2;   // diagnostics: k-tiles per phase, 1 | 2
+  if (!a.no_qs && cap == 256 && (dbg == 0 || dbg == 12) && scan8_qs_form(kind, a.half_q, a.row_bytes, a.nq_tiles)) {
+    g = 256;
+#ifdef HX_SCAN_DBG
+    if (dbg == 12) hipLaunchKernelGGL((k_scan8q<6, 2, 2>), dim3(256), dim3(512), 0, st, a); else
+#endif
+    if (qs_kp == 1) hipLaunchKernelGGL((k_scan8q<6, 0, 1>), dim3(256), dim3(512), 0, st, a);
+    else if (qs_kp == 3) hipLaunchKernelGGL((k_scan8q<6, 0, 3>), dim3(256), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((k_scan8q<6, 0, 2>), dim3(256), dim3(512), 0, st, a);
+    HX_HIP(hipGetLastError());
+    if (after_kernel) HX_HIP(hipEventRecord(after_kernel, st));
+    hipLaunchKernelGGL((k_scatter_log<KIND_I8, HX_S8_TS, false, true>), dim3(256), dim3(1024), 0, st, a.hitlog, a.hitcnt,
+                       a.logcap, (int)g, a.nq_tiles, a.tau, a.n_total, a.id_base, a.rinv_x, a.rinv_q, a.cand, a.cnt,
+                       a.overflow, a.cap);
+    HX_HIP(hipGetLastError());
+    return;
+  }
+#ifdef HX_SCAN_DBG
 #define HX_DBG_CASE(K, D) \
   if (kind == K && dbg == D) hipLaunchKernelGGL((k_scan8<K, HX_S8_TS, D>), dim3((unsigned)g), dim3(512), 0, st, a); else
   HX_DBG_CASE(KIND_F16, 1) HX_DBG_CASE(KIND_F16, 2) HX_DBG_CASE(KIND_F16, 3) HX_DBG_CASE(KIND_F16, 4)

@@ -540,6 +540,23 @@ def dense_route(B: int, L: int, cand: str = "i8", retry_level: int = 0):
     return tuple(int(x.value) for x in v)
 
 
+def scan8_form(B: int, row_bytes: int, kind: str = "i8") -> int:
+    """Kernel of the whole-collection candidate scan for B queries over rows of row_bytes bytes (hx_scan8_form): 0 = k_scan,
+    1 = k_scan8 (256 x 256 tile), 2 = its 256 x 128 form, 3 = k_scan8q, the query-stationary form.  No index, no device."""
+    if kind not in ("i8", "f16"):
+        raise ValueError("kind must be 'i8' or 'f16'")
+    v = C.c_int32()
+    check(_lib.lib().hx_scan8_form(B, row_bytes, 1 if kind == "i8" else 0, C.byref(v)))
+    return int(v.value)
+
+
+def scan8_log_waves(tiles: int, nq_tiles: int, qs: bool) -> float:
+    """Waves that share the log appends of a scan launch over `tiles` 256-row tiles (hx_scan8_log_waves)."""
+    v = C.c_double()
+    check(_lib.lib().hx_scan8_log_waves(tiles, nq_tiles, 1 if qs else 0, C.byref(v)))
+    return float(v.value)
+
+
 def h1_finish(reduced: torch.Tensor, world: int, B: int, lp: int, k3: int, dense_limit: int, sparse_limit: int,
               limit: int = 10, k: float = 2.0, rank_base: int = 0, nfail: Optional[torch.Tensor] = None):
     """reduced: the all-reduced (integer sum over the `world` ranks) result of h1_rescore_async.  Returns (keys [B, limit],
