@@ -143,6 +143,26 @@ int hx_truncate(hx_index* h, int64_t n_rows);
  * were named with hx_set_next_id (a shard of a sharded collection: renumbering is a collective matter).  Synchronises
  * the device (as hx_truncate) and returns when the compaction is done. */
 int hx_retain_rows(hx_index* h, const uint32_t* keep_host, int64_t mask_rows, int64_t* n_removed);
+/* Upsert by an existing id (client.upsert overwrites the point that already has the id, qdrant_handler.py:190-193):
+ * replace stored rows in place.  rows_host[m] = local rows in [0, hx_count), any order, unique; dense_host = [m, dim]
+ * raw fp32 in that order; indptr_host / idx_host / val_host = the CSR of the m new sparse vectors in that order.
+ * indptr_host NULL = the sparse vectors of those rows stay as they are (the dense-only form: the document-major CSR,
+ * the inverted index and the weight range are not touched).
+ * After the call the index is the index one gets by creating a new one and adding the final rows in their order:
+ * hx_count is unchanged, hx_nnz is the final rows'; every search entry returns (ids and fp32 score bits) what that
+ * index returns; hx_debug_row gives its bytes for the replaced rows and the old bytes for every other row; later
+ * hx_add_*, hx_retain_rows, hx_truncate, hx_save / hx_load behave as on it.  Every stored copy of a replaced row is
+ * derived in a staging block and scattered into place, the CSR is spliced from the first replaced document on
+ * (DESIGN.md section 18); the inverted index is dropped and rebuilt by the next search or hx_finalize (not by the
+ * dense-only form); the weight range (hx_sparse_wmax) is the final rows'.  Ids, capacities and the hx_stats counters
+ * stay; cand8_row_error_max keeps covering the replaced rows and the rows of a refused batch (an upper bound).
+ * m == 0: returns 0, nothing is touched.  Refused before any stored byte changes: a NULL index, m < 0, NULL rows_host /
+ * dense_host with m > 0, a row outside [0, hx_count), a duplicate row, a NaN / Inf dense element, a sparse batch
+ * hx_add_sparse would refuse, sparse vectors pending for rows not added yet, an index whose ids were named with
+ * hx_set_next_id.  Synchronises the device at its start and before it returns; its staging buffers (one derived copy
+ * of m rows, 8 bytes per posting from the first replaced document on) are freed before it returns. */
+int hx_replace_rows(hx_index* h, const int64_t* rows_host, int64_t m, const float* dense_host,
+                    const int64_t* indptr_host, const int32_t* idx_host, const float* val_host);
 /* build the on-device inverted index over everything added so far; searches
  * call it implicitly when the index is stale. */
 int hx_finalize(hx_index* h);
@@ -409,6 +429,16 @@ int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled);
  * heads with the rows, offsets and elements as the sparse CSR -- and drops one that lags. */
 int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* values_host,
                             int64_t n_values);
+/* The cells of rows that stay where they are (client.upsert of a point whose id exists overwrites its payload,
+ * qdrant_handler.py:190-193): rows_host[m] unique rows below `filled`, any order; cells_host = their m new cells, in the
+ * encoding of hx_payload_append.  Afterwards the column is the column to which the final cells were appended.  Refused,
+ * with the column unchanged: a row at or past `filled`, a duplicate row, a list column.  Synchronises the device. */
+int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const void* cells_host);
+/* The same for a LIST column (client.upsert, qdrant_handler.py:190-193): heads_host[m] / values_host / n_values in the
+ * encoding of hx_payload_append_lists, with its refusals.  The heads are scattered; offsets and elements are spliced
+ * from the first replaced row on, as hx_replace_rows splices the sparse CSR. */
+int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                             const void* values_host, int64_t n_values);
 /* The program: postfix over a per-row boolean stack (at most HX_PAY_MAX_STACK deep, exactly one entry at the end).
  *   HX_PAY_TRUE / _FALSE                 push a constant
  *   HX_PAY_IS_MISSING / _IS_NULL / _PRESENT  col   push the cell's state (PRESENT = neither missing nor null)

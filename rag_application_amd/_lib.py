@@ -71,6 +71,7 @@ _SIGS = {
     "hx_set_next_id": [_P, C.c_int64],
     "hx_truncate": [_P, C.c_int64],
     "hx_retain_rows": [_P, _P, C.c_int64, C.POINTER(C.c_int64)],
+    "hx_replace_rows": [_P, _P, C.c_int64, _P, _P, _P, _P],
     "hx_finalize": [_P],
     "hx_count": [_P, C.POINTER(C.c_int64)],
     "hx_nnz": [_P, C.POINTER(C.c_int64)],
@@ -115,6 +116,8 @@ _SIGS = {
     "hx_payload_mask": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int64), _P],
     "hx_payload_debug_cell": [_P, C.c_int32, C.c_int64, _P],
     "hx_payload_append_lists": [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64],
+    "hx_payload_replace": [_P, C.c_int32, _P, C.c_int64, _P],
+    "hx_payload_replace_lists": [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64],
     "hx_payload_debug_list": [_P, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), _P, C.c_int64, C.POINTER(C.c_int64)],
     "hx_bm25_embed_batch": [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, C.c_int64, _P],
     "hx_save": [_P, C.c_char_p],

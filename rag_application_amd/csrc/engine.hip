@@ -6,6 +6,7 @@
 #include "../../include/hx.h"
 #include "hx_common.hpp"
 #include "kernels.hpp"
+#include "replace.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -2057,6 +2058,42 @@ static void add_dense_dev(hx_index* h, const float* rows_dev, int64_t n, hipStre
 // Largest |value| a sparse vector may hold: products q_t * d_t then stay far inside fp32.
 constexpr float SPARSE_ABS_MAX = 1.0e18f;
 
+// The device checks of a sparse batch that already lies on the device: n rows whose offsets start at rows_ip, postings
+// idx_dev / val_dev [first, last).  Term ids in [0, 2^31) and unique within a vector (Qdrant rejects duplicates), finite
+// values with |v| <= SPARSE_ABS_MAX; *lo / *hi = the range of the values.  indptr / idx are the caller's host arrays of the
+// batch (offsets from 0): vectors too long for the wave compare are sorted from them.  Throws before anything is committed.
+static void check_sparse_batch_dev(hx_index* h, const int64_t* rows_ip, const int32_t* idx_dev, const float* val_dev, int64_t n,
+                                   int64_t first, int64_t last, const int64_t* indptr, const int32_t* idx, float* lo,
+                                   float* hi) {
+  constexpr int LONG_CAP = 4096;
+  int64_t* long_rows = (int64_t*)h->ws.get(WS_LONG_ROWS, (size_t)LONG_CAP * 8 + 32);
+  int* flags = (int*)(long_rows + LONG_CAP);             // [0] bad bits, [1] rows too long for the wave compare
+  uint32_t* mm = (uint32_t*)(flags + 2);                 // [0..2] min, max (orderable), non-finite count
+  const uint32_t init[5] = {0u, 0u, 0xFFFFFFFFu, 0u, 0u};
+  HX_HIP(hipMemcpy(flags, init, 20, hipMemcpyHostToDevice));
+  launch_csr_check(rows_ip, idx_dev, n, first, last, flags, nullptr);
+  launch_csr_unique(rows_ip, idx_dev, n, flags, long_rows, LONG_CAP, flags + 1, nullptr);
+  launch_minmax_f32(val_dev + first, last - first, (float*)mm, nullptr);
+  uint32_t got[5];
+  HX_HIP(hipMemcpy(got, flags, 20, hipMemcpyDeviceToHost));
+  HX_CHECK((got[0] & 1) == 0, "indptr not monotone");
+  HX_CHECK((got[0] & 2) == 0, "sparse index out of range [0, 2^31)");
+  HX_CHECK((got[0] & 4) == 0, "sparse indices must be unique within a vector");
+  if (got[1] > 0) {          // vectors of more than CSR_UNIQUE_WAVE_MAX terms: sorted here, from the caller's arrays
+    std::vector<int32_t> tmp;
+    for (int64_t r = 0; r < n; ++r) {
+      if (indptr[r + 1] - indptr[r] <= CSR_UNIQUE_WAVE_MAX) continue;
+      tmp.assign(idx + indptr[r], idx + indptr[r + 1]);
+      std::sort(tmp.begin(), tmp.end());
+      HX_CHECK(std::adjacent_find(tmp.begin(), tmp.end()) == tmp.end(), "sparse indices must be unique within a vector");
+    }
+  }
+  HX_CHECK(got[4] == 0, "sparse values must be finite and at most 1e18 in magnitude");
+  *lo = orderable_f32(got[2]);
+  *hi = orderable_f32(got[3]);
+  HX_CHECK(*lo >= -SPARSE_ABS_MAX && *hi <= SPARSE_ABS_MAX, "sparse values must be finite and at most 1e18 in magnitude");
+}
+
 // Sparse vectors of the NEXT n rows (paired with dense rows by position).  Validates everything on the
 // host before anything is committed: monotone indptr, term ids in [0, 2^31) and unique per vector, finite
 // values with |v| <= SPARSE_ABS_MAX.  Rows that were added without a sparse vector before are padded as
@@ -2091,34 +2128,8 @@ static void add_sparse_host(hx_index* h, const int64_t* indptr, const int32_t* i
   if (nnz) {
     HX_HIP(hipMemcpy(h->sp_idx + h->nnz, idx, (size_t)nnz * 4, hipMemcpyHostToDevice));
     HX_HIP(hipMemcpy(h->sp_val + h->nnz, val, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    constexpr int LONG_CAP = 4096;
-    int64_t* long_rows = (int64_t*)h->ws.get(WS_LONG_ROWS, (size_t)LONG_CAP * 8 + 32);
-    int* flags = (int*)(long_rows + LONG_CAP);             // [0] bad bits, [1] rows too long for the wave compare
-    uint32_t* mm = (uint32_t*)(flags + 2);                 // [0..2] min, max (orderable), non-finite count
-    const uint32_t init[5] = {0u, 0u, 0xFFFFFFFFu, 0u, 0u};
-    HX_HIP(hipMemcpy(flags, init, 20, hipMemcpyHostToDevice));
-    const int64_t* rows_ip = h->sp_indptr + h->sp_rows + pad;
-    launch_csr_check(rows_ip, h->sp_idx, n, h->nnz, h->nnz + nnz, flags, nullptr);
-    launch_csr_unique(rows_ip, h->sp_idx, n, flags, long_rows, LONG_CAP, flags + 1, nullptr);
-    launch_minmax_f32(h->sp_val + h->nnz, nnz, (float*)mm, nullptr);
-    uint32_t got[5];
-    HX_HIP(hipMemcpy(got, flags, 20, hipMemcpyDeviceToHost));
-    HX_CHECK((got[0] & 1) == 0, "indptr not monotone");
-    HX_CHECK((got[0] & 2) == 0, "sparse index out of range [0, 2^31)");
-    HX_CHECK((got[0] & 4) == 0, "sparse indices must be unique within a vector");
-    if (got[1] > 0) {          // vectors of more than CSR_UNIQUE_WAVE_MAX terms: sorted here, from the caller's arrays
-      std::vector<int32_t> tmp;
-      for (int64_t r = 0; r < n; ++r) {
-        if (indptr[r + 1] - indptr[r] <= CSR_UNIQUE_WAVE_MAX) continue;
-        tmp.assign(idx + indptr[r], idx + indptr[r + 1]);
-        std::sort(tmp.begin(), tmp.end());
-        HX_CHECK(std::adjacent_find(tmp.begin(), tmp.end()) == tmp.end(), "sparse indices must be unique within a vector");
-      }
-    }
-    HX_CHECK(got[4] == 0, "sparse values must be finite and at most 1e18 in magnitude");
-    lo = orderable_f32(got[2]);
-    hi = orderable_f32(got[3]);
-    HX_CHECK(lo >= -SPARSE_ABS_MAX && hi <= SPARSE_ABS_MAX, "sparse values must be finite and at most 1e18 in magnitude");
+    check_sparse_batch_dev(h, h->sp_indptr + h->sp_rows + pad, h->sp_idx, h->sp_val, n, h->nnz, h->nnz + nnz, indptr, idx,
+                           &lo, &hi);
     h->sp_wmin = h->sp_have_w ? std::min(h->sp_wmin, lo) : lo;
     h->sp_wmax = h->sp_have_w ? std::max(h->sp_wmax, hi) : hi;
     h->sp_have_w = true;
@@ -2517,6 +2528,232 @@ int hx_retain_rows(hx_index* h, const uint32_t* keep_host, int64_t mask_rows, in
     return 0;
   }
   retain_rows(h, keep_host, n_removed);
+  HX_CATCH
+}
+
+// ---- upsert by an existing id ---------------------------------------------------------------
+namespace hx {
+
+// the rows of a replace call -- in [0, limit), unique -- as the uint32 list the kernels read
+static std::vector<uint32_t> replace_rows_checked(const int64_t* rows_host, int64_t m, int64_t limit, const char* who) {
+  std::vector<uint32_t> r((size_t)m);
+  for (int64_t i = 0; i < m; ++i) {
+    HX_CHECK(rows_host[i] >= 0 && rows_host[i] < limit, std::string(who) + ": a row lies outside [0, count)");
+    r[(size_t)i] = (uint32_t)rows_host[i];
+  }
+  std::vector<uint32_t> s(r);
+  std::sort(s.begin(), s.end());
+  HX_CHECK(std::adjacent_find(s.begin(), s.end()) == s.end(), std::string(who) + ": the rows must be unique");
+  return r;
+}
+
+// The splice of a CSR whose documents [f, total) take new lengths (replace.hip): the map document -> batch position,
+// the new lengths and their exclusive prefix.  base = the offset of document f (it stays), moved = the postings from f
+// on after the call.  Synchronises `st`.
+struct SplicePlan {
+  int64_t f = 0, docs = 0, base = 0, moved = 0;
+  DevTmp map_, lenoff;
+  const uint32_t* map() const { return (const uint32_t*)map_.p; }
+  const int64_t* off() const { return (const int64_t*)lenoff.p + (docs + 1); }
+};
+static void splice_plan(SplicePlan& s, const int64_t* indptr, int64_t total, int64_t f, const uint32_t* rows_dev, int64_t m,
+                        const int64_t* new_indptr_dev, hipStream_t st) {
+  s.f = f;
+  s.docs = total - f;
+  s.map_.alloc((size_t)s.docs * 4);
+  HX_HIP(hipMemsetAsync(s.map_.p, 0xFF, (size_t)s.docs * 4, st));
+  launch_splice_map(rows_dev, m, f, s.docs, (uint32_t*)s.map_.p, st);
+  s.lenoff.alloc((size_t)(s.docs + 1) * 8 * 2);
+  int64_t* len = (int64_t*)s.lenoff.p;
+  int64_t* off = len + (s.docs + 1);
+  HX_HIP(hipMemsetAsync(len + s.docs, 0, 8, st));
+  launch_csr_splice_len(indptr + f, s.map(), new_indptr_dev, s.docs, len, st);
+  exclusive_scan_i64(len, off, s.docs, st);
+  HX_HIP(hipStreamSynchronize(st));
+  HX_HIP(hipMemcpy(&s.base, indptr + f, 8, hipMemcpyDeviceToHost));
+  HX_HIP(hipMemcpy(&s.moved, off + s.docs, 8, hipMemcpyDeviceToHost));
+}
+
+static void replace_rows(hx_index* h, const int64_t* rows_host, int64_t m, const float* dense_host, const int64_t* indptr,
+                         const int32_t* idx, const float* val) {
+  const int64_t n = h->n;
+  HX_CHECK(ids_identity(h) && h->ids.next < 0,
+           "hx_replace_rows: the ids of this index were named with hx_set_next_id (a shard of a sharded collection): "
+           "replacing its rows is not supported");
+  HX_CHECK(h->sp_rows <= n, "hx_replace_rows: sparse vectors are pending for rows not added yet");
+  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, n, "hx_replace_rows");
+  int64_t nnz_new = 0;
+  if (indptr) {
+    HX_CHECK(indptr[0] == 0, "indptr[0] must be 0");
+    nnz_new = indptr[m];
+    HX_CHECK(nnz_new >= 0, "negative nnz");
+    HX_CHECK(nnz_new == 0 || (idx && val), "idx/val is NULL");
+    for (int64_t r = 0; r < m; ++r) HX_CHECK(indptr[r + 1] >= indptr[r] && indptr[r + 1] <= nnz_new, "indptr not monotone");
+  }
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  hipStream_t st = nullptr;
+  DevTmp rows_dev_;
+  rows_dev_.alloc((size_t)m * 4);
+  HX_HIP(hipMemcpy(rows_dev_.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  const uint32_t* rows_dev = (const uint32_t*)rows_dev_.p;
+
+  // ---- the sparse batch: uploaded beside the index and checked there, as hx_add_sparse checks its batch ----
+  DevTmp nip, nidx, nval;
+  if (indptr) {
+    nip.alloc((size_t)(m + 1) * 8);
+    nidx.alloc((size_t)nnz_new * 4);
+    nval.alloc((size_t)nnz_new * 4);
+    HX_HIP(hipMemcpy(nip.p, indptr, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz_new) {
+      HX_HIP(hipMemcpy(nidx.p, idx, (size_t)nnz_new * 4, hipMemcpyHostToDevice));
+      HX_HIP(hipMemcpy(nval.p, val, (size_t)nnz_new * 4, hipMemcpyHostToDevice));
+      float lo = 0.f, hi = 0.f;
+      check_sparse_batch_dev(h, (const int64_t*)nip.p, (const int32_t*)nidx.p, (const float*)nval.p, m, 0, nnz_new, indptr, idx,
+                             &lo, &hi);
+    }
+  }
+
+  // ---- the dense rows: derived in a staging block laid out as the stored arrays are (k_prep_rows as the add path
+  // launches it), the batch's non-finite word read before anything stored changes ----
+  const bool c8 = h->cand8 && h->q8s && h->q8s_scale && h->s8_err;
+  HX_CHECK(!h->cand8 || c8, "int8 candidate copy enabled but not allocated");
+  struct Arr {
+    void* dst;
+    int64_t rb;                        // row bytes; 4 = one scale per row
+    DevTmp stage;
+  };
+  Arr arrs[10];
+  int na = 0;
+  auto add = [&](void* dst, int64_t rb) {
+    arrs[na].dst = dst;
+    arrs[na].rb = rb;
+    arrs[na].stage.alloc((size_t)(m * rb));
+    return arrs[na++].stage.p;
+  };
+  PrepRowsArgs a{};
+  a.dim = h->dim;
+  a.dim_pad = h->dim_pad;
+  a.dim_pad8 = h->dim_pad8;
+  a.dense = (float*)add(h->dense, (int64_t)h->dim_pad * 4);
+  a.dense_h = (_Float16*)add(h->dense_h, (int64_t)h->dim_pad * 2);
+  a.q8 = (int8_t*)add(h->q8, h->dim_pad8);
+  a.q8_rinv = (float*)add(h->q8_rinv, 4);
+  a.n_prefix = h->n_pre;
+  for (int p = 0; p < h->n_pre; ++p) {
+    a.psize[p] = h->psize[p];
+    a.pre[p] = (float*)add(h->pre[p], (int64_t)h->psize[p] * 4);
+  }
+  a.pre_h0 = h->n_pre > 0 ? (_Float16*)add(h->pre_h0, (int64_t)h->psize[0] * 2) : nullptr;
+  a.q8s = c8 ? (int8_t*)add(h->q8s, h->dim_pad8) : nullptr;
+  a.q8s_scale = c8 ? (float*)add(h->q8s_scale, 4) : nullptr;
+  a.err_max = c8 ? h->s8_err : nullptr;
+  const int64_t CH = 65536;
+  float* raw = (float*)h->ws.get(WS_RAW, (size_t)std::min(m, CH) * h->dim * 4);
+  int* chk = rows_check_begin(h, st);
+  a.nonfinite = chk;
+  for (int64_t r0 = 0; r0 < m; r0 += CH) {
+    const int64_t k = std::min(CH, m - r0);
+    HX_HIP(hipMemcpy(raw, dense_host + r0 * h->dim, (size_t)k * h->dim * 4, hipMemcpyHostToDevice));
+    PrepRowsArgs c = a;
+    c.raw = raw;
+    c.n = k;
+    c.dense += r0 * h->dim_pad;
+    c.dense_h += r0 * h->dim_pad;
+    c.q8 += r0 * h->dim_pad8;
+    c.q8_rinv += r0;
+    for (int p = 0; p < h->n_pre; ++p) c.pre[p] += r0 * h->psize[p];
+    if (c.pre_h0) c.pre_h0 += r0 * h->psize[0];
+    if (c8) {
+      c.q8s += r0 * h->dim_pad8;
+      c.q8s_scale += r0;
+    }
+    launch_prep_rows(c, st);
+    if (r0 + k >= m) rows_check_fetch(h, chk, st);
+    HX_HIP(hipStreamSynchronize(st));
+  }
+  rows_check_end(h, chk, st);
+
+  // ---- the CSR's plan: offsets, spare buffers, capacity ----
+  SplicePlan sp;
+  DevTmp idx2, val2;
+  int64_t new_nnz = h->nnz;
+  uint32_t* mm = nullptr;
+  if (indptr) {
+    const int64_t rmin = *std::min_element(rows.begin(), rows.end()), rmax = *std::max_element(rows.begin(), rows.end());
+    if (rmax >= h->sp_rows) {          // trailing rows that never got a sparse vector: empty documents, as finalize pads them
+      reserve_sparse(h, n, h->nnz);
+      std::vector<int64_t> tail((size_t)(n - h->sp_rows), h->nnz);
+      if (h->sp_rows == 0) {
+        const int64_t zero = 0;
+        HX_HIP(hipMemcpy(h->sp_indptr, &zero, 8, hipMemcpyHostToDevice));
+      }
+      HX_HIP(hipMemcpy(h->sp_indptr + h->sp_rows + 1, tail.data(), tail.size() * 8, hipMemcpyHostToDevice));
+      h->sp_rows = n;
+      h->sparse_stale = true;
+    }
+    splice_plan(sp, h->sp_indptr, h->sp_rows, rmin, rows_dev, m, (const int64_t*)nip.p, st);
+    new_nnz = sp.base + sp.moved;
+    HX_CHECK(new_nnz < 0xFFFFFFFFll, "nnz per shard must stay below 2^32");
+    if (sp.moved > 0) {
+      idx2.alloc((size_t)sp.moved * 4);
+      val2.alloc((size_t)sp.moved * 4);
+    }
+    reserve_sparse(h, h->sp_rows, new_nnz);
+    mm = (uint32_t*)h->ws.get(WS_SP_MM, 16);
+  }
+
+  // ---- the stored arrays change ----
+  for (int i = 0; i < na; ++i) {
+    if (arrs[i].rb == 4) launch_scatter_u32(arrs[i].stage.p, arrs[i].dst, rows_dev, m, st);
+    else launch_scatter_rows16(arrs[i].stage.p, arrs[i].dst, arrs[i].rb, rows_dev, m, st);
+  }
+  uint32_t got[3] = {0xFFFFFFFFu, 0u, 0u};
+  if (indptr) {
+    if (new_nnz > 0) {
+      HX_HIP(hipMemcpyAsync(mm, got, 12, hipMemcpyHostToDevice, st));
+      launch_minmax_f32(h->sp_val, sp.base, (float*)mm, st);        // the documents in front of the first replaced one
+      if (sp.moved > 0) {
+        launch_csr_splice(h->sp_indptr + sp.f, sp.map(), (const int64_t*)nip.p, sp.off(), sp.docs, h->sp_idx, h->sp_val,
+                          (const int32_t*)nidx.p, (const float*)nval.p, (int32_t*)idx2.p, (float*)val2.p, mm, st);
+        launch_copy_u32(idx2.p, h->sp_idx + sp.base, sp.moved, st);
+        launch_copy_u32(val2.p, h->sp_val + sp.base, sp.moved, st);
+      }
+      HX_HIP(hipMemcpyAsync(got, mm, 12, hipMemcpyDeviceToHost, st));
+    }
+    launch_csr_new_indptr(h->sp_indptr + sp.f, sp.off(), sp.docs, sp.base, st);
+  }
+  HX_HIP(hipDeviceSynchronize());
+
+  // ---- what was derived from the old rows ----
+  h->tm_q8.rows = h->tm_q8s.rows = -1;
+  h->mv.have = 0;                      // the gathered copies of the mask view: a masked query reads the new rows
+  h->mv.tm_q8.rows = h->mv.tm_q8s.rows = -1;
+  if (indptr) {
+    h->nnz = new_nnz;
+    if (new_nnz > 0 && got[0] <= got[1]) {
+      h->sp_wmin = orderable_f32(got[0]);
+      h->sp_wmax = orderable_f32(got[1]);
+      h->sp_have_w = true;
+    } else {
+      h->sp_wmin = h->sp_wmax = 0.f;
+      h->sp_have_w = false;
+    }
+    free_sparse_index(h);
+    h->sparse_stale = true;
+  }
+}
+
+}  // namespace hx
+
+int hx_replace_rows(hx_index* h, const int64_t* rows_host, int64_t m, const float* dense_host, const int64_t* indptr_host,
+                    const int32_t* idx_host, const float* val_host) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  HX_CHECK(m >= 0, "hx_replace_rows: m < 0");
+  HX_CHECK(m == 0 || (rows_host && dense_host), "hx_replace_rows: rows / dense is NULL");
+  if (m == 0) return 0;
+  replace_rows(h, rows_host, m, dense_host, indptr_host, idx_host, val_host);
   HX_CATCH
 }
 
@@ -3447,6 +3684,143 @@ int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host
     if (f64) HX_HIP(hipMemcpy(c.e1 + c.n_el, hi.data(), (size_t)total * 4, hipMemcpyHostToDevice));
   }
   c.filled = want;
+  c.n_el = want_el;
+  HX_CATCH
+}
+
+// ---- the cells of rows that stay where they are (upsert by an existing id) --------------------
+int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const void* cells_host) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(m >= 0, "payload: m < 0");
+  HX_CHECK(m == 0 || (rows_host && cells_host), "payload: rows / cells are NULL");
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_replace_lists (column kind)");
+  if (m == 0) return 0;
+  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, "hx_payload_replace");
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  const bool f64 = c.kind == HX_PAY_F64;
+  DevTmp rows_dev, lo_dev, hi_dev;
+  rows_dev.alloc((size_t)m * 4);
+  lo_dev.alloc((size_t)m * 4);
+  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  if (!f64) {
+    HX_HIP(hipMemcpy(lo_dev.p, cells_host, (size_t)m * 4, hipMemcpyHostToDevice));
+  } else {
+    const uint64_t* v = (const uint64_t*)cells_host;
+    std::vector<uint32_t> lo((size_t)m), hi((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+      lo[(size_t)i] = (uint32_t)v[i];
+      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
+    }
+    hi_dev.alloc((size_t)m * 4);
+    HX_HIP(hipMemcpy(lo_dev.p, lo.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+    HX_HIP(hipMemcpy(hi_dev.p, hi.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  }
+  launch_scatter_u32(lo_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, nullptr);
+  if (f64) launch_scatter_u32(hi_dev.p, c.p1, (const uint32_t*)rows_dev.p, m, nullptr);
+  HX_HIP(hipDeviceSynchronize());
+  HX_CATCH
+}
+
+int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                             const void* values_host, int64_t n_values) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_replace_lists needs a list column (column kind)");
+  HX_CHECK(m >= 0 && n_values >= 0, "payload: m < 0");
+  HX_CHECK((m == 0 || (rows_host && heads_host)) && (values_host || n_values == 0), "payload: rows / cells are NULL");
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  // ---- every refusal and every allocation before the column changes ----
+  std::vector<uint32_t> heads((size_t)m);
+  std::vector<int64_t> noff((size_t)m + 1);
+  int64_t total = 0;
+  noff[0] = 0;
+  for (int64_t i = 0; i < m; ++i) {
+    const uint32_t hd = heads_host[i];
+    const bool is_list = hd < HX_PAY_U32_NULL;
+    heads[(size_t)i] = is_list ? 0u : hd;
+    if (is_list) total += hd;
+    HX_CHECK(total <= n_values, "payload: the element counts of the heads do not sum to n_values");
+    noff[(size_t)i + 1] = total;
+  }
+  HX_CHECK(total == n_values, "payload: the element counts of the heads do not sum to n_values");
+  std::vector<uint32_t> lo, hi;
+  if (f64) {
+    const uint64_t* v = (const uint64_t*)values_host;
+    const double* d = (const double*)values_host;
+    lo.resize((size_t)total);
+    hi.resize((size_t)total);
+    for (int64_t i = 0; i < total; ++i) {
+      HX_CHECK(d[i] == d[i], "payload: a list element is a NaN");
+      lo[(size_t)i] = (uint32_t)v[i];
+      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
+    }
+  } else {
+    const uint32_t* v = (const uint32_t*)values_host;
+    for (int64_t i = 0; i < total; ++i) HX_CHECK(v[i] < HX_PAY_U32_NULL, "payload: a list element is a reserved code");
+  }
+  if (m == 0) return 0;
+  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, "hx_payload_replace_lists");
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  hipStream_t st = nullptr;
+  DevTmp rows_dev, heads_dev, noff_dev, n0, n1, t0, t1;
+  rows_dev.alloc((size_t)m * 4);
+  heads_dev.alloc((size_t)m * 4);
+  noff_dev.alloc((size_t)(m + 1) * 8);
+  n0.alloc((size_t)total * 4);
+  if (f64) n1.alloc((size_t)total * 4);
+  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(heads_dev.p, heads.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(noff_dev.p, noff.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+  if (total > 0) {
+    HX_HIP(hipMemcpy(n0.p, f64 ? (const void*)lo.data() : values_host, (size_t)total * 4, hipMemcpyHostToDevice));
+    if (f64) HX_HIP(hipMemcpy(n1.p, hi.data(), (size_t)total * 4, hipMemcpyHostToDevice));
+  }
+  // rows in front of the first replaced one keep their elements and offsets; the rest go the sparse CSR's way
+  SplicePlan sp;
+  splice_plan(sp, c.off, c.filled, *std::min_element(rows.begin(), rows.end()), (const uint32_t*)rows_dev.p, m,
+              (const int64_t*)noff_dev.p, st);
+  const int64_t want_el = sp.base + sp.moved;
+  HX_CHECK(want_el <= 0x7FFFFFFFll, "payload: a list column holds fewer than 2^31 elements");
+  if (sp.moved > 0) {
+    t0.alloc((size_t)sp.moved * 4);
+    if (f64) t1.alloc((size_t)sp.moved * 4);
+  }
+  if (want_el > c.el_cap) {
+    const int64_t nec = round_up(std::max<int64_t>(want_el, c.el_cap * 2), 256);
+    uint32_t* ne0 = pay_grown(c.e0, c.n_el, nec);
+    uint32_t* ne1 = nullptr;
+    if (f64) {
+      try {
+        ne1 = pay_grown(c.e1, c.n_el, nec);
+      } catch (...) {
+        (void)hipFree(ne0);
+        throw;
+      }
+    }
+    if (c.e0) (void)hipFree(c.e0);
+    if (c.e1) (void)hipFree(c.e1);
+    c.e0 = ne0;
+    c.e1 = ne1;
+    c.el_cap = nec;
+  }
+  // ---- the column changes ----
+  launch_scatter_u32(heads_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, st);
+  if (sp.moved > 0) {
+    launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e0, (const uint32_t*)n0.p,
+                          (uint32_t*)t0.p, st);
+    if (f64)
+      launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e1,
+                            (const uint32_t*)n1.p, (uint32_t*)t1.p, st);
+    launch_copy_u32(t0.p, c.e0 + sp.base, sp.moved, st);
+    if (f64) launch_copy_u32(t1.p, c.e1 + sp.base, sp.moved, st);
+  }
+  launch_csr_new_indptr(c.off + sp.f, sp.off(), sp.docs, sp.base, st);
+  HX_HIP(hipDeviceSynchronize());
   c.n_el = want_el;
   HX_CATCH
 }

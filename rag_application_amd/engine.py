@@ -156,6 +156,42 @@ class HxIndex:
         check(_lib.lib().hx_retain_rows(self._h, _ptr(words), rows, C.byref(removed)))
         return removed.value
 
+    @staticmethod
+    def _rows(rows) -> np.ndarray:
+        """the row list of a replace call: 1-d integers, unique (the engine checks the range)"""
+        r = np.asarray(rows)
+        if r.ndim != 1 or r.dtype.kind not in "iu":
+            raise TypeError("rows: a 1-d integer array")
+        r = np.ascontiguousarray(r, dtype=np.int64)
+        if np.unique(r).shape[0] != r.shape[0]:
+            raise ValueError("rows must be unique")
+        return r
+
+    def replace(self, rows, dense: np.ndarray, sp_indptr=None, sp_idx=None, sp_val=None):
+        """Upsert by an existing id (hx_replace_rows): the stored rows `rows` (any order, unique) take the raw vectors
+        `dense` [len(rows), dim] and the sparse vectors of the CSR, in that order, and stay where they are.
+        sp_indptr None = their sparse vectors stay as they are.  All or nothing."""
+        rows = self._rows(rows)
+        dense = np.ascontiguousarray(dense, dtype=np.float32)
+        if dense.ndim != 2 or dense.shape[1] != self.dim:
+            raise ValueError(f"Dense vector dimension mismatch. Expected {self.dim}, got {dense.shape[-1]}")
+        m = rows.shape[0]
+        if dense.shape[0] != m:
+            raise ValueError(f"{m} rows but {dense.shape[0]} dense vectors")
+        if sp_indptr is None:
+            if sp_idx is not None or sp_val is not None:
+                raise ValueError("sparse indices / values without indptr")
+            check(_lib.lib().hx_replace_rows(self._h, _ptr(rows), m, _ptr(dense), 0, 0, 0))
+            return
+        sp_indptr = np.ascontiguousarray(sp_indptr, dtype=np.int64)
+        sp_idx = np.ascontiguousarray(sp_idx if sp_idx is not None else [], dtype=np.int32)
+        sp_val = np.ascontiguousarray(sp_val if sp_val is not None else [], dtype=np.float32)
+        if sp_indptr.shape[0] != m + 1:
+            raise ValueError("sparse indptr must have n+1 entries")
+        if m and (sp_idx.shape[0] < sp_indptr[-1] or sp_val.shape[0] < sp_indptr[-1]):
+            raise ValueError("sparse indices / values are shorter than indptr says")
+        check(_lib.lib().hx_replace_rows(self._h, _ptr(rows), m, _ptr(dense), _ptr(sp_indptr), _ptr(sp_idx), _ptr(sp_val)))
+
     def synth_fill(self, n: int, seed_dense: int, seed_sparse: int = 0, tables=None):
         if tables is not None:
             cdf = np.ascontiguousarray(tables[0], dtype=np.uint32)
@@ -422,6 +458,29 @@ class HxIndex:
             raise TypeError("payload lists: 1-d np.uint32 heads and 1-d np.uint32 / np.float64 values")
         check(_lib.lib().hx_payload_append_lists(self._h, int(col), _ptr(heads), heads.shape[0], _ptr(values),
                                                  values.shape[0]))
+
+    def payload_replace(self, col: int, rows, cells: np.ndarray) -> None:
+        """New cells for the stored rows `rows` of a scalar column (hx_payload_replace): `cells` as payload_append takes
+        them, one per row, in the order of `rows`."""
+        rows = self._rows(rows)
+        cells = np.ascontiguousarray(cells)
+        if cells.dtype not in (np.uint32, np.uint64, np.float64) or cells.ndim != 1:
+            raise TypeError("payload cells: a 1-d np.uint32 (U32 column) or np.uint64 / np.float64 (F64 column) array")
+        if cells.shape[0] != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} rows but {cells.shape[0]} cells")
+        check(_lib.lib().hx_payload_replace(self._h, int(col), _ptr(rows), rows.shape[0], _ptr(cells)))
+
+    def payload_replace_lists(self, col: int, rows, heads: np.ndarray, values: np.ndarray) -> None:
+        """New cells for the stored rows `rows` of a list column (hx_payload_replace_lists): heads / values as
+        payload_append_lists takes them, in the order of `rows`."""
+        rows = self._rows(rows)
+        heads, values = np.ascontiguousarray(heads), np.ascontiguousarray(values)
+        if heads.dtype != np.uint32 or heads.ndim != 1 or values.dtype not in (np.uint32, np.float64) or values.ndim != 1:
+            raise TypeError("payload lists: 1-d np.uint32 heads and 1-d np.uint32 / np.float64 values")
+        if heads.shape[0] != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} rows but {heads.shape[0]} heads")
+        check(_lib.lib().hx_payload_replace_lists(self._h, int(col), _ptr(rows), rows.shape[0], _ptr(heads), _ptr(values),
+                                                  values.shape[0]))
 
     def payload_list(self, col: int, row: int, kind: int):
         """One row of a list column (hx_payload_debug_list): (head, elements) -- head = MISSING, NULL or the element

@@ -193,6 +193,27 @@ class _Collection:
                 logging.warning("payload index: appending to %r failed, the key is dropped: %s", key, e)
             self._poison(key)
 
+    def replace_payload_cells(self, rows, payloads) -> None:
+        """The cells of rows replaced in place, for every live key (hx_payload_replace / _replace_lists).  A value that
+        poisons a key, or an engine failure, drops that key's column, as append_payload_cells does."""
+        pi = getattr(self, "pindex", None)
+        if pi is None:
+            return
+        rows = np.asarray(rows, np.int64)
+        for key in pi.live_keys():
+            k = pi.keys[key]
+            try:
+                cells = pi.encode(key, payloads)
+                if cells is not None:
+                    if k.is_list:
+                        self.index.payload_replace_lists(k.col, rows, cells[0], cells[1])
+                    else:
+                        self.index.payload_replace(k.col, rows, cells)
+                    continue
+            except Exception as e:
+                logging.warning("payload index: replacing cells of %r failed, the key is dropped: %s", key, e)
+            self._poison(key)
+
     def close(self):
         self.index.close()
 
@@ -236,6 +257,8 @@ class QdrantHandler:
     _masked_search = True
     # delete_points renumbers the rows of ONE engine index (hx_retain_rows)
     _point_deletes = True
+    # upsert_points replaces rows of ONE engine index in place (hx_replace_rows)
+    _point_upserts = True
     # payload columns live in ONE engine index, beside the rows whose payloads this process holds
     _payload_indexes = True
 
@@ -382,36 +405,120 @@ class QdrantHandler:
         await self._run(add)
         return len(dense)
 
+    @staticmethod
+    def _document_payload(chunk):
+        """the payload of one document chunk (qdrant_handler.py:165-185)"""
+        metadata = chunk["chunk_metadata"]
+        return {
+            "document_id": metadata["document_id"],
+            "user_id": metadata["user_id"],
+            "file_name": metadata["file_name"],
+            "mime_type": metadata["mime_type"],
+            "file_size": metadata["file_size"],
+            "file_description": metadata["description"],
+            "file_path": metadata["file_path"],
+            "context_version": metadata["context_version"],
+            "chunk_number": metadata["chunk_number"],
+            "entities": metadata.get("entities"),
+            "relationships": metadata.get("relationships"),
+            "context": metadata.get("context"),
+            "document_summary": metadata["doc_summary"],
+            "content": str(chunk["content"]),
+            "page_number": metadata.get("page_number"),
+            "languages": metadata.get("languages"),
+            "element_id": metadata.get("element_id"),
+            "is_continuation": metadata.get("is_continuation"),
+            "category": metadata.get("category"),
+        }
+
     async def store_document_vectors(self, embedded_chunks: List[Dict[str, Any]], user_id: str):
         """Stores document chunks with multi-stage embeddings (qdrant_handler.py:120-198)."""
         try:
-            def payload(chunk):
-                metadata = chunk["chunk_metadata"]
-                return {
-                    "document_id": metadata["document_id"],
-                    "user_id": metadata["user_id"],
-                    "file_name": metadata["file_name"],
-                    "mime_type": metadata["mime_type"],
-                    "file_size": metadata["file_size"],
-                    "file_description": metadata["description"],
-                    "file_path": metadata["file_path"],
-                    "context_version": metadata["context_version"],
-                    "chunk_number": metadata["chunk_number"],
-                    "entities": metadata.get("entities"),
-                    "relationships": metadata.get("relationships"),
-                    "context": metadata.get("context"),
-                    "document_summary": metadata["doc_summary"],
-                    "content": str(chunk["content"]),
-                    "page_number": metadata.get("page_number"),
-                    "languages": metadata.get("languages"),
-                    "element_id": metadata.get("element_id"),
-                    "is_continuation": metadata.get("is_continuation"),
-                    "category": metadata.get("category"),
-                }
-            n = await self._store(user_id, embedded_chunks, payload)
+            n = await self._store(user_id, embedded_chunks, self._document_payload)
             logging.info("store_document_vectors: %d chunks added for %s", n, user_id)
         except Exception as e:
             logging.error("store_document_vectors failed: %s", e)
+            raise
+
+    # --------------------------------------------------------------------- upsert by id
+    def _upsert_sync(self, user_id, items, point_ids) -> int:
+        col = self._collections[str(user_id)]
+        if len(items) != len(point_ids):
+            raise ValueError(f"{len(items)} chunks but {len(point_ids)} point ids")
+        named = [str(p) for p in point_ids if p is not None]
+        if len(set(named)) != len(named):
+            raise ValueError("upsert_points: a point id is listed twice")
+        for item in items:
+            if len(item["dense_embedding"]) != col.dim:
+                raise ValueError(
+                    f"Dense vector dimension mismatch. Expected {col.dim}, got {len(item['dense_embedding'])}")
+        id_rows = col._id_rows()
+        if id_rows is None:
+            raise ValueError("upsert_points: the collection holds one id twice")
+
+        def pack(sel):
+            dense, indptr, idx, val = [], [0], [], []
+            for k in sel:
+                item = items[k]
+                dense.append(np.asarray(item["dense_embedding"], dtype=np.float32))
+                si, sv = _sparse_parts(item["sparse_embedding"]) if col.sparse_enabled else ([], [])
+                idx.extend(int(i) for i in si)
+                val.extend(float(v) for v in sv)
+                indptr.append(len(idx))
+            return (np.stack(dense), np.asarray(indptr, np.int64), np.asarray(idx, np.int32), np.asarray(val, np.float32))
+        old = [k for k, p in enumerate(point_ids) if p is not None and str(p) in id_rows]
+        new = [k for k, p in enumerate(point_ids) if p is None or str(p) not in id_rows]
+        rows = [id_rows[str(point_ids[k])] for k in old]
+        payloads = [self._document_payload(item) for item in items]
+        packed_new = pack(new) if new else None             # (everything that can raise in Python comes before the engine)
+        packed_old = pack(old) if old else None
+        n0 = len(col.ids)
+        # append first, then replace: a refused replace rolls the appended rows back, the call is all or nothing
+        if new:
+            col.index.add(*packed_new)
+            col.ids.extend(str(point_ids[k]) if point_ids[k] is not None else str(uuid.uuid4()) for k in new)
+            col.payloads.extend(payloads[k] for k in new)
+            col.append_payload_cells([payloads[k] for k in new])
+        if not old:
+            return 0
+        try:
+            col.index.replace(np.asarray(rows, np.int64), *packed_old)
+        except Exception:
+            if new:
+                col.index.truncate(n0)                      # (the payload columns are cut with the rows)
+                del col.ids[n0:]
+                del col.payloads[n0:]
+                col._idrows = None
+            raise
+        for r, k in zip(rows, old):
+            col.payloads[r] = payloads[k]
+        col.replace_payload_cells(rows, [payloads[k] for k in old])
+        col._masks.clear()                                  # a cached mask may be wrong for a replaced row
+        return len(old)
+
+    async def upsert_points(self, user_id: str, embedded_chunks: List[Dict[str, Any]],
+                            point_ids: List[Optional[str]]) -> int:
+        """client.upsert with ids the caller names (qdrant_handler.py:190-193; additive: the reference always draws a
+        fresh uuid4).  embedded_chunks as store_document_vectors takes them, point_ids one entry per chunk.  An id the
+        collection holds: that point is replaced IN PLACE -- dense vector, sparse vector, payload -- and keeps its row,
+        hence its rank among equal scores (hx_replace_rows).  An unknown id is appended under that id, None under a fresh
+        uuid4.  Returns the number of points replaced.  A duplicate id within the call, a length or dimension mismatch
+        or an empty user_id raises ValueError before anything changes; a batch the engine refuses leaves the collection
+        as it was.  Nothing is saved: call save_collection."""
+        try:
+            if not user_id:
+                raise ValueError("user_id cannot be empty")
+            if not self._point_upserts:
+                raise ValueError("upsert_points is not supported on a sharded collection")
+            if len(embedded_chunks) != len(point_ids):
+                raise ValueError(f"{len(embedded_chunks)} chunks but {len(point_ids)} point ids")
+            if str(user_id) not in self._collections:
+                await self.create_collection(user_id=user_id)
+            n = await self._run(self._upsert_sync, user_id, list(embedded_chunks), list(point_ids))
+            logging.info("upsert_points: %d points replaced for %s", n, user_id)
+            return n
+        except Exception as e:
+            logging.error("upsert_points(%s) failed: %s", user_id, e)
             raise
 
     async def store_chat_vectors(self, embedded_payload: List[Dict[str, Any]], user_id: str):

@@ -465,11 +465,13 @@ class ShardedHandler(QdrantHandler):
     (:297, :371), the rerank hook (:380), `persist_dir`, the error conventions -- with the engine index replaced by a
     sharded one.  The front rank holds point ids and payloads; worker ranks hold only their shard and run `serve()`.
     `timeout` (seconds) bounds every wait on another rank: a worker that died or hangs makes the front rank's call
-    fail (search -> [], mutation -> raise) instead of hanging it.  filter_stages="all" (row masks across shards) and
-    delete_points (renumbering the rows of every shard) are refused with a ValueError."""
+    fail (search -> [], mutation -> raise) instead of hanging it.  filter_stages="all" (row masks across shards),
+    delete_points (renumbering the rows of every shard) and upsert_points (replacing rows of a shard in place) are
+    refused with a ValueError."""
 
     _masked_search = False
     _point_deletes = False           # delete_points raises ValueError: nothing is sent to the ranks
+    _point_upserts = False           # upsert_points raises ValueError: nothing is sent to the ranks
     _payload_indexes = False         # create_payload_index raises ValueError: payloads live on the front rank only
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
