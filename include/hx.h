@@ -403,6 +403,8 @@ int hx_release_mask_view(hx_index* h);
 #define HX_PAY_F64 2
 #define HX_PAY_LIST_U32 3   /* list-valued fields: one state per row -- missing, null, or a list of */
 #define HX_PAY_LIST_F64 4   /* k >= 0 elements: U32 codes below HX_PAY_U32_NULL, or doubles that are not NaN              */
+#define HX_PAY_TEXT 5       /* text fields: one state per row -- missing, null, or a byte string of     */
+                            /* length >= 0 (the caller's lower-cased UTF-8; the engine only ever sees bytes)                   */
 #define HX_PAY_U32_MISSING 0xFFFFFFFFu
 #define HX_PAY_U32_NULL    0xFFFFFFFEu
 #define HX_PAY_F64_MISSING 0x7FF80000FFFFFFFFull
@@ -410,6 +412,8 @@ int hx_release_mask_view(hx_index* h);
 #define HX_PAY_MAX_COLUMNS 64
 #define HX_PAY_MAX_STACK   32
 #define HX_PAY_MAX_OPS     4096
+#define HX_PAY_TEXT_MAX_WORDS 32        /* patterns of one HX_PAY_TEXT_ALL */
+#define HX_PAY_TEXT_MAX_WORD_BYTES 64   /* bytes of one pattern */
 /* a new empty column; *col = its id (ids are never reused).  Refused when the index holds HX_PAY_MAX_COLUMNS columns. */
 int hx_payload_create(hx_index* h, int32_t kind, int32_t* col);
 /* an unknown or dropped column is an error, here and in every entry below */
@@ -439,6 +443,20 @@ int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64
  * from the first replaced row on, as hx_replace_rows splices the sparse CSR. */
 int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
                              const void* values_host, int64_t n_values);
+/* The cells of rows [filled, filled + n) of a TEXT column.  heads_host[i] = HX_PAY_U32_MISSING, HX_PAY_U32_NULL or the
+ * row's byte length (0 = the empty string); bytes_host = the rows' bytes one after another, n_bytes of them.  On the device
+ * the column is stored as a list column is: a head plane (uint32 per row: missing, null or the byte length), int64 offsets
+ * [filled + 1] counting 32-bit words, and one plane of words holding the bytes, every row padded with zero bytes to a
+ * multiple of four -- the padding is not text: the head's byte length bounds a match.  Refused, with the column unchanged:
+ * filled + n > hx_count, lengths that do not sum to n_bytes, a column that is not a text column ("kind" in the message;
+ * likewise hx_payload_append / _append_lists on a text column), a column that would hold 2^31 words (8 GB) or more.
+ * hx_truncate, hx_retain_rows, hx_payload_drop and hx_destroy treat it as they treat a list column. */
+int hx_payload_append_text(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* bytes_host,
+                           int64_t n_bytes);
+/* hx_payload_replace_lists for a TEXT column: heads_host[m] / bytes_host / n_bytes in the encoding of
+ * hx_payload_append_text, with its refusals and those of hx_payload_replace (a row at or past `filled`, a duplicate). */
+int hx_payload_replace_text(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                            const void* bytes_host, int64_t n_bytes);
 /* The program: postfix over a per-row boolean stack (at most HX_PAY_MAX_STACK deep, exactly one entry at the end).
  *   HX_PAY_TRUE / _FALSE                 push a constant
  *   HX_PAY_IS_MISSING / _IS_NULL / _PRESENT  col   push the cell's state (PRESENT = neither missing nor null)
@@ -456,7 +474,13 @@ int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host,
  * The ANY ops are false on a missing, null or empty row.  EQ / IN / LT / LE / GT / GE are refused on a list column, the
  * four list ops on a scalar column.
  * EQ, IN and the comparisons are false on a missing or null cell.  A set is `n` values on the host, ascending (equal
- * neighbours allowed): uint32 for a U32 column and ROW_IN, doubles (no NaN) for an F64 column. */
+ * neighbours allowed): uint32 for a U32 column and ROW_IN, doubles (no NaN) for an F64 column.
+ * Text columns take IS_MISSING / IS_NULL / PRESENT (the row's state) and
+ *   HX_PAY_TEXT_ALL  col imm = set index   every pattern of the set occurs in the row's bytes (a byte-substring test,
+ *                                         within the row's byte length); false on a missing or null row
+ * Its set is a pattern blob: hx_pay_set.vals points at bytes, n = their number; uint32 P, then uint32 len[P], then the
+ * patterns' bytes one after another, 1 <= P <= HX_PAY_TEXT_MAX_WORDS, 1 <= len <= HX_PAY_TEXT_MAX_WORD_BYTES.  Every
+ * other column op is refused on a text column, TEXT_ALL on every other column. */
 #define HX_PAY_TRUE 0
 #define HX_PAY_FALSE 1
 #define HX_PAY_IS_MISSING 2
@@ -476,6 +500,7 @@ int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host,
 #define HX_PAY_ANY_IN 16
 #define HX_PAY_ANY_RANGE 17
 #define HX_PAY_IS_EMPTY_LIST 18
+#define HX_PAY_TEXT_ALL 19
 typedef struct hx_pay_op {
   int32_t op;
   int32_t col;
@@ -490,14 +515,21 @@ typedef struct hx_pay_set {
  * call then synchronises `stream` once; with NULL nothing is read back and the call only enqueues work (the host
  * arguments are copied before it returns).  Refused before any device work: a referenced column that is unknown or not
  * filled to hx_count, a comparison on a U32 column, a list op on a scalar column or a scalar op on a list column,
- * ANY_RANGE on a U32 list column or with a set of other than two entries, a set index out of range, a set that is not ascending, more than
+ * ANY_RANGE on a U32 list column or with a set of other than two entries, TEXT_ALL on a column that is not a text column or
+ * any op but the three state ops and TEXT_ALL on one, a pattern blob whose size disagrees with its header or that holds
+ * no pattern, more than HX_PAY_TEXT_MAX_WORDS, an empty one or one above HX_PAY_TEXT_MAX_WORD_BYTES, a set index out of
+ * range, a set that is not ascending, more than
  * HX_PAY_MAX_OPS ops, a stack that would exceed HX_PAY_MAX_STACK entries or underflow or does not end with exactly one
  * entry. */
 int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets_host, int32_t n_sets,
                     uint32_t* mask_dev, int64_t* n_kept, void* stream);
 /* copy one cell to the host (4 bytes of a U32 column, 8 of an F64 column), as hx_debug_row does for vectors; refused on
- * a list column */
+ * a list or text column */
 int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host);
+/* copy one row of a text column to the host: *head = what hx_payload_append_text took for it (missing, null or the byte
+ * length), *count = its bytes (0 for a missing or null row), of which the first min(count, cap) go to bytes_out */
+int hx_payload_debug_text(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* bytes_out, int64_t cap,
+                          int64_t* count);
 /* copy one row of a list column to the host: *head = what hx_payload_append_lists took for it (missing, null or the
  * element count), *count = its elements, of which the first min(count, cap) go to values_out (uint32 or doubles) */
 int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,

@@ -119,6 +119,9 @@ _SIGS = {
     "hx_payload_replace": [_P, C.c_int32, _P, C.c_int64, _P],
     "hx_payload_replace_lists": [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64],
     "hx_payload_debug_list": [_P, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), _P, C.c_int64, C.POINTER(C.c_int64)],
+    "hx_payload_append_text": [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64],
+    "hx_payload_replace_text": [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64],
+    "hx_payload_debug_text": [_P, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), _P, C.c_int64, C.POINTER(C.c_int64)],
     "hx_bm25_embed_batch": [_P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P, _P, C.c_int64, _P],
     "hx_save": [_P, C.c_char_p],
     "hx_load": [C.c_char_p, C.c_int32, C.POINTER(_P)],

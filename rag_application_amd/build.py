@@ -17,7 +17,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("sparse2.hip", "sparse2_v64k.o", ("HX_SP_VARIANT=v64k", "HX_SEG_DOCS=65536", "HX_SP_THREADS=1024")),
            ("sprescore.hip", "sprescore.o", ()), ("mask.hip", "mask.o", ()), ("compact.hip", "compact.o", ()),
            ("replace.hip", "replace.o", ()),
-           ("payload.hip", "payload.o", ()),
+           ("payload.hip", "payload.o", ()), ("paytext.hip", "paytext.o", ()),
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("bm25.cpp", "bm25.o", ())]
 HEADERS = ["hx_common.hpp", "kernels.hpp", "replace.hpp", "wsort.hpp", os.path.join("..", "..", "include", "hx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",

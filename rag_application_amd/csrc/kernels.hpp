@@ -426,8 +426,10 @@ void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t 
 // A list column gives p0 = its head plane (p1 = NULL: the head reads as a U32 cell), off = its
 // int64 offsets [n + 1] and e0 / e1 = its element planes (e1 = the high words of doubles or NULL).  Codes from
 // PAY_D_FIRST_LIST on walk the elements; ANY_RANGE carries its closed interval in imm / imm2 (the bits of two doubles).
+// PAY_D_BITS is device-only: imm = a packed verdict plane in the mask's layout, written by
+// k_payload_text in front of the mask kernel on the same stream; the op pushes the row's bit of it.
 enum PayDevOp : uint32_t {
-  PAY_D_TRUE = 0, PAY_D_FALSE, PAY_D_AND, PAY_D_OR, PAY_D_NOT, PAY_D_ROW_IN,
+  PAY_D_TRUE = 0, PAY_D_FALSE, PAY_D_AND, PAY_D_OR, PAY_D_NOT, PAY_D_ROW_IN, PAY_D_BITS,
   PAY_D_FIRST_COL, PAY_D_IS_MISSING = PAY_D_FIRST_COL, PAY_D_IS_NULL, PAY_D_PRESENT, PAY_D_EQ_U32, PAY_D_IN_U32,
   PAY_D_EQ_F64, PAY_D_IN_F64, PAY_D_LT, PAY_D_LE, PAY_D_GT, PAY_D_GE,
   PAY_D_FIRST_LIST, PAY_D_IS_EMPTY_LIST = PAY_D_FIRST_LIST, PAY_D_ANY_EQ_U32, PAY_D_ANY_IN_U32, PAY_D_ANY_EQ_F64,
@@ -448,6 +450,19 @@ constexpr int PAY_INLINE_SET = 8;   // sets up to here are compared entry by ent
 // when kept is not NULL (the caller zeroes it).  grid_cap > 0 caps the grid (HX_DEBUG_PAY_GRID: tests).
 void launch_payload_mask(const PayOpDev* prog, int n_ops, int64_t n, uint32_t* mask, uint32_t* kept, int grid_cap,
                          hipStream_t st);
+// ---- paytext.hip: HX_PAY_TEXT_ALL -------------------------------------------------------------
+// One pattern as the kernel reads it: its length in bytes (1 to 64), the mask of its first min(len, 4) bytes and the
+// bytes themselves as little-endian words, zero-padded.
+struct PayTextPat {
+  uint32_t len, fmask;
+  uint32_t w[16];
+};
+// plane[ceil(n / 32)] (the mask's layout, bits at or past n zero): bit r = every one of the n_pats patterns (1 to 32)
+// occurs within the bytes of row r of a text column -- head = its head plane (missing, null or the byte length), off =
+// its int64 offsets in 32-bit words, text = its word plane (rows padded with zero bytes to a word; below 2^31 words, and
+// allocated to a multiple of four words).  grid_cap as launch_payload_mask takes it.
+void launch_payload_text(const uint32_t* head, const int64_t* off, const uint32_t* text, int64_t n, const PayTextPat* pats,
+                         int n_pats, uint32_t* plane, int grid_cap, hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

@@ -14,6 +14,8 @@
 //                    A list column (a head plane, int64 offsets, element planes) is matched by
 //                    the ANY_* ops: the wave walks the contiguous element run of its rows in chunks of 64, one element
 //                    per lane, and each row lane picks the bits of its own segment out of the chunk's ballot.
+//                    PAY_D_BITS (device-only) pushes the row's bit of a packed verdict plane that
+//                    another kernel wrote in front of this one: how HX_PAY_TEXT_ALL (paytext.hip) joins a program.
 #include "hx_common.hpp"
 #include "kernels.hpp"
 
@@ -144,6 +146,7 @@ __global__ void __launch_bounds__(PAY_WG) k_payload_mask(const PayOpDev* __restr
           case PAY_D_TRUE: b = true; break;
           case PAY_D_FALSE: b = false; break;
           case PAY_D_ROW_IN: b = pay_in_set<uint32_t>((const uint32_t*)op.imm, op.cnt, (uint32_t)row[u]); break;
+          case PAY_D_BITS: b = in[u] && ((((const uint32_t*)op.imm)[row[u] >> 5] >> (row[u] & 31)) & 1u); break;
           case PAY_D_IS_MISSING: b = missing; break;
           case PAY_D_IS_NULL: b = null; break;
           case PAY_D_PRESENT: b = !(missing || null); break;

@@ -16,7 +16,7 @@ from ._lib import HX_MODE_H1, HX_MODE_TREE, HxError, HxParams, HxProf, HxStats, 
 from .filters import pack_rows
 
 # payload index (hx.h): the column kinds; the cell codes and the ops of a program are in payload_index.py
-PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64 = 1, 2, 3, 4
+PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64, PAY_TEXT = 1, 2, 3, 4, 5
 
 SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_256_limit",
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
@@ -432,7 +432,7 @@ class HxIndex:
 
     # -- payload index (hx.h: hx_payload_*; payload_index.py compiles filters to the programs) ----------------------
     def payload_create(self, kind: int) -> int:
-        """A new empty column of `kind` (PAY_U32 / PAY_F64 / PAY_LIST_U32 / PAY_LIST_F64); returns its id
+        """A new empty column of `kind` (PAY_U32 / PAY_F64 / PAY_LIST_U32 / PAY_LIST_F64 / PAY_TEXT); returns its id
         (hx_payload_create)."""
         col = C.c_int32()
         check(_lib.lib().hx_payload_create(self._h, int(kind), C.byref(col)))
@@ -492,6 +492,41 @@ class HxIndex:
                                                C.byref(count)))
         return head.value, out[:count.value]
 
+    @staticmethod
+    def _text_cells(heads, data):
+        heads = np.ascontiguousarray(heads)
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = np.frombuffer(bytes(data), np.uint8)
+        data = np.ascontiguousarray(data)
+        if heads.dtype != np.uint32 or heads.ndim != 1 or data.dtype != np.uint8 or data.ndim != 1:
+            raise TypeError("payload text: 1-d np.uint32 heads and the rows' bytes (bytes or a 1-d np.uint8 array)")
+        return heads, data
+
+    def payload_append_text(self, col: int, heads: np.ndarray, data) -> None:
+        """The cells of the next len(heads) rows of a text column (hx_payload_append_text): heads np.uint32 -- MISSING,
+        NULL or the row's byte length --, data the rows' bytes one after another (bytes or np.uint8)."""
+        heads, data = self._text_cells(heads, data)
+        check(_lib.lib().hx_payload_append_text(self._h, int(col), _ptr(heads), heads.shape[0], _ptr(data), data.shape[0]))
+
+    def payload_replace_text(self, col: int, rows, heads: np.ndarray, data) -> None:
+        """New cells for the stored rows `rows` of a text column (hx_payload_replace_text): heads / data as
+        payload_append_text takes them, in the order of `rows`."""
+        rows = self._rows(rows)
+        heads, data = self._text_cells(heads, data)
+        if heads.shape[0] != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} rows but {heads.shape[0]} heads")
+        check(_lib.lib().hx_payload_replace_text(self._h, int(col), _ptr(rows), rows.shape[0], _ptr(heads), _ptr(data),
+                                                 data.shape[0]))
+
+    def payload_debug_text(self, col: int, row: int):
+        """One row of a text column (hx_payload_debug_text): (head, bytes) -- head = MISSING, NULL or the byte length."""
+        head, count = C.c_uint32(), C.c_int64()
+        check(_lib.lib().hx_payload_debug_text(self._h, int(col), int(row), C.byref(head), None, 0, C.byref(count)))
+        out = np.zeros(max(count.value, 1), dtype=np.uint8)
+        check(_lib.lib().hx_payload_debug_text(self._h, int(col), int(row), C.byref(head), _ptr(out), count.value,
+                                               C.byref(count)))
+        return head.value, out[:count.value].tobytes()
+
     def payload_rows(self, col: int) -> int:
         n = C.c_int64()
         check(_lib.lib().hx_payload_rows(self._h, int(col), C.byref(n)))
@@ -505,7 +540,7 @@ class HxIndex:
 
     def payload_mask(self, ops, sets=(), want_count: bool = True):
         """Evaluate a program (hx_payload_mask).  ops: (op, col, imm) triples, imm an int (a code, the bits of a double, a
-        set index); sets: sorted 1-d arrays, np.uint32 or np.float64.  Returns (mask, n_kept): the packed words as an int32
+        set index); sets: sorted 1-d arrays, np.uint32 or np.float64, or -- the pattern blob of TEXT_ALL -- bytes.  Returns (mask, n_kept): the packed words as an int32
         device tensor of ceil(count() / 32) entries -- what hybrid_query takes as `mask` -- and the number of set bits
         (None when want_count is False: the call then only enqueues work).  mask_host(mask) gives the numpy form."""
         arr = (_lib.HxPayOp * max(len(ops), 1))()
@@ -514,9 +549,11 @@ class HxIndex:
         keep = []
         sarr = (_lib.HxPaySet * max(len(sets), 1))()
         for k, s in enumerate(sets):
+            if isinstance(s, (bytes, bytearray)):         # a pattern blob: n = its bytes
+                s = np.frombuffer(bytes(s), np.uint8)
             s = np.ascontiguousarray(s)
-            if s.dtype not in (np.uint32, np.float64) or s.ndim != 1:
-                raise TypeError("payload set: a 1-d np.uint32 or np.float64 array")
+            if s.dtype not in (np.uint32, np.float64, np.uint8) or s.ndim != 1:
+                raise TypeError("payload set: a 1-d np.uint32 or np.float64 array, or the bytes of a pattern blob")
             keep.append(s)
             sarr[k].vals, sarr[k].n = s.ctypes.data, s.shape[0]
         nw = (self.count() + 31) // 32

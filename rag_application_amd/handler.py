@@ -150,6 +150,8 @@ class _Collection:
         k = _pindex._Key(schema)
         if k.is_list and not hasattr(self.index, "payload_append_lists"):
             raise ValueError("this collection's engine index has no list columns")
+        if k.is_text and not hasattr(self.index, "payload_append_text"):
+            raise ValueError("this collection's engine index has no text columns")
         pi.keys[key] = k
         cells = pi.encode(key, self.payloads)
         if cells is None:
@@ -166,6 +168,8 @@ class _Collection:
     def _append_cells(self, k, col: int, cells) -> None:
         if k.is_list:                                     # (heads, values): hx_payload_append_lists
             self.index.payload_append_lists(col, cells[0], cells[1])
+        elif k.is_text:                                   # (heads, bytes): hx_payload_append_text
+            self.index.payload_append_text(col, cells[0], cells[1])
         else:
             self.index.payload_append(col, cells)
 
@@ -194,7 +198,7 @@ class _Collection:
             self._poison(key)
 
     def replace_payload_cells(self, rows, payloads) -> None:
-        """The cells of rows replaced in place, for every live key (hx_payload_replace / _replace_lists).  A value that
+        """The cells of rows replaced in place, for every live key (hx_payload_replace / _replace_lists / _replace_text).  A value that
         poisons a key, or an engine failure, drops that key's column, as append_payload_cells does."""
         pi = getattr(self, "pindex", None)
         if pi is None:
@@ -207,6 +211,8 @@ class _Collection:
                 if cells is not None:
                     if k.is_list:
                         self.index.payload_replace_lists(k.col, rows, cells[0], cells[1])
+                    elif k.is_text:
+                        self.index.payload_replace_text(k.col, rows, cells[0], cells[1])
                     else:
                         self.index.payload_replace(k.col, rows, cells)
                     continue
@@ -353,7 +359,10 @@ class QdrantHandler:
         "keyword_list" | "number_list" ("integer_list" / "float_list") | "bool_list": a value is then None, a list of
         values of the element schema or one such value (the one-element list); a tuple, a nested list or dict, a None
         element or an element of another type makes the field stay on the Python path.
-        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload (or list) columns;
+        Text fields (the reference's `content`, `file_description`, `document_summary`, `context`) take the opt-in schema
+        "text": a value is then None or a `str`, and `match text` on the field is evaluated on the device (DESIGN.md
+        section 19); any other value makes the field stay on the Python path.
+        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload (list, text) columns;
         KeyError for an unknown collection."""
         try:
             if not self._payload_indexes:

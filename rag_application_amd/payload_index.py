@@ -21,7 +21,13 @@ List schemas ("keyword_list" | "number_list" | "bool_list"; DESIGN.md section 17
 missing, None, or a `list` of values of the element schema ([] included); a bare scalar of the element schema is stored
 as the one-element list (filters._values makes the two equivalent in every clause).  A tuple (() is not [] to
 is_empty), a nested list or dict, a None element, a NaN, an oversized int or an element of another type poisons the
-key.  The clauses compile to the list ops: one element has to meet a whole `range`, as filters._range asks."""
+key.  The clauses compile to the list ops: one element has to meet a whole `range`, as filters._range asks.
+
+The text schema ("text") is opt-in too: a row's value is missing, None, or a `str`, stored as the
+UTF-8 bytes of `value.lower()`; anything else (a number, a bool, a list, a dict, a string with a lone surrogate) poisons
+the key.  `match text` on such a key compiles to one TEXT_ALL over the distinct words of `str(text).lower().split()`,
+each as UTF-8 bytes: UTF-8 is self-synchronising, so a byte-substring test on the two encodings is Python's `w in hay`
+on the code points.  Lower-casing and splitting stay Python's; the engine only sees bytes."""
 from __future__ import annotations
 
 import math
@@ -33,16 +39,18 @@ import numpy as np
 from . import filters as _filters
 
 # hx.h
-PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64 = 1, 2, 3, 4
+PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64, PAY_TEXT = 1, 2, 3, 4, 5
 U32_MISSING, U32_NULL = 0xFFFFFFFF, 0xFFFFFFFE
 F64_MISSING, F64_NULL = 0x7FF80000FFFFFFFF, 0x7FF80000FFFFFFFE
 MAX_STACK, MAX_OPS, MAX_COLUMNS = 32, 4096, 64
 (TRUE, FALSE, IS_MISSING, IS_NULL, PRESENT, EQ, IN, LT, LE, GT, GE, ROW_IN, AND, OR, NOT, ANY_EQ, ANY_IN, ANY_RANGE,
- IS_EMPTY_LIST) = range(19)
+ IS_EMPTY_LIST, TEXT_ALL) = range(20)
+TEXT_MAX_WORDS, TEXT_MAX_WORD_BYTES = 32, 64
+TEXT_MAX_COLUMN_WORDS = 0x7FFFFFFF      # a text column holds fewer than 2^31 32-bit words
 
 SCHEMAS = {"keyword": "keyword", "number": "number", "integer": "number", "float": "number", "bool": "bool",
            "keyword_list": "keyword_list", "number_list": "number_list", "integer_list": "number_list",
-           "float_list": "number_list", "bool_list": "bool_list"}
+           "float_list": "number_list", "bool_list": "bool_list", "text": "text"}
 _CLAUSES = ("must", "should", "must_not")
 _MAX_KEYWORDS = U32_NULL            # codes 0 .. 0xFFFFFFFD
 
@@ -91,7 +99,13 @@ class _Key:
         return self.schema[:-5] if self.is_list else self.schema
 
     @property
+    def is_text(self) -> bool:
+        return self.schema == "text"
+
+    @property
     def kind(self) -> int:
+        if self.is_text:
+            return PAY_TEXT
         if self.is_list:
             return PAY_LIST_F64 if self.elem == "number" else PAY_LIST_U32
         return PAY_F64 if self.schema == "number" else PAY_U32
@@ -124,6 +138,8 @@ class PayloadIndex:
         n = len(payloads)
         if k.is_list:
             return self._encode_lists(k, key, payloads)
+        if k.is_text:
+            return self._encode_text(key, payloads)
         if k.schema == "number":
             vals = np.zeros(n, np.float64)
             special: List[Tuple[int, int]] = []
@@ -218,10 +234,45 @@ class PayloadIndex:
             heads[r] = len(row)
         return heads, np.array(vals, np.float64 if elem == "number" else np.uint32)
 
+    @staticmethod
+    def _encode_text(key: str, payloads):
+        """(heads, data) of a text key for hx_payload_append_text -- heads: np.uint32, MISSING / NULL / the row's byte
+        length; data: the rows' bytes one after another (bytes) -- or None when a value poisons the key: anything that is
+        not a `str` (a `str` is never == [], which keeps is_empty exact), a string with a lone surrogate, or rows whose
+        bytes, each padded to a 32-bit word, would pass the column limit."""
+        get, missing = _filters._get, _filters._MISSING
+        heads = np.empty(len(payloads), np.uint32)
+        parts: List[bytes] = []
+        words = 0
+        for r, p in enumerate(payloads):
+            v = get(p, key)
+            if v is missing:
+                heads[r] = U32_MISSING
+            elif v is None:
+                heads[r] = U32_NULL
+            elif type(v) is str:
+                try:
+                    b = v.lower().encode("utf-8")
+                except UnicodeEncodeError:
+                    return None
+                words += (len(b) + 3) // 4
+                if words > TEXT_MAX_COLUMN_WORDS:
+                    return None
+                heads[r] = len(b)
+                parts.append(b)
+            else:
+                return None
+        return heads, b"".join(parts)
+
+    @staticmethod
+    def text_blob(words: List[bytes]) -> bytes:
+        """The pattern blob of TEXT_ALL (hx.h): uint32 P, uint32 len[P], the patterns' bytes one after another."""
+        return struct.pack(f"<{1 + len(words)}I", len(words), *[len(w) for w in words]) + b"".join(words)
+
     # -- compiler --------------------------------------------------------------------------------------------------
     def compile(self, flt, id_rows: Optional[Callable[[], Dict[Any, int]]] = None):
         """(ops, sets) for hx_payload_mask -- ops: (op, column, imm) triples, sets: sorted np.uint32 / np.float64
-        arrays -- or None when the filter is declined (the reason is counted in `declined`).  Unknown clause names of
+        arrays, or the pattern blob (bytes) of a TEXT_ALL -- or None when the filter is declined (the reason is counted in `declined`).  Unknown clause names of
         the filter itself raise ValueError, as filters.matches does.  id_rows: gives the collection's id -> row
         dictionary (for has_id)."""
         if flt and isinstance(flt, dict):
@@ -369,6 +420,8 @@ class PayloadIndex:
     def _match(self, k: _Key, m, ops, sets):
         if not isinstance(m, dict):
             raise _Decline("match is not a dict")
+        if k.is_text:
+            return self._match_text(k, m, ops, sets)
         if "value" in m:
             v = m["value"]
             if v is not None and not isinstance(v, (str, bool, int, float)):
@@ -386,9 +439,36 @@ class PayloadIndex:
         else:
             raise _Decline("unsupported match")
 
+    def _match_text(self, k: _Key, m, ops, sets):
+        """A match on a text key.  `text` is filters._match's rule on bytes: every distinct word of
+        str(text).lower().split() is a byte substring of the stored lower-cased UTF-8; no word = the value is present."""
+        for form in ("value", "any", "except"):      # (the order filters._match tests them in)
+            if form in m:
+                raise _Decline(f"match {form} on a text key")
+        if "text" not in m:
+            raise _Decline("unsupported match")
+        words: List[bytes] = []
+        for w in dict.fromkeys(str(m["text"]).lower().split()):
+            try:
+                b = w.encode("utf-8")
+            except UnicodeEncodeError:
+                raise _Decline("match text word with a lone surrogate")
+            if len(b) > TEXT_MAX_WORD_BYTES:
+                raise _Decline("match text word over 64 bytes")
+            words.append(b)
+        if len(words) > TEXT_MAX_WORDS:
+            raise _Decline("match text with more than 32 words")
+        if not words:
+            ops.append((PRESENT, k.col, 0))
+            return
+        sets.append(self.text_blob(words))
+        ops.append((TEXT_ALL, k.col, len(sets) - 1))
+
     def _range(self, k: _Key, r, ops, sets):
         if not isinstance(r, dict):
             raise _Decline("range is not a dict")
+        if k.is_text:
+            raise _Decline("range on a text key")
         if k.elem != "number":                        # (filters._range: only numbers that are not bools are in a range)
             ops.append((FALSE, 0, 0))
             return
