@@ -535,6 +535,41 @@ int hx_payload_debug_text(hx_index* h, int32_t col, int64_t row, uint32_t* head,
 int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,
                           int64_t* count);
 
+/* ---- grouped search ---------------------------------------
+ * Qdrant's query_points_groups(group_by, limit, group_size) (additive: the reference calls query_points only,
+ * qdrant_handler.py:363-372): the best n_groups groups of a ranked list, at most group_size hits each, a row's group being
+ * its cell in an HX_PAY_U32 column (a keyword's code, 0 / 1 of a bool).  The list is walked in rank order: a row whose
+ * cell is HX_PAY_U32_MISSING or _NULL is skipped (Qdrant leaves out points without the field); a row whose group is
+ * open and holds fewer than group_size hits joins it; a row whose group is not open opens it while fewer than n_groups
+ * are open; every other row is dropped.  Groups come out ordered by their best hit, hits inside a group by rank.
+ *
+ * hx_group is the stage.  keys_dev [B x stride] + counts_dev [B] is a ranked list as the hybrid entries hand it out
+ * (global ids, best first); counts_dev NULL = all `stride` slots; a 0 slot inside a list is skipped and keeps its rank.
+ * A key whose row is not in this index (another shard's, or past hx_count) is skipped, its cell is not read.
+ *   out_keys_dev [B x n_groups x group_size]   slot g * group_size + r = the r-th hit of the g-th group: the input key
+ *                                              as it came (same id, same score bits), 0 = empty; every slot is written;
+ *   group_codes_dev [B x n_groups]             the g-th group's code, HX_PAY_U32_MISSING for a group that was not opened;
+ *   group_counts_dev [B]                       groups opened, at most n_groups.
+ * Everything is enqueued on `stream`; nothing is read back.  Refused before any device work: a NULL argument (counts_dev
+ * aside), B < 1, stride outside [1, 2048], n_groups or group_size below 1 or n_groups * group_size above 2048, an
+ * unknown column, a column whose kind is not HX_PAY_U32 ("kind" in the message), a column not filled to hx_count. */
+int hx_group(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+             int32_t n_groups, int32_t group_size, uint64_t* out_keys_dev, uint32_t* group_codes_dev,
+             int32_t* group_counts_dev, void* stream);
+/* The whole grouped query, host in, host out: hx_hybrid_query_host (mask_host NULL) or hx_hybrid_query_host_masked run
+ * with final_limit = the POOL size, then hx_group over the pool on the device, then the ids' map, the unpacking and the
+ * copy out.  The pool is the ranked list the root hands out: HX_MODE_TREE the re-scored union, at most
+ * min(dense_limit + rrf_limit, 2048) rows; HX_MODE_H1 the fused list, at most min(dense_limit + sparse_limit, 2048).
+ * group_pool = 0 asks for that maximum, a value in [1, maximum] for a shorter pool; anything else is refused.  p's own
+ * final_limit is not used (nor checked), and *p is not modified.  Outputs: scores_host / ids_host [B x n_groups x
+ * group_size] in the slot order of hx_group, empty slots (-inf, -1) as hx_unpack gives them; group_codes_host
+ * [B x n_groups]; group_counts_host [B].  Refusals: those of the plain call and those of hx_group. */
+int hx_hybrid_query_groups_host(hx_index* h, const float* q_dense_host, const int64_t* q_indptr_host,
+                                const int32_t* q_idx_host, const float* q_val_host, int32_t B, const hx_params* p,
+                                const uint32_t* mask_host, int64_t mask_rows, int32_t col, int32_t group_pool,
+                                int32_t n_groups, int32_t group_size, float* scores_host, int64_t* ids_host,
+                                uint32_t* group_codes_host, int32_t* group_counts_host);
+
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
  * Qdrant/bm25 :41, :123), batched (the reference's TODO :100): n texts -> CSR of (term id, weight)

@@ -95,7 +95,8 @@ enum WsSlot {
   WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
-  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES
+  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
+  WS_G_KEYS, WS_G_CODES, WS_G_CNT
 };
 
 template <typename T>
@@ -3396,11 +3397,66 @@ int hx_hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const 
   HX_CATCH
 }
 
-// hx_hybrid_query_host and its masked form: mask_host NULL = every row
+// ---- grouped search ----------------------------------------------------------------------------
+// the checks of hx_group on its sizes and its column, before any device work; returns the column's cells
+static const uint32_t* group_plane(hx_index* h, int32_t col, int32_t n_groups, int32_t group_size) {
+  HX_CHECK(n_groups >= 1 && group_size >= 1 && (int64_t)n_groups * group_size <= MAX_LIMIT,
+           "group: n_groups and group_size must be at least 1 and n_groups * group_size at most 2048");
+  const hx_index::PayCol* c = nullptr;
+  for (const auto& x : h->pay)
+    if (x.id == col) c = &x;
+  if (!c) throw Error("payload: unknown column " + std::to_string(col));
+  HX_CHECK(c->kind == HX_PAY_U32, "group: the column kind must be HX_PAY_U32 (keyword codes or bools)");
+  HX_CHECK(c->filled == h->n, "group: the column is not filled to the index's row count (hx_count)");
+  return c->p0;
+}
+static void group_enqueue(hx_index* h, const uint32_t* p0, const uint64_t* keys, const uint64_t* ikeys, int stride,
+                          const int* counts, int B, int n_groups, int group_size, uint64_t* out, uint32_t* codes,
+                          int* group_counts, hipStream_t st) {
+  GroupArgs g{};
+  g.keys = keys;
+  g.ikeys = ikeys;
+  g.stride = stride;
+  g.counts = counts;
+  g.p0 = p0;
+  g.n_rows = h->n;
+  g.id_base = (uint32_t)h->id_base;
+  g.n_groups = n_groups;
+  g.group_size = group_size;
+  g.out = out;
+  g.group_codes = codes;
+  g.group_counts = group_counts;
+  launch_group_select(g, B, st);
+}
+// what hx_hybrid_query_groups_host adds to hx_hybrid_query_host
+struct GroupSpec {
+  int32_t col, pool, n_groups, group_size;
+  uint32_t* codes_host;
+  int32_t* counts_host;
+};
+
+// hx_hybrid_query_host, its masked form (mask_host NULL = every row) and its grouped form (grp NULL = the plain lists;
+// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots)
 static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                              int32_t B, const hx_params* p, const uint32_t* mask_host, float* scores, int64_t* ids,
-                              int32_t* counts) {
-  HX_CHECK(h && qd && qip && scores && ids && counts && B > 0, "bad argument");
+                              int32_t B, const hx_params* p_in, const uint32_t* mask_host, float* scores, int64_t* ids,
+                              int32_t* counts, const GroupSpec* grp = nullptr) {
+  HX_CHECK(h && qd && qip && scores && ids && (counts || grp) && B > 0, "bad argument");
+  HX_CHECK(p_in != nullptr, "params is NULL");
+  hx_params pool_params = *p_in;          // (the caller's params are never written)
+  const hx_params* p = p_in;
+  const uint32_t* group_p0 = nullptr;
+  if (grp) {
+    HX_CHECK(grp->codes_host && grp->counts_host, "bad argument");
+    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
+    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
+    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
+    HX_CHECK(grp->pool >= 0 && grp->pool <= pool_max && pool_max >= 1,
+             "group_pool must be 0 (the whole pool) or in [1, the mode's pool size]");
+    pool_params.final_limit = grp->pool ? grp->pool : (int32_t)pool_max;
+    p = &pool_params;
+    check_params(p);
+    group_p0 = group_plane(h, grp->col, grp->n_groups, grp->group_size);
+  }
   check_params(p);
   h->set_device();
   hipStream_t st = nullptr;
@@ -3440,8 +3496,9 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
   float* dv = (float*)h->ws.get(WS_H_QV, (size_t)std::max<int64_t>(nnz, 1) * 4);
   uint64_t* ok = (uint64_t*)h->ws.get(WS_H_OUT, (size_t)B * L * 8);
   int* oc = (int*)h->ws.get(WS_H_OCNT, (size_t)B * 4);
-  float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * L * 4);
-  int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * L * 8);
+  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : L;   // slots of a query's result
+  float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * OL * 4);
+  int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * OL * 8);
   HX_HIP(hipMemcpyAsync(dq, qd, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
   HX_HIP(hipMemcpyAsync(dip, qip, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
   if (nnz) {
@@ -3455,6 +3512,21 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
     if (nw) HX_HIP(hipMemcpyAsync(dm, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
     masked_query_dev(h, dq, dip, dix, dv, B, p, dm, kept, ok, oc, st);
+  }
+  if (grp) {                             // the stage reads internal ids: before remap_out
+    const int G = grp->n_groups, GS = grp->n_groups * grp->group_size;
+    uint64_t* gk = (uint64_t*)h->ws.get(WS_G_KEYS, (size_t)B * GS * 8);
+    uint32_t* gc = (uint32_t*)h->ws.get(WS_G_CODES, (size_t)B * G * 4);
+    int* gn = (int*)h->ws.get(WS_G_CNT, (size_t)B * 4);
+    group_enqueue(h, group_p0, ok, ok, L, oc, B, G, grp->group_size, gk, gc, gn, st);
+    remap_out(h, gk, (int64_t)B * GS, st);
+    launch_unpack(gk, (int64_t)B * GS, osc, oid, st);
+    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * GS * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * GS * 8, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(grp->codes_host, gc, (size_t)B * G * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(grp->counts_host, gn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    return;
   }
   remap_out(h, ok, (int64_t)B * L, st);
   launch_unpack(ok, (int64_t)B * L, osc, oid, st);
@@ -3479,6 +3551,34 @@ int hx_hybrid_query_host_masked(hx_index* h, const float* qd, const int64_t* qip
   HX_CHECK(h && mask_host, "NULL argument");
   HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
   hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, counts);
+  HX_CATCH
+}
+
+int hx_group(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+             int32_t n_groups, int32_t group_size, uint64_t* out_keys_dev, uint32_t* group_codes_dev,
+             int32_t* group_counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && keys_dev && out_keys_dev && group_codes_dev && group_counts_dev, "NULL argument");
+  HX_CHECK(B >= 1, "group: B < 1");
+  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "group: stride out of range [1, 2048]");
+  const uint32_t* p0 = group_plane(h, col, n_groups, group_size);
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
+  group_enqueue(h, p0, keys_dev, ikeys, stride, counts_dev, B, n_groups, group_size, out_keys_dev, group_codes_dev,
+                group_counts_dev, st);
+  HX_CATCH
+}
+
+int hx_hybrid_query_groups_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows, int32_t col,
+                                int32_t group_pool, int32_t n_groups, int32_t group_size, float* scores, int64_t* ids,
+                                uint32_t* group_codes, int32_t* group_counts) {
+  HX_TRY
+  HX_CHECK(h, "NULL argument");
+  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  const GroupSpec g{col, group_pool, n_groups, group_size, group_codes, group_counts};
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, &g);
   HX_CATCH
 }
 

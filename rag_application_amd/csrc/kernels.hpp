@@ -463,6 +463,26 @@ struct PayTextPat {
 // allocated to a multiple of four words).  grid_cap as launch_payload_mask takes it.
 void launch_payload_text(const uint32_t* head, const int64_t* off, const uint32_t* text, int64_t n, const PayTextPat* pats,
                          int n_pats, uint32_t* plane, int grid_cap, hipStream_t st);
+// ---- group.hip: grouped search (hx_group) ------------------------------------------------------
+constexpr uint32_t HX_GROUP_MISSING = 0xFFFFFFFFu, HX_GROUP_NULL = 0xFFFFFFFEu;   // HX_PAY_U32_MISSING / _NULL of hx.h
+// Per query b: the ranked list keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same
+// slots with internal ids (id_base + row; the same pointer where the two id spaces are one), which name the row whose
+// cell p0[row] is the group.  out[b * G * S + g * S + r] = the r-th hit of the g-th group (a key of `keys`, 0 = empty),
+// group_codes[b * G + g] = its code (HX_GROUP_MISSING for a group that was not opened), group_counts[b] = groups opened.
+struct GroupArgs {
+  const uint64_t* keys;
+  const uint64_t* ikeys;
+  int stride;              // 1 .. 2048
+  const int* counts;
+  const uint32_t* p0;      // the cells of rows [0, n_rows)
+  int64_t n_rows;
+  uint32_t id_base;
+  int n_groups, group_size;   // G, S >= 1, G * S <= 2048
+  uint64_t* out;
+  uint32_t* group_codes;
+  int* group_counts;
+};
+void launch_group_select(const GroupArgs& a, int B, hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

@@ -590,6 +590,51 @@ class HxIndex:
                                                      _ptr(counts)))
         return scores, ids, counts
 
+    # -- grouped search (hx.h: hx_group / hx_hybrid_query_groups_host) -------------------------
+    def group(self, col: int, keys: torch.Tensor, counts: Optional[torch.Tensor], n_groups: int, group_size: int):
+        """The best n_groups groups of the ranked lists keys [B, stride] (+ counts [B], None = every slot), at most
+        group_size hits each, grouped by the cells of the U32 column `col` (hx_group).  Returns (out_keys
+        [B, n_groups, group_size] int64, 0 = an empty slot; group_codes [B, n_groups] int32 holding the uint32 codes,
+        -1 = HX_PAY_U32_MISSING = no such group; group_counts [B] int32).  Only enqueues work."""
+        keys = _need_cuda(keys, torch.int64, "keys")
+        if keys.dim() != 2:
+            raise HxError("keys must be a [B, stride] tensor")
+        if counts is not None:
+            counts = _need_cuda(counts, torch.int32, "counts")
+        B, stride = int(keys.shape[0]), int(keys.shape[1])
+        G, S = int(n_groups), int(group_size)
+        slots = G * S if 1 <= G <= 2048 and 1 <= S <= 2048 else 0      # (the engine refuses; nothing huge is allocated)
+        out = torch.empty((B, max(slots, 1)), dtype=torch.int64, device=keys.device)
+        codes = torch.empty((B, G if slots else 1), dtype=torch.int32, device=keys.device)
+        cnt = torch.empty((B,), dtype=torch.int32, device=keys.device)
+        check(_lib.lib().hx_group(self._h, int(col), _ptr(keys), stride, _ptr(counts), B, G, S, _ptr(out), _ptr(codes),
+                                  _ptr(cnt), _stream()))
+        return out.view(B, G, S), codes, cnt
+
+    def hybrid_query_groups_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
+                                 params: HxParams, col: int, n_groups: int, group_size: int, group_pool: int = 0,
+                                 mask=None):
+        """hybrid_query_host grouped by the U32 column `col` (hx_hybrid_query_groups_host): the query runs with
+        final_limit = the pool (group_pool = 0: the mode's whole pool; params.final_limit is not used), the pool is
+        grouped on the device.  Returns (scores [B, n_groups, group_size] float32, ids [B, n_groups, group_size] int64 --
+        empty slots (-inf, -1) --, group_codes [B, n_groups] uint32, group_counts [B] int32).  mask as hybrid_query_host."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
+        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
+        B, G, S = q.shape[0], int(n_groups), int(group_size)
+        if not (1 <= G <= 2048 and 1 <= S <= 2048 and G * S <= 2048):
+            raise HxError("group: n_groups and group_size must be at least 1 and n_groups * group_size at most 2048")
+        scores = np.empty((B, G, S), dtype=np.float32)
+        ids = np.empty((B, G, S), dtype=np.int64)
+        codes = np.empty((B, G), dtype=np.uint32)
+        counts = np.empty((B,), dtype=np.int32)
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        check(_lib.lib().hx_hybrid_query_groups_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                     C.byref(params), _ptr(words), rows, int(col), int(group_pool), G, S,
+                                                     _ptr(scores), _ptr(ids), _ptr(codes), _ptr(counts)))
+        return scores, ids, codes, counts
+
 
 # -- index-free stages -------------------------------------------------------------------
 def rrf(a_keys: torch.Tensor, a_cnt: torch.Tensor, b_keys: torch.Tensor, b_cnt: torch.Tensor,

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import engine as _engine
 from . import filters as _filters
+from . import grouping as _grouping
 from . import payload_index as _pindex
 from ._lib import HX_MODE_H1, HX_MODE_TREE
 
@@ -45,6 +46,14 @@ class ScoredPoint:
         return asdict(self)
 
     model_dump = dict
+
+
+@dataclass
+class PointGroup:
+    """One group of hybrid_search_groups (shape-compatible with qdrant_client.http.models.PointGroup): `id` = the value
+    of the group_by field its hits share (a str, a bool or an int), `hits` = its ScoredPoints, best first."""
+    id: Any
+    hits: List[ScoredPoint] = field(default_factory=list)
 
 
 @dataclass
@@ -267,6 +276,8 @@ class QdrantHandler:
     _point_upserts = True
     # payload columns live in ONE engine index, beside the rows whose payloads this process holds
     _payload_indexes = True
+    # hybrid_search_groups groups the pool of ONE engine index, by a column of that index or by this process's payloads
+    _grouped_search = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -553,13 +564,9 @@ class QdrantHandler:
             raise
 
     # ---------------------------------------------------------------------------- search
-    def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree",
-                     filter_stages="root"):
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
-        if filter_stages == "all" and not self._masked_search:
-            raise ValueError("filter_stages='all' is not supported on a sharded collection: use filter_stages='root'")
-        col = self._collections[str(user_id)]
+    @staticmethod
+    def _pack_queries(col, dense_vectors, sparse_vectors):
+        """the batch as the engine takes it: dense [B, dim] float32, the sparse queries as one CSR"""
         q = np.asarray(dense_vectors, dtype=np.float32).reshape(len(sparse_vectors), -1)
         if q.shape[1] != col.dim:
             raise ValueError(f"query dimension {q.shape[1]} != collection dimension {col.dim}")
@@ -573,6 +580,16 @@ class QdrantHandler:
         val = np.fromiter(itertools.chain.from_iterable(vv for _, vv in parts), dtype=np.float64, count=nnz)
         if nnz and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
             raise ValueError("sparse index out of range")
+        return q, indptr, idx, val
+
+    def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree",
+                     filter_stages="root"):
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if filter_stages == "all" and not self._masked_search:
+            raise ValueError("filter_stages='all' is not supported on a sharded collection: use filter_stages='root'")
+        col = self._collections[str(user_id)]
+        q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
         if mode not in ("tree", "h1"):
             raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
         # KeyError/TypeError like the reference when search_params lacks a key / is None
@@ -638,6 +655,119 @@ class QdrantHandler:
             return [r[:top_k] for r in res]
         except Exception as e:
             logging.error("hybrid search for %s failed: %s", user_id, e)
+            return []
+
+    # -------------------------------------------------------------------- grouped search
+    def _groups_sync(self, user_id, dense_vectors, sparse_vectors, group_by, limit, group_size, search_params, filters,
+                     mode, filter_stages, group_pool):
+        if not self._grouped_search:
+            raise ValueError("hybrid_search_groups is not supported on a sharded collection")
+        _grouping.check_sizes(limit, group_size)
+        if not isinstance(group_by, str) or not group_by:
+            raise ValueError("group_by must be a non-empty string (a payload key, dotted paths allowed)")
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if mode not in ("tree", "h1"):
+            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+        root_filter = bool(filters) and filter_stages == "root"
+        if root_filter and mode != "tree":
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
+        hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
+        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit),
+                       _grouping.MAX_SLOTS)
+        if group_pool is None:
+            pool = pool_max
+        elif isinstance(group_pool, bool) or not isinstance(group_pool, int) or not 1 <= group_pool <= pool_max:
+            raise ValueError(f"group_pool must be an integer in [1, {pool_max}] (this mode's pool) or None, "
+                             f"got {group_pool!r}")
+        else:
+            pool = group_pool
+        if pool < 1:
+            raise ValueError("the search_params leave an empty pool")
+        col = self._collections[str(user_id)]
+        q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
+        idx, val = idx.astype(np.int32), val.astype(np.float32)
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        cids, cpay = col.ids, col.payloads
+        pi = getattr(col, "pindex", None)
+        k = pi.keys.get(group_by) if pi is not None else None
+        if k is None:
+            reason = "group by an unindexed key"
+        elif k.col is None:
+            reason = "group by a poisoned key"
+        elif k.schema not in ("keyword", "bool"):
+            reason = "group by a key of another schema"
+        elif root_filter:
+            reason = "group with a root filter"
+        elif not hasattr(col.index, "hybrid_query_groups_host"):
+            reason = "group on an index without the grouped query"
+        else:
+            reason = None
+        if reason is None:
+            try:
+                mask = col.row_mask(filters) if filters else None
+                scores, rows, codes, counts = col.index.hybrid_query_groups_host(
+                    q, indptr, idx, val, hp, k.col, limit, group_size, group_pool=pool, mask=mask)
+                out = []
+                for sc, rw, cd, n in zip(scores.tolist(), rows.tolist(), codes.tolist(), counts.tolist()):
+                    out.append([PointGroup(id=k.value_of(cd[g]),
+                                           hits=[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r])
+                                                 for s, r in zip(sc[g], rw[g]) if r >= 0])
+                                for g in range(n)])
+                pi.group_device_calls += 1
+                return out
+            except Exception as e:                          # never a wrong group: the walk over the payloads is always right
+                logging.warning("grouped search: the device path failed, Python path taken: %s", e)
+                reason = "engine refused"
+        logging.warning("grouped search by %r takes the Python path: %s", group_by, reason)
+        if pi is not None:
+            pi.declined[reason] = pi.declined.get(reason, 0) + 1
+        hp.final_limit = pool
+        if filters and not root_filter:
+            scores, rows, counts = col.index.hybrid_query_host(q, indptr, idx, val, hp, mask=col.row_mask(filters))
+        else:
+            scores, rows, counts = col.index.hybrid_query_host(q, indptr, idx, val, hp)
+        out = []
+        for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist()):
+            pts = [ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+            if root_filter:                                 # the root's filter comes before the grouping, as in Qdrant
+                pts = [p for p in pts if _filters.matches(p.payload, filters, p.id)]
+            values = [_grouping.group_value(p.payload, group_by) for p in pts]
+            out.append([PointGroup(id=values[g[0]][1], hits=[pts[r] for r in g])
+                        for g in _grouping.group_ranked(values, limit, group_size)])
+        return out
+
+    async def hybrid_search_groups(self, user_id: str, dense_vectors, sparse_vectors, group_by: str, limit: int = 10,
+                                   group_size: int = 3, search_params: Optional[Dict[str, Any]] = None,
+                                   filters: Optional[Dict] = None, mode: str = "tree", filter_stages: str = "root",
+                                   group_pool: Optional[int] = None) -> List[List[PointGroup]]:
+        """Qdrant's query_points_groups for B queries in one engine call (additive; no reranking hook): per query the
+        best `limit` groups of the payload field `group_by` (a dotted path), at most `group_size` hits each, groups
+        ordered by their best hit, hits by rank (grouping.py states the walk).  What is grouped is the query's POOL: the
+        ranked list the engine returns with final_limit = the pool size -- mode "tree" the root's re-scored union,
+        min(dense_limit + 10, 2048) rows; mode "h1" the fused list, min(dense_limit + sparse_limit, 2048).  group_pool
+        asks for a shorter pool (1 .. that maximum).  search_params["final_limit"] must be there, as in every search, and
+        is NOT used: `limit` and `group_size` say how much comes back.  filters / filter_stages as in hybrid_search_batch:
+        "all" = the pool of the pre-filtered query, "root" (tree only) = the filter applied to the pool before grouping.
+        Points without the field, or with None there, are in no group; `str`, `bool` and `int` values form groups (1 and
+        True are different groups); floats, lists and dicts are skipped.
+        A field with a live "keyword" or "bool" payload index is grouped by one kernel over the pool on the device
+        (hx_hybrid_query_groups_host), with no filter or filter_stages="all"; everything else -- another schema, an
+        unindexed or poisoned key, a root filter, an engine refusal -- walks the pool's payloads in Python, logs a warning
+        and counts itself in the payload index's `declined`.  Both ways give the same groups.
+        Raises ValueError for arguments no search can serve (limit or group_size below 1, limit * group_size above 2048,
+        a group_pool out of range, mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages
+        or filter clause); any other failure is logged and gives [], as in every search."""
+        try:
+            return await self._run(self._groups_sync, user_id, dense_vectors, sparse_vectors, group_by, limit, group_size,
+                                   search_params, filters, mode, filter_stages, group_pool)
+        except ValueError as ve:
+            logging.error("grouped hybrid search for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("grouped hybrid search for %s failed: %s", user_id, e)
             return []
 
     async def rerank_with_colbert(self, query: str, documents: List[str], results: List[Dict],

@@ -89,6 +89,15 @@ class _Key:
         self.schema = schema
         self.col: Optional[int] = None     # the engine column; None = not live (poisoned, or its column was lost)
         self.codes: Dict[str, int] = {}    # keyword -> code
+        self._names: List[str] = []        # code -> keyword, built when a grouped search asks (value_of)
+
+    def value_of(self, code: int):
+        """The stored value a cell of a "keyword" or "bool" column stands for: what a grouped search names a group by."""
+        if self.schema == "bool":
+            return bool(code)
+        if len(self._names) != len(self.codes):           # codes are handed out in order and never taken back
+            self._names = list(self.codes)
+        return self._names[code]
 
     @property
     def is_list(self) -> bool:
@@ -117,6 +126,7 @@ class PayloadIndex:
         self.device_evals = 0              # masks evaluated by hx_payload_mask
         self.python_evals = 0              # masks evaluated by the Python loop
         self.declined: Dict[str, int] = {}  # reason -> filters that did not compile
+        self.group_device_calls = 0        # grouped searches served by hx_hybrid_query_groups_host
 
     # -- definitions -----------------------------------------------------------------------------------------------
     def definitions(self) -> Dict[str, str]:
