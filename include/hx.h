@@ -570,6 +570,49 @@ int hx_hybrid_query_groups_host(hx_index* h, const float* q_dense_host, const in
                                 int32_t n_groups, int32_t group_size, float* scores_host, int64_t* ids_host,
                                 uint32_t* group_codes_host, int32_t* group_counts_host);
 
+/* ---- MMR search --------------------------------------------
+ * Qdrant's NearestQuery(mmr=Mmr(diversity, candidates_limit)) (additive: the reference calls query_points without it,
+ * qdrant_handler.py:363-372; parity unpinned, the semantics below are this project's statement of it): maximal marginal
+ * relevance over a ranked pool.  d = diversity as fp32 in [0, 1], a = 1.0f - d; rel_i = the score of the key at pool
+ * position i; sim(i, j) = the spec dot product of the normalised fp32 rows of positions i and j over their padded width.
+ * Step 0 values position i at v_i = a * rel_i; step t > 0 at v_i = (a * rel_i) - (d * m_i), m_i = the largest sim(i, s)
+ * over the picks s so far (no clamp at 0).  Every product, difference and sum is one fp32 operation, round to nearest,
+ * never fused; v + 0.0f follows, so that -0 and +0 are one value.  A step picks the eligible, not yet picked position of
+ * the largest v, the smaller position on a tie; selection ends after `limit` picks or when no eligible position is left.
+ * Not eligible: a 0 slot, a position at or past counts_dev[b], a key whose row is not in this index (another shard's, or
+ * past hx_count), a row whose bit is clear in eligible_dev (packed as a row mask: bit r & 31 of word r >> 5 = row r).
+ *
+ * hx_mmr is the stage.  keys_dev [B x stride] + counts_dev [B] is a pool as the hybrid entries hand it out (global ids);
+ * counts_dev NULL = all `stride` slots; eligible_dev NULL = every row.
+ *   out_keys_dev [B x limit]     slot t = the input key of pick t as it came (same id, same score bits); the slots past
+ *                                the picks are 0, which hx_unpack turns into (-inf, -1); every slot is written;
+ *   out_values_dev [B x limit]   slot t = v of pick t; 0.0f past the picks;
+ *   out_counts_dev [B]           picks made.
+ * Everything is enqueued on `stream`; nothing is read back.  Refused before any device work, every output untouched: a
+ * NULL argument (counts_dev and eligible_dev aside), B < 1, stride outside [1, 2048], limit outside [1,
+ * HX_MMR_MAX_LIMIT], a diversity that is NaN or outside [0, 1], eligible_rows != hx_count when eligible_dev is given. */
+#define HX_MMR_MAX_LIMIT 256
+int hx_mmr(hx_index* h, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B, int32_t limit,
+           float diversity, const uint32_t* eligible_dev, int64_t eligible_rows, uint64_t* out_keys_dev,
+           float* out_values_dev, int32_t* out_counts_dev, void* stream);
+/* The whole MMR query, host in, host out.  The plain query runs on a copy of *p with final_limit = the POOL size
+ * (HX_MODE_TREE: the root's re-scored union, at most min(dense_limit + rrf_limit, 2048) rows, whose scores are the dense
+ * cosines; HX_MODE_H1: the fused list, at most min(dense_limit + sparse_limit, 2048), passed once through the re-score
+ * stage -- hx_rescore, full width, limit = the pool -- so that relevance is the dense cosine too: the scores that come
+ * back in H1 are those cosines, NOT the fused scores).  candidates_limit = 0 asks for that maximum, a value in [1,
+ * maximum] for a shorter pool; anything else is refused.  p's own final_limit is not used (nor checked), *p is not
+ * modified.  mask_host NULL = every row; otherwise mask_root_only = 0 runs the pre-filtered query (the mask holds in every
+ * stage, as hx_hybrid_query_host_masked) and mask_root_only = 1 runs the query unmasked and hands the mask to hx_mmr as
+ * its eligibility plane: the reference's root filter, which filters the union (HX_MODE_TREE only: refused in H1).
+ * Then hx_mmr over the pool on the device, the ids' map, the unpacking and the copy out.  Outputs: scores_host / ids_host
+ * / values_host [B x limit] in pick order, the slots past the picks (-inf, -1, 0.0f); counts_host [B].  Refusals: those
+ * of the plain call and those of hx_mmr. */
+int hx_hybrid_query_mmr_host(hx_index* h, const float* q_dense_host, const int64_t* q_indptr_host,
+                             const int32_t* q_idx_host, const float* q_val_host, int32_t B, const hx_params* p,
+                             const uint32_t* mask_host, int64_t mask_rows, int32_t mask_root_only,
+                             int32_t candidates_limit, int32_t limit, float diversity, float* scores_host,
+                             int64_t* ids_host, float* values_host, int32_t* counts_host);
+
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
  * Qdrant/bm25 :41, :123), batched (the reference's TODO :100): n texts -> CSR of (term id, weight)

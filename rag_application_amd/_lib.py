@@ -112,6 +112,9 @@ _SIGS = {
     "hx_group": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],
     "hx_hybrid_query_groups_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],
+    "hx_mmr": [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int64, _P, _P, _P, _P],
+    "hx_hybrid_query_mmr_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_float, _P, _P, _P, _P],
     "hx_payload_create": [_P, C.c_int32, C.POINTER(C.c_int32)],
     "hx_payload_drop": [_P, C.c_int32],
     "hx_payload_append": [_P, C.c_int32, _P, C.c_int64],

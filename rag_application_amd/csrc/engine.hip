@@ -96,7 +96,7 @@ enum WsSlot {
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
   WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
-  WS_G_KEYS, WS_G_CODES, WS_G_CNT
+  WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT
 };
 
 template <typename T>
@@ -3435,12 +3435,48 @@ struct GroupSpec {
   int32_t* counts_host;
 };
 
-// hx_hybrid_query_host, its masked form (mask_host NULL = every row) and its grouped form (grp NULL = the plain lists;
-// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots)
+// ---- MMR search -------------------------------------------------------------------------------
+// the checks of hx_mmr on its sizes, before any device work
+static void mmr_check(int32_t limit, float diversity) {
+  HX_CHECK(limit >= 1 && limit <= HX_MMR_MAX_LIMIT, "mmr: limit out of range [1, 256]");
+  HX_CHECK(diversity >= 0.0f && diversity <= 1.0f, "mmr: diversity must be in [0, 1]");   // (false for a NaN)
+}
+static void mmr_enqueue(hx_index* h, const uint64_t* keys, const uint64_t* ikeys, int stride, const int* counts, int B,
+                        int limit, float diversity, const uint32_t* eligible, uint64_t* out_keys, float* out_values,
+                        int* out_counts, hipStream_t st) {
+  HX_CHECK(h->dim_pad <= 4096, "mmr: rows wider than 4096 floats");
+  MmrArgs m{};
+  m.keys = keys;
+  m.ikeys = ikeys;
+  m.stride = stride;
+  m.counts = counts;
+  m.rows = h->dense;
+  m.dim_pad = (int)h->dim_pad;
+  m.n_rows = h->n;
+  m.id_base = (uint32_t)h->id_base;
+  m.eligible = eligible;
+  m.limit = limit;
+  m.diversity = diversity;
+  m.out_keys = out_keys;
+  m.out_values = out_values;
+  m.out_counts = out_counts;
+  launch_mmr_select(m, B, st);
+}
+// what hx_hybrid_query_mmr_host adds to hx_hybrid_query_host
+struct MmrSpec {
+  int32_t root_only, candidates, limit;
+  float diversity;
+  float* values_host;
+  int32_t* counts_host;
+};
+
+// hx_hybrid_query_host, its masked form (mask_host NULL = every row), its grouped form (grp NULL = the plain lists;
+// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots) and its
+// MMR form (mmr: the pool likewise, scores / ids receive the picks)
 static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
                               int32_t B, const hx_params* p_in, const uint32_t* mask_host, float* scores, int64_t* ids,
-                              int32_t* counts, const GroupSpec* grp = nullptr) {
-  HX_CHECK(h && qd && qip && scores && ids && (counts || grp) && B > 0, "bad argument");
+                              int32_t* counts, const GroupSpec* grp = nullptr, const MmrSpec* mmr = nullptr) {
+  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr) && B > 0, "bad argument");
   HX_CHECK(p_in != nullptr, "params is NULL");
   hx_params pool_params = *p_in;          // (the caller's params are never written)
   const hx_params* p = p_in;
@@ -3456,6 +3492,25 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     p = &pool_params;
     check_params(p);
     group_p0 = group_plane(h, grp->col, grp->n_groups, grp->group_size);
+  }
+  const uint32_t* root_mask = nullptr;    // the MMR call's root-only mask: the query runs unmasked, the stage reads it
+  if (mmr) {
+    HX_CHECK(mmr->values_host && mmr->counts_host, "bad argument");
+    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
+    HX_CHECK(mmr->root_only == 0 || mmr->root_only == 1, "mmr: mask_root_only must be 0 or 1");
+    HX_CHECK(!(mask_host && mmr->root_only && p_in->mode == HX_MODE_H1),
+             "mmr: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
+    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
+    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
+    HX_CHECK(mmr->candidates >= 0 && mmr->candidates <= pool_max && pool_max >= 1,
+             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
+    mmr_check(mmr->limit, mmr->diversity);
+    pool_params.final_limit = mmr->candidates ? mmr->candidates : (int32_t)pool_max;
+    p = &pool_params;
+    if (mmr->root_only) {
+      root_mask = mask_host;
+      mask_host = nullptr;
+    }
   }
   check_params(p);
   h->set_device();
@@ -3496,7 +3551,7 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
   float* dv = (float*)h->ws.get(WS_H_QV, (size_t)std::max<int64_t>(nnz, 1) * 4);
   uint64_t* ok = (uint64_t*)h->ws.get(WS_H_OUT, (size_t)B * L * 8);
   int* oc = (int*)h->ws.get(WS_H_OCNT, (size_t)B * 4);
-  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : L;   // slots of a query's result
+  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : mmr ? std::max(L, mmr->limit) : L;   // slots of a result
   float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * OL * 4);
   int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * OL * 8);
   HX_HIP(hipMemcpyAsync(dq, qd, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
@@ -3525,6 +3580,37 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * GS * 8, hipMemcpyDeviceToHost, st));
     HX_HIP(hipMemcpyAsync(grp->codes_host, gc, (size_t)B * G * 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipMemcpyAsync(grp->counts_host, gn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
+  if (mmr) {                             // the stage reads internal ids: before remap_out
+    const uint64_t* pool = ok;
+    const int* pcnt = oc;
+    if (p->mode == HX_MODE_H1) {         // relevance is the dense cosine: the fused list through the re-score stage
+      uint64_t* rk = (uint64_t*)h->ws.get(WS_MMR_POOL, (size_t)B * L * 8);
+      int* rc = (int*)h->ws.get(WS_MMR_PCNT, (size_t)B * 4);
+      rescore(h, dq, B, 0, ok, L, oc, L, rk, rc, st);
+      pool = rk;
+      pcnt = rc;
+    }
+    const uint32_t* elig = nullptr;
+    if (root_mask) {
+      const int64_t nw = (h->n + 31) / 32;
+      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+      elig = dm;
+    }
+    const int ML = mmr->limit;
+    uint64_t* mk = (uint64_t*)h->ws.get(WS_MMR_KEYS, (size_t)B * ML * 8);
+    float* mv = (float*)h->ws.get(WS_MMR_VAL, (size_t)B * ML * 4);
+    int* mn = (int*)h->ws.get(WS_MMR_CNT, (size_t)B * 4);
+    mmr_enqueue(h, pool, pool, L, pcnt, B, ML, mmr->diversity, elig, mk, mv, mn, st);
+    remap_out(h, mk, (int64_t)B * ML, st);
+    launch_unpack(mk, (int64_t)B * ML, osc, oid, st);
+    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * ML * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * ML * 8, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(mmr->values_host, mv, (size_t)B * ML * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(mmr->counts_host, mn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     return;
   }
@@ -3579,6 +3665,35 @@ int hx_hybrid_query_groups_host(hx_index* h, const float* qd, const int64_t* qip
   HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
   const GroupSpec g{col, group_pool, n_groups, group_size, group_codes, group_counts};
   hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, &g);
+  HX_CATCH
+}
+
+int hx_mmr(hx_index* h, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B, int32_t limit,
+           float diversity, const uint32_t* eligible_dev, int64_t eligible_rows, uint64_t* out_keys_dev,
+           float* out_values_dev, int32_t* out_counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && keys_dev && out_keys_dev && out_values_dev && out_counts_dev, "NULL argument");
+  HX_CHECK(B >= 1, "mmr: B < 1");
+  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "mmr: stride out of range [1, 2048]");
+  mmr_check(limit, diversity);
+  HX_CHECK(!eligible_dev || eligible_rows == h->n, "mmr: eligible_rows must equal the index's row count (hx_count)");
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
+  mmr_enqueue(h, keys_dev, ikeys, stride, counts_dev, B, limit, diversity, eligible_dev, out_keys_dev, out_values_dev,
+              out_counts_dev, st);
+  HX_CATCH
+}
+
+int hx_hybrid_query_mmr_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                             int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
+                             int32_t mask_root_only, int32_t candidates_limit, int32_t limit, float diversity,
+                             float* scores, int64_t* ids, float* values, int32_t* counts) {
+  HX_TRY
+  HX_CHECK(h, "NULL argument");
+  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  const MmrSpec m{mask_root_only, candidates_limit, limit, diversity, values, counts};
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, &m);
   HX_CATCH
 }
 

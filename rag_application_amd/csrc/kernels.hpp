@@ -483,6 +483,29 @@ struct GroupArgs {
   int* group_counts;
 };
 void launch_group_select(const GroupArgs& a, int B, hipStream_t st);
+// ---- mmr.hip: MMR search (hx_mmr) --------------------------------------------------------------
+// Per query b: the ranked pool keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same
+// slots with internal ids (id_base + row), which name the fp32 row rows[row * dim_pad ..].  A position is eligible when
+// its key is not 0, its row is in [0, n_rows) and (eligible != NULL) bit row & 31 of eligible[row >> 5] is set.
+// out_keys[b * limit + t] = the key of pick t as it came, out_values[b * limit + t] = its v; the slots past the picks are
+// 0 / 0.0f; out_counts[b] = picks.
+struct MmrArgs {
+  const uint64_t* keys;
+  const uint64_t* ikeys;
+  int stride;              // 1 .. 2048
+  const int* counts;
+  const float* rows;       // the normalised fp32 rows, dim_pad floats each (dim_pad a multiple of 64, at most 4096)
+  int dim_pad;
+  int64_t n_rows;
+  uint32_t id_base;
+  const uint32_t* eligible;
+  int limit;               // 1 .. 256
+  float diversity;         // in [0, 1]
+  uint64_t* out_keys;
+  float* out_values;
+  int* out_counts;
+};
+void launch_mmr_select(const MmrArgs& a, int B, hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

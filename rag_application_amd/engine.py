@@ -635,6 +635,56 @@ class HxIndex:
                                                      _ptr(scores), _ptr(ids), _ptr(codes), _ptr(counts)))
         return scores, ids, codes, counts
 
+    # -- MMR search (hx.h: hx_mmr / hx_hybrid_query_mmr_host) ----------------------------------
+    def mmr(self, keys: torch.Tensor, counts: Optional[torch.Tensor], limit: int, diversity: float, eligible=None):
+        """Maximal marginal relevance over the ranked pools keys [B, stride] (+ counts [B], None = every slot): `limit`
+        picks per query (hx_mmr).  eligible: None, or a row mask as hybrid_query_host takes it (a bool array of one entry
+        per row, or packed uint32 words); rows whose bit is clear are never picked.  Returns (out_keys [B, limit] int64, 0
+        past the picks; values [B, limit] float32, the picks' MMR values; counts [B] int32).  Only enqueues work."""
+        keys = _need_cuda(keys, torch.int64, "keys")
+        if keys.dim() != 2:
+            raise HxError("keys must be a [B, stride] tensor")
+        if counts is not None:
+            counts = _need_cuda(counts, torch.int32, "counts")
+        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        slots = L if 1 <= L <= 256 else 1                   # (the engine refuses; nothing huge is allocated)
+        words, rows = None, 0
+        if eligible is not None:
+            w, rows = self._mask(eligible)
+            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
+        out = torch.empty((B, slots), dtype=torch.int64, device=keys.device)
+        val = torch.empty((B, slots), dtype=torch.float32, device=keys.device)
+        cnt = torch.empty((B,), dtype=torch.int32, device=keys.device)
+        check(_lib.lib().hx_mmr(self._h, _ptr(keys), stride, _ptr(counts), B, L, float(diversity), _ptr(words), rows,
+                                _ptr(out), _ptr(val), _ptr(cnt), _stream()))
+        return out, val, cnt
+
+    def hybrid_query_mmr_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
+                              params: HxParams, limit: int, diversity: float, candidates_limit: int = 0, mask=None,
+                              mask_root_only: bool = False):
+        """hybrid_query_host followed by MMR over its pool (hx_hybrid_query_mmr_host): the query runs with final_limit =
+        the pool (candidates_limit = 0: the mode's whole pool; params.final_limit is not used), `limit` hits are picked on
+        the device.  mask as hybrid_query_host; mask_root_only: the query runs unmasked and only the picks honour the mask
+        (tree mode).  Returns (scores [B, limit] float32 -- the dense cosines, in both modes --, ids [B, limit] int64,
+        values [B, limit] float32, counts [B] int32) in pick order, the slots past the picks (-inf, -1, 0)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
+        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
+        B, L = q.shape[0], int(limit)
+        if not 1 <= L <= 256:
+            raise HxError("mmr: limit out of range [1, 256]")
+        scores = np.empty((B, L), dtype=np.float32)
+        ids = np.empty((B, L), dtype=np.int64)
+        values = np.empty((B, L), dtype=np.float32)
+        counts = np.empty((B,), dtype=np.int32)
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        check(_lib.lib().hx_hybrid_query_mmr_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                  C.byref(params), _ptr(words), rows, int(bool(mask_root_only)),
+                                                  int(candidates_limit), L, float(diversity), _ptr(scores), _ptr(ids),
+                                                  _ptr(values), _ptr(counts)))
+        return scores, ids, values, counts
+
 
 # -- index-free stages -------------------------------------------------------------------
 def rrf(a_keys: torch.Tensor, a_cnt: torch.Tensor, b_keys: torch.Tensor, b_cnt: torch.Tensor,

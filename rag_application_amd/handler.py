@@ -57,6 +57,14 @@ class PointGroup:
 
 
 @dataclass
+class MmrPoint(ScoredPoint):
+    """One hit of hybrid_search_mmr: a ScoredPoint whose `score` is its relevance (the dense cosine to the query) and
+    whose `mmr_score` is the value it was picked at, (1 - diversity) * score - diversity * (its largest similarity to
+    the hits picked before it)."""
+    mmr_score: float = 0.0
+
+
+@dataclass
 class SparseVector:
     """Shape-compatible with qdrant_client.http.models.SparseVector."""
     indices: List[int] = field(default_factory=list)
@@ -263,6 +271,7 @@ class _Collection:
 
 
 FILTER_STAGES = ("root", "all")
+MMR_MAX_LIMIT = 256                   # HX_MMR_MAX_LIMIT of hx.h: most hits hybrid_search_mmr picks per query
 
 
 class QdrantHandler:
@@ -278,6 +287,8 @@ class QdrantHandler:
     _payload_indexes = True
     # hybrid_search_groups groups the pool of ONE engine index, by a column of that index or by this process's payloads
     _grouped_search = True
+    # hybrid_search_mmr picks from the pool of ONE engine index, by the rows of that index
+    _mmr_search = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -768,6 +779,75 @@ class QdrantHandler:
             raise
         except Exception as e:
             logging.error("grouped hybrid search for %s failed: %s", user_id, e)
+            return []
+
+    # ------------------------------------------------------------------------ MMR search
+    def _mmr_sync(self, user_id, dense_vectors, sparse_vectors, limit, diversity, candidates_limit, search_params, filters,
+                  mode, filter_stages):
+        if not self._mmr_search:
+            raise ValueError("hybrid_search_mmr is not supported on a sharded collection")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= MMR_MAX_LIMIT:
+            raise ValueError(f"limit must be an integer in [1, {MMR_MAX_LIMIT}], got {limit!r}")
+        if isinstance(diversity, bool) or not isinstance(diversity, (int, float)) or not 0.0 <= diversity <= 1.0:
+            raise ValueError(f"diversity must be a number in [0, 1], got {diversity!r}")
+        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
+                                             or candidates_limit < 1):
+            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if mode not in ("tree", "h1"):
+            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+        root_filter = bool(filters) and filter_stages == "root"
+        if root_filter and mode != "tree":
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
+        hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
+        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
+        if pool_max < 1:
+            raise ValueError("the search_params leave an empty pool")
+        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        col = self._collections[str(user_id)]
+        q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
+        mask = None
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            mask = col.row_mask(filters)
+        scores, rows, values, counts = col.index.hybrid_query_mmr_host(
+            q, indptr, idx.astype(np.int32), val.astype(np.float32), hp, limit, float(diversity), candidates_limit=pool,
+            mask=mask, mask_root_only=root_filter)
+        cids, cpay = col.ids, col.payloads
+        return [[MmrPoint(id=cids[r], version=0, score=s, payload=cpay[r], mmr_score=v)
+                 for s, r, v in zip(sc[:n], rw[:n], vl[:n])]
+                for sc, rw, vl, n in zip(scores.tolist(), rows.tolist(), values.tolist(), counts.tolist())]
+
+    async def hybrid_search_mmr(self, user_id: str, dense_vectors, sparse_vectors, limit: int = 10, diversity: float = 0.5,
+                                candidates_limit: Optional[int] = 100, search_params: Optional[Dict[str, Any]] = None,
+                                filters: Optional[Dict] = None, mode: str = "tree",
+                                filter_stages: str = "root") -> List[List[MmrPoint]]:
+        """Qdrant's NearestQuery(mmr=Mmr(diversity, candidates_limit)) for B queries in one engine call (additive; no
+        reranking hook): per query `limit` hits of the query's POOL, picked one by one by maximal marginal relevance --
+        the next hit is the one with the largest (1 - diversity) * relevance - diversity * (largest similarity to the hits
+        picked so far); include/hx.h states the arithmetic.  Relevance is the dense cosine to the query and similarity
+        the dense cosine between two stored rows, in both modes.  The pool is the ranked list the engine returns with
+        final_limit = the pool size -- mode "tree" the root's re-scored union, min(dense_limit + 10, 2048) rows; mode
+        "h1" the fused list, min(dense_limit + sparse_limit, 2048), re-scored by the dense cosine (so `score` is that
+        cosine, NOT the fused score hybrid_search_batch returns in this mode).  candidates_limit asks for a shorter pool;
+        above the pool's maximum it is clipped to it, None = the maximum.  search_params["final_limit"] must be there, as
+        in every search, and is NOT used.  filters / filter_stages as in hybrid_search_batch: "all" = the pool of the
+        pre-filtered query, "root" (tree only) = the pool of the unfiltered query, of which only the points the filter
+        keeps can be picked.  Returns per query the hits in pick order: `score` = the relevance, `mmr_score` = the value
+        the hit was picked at.  All of it runs on the device (hx_hybrid_query_mmr_host); there is no Python path.
+        Raises ValueError for arguments no search can serve (a limit outside [1, 256], a diversity outside [0, 1], a
+        candidates_limit below 1, mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or
+        filter clause); any other failure is logged and gives [], as in every search."""
+        try:
+            return await self._run(self._mmr_sync, user_id, dense_vectors, sparse_vectors, limit, diversity,
+                                   candidates_limit, search_params, filters, mode, filter_stages)
+        except ValueError as ve:
+            logging.error("MMR hybrid search for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("MMR hybrid search for %s failed: %s", user_id, e)
             return []
 
     async def rerank_with_colbert(self, query: str, documents: List[str], results: List[Dict],
