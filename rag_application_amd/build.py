@@ -19,8 +19,10 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("replace.hip", "replace.o", ()),
            ("payload.hip", "payload.o", ()), ("paytext.hip", "paytext.o", ()),
            ("group.hip", "group.o", ()), ("mmr.hip", "mmr.o", ()),
-           ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("bm25.cpp", "bm25.o", ())]
-HEADERS = ["hx_common.hpp", "kernels.hpp", "replace.hpp", "wsort.hpp", os.path.join("..", "..", "include", "hx.h")]
+           ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),
+           ("paystore.hip", "paystore.o", ()), ("bm25.cpp", "bm25.o", ())]
+HEADERS = ["hx_common.hpp", "index.hpp", "kernels.hpp", "replace.hpp", "wsort.hpp",
+           os.path.join("..", "..", "include", "hx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-function"]
 

@@ -3,7 +3,7 @@
 // rows[0, count) is the ascending list of kept rows (mask.hip); row i of the result is old row rows[i], so a row only
 // ever moves DOWN (i <= rows[i]) and the rows in front of the first deleted one do not move at all.  One in-place
 // gather launch would still race: the workgroup that writes position p may run before the one that has to read old
-// row p.  The host (engine.hip) therefore cuts the destination rows into stream-ordered chunks [d0, d1) of two kinds:
+// row p.  The host (lifecycle.hip) therefore cuts the destination rows into stream-ordered chunks [d0, d1) of two kinds:
 //   direct   rows[d0] >= d1: every source row of the chunk lies at or past d1, every destination row below it -- the
 //            launch reads nothing it writes, the gather goes straight into place;
 //   bounced  otherwise: the chunk is gathered into a bounce buffer small enough to stay in the Infinity Cache and

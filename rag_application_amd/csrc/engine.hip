@@ -3,10 +3,9 @@
 // The stage functions restate the nested-Prefetch query of the reference
 // (app/core/vector_store/qdrant/qdrant_handler.py:296-372) as launches on one HIP
 // stream.  See include/hx.h for the boundary and DESIGN.md for the algorithms.
-#include "../../include/hx.h"
-#include "hx_common.hpp"
-#include "kernels.hpp"
-#include "replace.hpp"
+// The state of a collection (struct hx_index) is in index.hpp; what removes or rewrites stored rows is in
+// lifecycle.hip, the payload index in paystore.hip.
+#include "index.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -16,10 +15,8 @@
 #include <limits>
 #include <functional>
 #include <map>
-#include <memory>
 #include <mutex>
 #include <tuple>
-#include <cmath>
 #include <numeric>
 #include <vector>
 
@@ -27,27 +24,6 @@ namespace hx {
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
-
-struct Workspace {
-  std::map<int, std::pair<void*, size_t>> slots;
-  void* get(int id, size_t bytes) {
-    auto& s = slots[id];
-    if (s.second < bytes) {
-      if (s.first) HX_HIP(hipFree(s.first));
-      s.first = nullptr;
-      s.second = 0;
-      const size_t want = (bytes + 255) / 256 * 256;
-      HX_HIP(hipMalloc(&s.first, want));
-      s.second = want;
-    }
-    return s.first;
-  }
-  void release() {
-    for (auto& kv : slots)
-      if (kv.second.first) (void)hipFree(kv.second.first);
-    slots.clear();
-  }
-};
 
 // Scratch of the index-free entries (hx_rrf, hx_merge, hx_h1_fuse): one Workspace per (device, calling thread), so
 // two threads fusing lists on one device never share buffers.  A thread that exits hands its workspaces to a pool
@@ -85,194 +61,6 @@ struct ThreadWorkspaces {
   }
 };
 
-enum WsSlot {
-  WS_QN = 1, WS_QH, WS_Q8, WS_RINVQ, WS_CAND, WS_CAND2, WS_CNT, WS_CNT2, WS_OVF, WS_TAU, WS_FAIL,
-  WS_NFAIL, WS_QSEL, WS_FB_KEYS, WS_FB_CNT, WS_FB_INCNT, WS_SP_PARTS, WS_SP_PCNT, WS_RAW, WS_RS_TMP,
-  WS_T_A, WS_T_ACNT, WS_T_B, WS_T_BCNT, WS_T_C, WS_T_CCNT, WS_T_D, WS_T_DCNT, WS_T_E, WS_T_ECNT,
-  WS_T_F, WS_T_FCNT, WS_T_G, WS_T_GCNT, WS_H_QD, WS_H_QIP, WS_H_QIX, WS_H_QV, WS_H_OUT, WS_H_OCNT,
-  WS_H_SC, WS_H_ID, WS_SYN_NNZ, WS_RRF_TMP, WS_MISC, WS_SP_CAND, WS_SP_PARK, WS_SP_ORDER, WS_HITLOG, WS_HITCNT, WS_KEPT,
-  WS_F_DALL, WS_F_SALL, WS_F_D, WS_F_S, WS_F_DC, WS_F_SC,
-  WS_SP_TI0, WS_SP_TI1, WS_SP_QS, WS_SP_MARGIN, WS_SP_FLAG, WS_SP_WORK, WS_SP_FAIL, WS_SP_LIST, WS_SP_LCNT,
-  WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
-  WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
-  WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
-  WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT
-};
-
-template <typename T>
-static void grow_copy(T*& p, int64_t old_elems, int64_t new_elems, bool zero_tail) {
-  T* np_ = nullptr;
-  HX_HIP(hipMalloc((void**)&np_, (size_t)std::max<int64_t>(new_elems, 1) * sizeof(T)));
-  if (zero_tail) HX_HIP(hipMemset(np_, 0, (size_t)std::max<int64_t>(new_elems, 1) * sizeof(T)));
-  if (p && old_elems > 0) HX_HIP(hipMemcpy(np_, p, (size_t)old_elems * sizeof(T), hipMemcpyDeviceToDevice));
-  if (p) HX_HIP(hipFree(p));
-  p = np_;
-}
-
-}  // namespace hx
-
-using namespace hx;
-
-struct hx_index {
-  int dim = 0, dim_pad = 0, dim_pad8 = 0, device = 0;
-  int n_pre = 0;
-  int psize[3] = {0, 0, 0};
-  int64_t id_base = 0;
-  int64_t n = 0, cap = 0;
-  float* dense = nullptr;
-  _Float16* dense_h = nullptr;
-  int8_t* q8 = nullptr;
-  float* q8_rinv = nullptr;
-  float* pre[3] = {nullptr, nullptr, nullptr};
-  _Float16* pre_h0 = nullptr;
-  // Candidate-pass copy of the normalised rows (DESIGN.md "int8 candidate pass"): rint(x * 127 / max|x|), the
-  // row's scale, and -- one device word -- the largest quantisation error ||x - scale * x8|| of any row so far
-  // (fp32 bits, rounded up; a rollback leaves it as it is: an upper bound is all the certificate needs).
-  int8_t* q8s = nullptr;
-  float* q8s_scale = nullptr;
-  uint32_t* s8_err = nullptr;
-  int cand8 = 1;                      // 0: fp16 candidates only, no int8 copy is kept (HX_DENSE_CAND=f16)
-  bool cand8_off = false;             // hx_set_dense_candidates(h, 0): the copy is kept but the fp16 scan nominates
-  int64_t cand8_queries = 0, cand8_failed = 0;   // queries the int8 candidate pass took / could not certify
-  int64_t tree_redone = 0;            // tree batches run again the synchronous way (a deferred flag was set)
-  // Adaptive guards of the two speculative paths (hx_stats): windows of recent outcomes
-  int64_t c8_win_q = 0, c8_win_f = 0; // queries / uncertified queries of the current window of the int8 candidate pass
-  bool cand8_auto_off = false;        // ... switched off by the guard (hx_set_dense_candidates(h, 1) switches it on again)
-  int tree_win_n = 0, tree_win_redone = 0;
-  bool tree_spec_off = false;
-  int done_zeroed[2] = {0, 0};        // entries of the finish kernel's per-query counters known to be zero (level 0 / retry level)
-  bool no_finish_fuse = false;        // HX_DEBUG_NO_FINISH_FUSE (tests): the dense stage's tail always as three launches
-  int finish_nb = 0;                  // HX_DEBUG_FINISH_NB (tests): blocks per query of k_dense_finish, 0 = one per four candidates
-  // query-tile routing of the scans (read from the environment at hx_create: tests and diagnostics):
-  //   B <= 32: k_scan 128 x 32; <= bn64_max: k_scan 128 x 64; <= bn128_max: 128 queries per tile -- the staggered kernel's
-  //   256 x 128 form (scan8.hip, HQ) unless no_hq, then k_scan 128 x 128; above: the staggered 256 x 256 kernel
-  int bn32_max = 32, bn64_max = 32, bn128_max = 128;
-  // second stream of the one-call H1 step: the sparse stage runs beside the dense stage's tail (hybrid_query_dev)
-  hipStream_t st2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool overlap_tail = true;           // HX_DEBUG_NO_OVERLAP (diagnostics): everything on the caller's stream
-  bool beside = false;                // a stage of this call runs on the second stream while the dense scans run
-  int scan_oversub = 4;               // ScanArgs.oversub of those scans (HX_DEBUG_SCAN_OVERSUB)
-  int sp_host_late_min_b = 128;       // batches from here on: the host enqueues the dense scans before the sparse stage (HX_DEBUG_SP_HOST_LATE_MIN_B)
-  int fork_early_max = 1 << 30;       // batches of at most this many queries start the sparse stage beside the dense SCAN
-                                      // (HX_DEBUG_FORK_EARLY_MAX=0: beside the stage's tail only, as round 4 began)
-  bool no_hq = false;
-  bool no_qs = false;                 // HX_DEBUG_NO_QS (tests): never the query-stationary form of the staggered kernel (k_scan8q)
-  // doc-major sparse staging (device)
-  int64_t* sp_indptr = nullptr;  // [sp_rows_cap + 1]
-  int32_t* sp_idx = nullptr;
-  float* sp_val = nullptr;
-  int64_t sp_rows = 0, sp_rows_cap = 0, nnz = 0, nnz_cap = 0;
-  bool sparse_stale = false;
-  // Inverted index = an immutable BASE over documents [0, base.n_docs) plus a TAIL over the documents added
-  // since (rebuilt on every finalize from the tail's postings only); the base is rebuilt once the tail has
-  // grown to a quarter of it.  Both are searched by the same select kernel; the exact scores come from the
-  // document-major CSR, which covers every document.
-  struct SparseIx {
-    SparseBuildOut sp{};
-    int64_t doc0 = 0, n_docs = 0;
-    int n_segments = 0;
-    int seg_docs = SEG_DOCS_SMALL;
-  };
-  SparseIx sp_base, sp_tail;
-  int seg_docs_force = 0;             // HX_DEBUG_SEG_DOCS (tests): 32768 / 65536, 0 = by size
-  int sp_cut_step = 0;                // HX_DEBUG_SP_CUTSTEP (diagnostics): keys between cuts of the select pass, 0 = default
-  int64_t tail_min_force = -1;        // HX_DEBUG_TAIL_MIN (tests): documents a tail may hold before the base is rebuilt
-  int64_t compact_chunk = 0;          // HX_DEBUG_COMPACT_CHUNK (tests): rows per chunk of hx_retain_rows, 0 = by the bounce buffer's size
-  float sp_wmin = 0.f, sp_wmax = 0.f; // range of the document weights (all finite: checked at ingest)
-  float sp_wmax_shared = 0.f;         // hx_set_sparse_wmax: the largest weight of any shard of the collection (0: unset)
-  bool sp_have_w = false;
-  int64_t sparse_fallbacks = 0;       // queries served by the document-at-a-time path
-  Workspace ws;
-  int64_t dense_fallbacks = 0, i8_fallbacks = 0, retries = 0;
-  // max of a per-row scale over every 256-row tile: the int8 scans' column bound (scan8.hip)
-  struct TileMax {
-    float* v = nullptr;
-    int64_t rows = -1, cap = 0;
-  };
-  TileMax tm_q8, tm_q8s;            // of q8_rinv (the "quantized" stage) and of q8s_scale (the candidate pass)
-  int scan_logcap = SCAN8_LOGCAP;   // entries per wave log (HX_DEBUG_SCAN8_LOGCAP shrinks it: tests)
-  // optional HIP-event profile of the scan / sparse kernels (hx_profile)
-  struct ProfRec { hipEvent_t a, b; int what; double flops, bytes; };
-  bool prof = false;
-  std::vector<ProfRec> prof_recs;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
-  unsigned long long* sp_counter = nullptr;   // postings of the queries' terms (k_sparse_prep) while profiling
-  // One host round trip per batch for all the stages' failure flags: the small counters travel into this pinned
-  // buffer ([0] a dense stage's failure count, [1..2] the sparse stage's summary) behind ONE synchronisation.
-  int* pin = nullptr;
-  bool sp_sum_pending = false;        // a sparse_enqueue's summary has not been consumed by sparse_resolve yet
-  bool sp_sum_fetched = false;        // ... and is already in sp_sum (a dense stage's flag read took it along)
-  int sp_sum[2] = {0, 0};             // flagged-or-failed queries, any invalid query
-
-  // Insertion-order ids under row sharding.  Inside the engine a row's id is id_base + local
-  // row.  What crosses the ABI is the row's GLOBAL id: rows arrive in blocks, block k = local rows
-  // [row0[k], row0[k + 1]) with global ids gid0[k], gid0[k] + 1, ... (hx_set_next_id names the first id of the next
-  // block; without it a block continues the previous one).  Both columns ascend, so the map is monotone: the order
-  // (score desc, id asc) of a list is the same in both id spaces, and the remap is one pass over the keys a stage
-  // hands out (and over the candidate keys hx_rescore takes in).  One block starting at id_base = the identity.
-  struct IdBlocks {
-    std::vector<uint32_t> row0, gid0;
-    uint32_t* dev = nullptr;          // row0[0, nb) then gid0[0, nb)
-    int dev_cap = 0;
-    bool dirty = false;
-    int64_t next = -1;                // hx_set_next_id: global id of the next appended row (-1: continue)
-    int64_t end = -1;                 // global id after the last row (-1: no row yet)
-  } ids;
-
-  // Pre-filtered query (hx_hybrid_query_*_masked): while `on`, the whole-collection scans read
-  // these gathered copies of the kept rows (view row i = local row rows[i]) and map their candidates back to this index's
-  // rows before anything reads rows by id; the sparse stage tests `keep` at harvest.  A copy is gathered on first use in a
-  // call (bit of `have`); the buffers hold `cap` rows (a power of two), persist across calls and are freed by
-  // hx_release_mask_view or when a call needs more rows.
-  struct MaskView {
-    bool on = false;
-    int64_t n = 0, cap = 0;
-    const uint32_t* keep = nullptr;
-    const uint32_t* rows = nullptr;
-    unsigned have = 0;
-    int8_t* q8s = nullptr;
-    float* q8s_scale = nullptr;
-    _Float16* dense_h = nullptr;
-    _Float16* pre_h0 = nullptr;
-    int8_t* q8 = nullptr;
-    float* q8_rinv = nullptr;
-    TileMax tm_q8, tm_q8s;
-  } mv;
-
-  // Payload index (hx_payload_*): columns of one (U32) or two (F64: low word, high word) planes of
-  // uint32 per row, filled for rows [0, filled), filled <= n.  Ids are never reused.  A program and its sets travel
-  // through one pinned staging buffer; pay_ev says when the device has taken the last one.
-  // A list column (HX_PAY_LIST_*): p0 = the head plane (missing / null / 0 = a list), off = int64
-  // offsets [filled + 1] into the element planes e0 (codes, or the low words of doubles) and e1 (the high words).
-  // A text column (HX_PAY_TEXT) is stored the same way: p0 = the head plane (missing / null / the
-  // row's byte length), off counts 32-bit words, e0 = the rows' bytes, each row padded with zero bytes to a word.
-  struct PayCol {
-    int id = 0, kind = 0;
-    uint32_t* p0 = nullptr;
-    uint32_t* p1 = nullptr;
-    int64_t filled = 0, cap = 0;
-    int64_t* off = nullptr;
-    uint32_t* e0 = nullptr;
-    uint32_t* e1 = nullptr;
-    int64_t n_el = 0, el_cap = 0;
-    bool list() const { return kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64; }
-    bool text() const { return kind == HX_PAY_TEXT; }
-    bool csr() const { return list() || text(); }      // offsets and element planes: what the lifecycle moves
-  };
-  std::vector<PayCol> pay;
-  int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap
-  int pay_next_id = 0;
-  uint8_t* pay_pin = nullptr;
-  size_t pay_pin_cap = 0;
-  hipEvent_t pay_ev = nullptr;
-  bool pay_ev_pending = false;
-
-  void set_device() const { HX_HIP(hipSetDevice(device)); }
-};
-
-namespace hx {
-
 void launch_sparse_select(const SparseSelectArgs& a, hipStream_t st) {
   if (a.ix.seg_docs == SEG_DOCS_LARGE) v64k::launch_sparse_select_variant(a, st);
   else v32k::launch_sparse_select_variant(a, st);
@@ -281,40 +69,59 @@ void launch_sparse_select(const SparseSelectArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------------------------
 // storage
 // ---------------------------------------------------------------------------------
-static void pay_free(hx_index::PayCol& c) {
-  if (c.p0) (void)hipFree(c.p0);
-  if (c.p1) (void)hipFree(c.p1);
-  if (c.off) (void)hipFree(c.off);
-  if (c.e0) (void)hipFree(c.e0);
-  if (c.e1) (void)hipFree(c.e1);
-  c.p0 = c.p1 = c.e0 = c.e1 = nullptr;
-  c.off = nullptr;
-  c.filled = c.cap = c.n_el = c.el_cap = 0;
+// The stored per-row arrays (index.hpp: RowArray).  The order is the one they are grown and compacted in, and -- leaving
+// out the derived candidate copy -- the order of a saved file: it does not change.
+std::vector<RowArray> row_arrays(hx_index* h) {
+  std::vector<RowArray> r;
+  auto add = [&](auto*& field, int64_t rb, bool in_file, size_t arg) { r.push_back({(void**)&field, rb, in_file, arg}); };
+  add(h->dense, (int64_t)h->dim_pad * 4, true, offsetof(PrepRowsArgs, dense));
+  add(h->dense_h, (int64_t)h->dim_pad * 2, true, offsetof(PrepRowsArgs, dense_h));
+  add(h->q8, h->dim_pad8, true, offsetof(PrepRowsArgs, q8));
+  add(h->q8_rinv, 4, true, offsetof(PrepRowsArgs, q8_rinv));
+  if (h->cand8) {
+    add(h->q8s, h->dim_pad8, false, offsetof(PrepRowsArgs, q8s));
+    add(h->q8s_scale, 4, false, offsetof(PrepRowsArgs, q8s_scale));
+  }
+  for (int p = 0; p < h->n_pre; ++p)
+    add(h->pre[p], (int64_t)h->psize[p] * 4, true, offsetof(PrepRowsArgs, pre) + (size_t)p * sizeof(float*));
+  if (h->n_pre > 0) add(h->pre_h0, (int64_t)h->psize[0] * 2, true, offsetof(PrepRowsArgs, pre_h0));
+  return r;
 }
 
-static void reserve_rows(hx_index* h, int64_t want) {
+PrepRowsArgs prep_rows_args(hx_index* h, const std::vector<RowArray>& ra, void* const* base, int64_t r) {
+  HX_CHECK(!h->cand8 || (h->q8s && h->q8s_scale && h->s8_err), "int8 candidate copy enabled but not allocated");
+  PrepRowsArgs a{};
+  a.dim = h->dim;
+  a.dim_pad = h->dim_pad;
+  a.dim_pad8 = h->dim_pad8;
+  a.n_prefix = h->n_pre;
+  for (int p = 0; p < h->n_pre; ++p) a.psize[p] = h->psize[p];
+  a.err_max = h->cand8 ? h->s8_err : nullptr;
+  for (size_t i = 0; i < ra.size(); ++i) {
+    void* row = (uint8_t*)base[i] + r * ra[i].rb;
+    std::memcpy((uint8_t*)&a + ra[i].arg, &row, sizeof row);
+  }
+  return a;
+}
+
+void reserve_rows(hx_index* h, int64_t want) {
   if (want <= h->cap) return;
   int64_t nc = std::max<int64_t>(want, h->cap * 2);
   nc = round_up(nc, 256);
-  const int64_t n = h->n;
-  grow_copy(h->dense, n * h->dim_pad, nc * h->dim_pad, false);
-  grow_copy(h->dense_h, n * h->dim_pad, nc * h->dim_pad, false);
-  grow_copy(h->q8, n * h->dim_pad8, nc * h->dim_pad8, false);
-  grow_copy(h->q8_rinv, n, nc + 256, true);
-  if (h->cand8) {
-    grow_copy(h->q8s, n * h->dim_pad8, nc * h->dim_pad8, false);
-    grow_copy(h->q8s_scale, n, nc + 256, true);
-    if (!h->s8_err) {
-      HX_HIP(hipMalloc((void**)&h->s8_err, 4));
-      HX_HIP(hipMemset(h->s8_err, 0, 4));
-    }
+  for (const RowArray& a : row_arrays(h)) {
+    const bool scale = a.rb == 4;      // zeroed, and a tile of zeros behind the last row
+    uint8_t* p = (uint8_t*)a.p();
+    grow_copy(p, h->n * a.rb, (scale ? nc + 256 : nc) * a.rb, scale);
+    a.set(p);
   }
-  for (int p = 0; p < h->n_pre; ++p) grow_copy(h->pre[p], n * h->psize[p], nc * h->psize[p], false);
-  if (h->n_pre > 0) grow_copy(h->pre_h0, n * h->psize[0], nc * h->psize[0], false);
+  if (h->cand8 && !h->s8_err) {
+    HX_HIP(hipMalloc((void**)&h->s8_err, 4));
+    HX_HIP(hipMemset(h->s8_err, 0, 4));
+  }
   h->cap = nc;
 }
 
-static void reserve_sparse(hx_index* h, int64_t rows, int64_t nnz) {
+void reserve_sparse(hx_index* h, int64_t rows, int64_t nnz) {
   if (rows > h->sp_rows_cap) {
     int64_t nc = std::max<int64_t>(rows, h->sp_rows_cap * 2);
     nc = round_up(nc, 256);
@@ -367,49 +174,35 @@ struct ProfScope {
 
 // nonfinite (optional, device): set to 1 when a row holds a NaN or +-Inf element (rows_check_begin / rows_check_end)
 static void prep_rows_device(hx_index* h, const float* raw_dev, int64_t n, hipStream_t st, int* nonfinite = nullptr) {
-  PrepRowsArgs a{};
+  const std::vector<RowArray> ra = row_arrays(h);
+  std::vector<void*> stored;
+  // K1/K2 of SURVEY 8(d): the raw row read once, every derived copy written once
+  double per_row = (double)h->dim * 4;
+  for (const RowArray& x : ra) {
+    stored.push_back(x.p());
+    per_row += (double)x.rb;
+  }
+  PrepRowsArgs a = prep_rows_args(h, ra, stored.data(), h->n);
   a.raw = raw_dev;
   a.nonfinite = nonfinite;
-  a.dim = h->dim;
-  a.dim_pad = h->dim_pad;
   a.n = n;
-  a.dense = h->dense + h->n * h->dim_pad;
-  a.dense_h = h->dense_h + h->n * h->dim_pad;
-  a.q8 = h->q8 + h->n * h->dim_pad8;
-  a.dim_pad8 = h->dim_pad8;
-  a.q8_rinv = h->q8_rinv + h->n;
-  a.n_prefix = h->n_pre;
-  for (int p = 0; p < h->n_pre; ++p) {
-    a.psize[p] = h->psize[p];
-    a.pre[p] = h->pre[p] + h->n * h->psize[p];
-  }
-  a.pre_h0 = h->n_pre > 0 ? h->pre_h0 + h->n * h->psize[0] : nullptr;
-  const bool c8 = h->cand8 && h->q8s && h->q8s_scale && h->s8_err;   // (never an offset from a null base)
-  HX_CHECK(!h->cand8 || c8, "int8 candidate copy enabled but not allocated");
-  a.q8s = c8 ? h->q8s + h->n * h->dim_pad8 : nullptr;
-  a.q8s_scale = c8 ? h->q8s_scale + h->n : nullptr;
-  a.err_max = c8 ? h->s8_err : nullptr;
-  // K1/K2 of SURVEY 8(d): the raw row read once, every derived copy written once
-  double per_row = (double)h->dim * 4 + (double)h->dim_pad * 6 + (double)h->dim_pad8 * (h->cand8 ? 2 : 1) + (h->cand8 ? 8 : 4);
-  for (int p = 0; p < h->n_pre; ++p) per_row += (double)h->psize[p] * 4;
-  if (h->n_pre > 0) per_row += (double)h->psize[0] * 2;
   ProfScope ps(h, st, 4, 0.0, per_row * (double)n);
   launch_prep_rows(a, st);
 }
 
-static void free_sparse_ix(hx_index::SparseIx& x) {
+void free_sparse_ix(hx_index::SparseIx& x) {
   if (x.sp.post) (void)hipFree(x.sp.post);
   if (x.sp.ptr) (void)hipFree(x.sp.ptr);
   if (x.sp.uterms) (void)hipFree(x.sp.uterms);
   x = hx_index::SparseIx{};
 }
-static void free_sparse_index(hx_index* h) {
+void free_sparse_index(hx_index* h) {
   free_sparse_ix(h->sp_base);
   free_sparse_ix(h->sp_tail);
 }
 
 // merge the range of val[from, to) (device) into the index's weight range; non-finite values are refused
-static void track_weights_dev(hx_index* h, const float* val, int64_t n, hipStream_t st) {
+void track_weights_dev(hx_index* h, const float* val, int64_t n, hipStream_t st) {
   if (n <= 0) return;
   uint32_t* mm = (uint32_t*)h->ws.get(WS_SP_MM, 16);
   const uint32_t init[3] = {0xFFFFFFFFu, 0u, 0u};
@@ -470,7 +263,7 @@ static void finalize(hx_index* h, hipStream_t st) {
 // ---------------------------------------------------------------------------------
 // global (insertion-order) ids: hx_index::IdBlocks
 // ---------------------------------------------------------------------------------
-static bool ids_identity(const hx_index* h) {
+bool ids_identity(const hx_index* h) {
   const auto& b = h->ids;
   return b.row0.empty() || (b.row0.size() == 1 && (int64_t)b.gid0[0] == h->id_base);
 }
@@ -945,7 +738,7 @@ static void mv_need(hx_index* h, unsigned what, hipStream_t st) {
   v.have |= what;
 }
 
-static int* host_pin(hx_index* h) {
+int* host_pin(hx_index* h) {
   if (!h->pin) HX_HIP(hipHostMalloc((void**)&h->pin, 64, hipHostMallocDefault));
   return h->pin;
 }
@@ -1792,7 +1585,7 @@ static void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
 // the int8 guard window.
 
 // kept rows of the mask on the device -> rows (ascending), count written to *count_dev
-static void mask_rows_dev(hx_index* h, const uint32_t* mask_dev, uint32_t*& rows, uint32_t*& count_dev, hipStream_t st) {
+void mask_rows_dev(hx_index* h, const uint32_t* mask_dev, uint32_t*& rows, uint32_t*& count_dev, hipStream_t st) {
   const int64_t nw = (h->n + 31) / 32;
   uint32_t* blk = (uint32_t*)h->ws.get(WS_M_BLK, (size_t)((nw + 255) / 256 + 1) * 4 + 4);
   rows = (uint32_t*)h->ws.get(WS_M_ROWS, (size_t)std::max<int64_t>(h->n, 1) * 4);
@@ -1873,19 +1666,6 @@ static void check_params(const hx_params* p) {
 // =================================================================================
 // C ABI
 // =================================================================================
-#define HX_TRY try {
-#define HX_CATCH                                  \
-  }                                               \
-  catch (const std::exception& e) {               \
-    hx::set_last_error(e.what());                 \
-    return 1;                                     \
-  }                                               \
-  catch (...) {                                   \
-    hx::set_last_error("unknown error");          \
-    return 1;                                     \
-  }                                               \
-  return 0;
-
 extern "C" {
 
 const char* hx_last_error(void) { return hx::g_last_error.c_str(); }
@@ -1952,9 +1732,8 @@ int hx_destroy(hx_index* h) {
   (void)hipDeviceSynchronize();
   try { mv_release(h); } catch (...) {}
   free_sparse_index(h);
-  void* ptrs[] = {h->dense, h->dense_h, h->q8, h->q8_rinv, h->pre[0], h->pre[1], h->pre[2], h->pre_h0,
-                  h->sp_indptr, h->sp_idx, h->sp_val, h->sp_counter, h->q8s, h->q8s_scale, h->s8_err,
-                  h->tm_q8.v, h->tm_q8s.v};
+  std::vector<void*> ptrs = {h->sp_indptr, h->sp_idx, h->sp_val, h->sp_counter, h->s8_err, h->tm_q8.v, h->tm_q8s.v};
+  for (const RowArray& a : row_arrays(h)) ptrs.push_back(a.p());
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (h->pin) (void)hipHostFree(h->pin);
@@ -1979,21 +1758,25 @@ int hx_reserve(hx_index* h, int64_t n_rows, int64_t nnz) {
   HX_CATCH
 }
 
+}  // extern "C"
+
+namespace hx {
+
 // ---- ingest (store_document_vectors -> upsert, qdrant_handler.py:120-198) -----------------------------
 // Dense rows must be finite.  Word [0] of WS_ROWS_CHECK is the batch's flag (k_prep_rows raises it
 // for a row with a NaN or +-Inf element), word [1] the largest row quantisation error before the batch: a refused batch
 // restores it, so that it leaves the certificates of later queries as they were.  The flag reaches the host in pin[12],
 // copied behind the batch's last launch and read after the synchronisation the ingest makes anyway.
-static int* rows_check_begin(hx_index* h, hipStream_t st) {
+int* rows_check_begin(hx_index* h, hipStream_t st) {
   int* w = (int*)h->ws.get(WS_ROWS_CHECK, 8);
   HX_HIP(hipMemsetAsync(w, 0, 4, st));
   if (h->s8_err) HX_HIP(hipMemcpyAsync(w + 1, h->s8_err, 4, hipMemcpyDeviceToDevice, st));
   return w;
 }
-static void rows_check_fetch(hx_index* h, int* w, hipStream_t st) {
+void rows_check_fetch(hx_index* h, int* w, hipStream_t st) {
   HX_HIP(hipMemcpyAsync(host_pin(h) + 12, w, 4, hipMemcpyDeviceToHost, st));
 }
-static void rows_check_end(hx_index* h, int* w, hipStream_t st) {   // (after the stream is synchronised)
+void rows_check_end(hx_index* h, int* w, hipStream_t st) {   // (after the stream is synchronised)
   if (host_pin(h)[12] == 0) return;
   if (h->s8_err) {
     HX_HIP(hipMemcpyAsync(h->s8_err, w + 1, 4, hipMemcpyDeviceToDevice, st));
@@ -2067,9 +1850,8 @@ constexpr float SPARSE_ABS_MAX = 1.0e18f;
 // idx_dev / val_dev [first, last).  Term ids in [0, 2^31) and unique within a vector (Qdrant rejects duplicates), finite
 // values with |v| <= SPARSE_ABS_MAX; *lo / *hi = the range of the values.  indptr / idx are the caller's host arrays of the
 // batch (offsets from 0): vectors too long for the wave compare are sorted from them.  Throws before anything is committed.
-static void check_sparse_batch_dev(hx_index* h, const int64_t* rows_ip, const int32_t* idx_dev, const float* val_dev, int64_t n,
-                                   int64_t first, int64_t last, const int64_t* indptr, const int32_t* idx, float* lo,
-                                   float* hi) {
+void check_sparse_batch_dev(hx_index* h, const int64_t* rows_ip, const int32_t* idx_dev, const float* val_dev, int64_t n,
+                            int64_t first, int64_t last, const int64_t* indptr, const int32_t* idx, float* lo, float* hi) {
   constexpr int LONG_CAP = 4096;
   int64_t* long_rows = (int64_t*)h->ws.get(WS_LONG_ROWS, (size_t)LONG_CAP * 8 + 32);
   int* flags = (int*)(long_rows + LONG_CAP);             // [0] bad bits, [1] rows too long for the wave compare
@@ -2143,6 +1925,10 @@ static void add_sparse_host(hx_index* h, const int64_t* indptr, const int32_t* i
   h->nnz += nnz;
   h->sparse_stale = true;
 }
+
+}  // namespace hx
+
+extern "C" {
 
 int hx_add_dense(hx_index* h, const float* rows_host, int64_t n) {
   HX_TRY
@@ -2218,547 +2004,6 @@ int hx_add_rows_dev(hx_index* h, const float* rows_dev, const int64_t* indptr, c
   NextIdGuard guard{h};
   HX_CHECK(n <= 0 || rows_dev, "rows is NULL");
   add_rows_atomic(h, indptr, idx, val, n, [&]() { add_dense_dev(h, rows_dev, n, (hipStream_t)stream); });
-  HX_CATCH
-}
-
-// Roll the collection back to its first n_rows rows (a batch that one shard of a sharded collection could not
-// store is undone on the shards that did store it; qdrant_handler.py:190-193 upserts a batch as one request).
-int hx_truncate(hx_index* h, int64_t n_rows) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  HX_CHECK(n_rows >= 0 && n_rows <= h->n, "hx_truncate: n_rows out of range [0, count]");
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  h->ids.next = -1;
-  for (auto& c : h->pay) {
-    if (c.csr() && c.filled > n_rows)      // (the elements past off[n_rows] are dead)
-      HX_HIP(hipMemcpy(&c.n_el, c.off + n_rows, 8, hipMemcpyDeviceToHost));
-    c.filled = std::min(c.filled, n_rows);
-  }
-  if (n_rows == h->n && h->sp_rows <= n_rows) return 0;
-  h->n = n_rows;
-  h->tm_q8.rows = h->tm_q8s.rows = -1;
-  if (h->sp_rows > n_rows) {
-    int64_t nnz = 0;
-    if (n_rows > 0) HX_HIP(hipMemcpy(&nnz, h->sp_indptr + n_rows, 8, hipMemcpyDeviceToHost));
-    h->sp_rows = n_rows;
-    h->nnz = nnz;
-  }
-  // the inverted index: a base that reaches past the cut is rebuilt, the tail always is.  The weight range stays
-  // as it was: an upper bound of the remaining weights is all the select pass needs.
-  free_sparse_ix(h->sp_tail);
-  if (h->sp_base.n_docs > h->sp_rows) free_sparse_ix(h->sp_base);
-  h->sparse_stale = true;
-  auto& b = h->ids;
-  while (!b.row0.empty() && (int64_t)b.row0.back() >= n_rows) {
-    b.row0.pop_back();
-    b.gid0.pop_back();
-  }
-  b.end = b.row0.empty() ? -1 : (int64_t)b.gid0.back() + (n_rows - (int64_t)b.row0.back());
-  b.dirty = true;
-  HX_CATCH
-}
-
-// ---- per-point deletes ----------------------------------------------------------------------
-namespace hx {
-
-// The kept rows of a host mask, for the chunk plan: rank -> row without the list itself (that one is built on the device).
-struct KeepIndex {
-  const uint32_t* m;
-  int64_t n, nw;
-  std::vector<int64_t> cum;          // set bits in front of word w; cum[nw] = the kept rows
-  uint32_t word(int64_t w) const {
-    uint32_t v = m[w];
-    const int tail = (int)(n & 31);
-    if (w == nw - 1 && tail) v &= (1u << tail) - 1u;
-    return v;
-  }
-  KeepIndex(const uint32_t* mask, int64_t n_) : m(mask), n(n_), nw((n_ + 31) / 32), cum((size_t)((n_ + 31) / 32) + 1, 0) {
-    for (int64_t w = 0; w < nw; ++w) cum[(size_t)w + 1] = cum[(size_t)w] + __builtin_popcount(word(w));
-  }
-  int64_t kept() const { return cum[(size_t)nw]; }
-  int64_t kept_below(int64_t r) const {          // kept rows in [0, r), r <= n
-    if (r >= n) return kept();
-    const int64_t w = r >> 5;
-    return cum[(size_t)w] + __builtin_popcount(word(w) & ((1u << (r & 31)) - 1u));
-  }
-  int64_t row_of(int64_t i) const {              // the i-th kept row, i < kept()
-    const int64_t w = (std::upper_bound(cum.begin(), cum.end(), i) - cum.begin()) - 1;
-    uint32_t v = word(w);
-    for (int64_t k = i - cum[(size_t)w]; k > 0; --k) v &= v - 1u;
-    return w * 32 + (__builtin_ffs((int)v) - 1);
-  }
-  int64_t first_removed() const {                // rows in front of it do not move
-    for (int64_t w = 0; w < nw; ++w) {
-      const uint32_t full = (w == nw - 1 && (n & 31)) ? (1u << (n & 31)) - 1u : 0xFFFFFFFFu;
-      const uint32_t gone = ~word(w) & full;
-      if (gone) return w * 32 + (__builtin_ffs((int)gone) - 1);
-    }
-    return n;
-  }
-};
-
-// Bytes of the bounce buffer of a bounced chunk: the chunk is written there, read back and written into place while
-// its source rows stream past -- three times its size between the two uses of a line, inside the 256 MiB Infinity Cache.
-constexpr int64_t COMPACT_BOUNCE_BYTES = 32ll << 20;
-
-struct CompactChunk {
-  int64_t d0, d1;
-  bool direct;
-};
-// Destination rows [first, count) in stream-ordered chunks (compact.hip): a chunk whose first source row lies at or
-// past its end is gathered in place, any other goes through the bounce buffer, `chunk` rows at a time.
-static std::vector<CompactChunk> compact_plan(const KeepIndex& k, int64_t first, int64_t count, int64_t chunk) {
-  std::vector<CompactChunk> plan;
-  for (int64_t d = first; d < count;) {
-    const int64_t shift = k.row_of(d) - d;       // >= 1 from the first removed row on
-    const bool direct = shift >= chunk;
-    const int64_t e = std::min(count, d + (direct ? shift : chunk));
-    plan.push_back({d, e, direct});
-    d = e;
-  }
-  return plan;
-}
-
-struct DevTmp {                      // a temporary of one call
-  void* p = nullptr;
-  void alloc(size_t bytes) { HX_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
-  ~DevTmp() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-static void retain_rows(hx_index* h, const uint32_t* keep, int64_t* n_removed) {
-  const int64_t n = h->n;
-  const KeepIndex k(keep, n);
-  const int64_t count = k.kept();
-  if (n_removed) *n_removed = n - count;
-  if (count == n) return;                          // nothing to do: nothing touched, nothing invalidated
-  HX_CHECK(h->sp_rows <= n, "hx_retain_rows: sparse vectors are pending for rows not added yet");
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  hipStream_t st = nullptr;
-  const int64_t first = k.first_removed();
-  const bool sparse = h->sp_rows > 0 && h->sp_indptr != nullptr;
-  const int64_t kept_sp = sparse ? k.kept_below(h->sp_rows) : 0;   // kept documents that have a sparse row
-
-  // ---- everything that can fail comes first: the row list, the plans, the temporaries, the CSR offsets ----
-  struct Arr {
-    void* p;
-    int64_t rb;                      // row bytes; 4 = one scale per row
-    std::vector<CompactChunk> plan;
-  };
-  std::vector<Arr> arrs;
-  if (count > 0) {
-    auto add = [&](void* p, int64_t rb) {
-      if (p) arrs.push_back({p, rb, {}});
-    };
-    add(h->dense, (int64_t)h->dim_pad * 4);
-    add(h->dense_h, (int64_t)h->dim_pad * 2);
-    add(h->q8, h->dim_pad8);
-    add(h->q8_rinv, 4);
-    add(h->q8s, h->dim_pad8);
-    add(h->q8s_scale, 4);
-    for (int p = 0; p < h->n_pre; ++p) add(h->pre[p], (int64_t)h->psize[p] * 4);
-    if (h->n_pre > 0) add(h->pre_h0, (int64_t)h->psize[0] * 2);
-    for (auto& c : h->pay)           // the payload columns that cover every row move with the rows; a lagging one is dropped
-      if (c.filled == n) {
-        add(c.p0, 4);
-        add(c.p1, 4);
-      }
-  }
-  int64_t bounce_bytes = 0;
-  for (auto& a : arrs) {
-    const int64_t chunk = h->compact_chunk > 0 ? h->compact_chunk : std::max<int64_t>(COMPACT_BOUNCE_BYTES / a.rb, 1);
-    a.plan = compact_plan(k, first, count, chunk);
-    for (const auto& c : a.plan)
-      if (!c.direct) bounce_bytes = std::max(bounce_bytes, (c.d1 - c.d0) * a.rb);
-  }
-  uint32_t* rows = nullptr;
-  if (count > 0) {
-    const int64_t nw = (n + 31) / 32;
-    uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)nw * 4);
-    HX_HIP(hipMemcpyAsync(dm, keep, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-    uint32_t* count_dev = nullptr;
-    mask_rows_dev(h, dm, rows, count_dev, st);
-  }
-  DevTmp bounce, sp_idx2, sp_val2;
-  if (bounce_bytes > 0) bounce.alloc((size_t)bounce_bytes);
-  // the list columns that cover every row (section 17): the head plane is in `arrs`; offsets and elements go the sparse
-  // CSR's way -- rows [0, first) stay, the kept rows behind them move to lbase + loff[j]
-  struct ListPlan {
-    hx_index::PayCol* c;
-    int64_t lbase = 0, moved = 0;
-    DevTmp lenoff, t0, t1;
-    int64_t* loff = nullptr;
-  };
-  std::vector<std::unique_ptr<ListPlan>> lists;
-  const int64_t lm = count - std::min(first, count);     // kept rows at or behind the first removed one
-  for (auto& c : h->pay) {
-    if (!c.csr() || c.filled != n) continue;
-    auto lp = std::make_unique<ListPlan>();
-    lp->c = &c;
-    HX_HIP(hipMemcpy(&lp->lbase, c.off + std::min(first, count), 8, hipMemcpyDeviceToHost));
-    if (lm > 0) {
-      lp->lenoff.alloc((size_t)(lm + 1) * 8 * 2);
-      int64_t* len = (int64_t*)lp->lenoff.p;
-      lp->loff = len + (lm + 1);
-      HX_HIP(hipMemsetAsync(len + lm, 0, 8, st));
-      launch_csr_keep_len(c.off, rows + first, lm, len, st);
-      exclusive_scan_i64(len, lp->loff, lm, st);
-      HX_HIP(hipMemcpy(&lp->moved, lp->loff + lm, 8, hipMemcpyDeviceToHost));
-      if (lp->moved > 0) {
-        lp->t0.alloc((size_t)lp->moved * 4);
-        if (c.e1) lp->t1.alloc((size_t)lp->moved * 4);
-      }
-    }
-    lists.push_back(std::move(lp));
-  }
-  // CSR: the documents [0, first) stay; kept documents [first, kept_sp) move to the offsets base + off[j]
-  const int64_t m = std::max<int64_t>(kept_sp - first, 0);
-  int64_t base = 0, moved = 0, new_nnz = 0;
-  int64_t* off = nullptr;
-  uint32_t* mm = nullptr;
-  if (sparse && kept_sp > 0) {
-    mm = (uint32_t*)h->ws.get(WS_SP_MM, 16);
-    HX_HIP(hipMemcpy(&base, h->sp_indptr + std::min(first, kept_sp), 8, hipMemcpyDeviceToHost));
-    if (m > 0) {
-      int64_t* len = (int64_t*)h->ws.get(WS_C_LEN, (size_t)(m + 1) * 8 * 2);
-      off = len + (m + 1);
-      HX_HIP(hipMemsetAsync(len + m, 0, 8, st));
-      launch_csr_keep_len(h->sp_indptr, rows + first, m, len, st);
-      exclusive_scan_i64(len, off, m, st);
-      HX_HIP(hipMemcpy(&moved, off + m, 8, hipMemcpyDeviceToHost));
-      if (moved > 0) {
-        sp_idx2.alloc((size_t)moved * 4);
-        sp_val2.alloc((size_t)moved * 4);
-      }
-    }
-    new_nnz = base + moved;
-  }
-
-  // ---- the rows move ----
-  for (const auto& a : arrs) {
-    uint8_t* p = (uint8_t*)a.p;
-    for (const auto& c : a.plan) {
-      const int64_t cnt = c.d1 - c.d0;
-      void* dst = c.direct ? (void*)(p + c.d0 * a.rb) : bounce.p;
-      if (a.rb == 4) launch_compact_u32(p, dst, rows + c.d0, cnt, st);
-      else launch_compact_rows16(p, dst, a.rb, rows + c.d0, cnt, st);
-      if (c.direct) continue;
-      if (a.rb == 4) launch_copy_u32(bounce.p, p + c.d0 * 4, cnt, st);
-      else launch_copy16(bounce.p, p + c.d0 * a.rb, cnt * a.rb, st);
-    }
-  }
-  // (the per-row scales behind the last row are zero in a freshly grown buffer)
-  if (h->q8_rinv) HX_HIP(hipMemsetAsync(h->q8_rinv + count, 0, (size_t)(n - count) * 4, st));
-  if (h->q8s_scale) HX_HIP(hipMemsetAsync(h->q8s_scale + count, 0, (size_t)(n - count) * 4, st));
-  uint32_t got[3] = {0xFFFFFFFFu, 0u, 0u};
-  if (mm && new_nnz > 0) {
-    HX_HIP(hipMemcpyAsync(mm, got, 12, hipMemcpyHostToDevice, st));
-    launch_minmax_f32(h->sp_val, base, (float*)mm, st);           // the documents that stay where they are
-    if (moved > 0) {
-      launch_csr_compact(h->sp_indptr, rows + first, off, m, h->sp_idx, h->sp_val, (int32_t*)sp_idx2.p, (float*)sp_val2.p,
-                         mm, st);
-      // (4-byte words: base need not be a multiple of 4 postings)
-      launch_copy_u32(sp_idx2.p, h->sp_idx + base, moved, st);
-      launch_copy_u32(sp_val2.p, h->sp_val + base, moved, st);
-    }
-    HX_HIP(hipMemcpyAsync(got, mm, 12, hipMemcpyDeviceToHost, st));
-  }
-  if (m > 0) launch_csr_new_indptr(h->sp_indptr + first, off, m, base, st);
-  for (auto& lp : lists) {
-    hx_index::PayCol& c = *lp->c;
-    if (lp->moved > 0) {
-      launch_csr_compact_u32(c.off, rows + first, lp->loff, lm, c.e0, (uint32_t*)lp->t0.p, st);
-      if (c.e1) launch_csr_compact_u32(c.off, rows + first, lp->loff, lm, c.e1, (uint32_t*)lp->t1.p, st);
-      launch_copy_u32(lp->t0.p, c.e0 + lp->lbase, lp->moved, st);
-      if (c.e1) launch_copy_u32(lp->t1.p, c.e1 + lp->lbase, lp->moved, st);
-    }
-    if (lm > 0) launch_csr_new_indptr(c.off + first, lp->loff, lm, lp->lbase, st);
-    c.n_el = lp->lbase + lp->moved;
-  }
-  HX_HIP(hipDeviceSynchronize());
-
-  // ---- the index of the kept rows ----
-  h->n = count;
-  for (size_t i = h->pay.size(); i-- > 0;) {
-    if (h->pay[i].filled == n) {
-      h->pay[i].filled = count;
-      continue;
-    }
-    pay_free(h->pay[i]);
-    h->pay.erase(h->pay.begin() + (long)i);
-  }
-  h->tm_q8.rows = h->tm_q8s.rows = -1;
-  if (sparse) {
-    h->sp_rows = kept_sp;
-    h->nnz = new_nnz;
-    if (new_nnz > 0 && got[0] <= got[1]) {
-      h->sp_wmin = orderable_f32(got[0]);
-      h->sp_wmax = orderable_f32(got[1]);
-      h->sp_have_w = true;
-    } else {
-      h->sp_wmin = h->sp_wmax = 0.f;
-      h->sp_have_w = false;
-    }
-  }
-  free_sparse_index(h);
-  h->sparse_stale = true;
-  auto& b = h->ids;
-  b.row0.clear();
-  b.gid0.clear();
-  if (count > 0) {
-    b.row0.push_back(0u);
-    b.gid0.push_back((uint32_t)h->id_base);
-  }
-  b.end = count > 0 ? h->id_base + count : -1;
-  b.next = -1;
-  b.dirty = true;
-}
-
-}  // namespace hx
-
-int hx_retain_rows(hx_index* h, const uint32_t* keep_host, int64_t mask_rows, int64_t* n_removed) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  HX_CHECK(mask_rows >= 0, "hx_retain_rows: mask_rows < 0");
-  HX_CHECK(keep_host || mask_rows == 0, "hx_retain_rows: mask is NULL");
-  HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  HX_CHECK(ids_identity(h) && h->ids.next < 0,
-           "hx_retain_rows: the ids of this index were named with hx_set_next_id (a shard of a sharded collection): "
-           "renumbering them is not supported");
-  if (mask_rows == 0) {
-    if (n_removed) *n_removed = 0;
-    return 0;
-  }
-  retain_rows(h, keep_host, n_removed);
-  HX_CATCH
-}
-
-// ---- upsert by an existing id ---------------------------------------------------------------
-namespace hx {
-
-// the rows of a replace call -- in [0, limit), unique -- as the uint32 list the kernels read
-static std::vector<uint32_t> replace_rows_checked(const int64_t* rows_host, int64_t m, int64_t limit, const char* who) {
-  std::vector<uint32_t> r((size_t)m);
-  for (int64_t i = 0; i < m; ++i) {
-    HX_CHECK(rows_host[i] >= 0 && rows_host[i] < limit, std::string(who) + ": a row lies outside [0, count)");
-    r[(size_t)i] = (uint32_t)rows_host[i];
-  }
-  std::vector<uint32_t> s(r);
-  std::sort(s.begin(), s.end());
-  HX_CHECK(std::adjacent_find(s.begin(), s.end()) == s.end(), std::string(who) + ": the rows must be unique");
-  return r;
-}
-
-// The splice of a CSR whose documents [f, total) take new lengths (replace.hip): the map document -> batch position,
-// the new lengths and their exclusive prefix.  base = the offset of document f (it stays), moved = the postings from f
-// on after the call.  Synchronises `st`.
-struct SplicePlan {
-  int64_t f = 0, docs = 0, base = 0, moved = 0;
-  DevTmp map_, lenoff;
-  const uint32_t* map() const { return (const uint32_t*)map_.p; }
-  const int64_t* off() const { return (const int64_t*)lenoff.p + (docs + 1); }
-};
-static void splice_plan(SplicePlan& s, const int64_t* indptr, int64_t total, int64_t f, const uint32_t* rows_dev, int64_t m,
-                        const int64_t* new_indptr_dev, hipStream_t st) {
-  s.f = f;
-  s.docs = total - f;
-  s.map_.alloc((size_t)s.docs * 4);
-  HX_HIP(hipMemsetAsync(s.map_.p, 0xFF, (size_t)s.docs * 4, st));
-  launch_splice_map(rows_dev, m, f, s.docs, (uint32_t*)s.map_.p, st);
-  s.lenoff.alloc((size_t)(s.docs + 1) * 8 * 2);
-  int64_t* len = (int64_t*)s.lenoff.p;
-  int64_t* off = len + (s.docs + 1);
-  HX_HIP(hipMemsetAsync(len + s.docs, 0, 8, st));
-  launch_csr_splice_len(indptr + f, s.map(), new_indptr_dev, s.docs, len, st);
-  exclusive_scan_i64(len, off, s.docs, st);
-  HX_HIP(hipStreamSynchronize(st));
-  HX_HIP(hipMemcpy(&s.base, indptr + f, 8, hipMemcpyDeviceToHost));
-  HX_HIP(hipMemcpy(&s.moved, off + s.docs, 8, hipMemcpyDeviceToHost));
-}
-
-static void replace_rows(hx_index* h, const int64_t* rows_host, int64_t m, const float* dense_host, const int64_t* indptr,
-                         const int32_t* idx, const float* val) {
-  const int64_t n = h->n;
-  HX_CHECK(ids_identity(h) && h->ids.next < 0,
-           "hx_replace_rows: the ids of this index were named with hx_set_next_id (a shard of a sharded collection): "
-           "replacing its rows is not supported");
-  HX_CHECK(h->sp_rows <= n, "hx_replace_rows: sparse vectors are pending for rows not added yet");
-  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, n, "hx_replace_rows");
-  int64_t nnz_new = 0;
-  if (indptr) {
-    HX_CHECK(indptr[0] == 0, "indptr[0] must be 0");
-    nnz_new = indptr[m];
-    HX_CHECK(nnz_new >= 0, "negative nnz");
-    HX_CHECK(nnz_new == 0 || (idx && val), "idx/val is NULL");
-    for (int64_t r = 0; r < m; ++r) HX_CHECK(indptr[r + 1] >= indptr[r] && indptr[r + 1] <= nnz_new, "indptr not monotone");
-  }
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  hipStream_t st = nullptr;
-  DevTmp rows_dev_;
-  rows_dev_.alloc((size_t)m * 4);
-  HX_HIP(hipMemcpy(rows_dev_.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-  const uint32_t* rows_dev = (const uint32_t*)rows_dev_.p;
-
-  // ---- the sparse batch: uploaded beside the index and checked there, as hx_add_sparse checks its batch ----
-  DevTmp nip, nidx, nval;
-  if (indptr) {
-    nip.alloc((size_t)(m + 1) * 8);
-    nidx.alloc((size_t)nnz_new * 4);
-    nval.alloc((size_t)nnz_new * 4);
-    HX_HIP(hipMemcpy(nip.p, indptr, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz_new) {
-      HX_HIP(hipMemcpy(nidx.p, idx, (size_t)nnz_new * 4, hipMemcpyHostToDevice));
-      HX_HIP(hipMemcpy(nval.p, val, (size_t)nnz_new * 4, hipMemcpyHostToDevice));
-      float lo = 0.f, hi = 0.f;
-      check_sparse_batch_dev(h, (const int64_t*)nip.p, (const int32_t*)nidx.p, (const float*)nval.p, m, 0, nnz_new, indptr, idx,
-                             &lo, &hi);
-    }
-  }
-
-  // ---- the dense rows: derived in a staging block laid out as the stored arrays are (k_prep_rows as the add path
-  // launches it), the batch's non-finite word read before anything stored changes ----
-  const bool c8 = h->cand8 && h->q8s && h->q8s_scale && h->s8_err;
-  HX_CHECK(!h->cand8 || c8, "int8 candidate copy enabled but not allocated");
-  struct Arr {
-    void* dst;
-    int64_t rb;                        // row bytes; 4 = one scale per row
-    DevTmp stage;
-  };
-  Arr arrs[10];
-  int na = 0;
-  auto add = [&](void* dst, int64_t rb) {
-    arrs[na].dst = dst;
-    arrs[na].rb = rb;
-    arrs[na].stage.alloc((size_t)(m * rb));
-    return arrs[na++].stage.p;
-  };
-  PrepRowsArgs a{};
-  a.dim = h->dim;
-  a.dim_pad = h->dim_pad;
-  a.dim_pad8 = h->dim_pad8;
-  a.dense = (float*)add(h->dense, (int64_t)h->dim_pad * 4);
-  a.dense_h = (_Float16*)add(h->dense_h, (int64_t)h->dim_pad * 2);
-  a.q8 = (int8_t*)add(h->q8, h->dim_pad8);
-  a.q8_rinv = (float*)add(h->q8_rinv, 4);
-  a.n_prefix = h->n_pre;
-  for (int p = 0; p < h->n_pre; ++p) {
-    a.psize[p] = h->psize[p];
-    a.pre[p] = (float*)add(h->pre[p], (int64_t)h->psize[p] * 4);
-  }
-  a.pre_h0 = h->n_pre > 0 ? (_Float16*)add(h->pre_h0, (int64_t)h->psize[0] * 2) : nullptr;
-  a.q8s = c8 ? (int8_t*)add(h->q8s, h->dim_pad8) : nullptr;
-  a.q8s_scale = c8 ? (float*)add(h->q8s_scale, 4) : nullptr;
-  a.err_max = c8 ? h->s8_err : nullptr;
-  const int64_t CH = 65536;
-  float* raw = (float*)h->ws.get(WS_RAW, (size_t)std::min(m, CH) * h->dim * 4);
-  int* chk = rows_check_begin(h, st);
-  a.nonfinite = chk;
-  for (int64_t r0 = 0; r0 < m; r0 += CH) {
-    const int64_t k = std::min(CH, m - r0);
-    HX_HIP(hipMemcpy(raw, dense_host + r0 * h->dim, (size_t)k * h->dim * 4, hipMemcpyHostToDevice));
-    PrepRowsArgs c = a;
-    c.raw = raw;
-    c.n = k;
-    c.dense += r0 * h->dim_pad;
-    c.dense_h += r0 * h->dim_pad;
-    c.q8 += r0 * h->dim_pad8;
-    c.q8_rinv += r0;
-    for (int p = 0; p < h->n_pre; ++p) c.pre[p] += r0 * h->psize[p];
-    if (c.pre_h0) c.pre_h0 += r0 * h->psize[0];
-    if (c8) {
-      c.q8s += r0 * h->dim_pad8;
-      c.q8s_scale += r0;
-    }
-    launch_prep_rows(c, st);
-    if (r0 + k >= m) rows_check_fetch(h, chk, st);
-    HX_HIP(hipStreamSynchronize(st));
-  }
-  rows_check_end(h, chk, st);
-
-  // ---- the CSR's plan: offsets, spare buffers, capacity ----
-  SplicePlan sp;
-  DevTmp idx2, val2;
-  int64_t new_nnz = h->nnz;
-  uint32_t* mm = nullptr;
-  if (indptr) {
-    const int64_t rmin = *std::min_element(rows.begin(), rows.end()), rmax = *std::max_element(rows.begin(), rows.end());
-    if (rmax >= h->sp_rows) {          // trailing rows that never got a sparse vector: empty documents, as finalize pads them
-      reserve_sparse(h, n, h->nnz);
-      std::vector<int64_t> tail((size_t)(n - h->sp_rows), h->nnz);
-      if (h->sp_rows == 0) {
-        const int64_t zero = 0;
-        HX_HIP(hipMemcpy(h->sp_indptr, &zero, 8, hipMemcpyHostToDevice));
-      }
-      HX_HIP(hipMemcpy(h->sp_indptr + h->sp_rows + 1, tail.data(), tail.size() * 8, hipMemcpyHostToDevice));
-      h->sp_rows = n;
-      h->sparse_stale = true;
-    }
-    splice_plan(sp, h->sp_indptr, h->sp_rows, rmin, rows_dev, m, (const int64_t*)nip.p, st);
-    new_nnz = sp.base + sp.moved;
-    HX_CHECK(new_nnz < 0xFFFFFFFFll, "nnz per shard must stay below 2^32");
-    if (sp.moved > 0) {
-      idx2.alloc((size_t)sp.moved * 4);
-      val2.alloc((size_t)sp.moved * 4);
-    }
-    reserve_sparse(h, h->sp_rows, new_nnz);
-    mm = (uint32_t*)h->ws.get(WS_SP_MM, 16);
-  }
-
-  // ---- the stored arrays change ----
-  for (int i = 0; i < na; ++i) {
-    if (arrs[i].rb == 4) launch_scatter_u32(arrs[i].stage.p, arrs[i].dst, rows_dev, m, st);
-    else launch_scatter_rows16(arrs[i].stage.p, arrs[i].dst, arrs[i].rb, rows_dev, m, st);
-  }
-  uint32_t got[3] = {0xFFFFFFFFu, 0u, 0u};
-  if (indptr) {
-    if (new_nnz > 0) {
-      HX_HIP(hipMemcpyAsync(mm, got, 12, hipMemcpyHostToDevice, st));
-      launch_minmax_f32(h->sp_val, sp.base, (float*)mm, st);        // the documents in front of the first replaced one
-      if (sp.moved > 0) {
-        launch_csr_splice(h->sp_indptr + sp.f, sp.map(), (const int64_t*)nip.p, sp.off(), sp.docs, h->sp_idx, h->sp_val,
-                          (const int32_t*)nidx.p, (const float*)nval.p, (int32_t*)idx2.p, (float*)val2.p, mm, st);
-        launch_copy_u32(idx2.p, h->sp_idx + sp.base, sp.moved, st);
-        launch_copy_u32(val2.p, h->sp_val + sp.base, sp.moved, st);
-      }
-      HX_HIP(hipMemcpyAsync(got, mm, 12, hipMemcpyDeviceToHost, st));
-    }
-    launch_csr_new_indptr(h->sp_indptr + sp.f, sp.off(), sp.docs, sp.base, st);
-  }
-  HX_HIP(hipDeviceSynchronize());
-
-  // ---- what was derived from the old rows ----
-  h->tm_q8.rows = h->tm_q8s.rows = -1;
-  h->mv.have = 0;                      // the gathered copies of the mask view: a masked query reads the new rows
-  h->mv.tm_q8.rows = h->mv.tm_q8s.rows = -1;
-  if (indptr) {
-    h->nnz = new_nnz;
-    if (new_nnz > 0 && got[0] <= got[1]) {
-      h->sp_wmin = orderable_f32(got[0]);
-      h->sp_wmax = orderable_f32(got[1]);
-      h->sp_have_w = true;
-    } else {
-      h->sp_wmin = h->sp_wmax = 0.f;
-      h->sp_have_w = false;
-    }
-    free_sparse_index(h);
-    h->sparse_stale = true;
-  }
-}
-
-}  // namespace hx
-
-int hx_replace_rows(hx_index* h, const int64_t* rows_host, int64_t m, const float* dense_host, const int64_t* indptr_host,
-                    const int32_t* idx_host, const float* val_host) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  HX_CHECK(m >= 0, "hx_replace_rows: m < 0");
-  HX_CHECK(m == 0 || (rows_host && dense_host), "hx_replace_rows: rows / dense is NULL");
-  if (m == 0) return 0;
-  replace_rows(h, rows_host, m, dense_host, indptr_host, idx_host, val_host);
   HX_CATCH
 }
 
@@ -3402,13 +2647,10 @@ int hx_hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const 
 static const uint32_t* group_plane(hx_index* h, int32_t col, int32_t n_groups, int32_t group_size) {
   HX_CHECK(n_groups >= 1 && group_size >= 1 && (int64_t)n_groups * group_size <= MAX_LIMIT,
            "group: n_groups and group_size must be at least 1 and n_groups * group_size at most 2048");
-  const hx_index::PayCol* c = nullptr;
-  for (const auto& x : h->pay)
-    if (x.id == col) c = &x;
-  if (!c) throw Error("payload: unknown column " + std::to_string(col));
-  HX_CHECK(c->kind == HX_PAY_U32, "group: the column kind must be HX_PAY_U32 (keyword codes or bools)");
-  HX_CHECK(c->filled == h->n, "group: the column is not filled to the index's row count (hx_count)");
-  return c->p0;
+  const hx_index::PayCol& c = pay_col(h, col);
+  HX_CHECK(c.kind == HX_PAY_U32, "group: the column kind must be HX_PAY_U32 (keyword codes or bools)");
+  HX_CHECK(c.filled == h->n, "group: the column is not filled to the index's row count (hx_count)");
+  return c.p0;
 }
 static void group_enqueue(hx_index* h, const uint32_t* p0, const uint64_t* keys, const uint64_t* ikeys, int stride,
                           const int* counts, int B, int n_groups, int group_size, uint64_t* out, uint32_t* codes,
@@ -3719,690 +2961,6 @@ int hx_release_mask_view(hx_index* h) {
   HX_CATCH
 }
 
-// ---- payload index ---------------------------------------------------------------------------
-static hx_index::PayCol& pay_col(hx_index* h, int32_t col) {
-  for (auto& c : h->pay)
-    if (c.id == col) return c;
-  throw Error("payload: unknown column " + std::to_string(col));
-}
-
-int hx_payload_create(hx_index* h, int32_t kind, int32_t* col) {
-  HX_TRY
-  HX_CHECK(h && col, "NULL argument");
-  HX_CHECK(kind == HX_PAY_U32 || kind == HX_PAY_F64 || kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64 ||
-               kind == HX_PAY_TEXT,
-           "payload: kind must be HX_PAY_U32, HX_PAY_F64, HX_PAY_LIST_U32, HX_PAY_LIST_F64 or HX_PAY_TEXT");
-  HX_CHECK((int)h->pay.size() < HX_PAY_MAX_COLUMNS, "payload: an index holds at most 64 columns");
-  hx_index::PayCol c;
-  c.id = h->pay_next_id++;
-  c.kind = kind;
-  h->pay.push_back(c);
-  *col = c.id;
-  HX_CATCH
-}
-
-int hx_payload_drop(hx_index* h, int32_t col) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  pay_free(c);
-  h->pay.erase(h->pay.begin() + (&c - h->pay.data()));
-  HX_CATCH
-}
-
-int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled) {
-  HX_TRY
-  HX_CHECK(h && filled, "NULL argument");
-  *filled = pay_col(h, col).filled;
-  HX_CATCH
-}
-
-int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t n) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(n >= 0, "payload: n < 0");
-  HX_CHECK(cells_host || n == 0, "payload: cells are NULL");
-  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_append_lists (column kind)");
-  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_append_text (column kind)");
-  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
-  if (n == 0) return 0;
-  h->set_device();
-  const bool f64 = c.kind == HX_PAY_F64;
-  const int64_t want = c.filled + n;
-  if (want > c.cap) {                  // (everything that can fail comes before the column changes)
-    const int64_t nc = round_up(std::max<int64_t>(std::max(want, c.cap * 2), h->cap), 256);
-    HX_HIP(hipDeviceSynchronize());
-    uint32_t *a = nullptr, *b = nullptr;
-    HX_HIP(hipMalloc((void**)&a, (size_t)nc * 4));
-    if (f64 && hipMalloc((void**)&b, (size_t)nc * 4) != hipSuccess) {
-      (void)hipFree(a);
-      throw Error("payload: out of device memory");
-    }
-    if (c.filled > 0) {
-      HX_HIP(hipMemcpy(a, c.p0, (size_t)c.filled * 4, hipMemcpyDeviceToDevice));
-      if (f64) HX_HIP(hipMemcpy(b, c.p1, (size_t)c.filled * 4, hipMemcpyDeviceToDevice));
-    }
-    if (c.p0) (void)hipFree(c.p0);
-    if (c.p1) (void)hipFree(c.p1);
-    c.p0 = a;
-    c.p1 = b;
-    c.cap = nc;
-  }
-  if (!f64) {
-    HX_HIP(hipMemcpy(c.p0 + c.filled, cells_host, (size_t)n * 4, hipMemcpyHostToDevice));
-  } else {
-    const uint64_t* v = (const uint64_t*)cells_host;
-    std::vector<uint32_t> lo((size_t)n), hi((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-      lo[(size_t)i] = (uint32_t)v[i];
-      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
-    }
-    HX_HIP(hipMemcpy(c.p0 + c.filled, lo.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-    HX_HIP(hipMemcpy(c.p1 + c.filled, hi.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  }
-  c.filled = want;
-  HX_CATCH
-}
-
-// grow a device array to `want` entries keeping the first `keep` (the new one is made before the old one goes)
-extern "C++" template <typename T>
-static T* pay_grown(const T* old, int64_t keep, int64_t want) {
-  T* a = nullptr;
-  if (hipMalloc((void**)&a, (size_t)want * sizeof(T)) != hipSuccess) throw Error("payload: out of device memory");
-  if (keep > 0 && hipMemcpy(a, old, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
-    (void)hipFree(a);
-    throw Error("payload: device copy failed");
-  }
-  return a;
-}
-
-// Store the checked cells of rows [filled, filled + n) of a list or text column: heads[n] as the head plane keeps them,
-// off[n + 1] = the rows' offsets (off[0] = n_el), e0_host / e1_host = `total` new words per element plane (e1_host: the
-// high words of a HX_PAY_LIST_F64 column, NULL otherwise).  Every allocation comes before the column changes.
-static void pay_store_csr(hx_index* h, hx_index::PayCol& c, const uint32_t* heads, const int64_t* off, int64_t n,
-                          const void* e0_host, const void* e1_host, int64_t total) {
-  const bool f64 = c.kind == HX_PAY_LIST_F64;
-  if (n == 0) return;
-  h->set_device();
-  const int64_t want = c.filled + n, want_el = c.n_el + total;
-  uint32_t *np0 = nullptr, *ne0 = nullptr, *ne1 = nullptr;
-  int64_t* noff = nullptr;
-  int64_t nc = c.cap, nec = c.el_cap;
-  try {
-    if (want > c.cap || !c.off) {
-      nc = round_up(std::max<int64_t>(std::max(want, c.cap * 2), h->cap), 256);
-      HX_HIP(hipDeviceSynchronize());
-      np0 = pay_grown(c.p0, c.filled, nc);
-      noff = pay_grown(c.off, c.off ? c.filled + 1 : 0, nc + 1);
-    }
-    if (want_el > c.el_cap) {
-      nec = round_up(std::max<int64_t>(want_el, c.el_cap * 2), 256);
-      HX_HIP(hipDeviceSynchronize());
-      ne0 = pay_grown(c.e0, c.n_el, nec);
-      if (f64) ne1 = pay_grown(c.e1, c.n_el, nec);
-    }
-  } catch (...) {
-    for (void* q : {(void*)np0, (void*)noff, (void*)ne0, (void*)ne1})
-      if (q) (void)hipFree(q);
-    throw;
-  }
-  if (np0) {
-    if (c.p0) (void)hipFree(c.p0);
-    if (c.off) (void)hipFree(c.off);
-    c.p0 = np0;
-    c.off = noff;
-    c.cap = nc;
-  }
-  if (ne0) {
-    if (c.e0) (void)hipFree(c.e0);
-    if (c.e1) (void)hipFree(c.e1);
-    c.e0 = ne0;
-    c.e1 = ne1;
-    c.el_cap = nec;
-  }
-  // (the cells behind `filled` and the elements behind n_el are dead until `filled` moves: a failed copy changes nothing)
-  HX_HIP(hipMemcpy(c.p0 + c.filled, heads, (size_t)n * 4, hipMemcpyHostToDevice));
-  HX_HIP(hipMemcpy(c.off + c.filled, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
-  if (total > 0) {
-    HX_HIP(hipMemcpy(c.e0 + c.n_el, e0_host, (size_t)total * 4, hipMemcpyHostToDevice));
-    if (f64) HX_HIP(hipMemcpy(c.e1 + c.n_el, e1_host, (size_t)total * 4, hipMemcpyHostToDevice));
-  }
-  c.filled = want;
-  c.n_el = want_el;
-}
-
-int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* values_host,
-                            int64_t n_values) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.list(), "payload: hx_payload_append_lists needs a list column (column kind)");
-  HX_CHECK(n >= 0 && n_values >= 0, "payload: n < 0");
-  HX_CHECK((heads_host || n == 0) && (values_host || n_values == 0), "payload: cells are NULL");
-  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
-  const bool f64 = c.kind == HX_PAY_LIST_F64;
-  // ---- every refusal and every allocation before the column changes ----
-  std::vector<uint32_t> heads((size_t)n);
-  std::vector<int64_t> off((size_t)n + 1);
-  int64_t total = 0;
-  off[0] = c.n_el;
-  for (int64_t i = 0; i < n; ++i) {
-    const uint32_t hd = heads_host[i];
-    const bool is_list = hd < HX_PAY_U32_NULL;
-    heads[(size_t)i] = is_list ? 0u : hd;
-    if (is_list) total += hd;
-    HX_CHECK(total <= n_values, "payload: the element counts of the heads do not sum to n_values");
-    off[(size_t)i + 1] = c.n_el + total;
-  }
-  HX_CHECK(total == n_values, "payload: the element counts of the heads do not sum to n_values");
-  HX_CHECK(c.n_el + total <= 0x7FFFFFFFll, "payload: a list column holds fewer than 2^31 elements");
-  std::vector<uint32_t> lo, hi;
-  if (f64) {
-    const uint64_t* v = (const uint64_t*)values_host;
-    const double* d = (const double*)values_host;
-    lo.resize((size_t)total);
-    hi.resize((size_t)total);
-    for (int64_t i = 0; i < total; ++i) {
-      HX_CHECK(d[i] == d[i], "payload: a list element is a NaN");
-      lo[(size_t)i] = (uint32_t)v[i];
-      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
-    }
-  } else {
-    const uint32_t* v = (const uint32_t*)values_host;
-    for (int64_t i = 0; i < total; ++i) HX_CHECK(v[i] < HX_PAY_U32_NULL, "payload: a list element is a reserved code");
-  }
-  pay_store_csr(h, c, heads.data(), off.data(), n, f64 ? (const void*)lo.data() : values_host, f64 ? hi.data() : nullptr, total);
-  HX_CATCH
-}
-
-// ---- the cells of rows that stay where they are (upsert by an existing id) --------------------
-int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const void* cells_host) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(m >= 0, "payload: m < 0");
-  HX_CHECK(m == 0 || (rows_host && cells_host), "payload: rows / cells are NULL");
-  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_replace_lists (column kind)");
-  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_replace_text (column kind)");
-  if (m == 0) return 0;
-  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, "hx_payload_replace");
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  const bool f64 = c.kind == HX_PAY_F64;
-  DevTmp rows_dev, lo_dev, hi_dev;
-  rows_dev.alloc((size_t)m * 4);
-  lo_dev.alloc((size_t)m * 4);
-  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-  if (!f64) {
-    HX_HIP(hipMemcpy(lo_dev.p, cells_host, (size_t)m * 4, hipMemcpyHostToDevice));
-  } else {
-    const uint64_t* v = (const uint64_t*)cells_host;
-    std::vector<uint32_t> lo((size_t)m), hi((size_t)m);
-    for (int64_t i = 0; i < m; ++i) {
-      lo[(size_t)i] = (uint32_t)v[i];
-      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
-    }
-    hi_dev.alloc((size_t)m * 4);
-    HX_HIP(hipMemcpy(lo_dev.p, lo.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-    HX_HIP(hipMemcpy(hi_dev.p, hi.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-  }
-  launch_scatter_u32(lo_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, nullptr);
-  if (f64) launch_scatter_u32(hi_dev.p, c.p1, (const uint32_t*)rows_dev.p, m, nullptr);
-  HX_HIP(hipDeviceSynchronize());
-  HX_CATCH
-}
-
-// Replace the checked cells of m stored rows of a list or text column: heads[m] as the head plane keeps them, noff[m + 1] =
-// the new rows' offsets from 0, e0_host / e1_host = their `total` words per element plane.  The heads are scattered; offsets
-// and elements are spliced from the first replaced row on.  Every refusal and allocation comes before the column changes.
-static void pay_splice_csr(hx_index* h, hx_index::PayCol& c, const int64_t* rows_host, int64_t m, const uint32_t* heads,
-                           const int64_t* noff, const void* e0_host, const void* e1_host, int64_t total, const char* who) {
-  const bool f64 = c.kind == HX_PAY_LIST_F64;
-  if (m == 0) return;
-  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, who);
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  hipStream_t st = nullptr;
-  DevTmp rows_dev, heads_dev, noff_dev, n0, n1, t0, t1;
-  rows_dev.alloc((size_t)m * 4);
-  heads_dev.alloc((size_t)m * 4);
-  noff_dev.alloc((size_t)(m + 1) * 8);
-  n0.alloc((size_t)total * 4);
-  if (f64) n1.alloc((size_t)total * 4);
-  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
-  HX_HIP(hipMemcpy(heads_dev.p, heads, (size_t)m * 4, hipMemcpyHostToDevice));
-  HX_HIP(hipMemcpy(noff_dev.p, noff, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
-  if (total > 0) {
-    HX_HIP(hipMemcpy(n0.p, e0_host, (size_t)total * 4, hipMemcpyHostToDevice));
-    if (f64) HX_HIP(hipMemcpy(n1.p, e1_host, (size_t)total * 4, hipMemcpyHostToDevice));
-  }
-  // rows in front of the first replaced one keep their elements and offsets; the rest go the sparse CSR's way
-  SplicePlan sp;
-  splice_plan(sp, c.off, c.filled, *std::min_element(rows.begin(), rows.end()), (const uint32_t*)rows_dev.p, m,
-              (const int64_t*)noff_dev.p, st);
-  const int64_t want_el = sp.base + sp.moved;
-  HX_CHECK(want_el <= 0x7FFFFFFFll, c.text() ? "payload: a text column holds fewer than 2^31 words" : "payload: a list column holds fewer than 2^31 elements");
-  if (sp.moved > 0) {
-    t0.alloc((size_t)sp.moved * 4);
-    if (f64) t1.alloc((size_t)sp.moved * 4);
-  }
-  if (want_el > c.el_cap) {
-    const int64_t nec = round_up(std::max<int64_t>(want_el, c.el_cap * 2), 256);
-    uint32_t* ne0 = pay_grown(c.e0, c.n_el, nec);
-    uint32_t* ne1 = nullptr;
-    if (f64) {
-      try {
-        ne1 = pay_grown(c.e1, c.n_el, nec);
-      } catch (...) {
-        (void)hipFree(ne0);
-        throw;
-      }
-    }
-    if (c.e0) (void)hipFree(c.e0);
-    if (c.e1) (void)hipFree(c.e1);
-    c.e0 = ne0;
-    c.e1 = ne1;
-    c.el_cap = nec;
-  }
-  // ---- the column changes ----
-  launch_scatter_u32(heads_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, st);
-  if (sp.moved > 0) {
-    launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e0, (const uint32_t*)n0.p,
-                          (uint32_t*)t0.p, st);
-    if (f64)
-      launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e1,
-                            (const uint32_t*)n1.p, (uint32_t*)t1.p, st);
-    launch_copy_u32(t0.p, c.e0 + sp.base, sp.moved, st);
-    if (f64) launch_copy_u32(t1.p, c.e1 + sp.base, sp.moved, st);
-  }
-  launch_csr_new_indptr(c.off + sp.f, sp.off(), sp.docs, sp.base, st);
-  HX_HIP(hipDeviceSynchronize());
-  c.n_el = want_el;
-}
-
-int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
-                             const void* values_host, int64_t n_values) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.list(), "payload: hx_payload_replace_lists needs a list column (column kind)");
-  HX_CHECK(m >= 0 && n_values >= 0, "payload: m < 0");
-  HX_CHECK((m == 0 || (rows_host && heads_host)) && (values_host || n_values == 0), "payload: rows / cells are NULL");
-  const bool f64 = c.kind == HX_PAY_LIST_F64;
-  // ---- every refusal and every allocation before the column changes ----
-  std::vector<uint32_t> heads((size_t)m);
-  std::vector<int64_t> noff((size_t)m + 1);
-  int64_t total = 0;
-  noff[0] = 0;
-  for (int64_t i = 0; i < m; ++i) {
-    const uint32_t hd = heads_host[i];
-    const bool is_list = hd < HX_PAY_U32_NULL;
-    heads[(size_t)i] = is_list ? 0u : hd;
-    if (is_list) total += hd;
-    HX_CHECK(total <= n_values, "payload: the element counts of the heads do not sum to n_values");
-    noff[(size_t)i + 1] = total;
-  }
-  HX_CHECK(total == n_values, "payload: the element counts of the heads do not sum to n_values");
-  std::vector<uint32_t> lo, hi;
-  if (f64) {
-    const uint64_t* v = (const uint64_t*)values_host;
-    const double* d = (const double*)values_host;
-    lo.resize((size_t)total);
-    hi.resize((size_t)total);
-    for (int64_t i = 0; i < total; ++i) {
-      HX_CHECK(d[i] == d[i], "payload: a list element is a NaN");
-      lo[(size_t)i] = (uint32_t)v[i];
-      hi[(size_t)i] = (uint32_t)(v[i] >> 32);
-    }
-  } else {
-    const uint32_t* v = (const uint32_t*)values_host;
-    for (int64_t i = 0; i < total; ++i) HX_CHECK(v[i] < HX_PAY_U32_NULL, "payload: a list element is a reserved code");
-  }
-  pay_splice_csr(h, c, rows_host, m, heads.data(), noff.data(), f64 ? (const void*)lo.data() : values_host,
-                 f64 ? hi.data() : nullptr, total, "hx_payload_replace_lists");
-  HX_CATCH
-}
-
-int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,
-                          int64_t* count) {
-  HX_TRY
-  HX_CHECK(h && head && count, "NULL argument");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.list(), "payload: hx_payload_debug_list needs a list column (column kind)");
-  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
-  HX_CHECK(cap >= 0 && (values_out || cap == 0), "payload: bad output buffer");
-  h->set_device();
-  uint32_t hd = 0;
-  int64_t o[2] = {0, 0};
-  HX_HIP(hipMemcpy(&hd, c.p0 + row, 4, hipMemcpyDeviceToHost));
-  HX_HIP(hipMemcpy(o, c.off + row, 16, hipMemcpyDeviceToHost));
-  const int64_t len = o[1] - o[0];
-  HX_CHECK(len >= 0 && o[0] >= 0 && o[1] <= c.n_el, "payload: corrupt list offsets");
-  *count = len;
-  *head = hd >= HX_PAY_U32_NULL ? hd : (uint32_t)len;
-  const int64_t k = std::min(len, cap);
-  if (k <= 0) return 0;
-  if (c.kind == HX_PAY_LIST_U32) {
-    HX_HIP(hipMemcpy(values_out, c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<uint32_t> lo((size_t)k), hi((size_t)k);
-    HX_HIP(hipMemcpy(lo.data(), c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
-    HX_HIP(hipMemcpy(hi.data(), c.e1 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
-    uint64_t* out = (uint64_t*)values_out;
-    for (int64_t i = 0; i < k; ++i) out[i] = ((uint64_t)hi[(size_t)i] << 32) | lo[(size_t)i];
-  }
-  HX_CATCH
-}
-
-// ---- text columns (HX_PAY_TEXT) ----------------------------------------------------------------
-// The checked cells of n text rows as the column stores them: off[n + 1] = the rows' offsets in 32-bit words from `base`,
-// words = the rows' bytes one after another, each row padded with zero bytes to a word.  Refuses lengths that do not sum
-// to n_bytes.
-static void pay_text_pack(const uint32_t* heads_host, int64_t n, const void* bytes_host, int64_t n_bytes, int64_t base,
-                          std::vector<int64_t>& off, std::vector<uint32_t>& words) {
-  off.resize((size_t)n + 1);
-  off[0] = base;
-  int64_t total = 0, n_words = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    const uint32_t hd = heads_host[i];
-    if (hd < HX_PAY_U32_NULL) {
-      total += hd;
-      n_words += ((int64_t)hd + 3) / 4;
-    }
-    HX_CHECK(total <= n_bytes, "payload: the byte lengths of the heads do not sum to n_bytes");
-    off[(size_t)i + 1] = base + n_words;
-  }
-  HX_CHECK(total == n_bytes, "payload: the byte lengths of the heads do not sum to n_bytes");
-  words.assign((size_t)n_words, 0u);
-  const uint8_t* src = (const uint8_t*)bytes_host;
-  for (int64_t i = 0; i < n; ++i) {
-    const uint32_t hd = heads_host[i];
-    if (hd >= HX_PAY_U32_NULL || hd == 0u) continue;
-    std::memcpy((uint8_t*)words.data() + (size_t)(off[(size_t)i] - base) * 4, src, hd);
-    src += hd;
-  }
-}
-
-int hx_payload_append_text(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* bytes_host,
-                           int64_t n_bytes) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.text(), "payload: hx_payload_append_text needs a text column (column kind)");
-  HX_CHECK(n >= 0 && n_bytes >= 0, "payload: n < 0");
-  HX_CHECK((heads_host || n == 0) && (bytes_host || n_bytes == 0), "payload: cells are NULL");
-  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
-  // ---- every refusal and every allocation before the column changes ----
-  std::vector<int64_t> off;
-  std::vector<uint32_t> words;
-  pay_text_pack(heads_host, n, bytes_host, n_bytes, c.n_el, off, words);
-  HX_CHECK(c.n_el + (int64_t)words.size() <= 0x7FFFFFFFll, "payload: a text column holds fewer than 2^31 words");
-  pay_store_csr(h, c, heads_host, off.data(), n, words.data(), nullptr, (int64_t)words.size());
-  HX_CATCH
-}
-
-int hx_payload_replace_text(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
-                            const void* bytes_host, int64_t n_bytes) {
-  HX_TRY
-  HX_CHECK(h, "index is NULL");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.text(), "payload: hx_payload_replace_text needs a text column (column kind)");
-  HX_CHECK(m >= 0 && n_bytes >= 0, "payload: m < 0");
-  HX_CHECK((m == 0 || (rows_host && heads_host)) && (bytes_host || n_bytes == 0), "payload: rows / cells are NULL");
-  std::vector<int64_t> noff;
-  std::vector<uint32_t> words;
-  pay_text_pack(heads_host, m, bytes_host, n_bytes, 0, noff, words);
-  pay_splice_csr(h, c, rows_host, m, heads_host, noff.data(), words.data(), nullptr, (int64_t)words.size(),
-                 "hx_payload_replace_text");
-  HX_CATCH
-}
-
-int hx_payload_debug_text(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* bytes_out, int64_t cap,
-                          int64_t* count) {
-  HX_TRY
-  HX_CHECK(h && head && count, "NULL argument");
-  auto& c = pay_col(h, col);
-  HX_CHECK(c.text(), "payload: hx_payload_debug_text needs a text column (column kind)");
-  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
-  HX_CHECK(cap >= 0 && (bytes_out || cap == 0), "payload: bad output buffer");
-  h->set_device();
-  uint32_t hd = 0;
-  int64_t o[2] = {0, 0};
-  HX_HIP(hipMemcpy(&hd, c.p0 + row, 4, hipMemcpyDeviceToHost));
-  HX_HIP(hipMemcpy(o, c.off + row, 16, hipMemcpyDeviceToHost));
-  const int64_t len = hd < HX_PAY_U32_NULL ? (int64_t)hd : 0;
-  HX_CHECK(o[0] >= 0 && o[1] <= c.n_el && o[1] - o[0] == (len + 3) / 4, "payload: corrupt text offsets");
-  *head = hd;
-  *count = len;
-  const int64_t k = std::min(len, cap);
-  if (k <= 0) return 0;
-  std::vector<uint32_t> words((size_t)(k + 3) / 4);
-  HX_HIP(hipMemcpy(words.data(), c.e0 + o[0], words.size() * 4, hipMemcpyDeviceToHost));
-  std::memcpy(bytes_out, words.data(), (size_t)k);
-  HX_CATCH
-}
-
-int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host) {
-  HX_TRY
-  HX_CHECK(h && out_host, "NULL argument");
-  auto& c = pay_col(h, col);
-  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_debug_list (column kind)");
-  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_debug_text (column kind)");
-  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
-  h->set_device();
-  HX_HIP(hipMemcpy(out_host, c.p0 + row, 4, hipMemcpyDeviceToHost));
-  if (c.kind == HX_PAY_F64) HX_HIP(hipMemcpy((uint8_t*)out_host + 4, c.p1 + row, 4, hipMemcpyDeviceToHost));
-  HX_CATCH
-}
-
-int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets, int32_t n_sets,
-                    uint32_t* mask_dev, int64_t* n_kept, void* stream) {
-  HX_TRY
-  HX_CHECK(h && ops && (mask_dev || h->n == 0), "NULL argument");
-  HX_CHECK(n_ops >= 1 && n_ops <= HX_PAY_MAX_OPS, "payload: a program holds 1 to 4096 ops");
-  HX_CHECK(n_sets >= 0 && (sets || n_sets == 0), "payload: bad sets");
-  // ---- every refusal, before any device work ----
-  std::vector<PayOpDev> prog((size_t)n_ops);
-  std::vector<int8_t> set_kind((size_t)n_sets, 0);        // 0 = unused, 1 = uint32, 2 = double, 3 = a pattern blob
-  struct TextOp {                                         // one HX_PAY_TEXT_ALL: a k_payload_text launch + PAY_D_BITS
-    int at;
-    const hx_index::PayCol* c;
-    std::vector<PayTextPat> pats;
-    size_t pat_off = 0;
-  };
-  std::vector<TextOp> texts;
-  int depth = 0;
-  for (int i = 0; i < n_ops; ++i) {
-    const hx_pay_op& o = ops[i];
-    PayOpDev d{0u, 0u, o.imm, nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
-    int pops = 0;
-    const hx_index::PayCol* c = nullptr;
-    const bool list_op = o.op >= HX_PAY_ANY_EQ && o.op <= HX_PAY_IS_EMPTY_LIST;
-    const bool reads_col = (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_GE) || list_op || o.op == HX_PAY_TEXT_ALL;
-    if (reads_col) {
-      c = &pay_col(h, o.col);
-      HX_CHECK(c->filled == h->n, "payload: column " + std::to_string(o.col) + " is not filled to the index's row count");
-      d.p0 = c->p0;
-      d.p1 = c->kind == HX_PAY_F64 ? c->p1 : nullptr;
-      if (c->list()) {                 // (filled == hx_count > 0 below: off is allocated; no element = never read)
-        d.off = c->off;
-        d.e0 = c->e0;
-        d.e1 = c->kind == HX_PAY_LIST_F64 ? c->e1 : nullptr;
-      }
-      HX_CHECK(!c->text() || (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_PRESENT) || o.op == HX_PAY_TEXT_ALL,
-               "payload: a text column takes IS_MISSING / IS_NULL / PRESENT / TEXT_ALL only");
-      HX_CHECK(!list_op || c->list(), "payload: ANY_EQ / ANY_IN / ANY_RANGE / IS_EMPTY_LIST need a list column");
-      HX_CHECK(!(o.op >= HX_PAY_EQ && o.op <= HX_PAY_GE) || !c->list(),
-               "payload: EQ / IN / LT / LE / GT / GE need a scalar column (a list column takes the ANY ops)");
-      HX_CHECK(o.op != HX_PAY_TEXT_ALL || c->text(),
-               "payload: unknown op " + std::to_string(o.op) + " for this column's kind: TEXT_ALL needs a text column");
-    }
-    const bool f64 = c && (c->kind == HX_PAY_F64 || c->kind == HX_PAY_LIST_F64);
-    switch (o.op) {
-      case HX_PAY_TRUE: d.op = PAY_D_TRUE; break;
-      case HX_PAY_FALSE: d.op = PAY_D_FALSE; break;
-      case HX_PAY_IS_MISSING: d.op = PAY_D_IS_MISSING; break;
-      case HX_PAY_IS_NULL: d.op = PAY_D_IS_NULL; break;
-      case HX_PAY_PRESENT: d.op = PAY_D_PRESENT; break;
-      case HX_PAY_EQ: d.op = f64 ? PAY_D_EQ_F64 : PAY_D_EQ_U32; break;
-      case HX_PAY_IN: d.op = f64 ? PAY_D_IN_F64 : PAY_D_IN_U32; break;
-      case HX_PAY_LT: d.op = PAY_D_LT; break;
-      case HX_PAY_LE: d.op = PAY_D_LE; break;
-      case HX_PAY_GT: d.op = PAY_D_GT; break;
-      case HX_PAY_GE: d.op = PAY_D_GE; break;
-      case HX_PAY_ROW_IN: d.op = PAY_D_ROW_IN; break;
-      case HX_PAY_AND: d.op = PAY_D_AND; pops = 2; break;
-      case HX_PAY_OR: d.op = PAY_D_OR; pops = 2; break;
-      case HX_PAY_NOT: d.op = PAY_D_NOT; pops = 1; break;
-      case HX_PAY_ANY_EQ: d.op = f64 ? PAY_D_ANY_EQ_F64 : PAY_D_ANY_EQ_U32; break;
-      case HX_PAY_ANY_IN: d.op = f64 ? PAY_D_ANY_IN_F64 : PAY_D_ANY_IN_U32; break;
-      case HX_PAY_ANY_RANGE: d.op = PAY_D_ANY_RANGE; break;
-      case HX_PAY_IS_EMPTY_LIST: d.op = PAY_D_IS_EMPTY_LIST; break;
-      case HX_PAY_TEXT_ALL: {          // the blob: uint32 P, uint32 len[P], the patterns' bytes one after another
-        HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
-        const hx_pay_set& ps = sets[o.imm];
-        HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == 3, "payload: one set used as values and as a pattern blob");
-        set_kind[(size_t)o.imm] = 3;
-        HX_CHECK(ps.vals && ps.n >= 4, "payload: a pattern blob starts with its pattern count");
-        const uint8_t* blob = (const uint8_t*)ps.vals;
-        uint32_t np = 0;
-        std::memcpy(&np, blob, 4);
-        HX_CHECK(np >= 1 && np <= HX_PAY_TEXT_MAX_WORDS, "payload: a pattern blob holds 1 to 32 patterns");
-        HX_CHECK(ps.n >= 4 + 4 * (int64_t)np, "payload: the pattern blob's size disagrees with its header");
-        TextOp t;
-        t.at = i;
-        t.c = c;
-        t.pats.assign(np, PayTextPat{});
-        int64_t at = 4 + 4 * (int64_t)np;
-        for (uint32_t k = 0; k < np; ++k) {
-          uint32_t len = 0;
-          std::memcpy(&len, blob + 4 + 4 * k, 4);
-          HX_CHECK(len >= 1 && len <= HX_PAY_TEXT_MAX_WORD_BYTES, "payload: a pattern holds 1 to 64 bytes");
-          HX_CHECK(at + len <= ps.n, "payload: the pattern blob's size disagrees with its header");
-          PayTextPat& pt = t.pats[k];
-          pt.len = len;
-          pt.fmask = len >= 4 ? 0xFFFFFFFFu : (1u << (8 * len)) - 1u;
-          std::memcpy(pt.w, blob + at, len);
-          at += len;
-        }
-        HX_CHECK(at == ps.n, "payload: the pattern blob's size disagrees with its header");
-        texts.push_back(std::move(t));
-        d.op = PAY_D_BITS;
-        d.p0 = nullptr;                // (not a column op on the device: the plane travels in imm)
-        d.off = nullptr;
-        d.e0 = nullptr;
-        break;
-      }
-      default: throw Error("payload: unknown op " + std::to_string(o.op));
-    }
-    if (o.op >= HX_PAY_LT && o.op <= HX_PAY_GE) HX_CHECK(f64, "payload: LT / LE / GT / GE need an F64 column");
-    if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(f64, "payload: ANY_RANGE needs an F64 list column");
-    if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN || o.op == HX_PAY_ANY_IN || o.op == HX_PAY_ANY_RANGE) {
-      HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
-      if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(sets[o.imm].n == 2, "payload: the set of ANY_RANGE holds exactly two doubles, lo <= hi");
-      const int8_t kind = f64 ? 2 : 1;
-      HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == kind, "payload: one set used as uint32 and as double");
-      set_kind[(size_t)o.imm] = kind;
-    }
-    HX_CHECK(depth >= pops, "payload: stack underflow at op " + std::to_string(i));
-    depth += 1 - pops;
-    HX_CHECK(depth <= HX_PAY_MAX_STACK, "payload: the stack exceeds 32 entries at op " + std::to_string(i));
-    prog[(size_t)i] = d;
-  }
-  HX_CHECK(depth == 1, "payload: the program must leave exactly one entry on the stack");
-  const size_t prog_bytes = (size_t)n_ops * sizeof(PayOpDev);
-  std::vector<size_t> set_off((size_t)n_sets, 0);
-  size_t bytes = prog_bytes;
-  for (int s = 0; s < n_sets; ++s) {
-    if (!set_kind[(size_t)s] || set_kind[(size_t)s] == 3) continue;   // (a pattern blob travels per op, checked above)
-    const int64_t m = sets[s].n;
-    HX_CHECK(m >= 0 && m <= 0xFFFFFFFFll && (sets[s].vals || m == 0), "payload: bad set");
-    bool ok = true;
-    if (set_kind[(size_t)s] == 1) {
-      const uint32_t* v = (const uint32_t*)sets[s].vals;
-      for (int64_t i = 1; i < m; ++i) ok &= v[i - 1] <= v[i];
-    } else {
-      const double* v = (const double*)sets[s].vals;
-      for (int64_t i = 0; i < m; ++i) ok &= v[i] == v[i] && (i == 0 || v[i - 1] <= v[i]);
-    }
-    HX_CHECK(ok, "payload: set " + std::to_string(s) + " is not sorted ascending");
-    set_off[(size_t)s] = bytes;
-    bytes += (size_t)round_up(std::max<int64_t>(m, 1) * (set_kind[(size_t)s] == 1 ? 4 : 8), 8);
-  }
-  for (auto& t : texts) {
-    t.pat_off = bytes;
-    bytes += (size_t)round_up((int64_t)(t.pats.size() * sizeof(PayTextPat)), 8);
-  }
-  const int64_t n = h->n;
-  if (n == 0) {
-    if (n_kept) *n_kept = 0;
-    return 0;
-  }
-  // ---- the program, its sets and its patterns: one pinned staging buffer, one copy ----
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  if (h->pay_ev_pending) {              // the device has taken the previous call's program
-    HX_HIP(hipEventSynchronize(h->pay_ev));
-    h->pay_ev_pending = false;
-  }
-  if (bytes > h->pay_pin_cap) {
-    if (h->pay_pin) HX_HIP(hipHostFree(h->pay_pin));
-    h->pay_pin = nullptr;
-    h->pay_pin_cap = 0;
-    const size_t want = (size_t)round_up((int64_t)bytes * 2, 4096);
-    HX_HIP(hipHostMalloc((void**)&h->pay_pin, want, hipHostMallocDefault));
-    h->pay_pin_cap = want;
-  }
-  if (!h->pay_ev) HX_HIP(hipEventCreateWithFlags(&h->pay_ev, hipEventDisableTiming));
-  uint8_t* dev = (uint8_t*)h->ws.get(WS_PAY_PROG, bytes);
-  // one packed verdict plane per TEXT_ALL, written by k_payload_text in front of the mask kernel
-  const int64_t plane_words = (n + 31) / 32;
-  uint32_t* planes = texts.empty() ? nullptr : (uint32_t*)h->ws.get(WS_PAY_PLANES, texts.size() * (size_t)plane_words * 4);
-  for (size_t t = 0; t < texts.size(); ++t) prog[(size_t)texts[t].at].imm = (uint64_t)(uintptr_t)(planes + t * (size_t)plane_words);
-  for (int i = 0; i < n_ops; ++i) {
-    PayOpDev& d = prog[(size_t)i];
-    if (d.op == PAY_D_ANY_RANGE) {     // (two doubles, checked above: the closed interval travels in the op itself)
-      const uint64_t* v = (const uint64_t*)sets[(size_t)d.imm].vals;
-      d.imm = v[0];
-      d.imm2 = v[1];
-      continue;
-    }
-    if (d.op != PAY_D_ROW_IN && d.op != PAY_D_IN_U32 && d.op != PAY_D_IN_F64 && d.op != PAY_D_ANY_IN_U32 &&
-        d.op != PAY_D_ANY_IN_F64)
-      continue;
-    const size_t s = (size_t)d.imm;
-    d.cnt = (uint32_t)sets[s].n;
-    d.imm = (uint64_t)(uintptr_t)(dev + set_off[s]);
-  }
-  std::memcpy(h->pay_pin, prog.data(), prog_bytes);
-  for (int s = 0; s < n_sets; ++s)
-    if (set_kind[(size_t)s] && set_kind[(size_t)s] != 3 && sets[s].n > 0)
-      std::memcpy(h->pay_pin + set_off[(size_t)s], sets[s].vals, (size_t)sets[s].n * (set_kind[(size_t)s] == 1 ? 4 : 8));
-  for (const auto& t : texts) std::memcpy(h->pay_pin + t.pat_off, t.pats.data(), t.pats.size() * sizeof(PayTextPat));
-  HX_HIP(hipMemcpyAsync(dev, h->pay_pin, bytes, hipMemcpyHostToDevice, st));
-  HX_HIP(hipEventRecord(h->pay_ev, st));
-  h->pay_ev_pending = true;
-  uint32_t* kept = nullptr;
-  if (n_kept) {
-    kept = (uint32_t*)h->ws.get(WS_PAY_KEPT, 4);
-    HX_HIP(hipMemsetAsync(kept, 0, 4, st));
-  }
-  for (size_t t = 0; t < texts.size(); ++t)
-    launch_payload_text(texts[t].c->p0, texts[t].c->off, texts[t].c->e0, n, (const PayTextPat*)(dev + texts[t].pat_off),
-                        (int)texts[t].pats.size(), planes + t * (size_t)plane_words, h->pay_grid, st);
-  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, h->pay_grid, st);
-  if (n_kept) {
-    uint32_t* pin = (uint32_t*)host_pin(h) + 14;
-    HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    *n_kept = pin[0];
-  }
-  HX_CATCH
-}
-
 int hx_get_stats(hx_index* h, hx_stats* out) {
   HX_TRY
   HX_CHECK(h && out, "NULL argument");
@@ -4533,209 +3091,6 @@ int hx_debug_row(hx_index* h, int32_t which, int64_t row, void* out_host) {
   } else {
     throw Error("bad `which`");
   }
-  HX_CATCH
-}
-
-// ---- persistence -------------------------------------------------
-// The reference asks Qdrant for on-disk storage (qdrant_handler.py:47-55, 62: on_disk=True,
-// memmap_threshold).  A collection is written as one file: header, then the device arrays as they
-// stand (derived vectors are stored, not re-derived: loading reproduces the index bit for bit) and
-// the doc-major sparse CSR; the inverted index is rebuilt on load (K9, ~1.4 s per 10^9 postings).
-namespace {
-struct HxFileHeader {
-  char magic[8];             // "HXIDX\0\0\2" (version 1: no id-block table, n_blocks reads 0)
-  int32_t dim, n_pre, psize[3], n_blocks;
-  int64_t id_base, n, sp_rows, nnz;
-};
-const char HX_MAGIC[8] = {'H', 'X', 'I', 'D', 'X', 0, 0, 2};
-constexpr size_t HX_IO_CHUNK = (size_t)64 << 20;
-
-struct File {
-  FILE* f;
-  explicit File(const char* path, const char* mode) : f(fopen(path, mode)) {
-    if (!f) throw Error(std::string("cannot open ") + path);
-  }
-  ~File() { if (f) fclose(f); }
-};
-void dev_to_file(FILE* f, const void* dev, size_t bytes, std::vector<char>& buf) {
-  for (size_t o = 0; o < bytes; o += HX_IO_CHUNK) {
-    const size_t m = std::min(HX_IO_CHUNK, bytes - o);
-    HX_HIP(hipMemcpy(buf.data(), (const char*)dev + o, m, hipMemcpyDeviceToHost));
-    HX_CHECK(fwrite(buf.data(), 1, m, f) == m, "short write");
-  }
-}
-void file_to_dev(FILE* f, void* dev, size_t bytes, std::vector<char>& buf) {
-  for (size_t o = 0; o < bytes; o += HX_IO_CHUNK) {
-    const size_t m = std::min(HX_IO_CHUNK, bytes - o);
-    HX_CHECK(fread(buf.data(), 1, m, f) == m, "short read: truncated index file");
-    HX_HIP(hipMemcpy((char*)dev + o, buf.data(), m, hipMemcpyHostToDevice));
-  }
-}
-}  // namespace
-
-int hx_save(hx_index* h, const char* path) {
-  HX_TRY
-  HX_CHECK(h && path, "NULL argument");
-  h->set_device();
-  HX_HIP(hipDeviceSynchronize());
-  File fl(path, "wb");
-  HxFileHeader hd{};
-  memcpy(hd.magic, HX_MAGIC, 8);
-  hd.dim = h->dim;
-  hd.n_pre = h->n_pre;
-  for (int p = 0; p < 3; ++p) hd.psize[p] = h->psize[p];
-  hd.id_base = h->id_base;
-  hd.n = h->n;
-  hd.sp_rows = h->sp_rows;
-  hd.nnz = h->nnz;
-  hd.n_blocks = (int32_t)h->ids.row0.size();
-  HX_CHECK(fwrite(&hd, sizeof hd, 1, fl.f) == 1, "short write");
-  if (hd.n_blocks) {         // the id-block table: row0 column, then gid0 column
-    HX_CHECK(fwrite(h->ids.row0.data(), 4, (size_t)hd.n_blocks, fl.f) == (size_t)hd.n_blocks, "short write");
-    HX_CHECK(fwrite(h->ids.gid0.data(), 4, (size_t)hd.n_blocks, fl.f) == (size_t)hd.n_blocks, "short write");
-  }
-  std::vector<char> buf(HX_IO_CHUNK);
-  const size_t n = (size_t)h->n;
-  dev_to_file(fl.f, h->dense, n * h->dim_pad * 4, buf);
-  dev_to_file(fl.f, h->dense_h, n * h->dim_pad * 2, buf);
-  dev_to_file(fl.f, h->q8, n * h->dim_pad8, buf);
-  dev_to_file(fl.f, h->q8_rinv, n * 4, buf);
-  for (int p = 0; p < h->n_pre; ++p) dev_to_file(fl.f, h->pre[p], n * h->psize[p] * 4, buf);
-  if (h->n_pre > 0) dev_to_file(fl.f, h->pre_h0, n * h->psize[0] * 2, buf);
-  if (h->sp_rows > 0) {
-    dev_to_file(fl.f, h->sp_indptr, ((size_t)h->sp_rows + 1) * 8, buf);
-    dev_to_file(fl.f, h->sp_idx, (size_t)h->nnz * 4, buf);
-    dev_to_file(fl.f, h->sp_val, (size_t)h->nnz * 4, buf);
-  }
-  HX_CHECK(fflush(fl.f) == 0, "flush failed");
-  HX_CATCH
-}
-
-int hx_load(const char* path, int32_t device, hx_index** out) {
-  HX_TRY
-  HX_CHECK(path && out, "NULL argument");
-  File fl(path, "rb");
-  HxFileHeader hd{};
-  HX_CHECK(fread(&hd, sizeof hd, 1, fl.f) == 1, "short read: not an index file");
-  HX_CHECK(memcmp(hd.magic, HX_MAGIC, 7) == 0 && (hd.magic[7] == 1 || hd.magic[7] == 2),
-           "not an hx index file (bad magic / version)");
-  if (hd.magic[7] == 1) hd.n_blocks = 0;     // version 1: ids are id_base + row
-  // The header is not trusted: every size is checked against the limits of the add path and against the
-  // length of the file BEFORE anything is allocated (a corrupt count must not become a huge hipMalloc).
-  HX_CHECK(hd.n >= 0 && hd.sp_rows >= 0 && hd.nnz >= 0 && hd.n_pre >= 0 && hd.n_pre <= 3, "corrupt header");
-  HX_CHECK(hd.dim >= 1 && hd.dim <= 4096, "corrupt header: dim");
-  HX_CHECK(hd.id_base >= 0 && hd.id_base + hd.n < 0xFFFFFFFFll, "corrupt header: row ids");
-  HX_CHECK(hd.nnz < 0xFFFFFFFFll && hd.sp_rows <= hd.n && (hd.sp_rows > 0 || hd.nnz == 0), "corrupt header: sparse counts");
-  {
-    const int64_t dp = round_up(hd.dim, 64), dp8 = round_up(hd.dim, 128);
-    int64_t per_row = dp * 4 + dp * 2 + dp8 + 4;
-    for (int p = 0; p < hd.n_pre; ++p) {
-      HX_CHECK(hd.psize[p] >= 64 && hd.psize[p] <= hd.dim && hd.psize[p] % 64 == 0, "corrupt header: prefix sizes");
-      per_row += (int64_t)hd.psize[p] * 4;
-    }
-    if (hd.n_pre > 0) per_row += (int64_t)hd.psize[0] * 2;
-    HX_CHECK(hd.n_blocks >= 0 && hd.n_blocks <= hd.n, "corrupt header: id blocks");
-    int64_t want = (int64_t)sizeof hd + (int64_t)hd.n_blocks * 8 + hd.n * per_row;
-    if (hd.sp_rows > 0) want += (hd.sp_rows + 1) * 8 + hd.nnz * 8;
-    HX_CHECK(fseek(fl.f, 0, SEEK_END) == 0, "cannot seek");
-    const int64_t have = (int64_t)ftell(fl.f);
-    HX_CHECK(fseek(fl.f, (long)sizeof hd, SEEK_SET) == 0, "cannot seek");
-    HX_CHECK(have == want, "index file length does not match its header (truncated or corrupt)");
-  }
-  // the id-block table: both columns ascend strictly from row 0, a block's ids end before the next block's begin,
-  // the last id stays below 2^32 - 1
-  std::vector<uint32_t> row0((size_t)hd.n_blocks), gid0((size_t)hd.n_blocks);
-  if (hd.n_blocks) {
-    HX_CHECK(fread(row0.data(), 4, row0.size(), fl.f) == row0.size(), "short read: truncated index file");
-    HX_CHECK(fread(gid0.data(), 4, gid0.size(), fl.f) == gid0.size(), "short read: truncated index file");
-    HX_CHECK(row0[0] == 0, "corrupt index file: id blocks");
-    for (size_t k = 0; k < row0.size(); ++k) {
-      const int64_t len = (k + 1 < row0.size() ? (int64_t)row0[k + 1] : hd.n) - (int64_t)row0[k];
-      HX_CHECK(len >= 1 && (int64_t)gid0[k] + len < 0xFFFFFFFFll, "corrupt index file: id blocks");
-      HX_CHECK(k + 1 == row0.size() || (int64_t)gid0[k] + len <= (int64_t)gid0[k + 1], "corrupt index file: id blocks");
-    }
-  } else if (hd.n > 0) {
-    row0.assign(1, 0u);
-    gid0.assign(1, (uint32_t)hd.id_base);
-  }
-  hx_index* h = nullptr;
-  const int rc = hx_create(hd.dim, hd.psize, hd.n_pre, device, hd.id_base, &h);
-  if (rc != 0) return rc;
-  try {
-    h->set_device();
-    if (!row0.empty()) {
-      h->ids.end = (int64_t)gid0.back() + (hd.n - (int64_t)row0.back());
-      h->ids.row0.swap(row0);
-      h->ids.gid0.swap(gid0);
-      h->ids.dirty = true;
-    }
-    std::vector<char> buf(HX_IO_CHUNK);
-    const size_t n = (size_t)hd.n;
-    reserve_rows(h, hd.n);
-    file_to_dev(fl.f, h->dense, n * h->dim_pad * 4, buf);
-    file_to_dev(fl.f, h->dense_h, n * h->dim_pad * 2, buf);
-    file_to_dev(fl.f, h->q8, n * h->dim_pad8, buf);
-    file_to_dev(fl.f, h->q8_rinv, n * 4, buf);
-    for (int p = 0; p < h->n_pre; ++p) file_to_dev(fl.f, h->pre[p], n * h->psize[p] * 4, buf);
-    if (h->n_pre > 0) file_to_dev(fl.f, h->pre_h0, n * h->psize[0] * 2, buf);
-    h->n = hd.n;
-    // the candidate copy is derived data (not in the file): one pass over the stored rows
-    if (h->cand8) launch_requant_rows(h->dense, h->dim_pad, h->dim_pad8, hd.n, h->q8s, h->q8s_scale, h->s8_err, nullptr);
-    if (hd.sp_rows > 0) {
-      reserve_sparse(h, hd.sp_rows, hd.nnz);
-      file_to_dev(fl.f, h->sp_indptr, ((size_t)hd.sp_rows + 1) * 8, buf);
-      file_to_dev(fl.f, h->sp_idx, (size_t)hd.nnz * 4, buf);
-      file_to_dev(fl.f, h->sp_val, (size_t)hd.nnz * 4, buf);
-      // what the add path guarantees and the kernels rely on: monotone indptr from 0 to nnz, term ids in
-      // [0, 2^31), finite values
-      int* bad = (int*)h->ws.get(WS_MISC, 4);
-      HX_HIP(hipMemset(bad, 0, 4));
-      launch_csr_check(h->sp_indptr, h->sp_idx, hd.sp_rows, 0, hd.nnz, bad, nullptr);
-      int hbad = 0;
-      HX_HIP(hipMemcpy(&hbad, bad, 4, hipMemcpyDeviceToHost));
-      HX_CHECK(hbad == 0, "corrupt index file: sparse CSR is inconsistent");
-      // term ids unique within a row (hx_add_sparse enforces it; the exact pass finds a query term with ONE ballot)
-      constexpr int LONG_CAP = 4096;
-      int64_t* long_rows = (int64_t*)h->ws.get(WS_LONG_ROWS, (size_t)LONG_CAP * 8 + 8);
-      int* n_long = (int*)(long_rows + LONG_CAP);
-      HX_HIP(hipMemset(n_long, 0, 4));
-      launch_csr_unique(h->sp_indptr, h->sp_idx, hd.sp_rows, bad, long_rows, LONG_CAP, n_long, nullptr);
-      int hn_long = 0;
-      HX_HIP(hipMemcpy(&hbad, bad, 4, hipMemcpyDeviceToHost));
-      HX_HIP(hipMemcpy(&hn_long, n_long, 4, hipMemcpyDeviceToHost));
-      HX_CHECK(hbad == 0, "corrupt index file: a sparse vector repeats a term id");
-      if (hn_long > 0) {            // the rows too long for the wave compare: sorted on the host
-        std::vector<int64_t> rows;
-        if (hn_long <= LONG_CAP) {
-          rows.resize((size_t)hn_long);
-          HX_HIP(hipMemcpy(rows.data(), long_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-        } else {                    // more of them than the device list holds (hx_add_sparse accepts any number): find
-                                    // them all from the offsets -- a valid file, not a corrupt one
-          std::vector<int64_t> ip((size_t)hd.sp_rows + 1);
-          HX_HIP(hipMemcpy(ip.data(), h->sp_indptr, ip.size() * 8, hipMemcpyDeviceToHost));
-          for (int64_t r = 0; r < hd.sp_rows; ++r)
-            if (ip[(size_t)r + 1] - ip[(size_t)r] > CSR_UNIQUE_WAVE_MAX) rows.push_back(r);
-        }
-        std::vector<int32_t> ids;
-        for (int64_t r : rows) {
-          int64_t be[2];
-          HX_HIP(hipMemcpy(be, h->sp_indptr + r, 16, hipMemcpyDeviceToHost));
-          ids.resize((size_t)(be[1] - be[0]));
-          HX_HIP(hipMemcpy(ids.data(), h->sp_idx + be[0], ids.size() * 4, hipMemcpyDeviceToHost));
-          std::sort(ids.begin(), ids.end());
-          HX_CHECK(std::adjacent_find(ids.begin(), ids.end()) == ids.end(), "corrupt index file: a sparse vector repeats a term id");
-        }
-      }
-      track_weights_dev(h, h->sp_val, hd.nnz, nullptr);
-      h->sp_rows = hd.sp_rows;
-      h->nnz = hd.nnz;
-      h->sparse_stale = true;
-    }
-  } catch (...) {
-    (void)hx_destroy(h);
-    throw;
-  }
-  *out = h;
   HX_CATCH
 }
 

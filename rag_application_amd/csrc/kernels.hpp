@@ -384,7 +384,7 @@ void launch_view_ids(uint64_t* keys, int64_t n, const uint32_t* rows, uint32_t c
 
 // ---- compact.hip: per-point deletes (hx_retain_rows) ------------------------------------------------------------------
 // dst row i = src row rows[i], i < count (row_bytes a multiple of 16; one 4-byte value per row for _u32).  src and dst
-// may be one allocation as long as the launch reads no byte it writes (engine.hip cuts the rows into such chunks).
+// may be one allocation as long as the launch reads no byte it writes (lifecycle.hip cuts the rows into such chunks).
 void launch_compact_rows16(const void* src, void* dst, int64_t row_bytes, const uint32_t* rows, int64_t count,
                            hipStream_t st);
 void launch_compact_u32(const void* src, void* dst, const uint32_t* rows, int64_t count, hipStream_t st);
@@ -420,7 +420,7 @@ void synth_sparse_fill(int64_t doc0_global, int64_t n, uint32_t seed, const uint
 void exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t st);  // out[n] = total
 
 // ---- payload.hip: the payload index (hx_payload_mask) ----------------------------------------------
-// One op of a program as the kernel reads it: engine.hip resolves the columns of hx_pay_op to their planes (p0 = the
+// One op of a program as the kernel reads it: paystore.hip resolves the columns of hx_pay_op to their planes (p0 = the
 // cell of a U32 column or the low word of an F64 cell, p1 = its high word or NULL) and the sets to device pointers
 // (imm; cnt = entries).  Codes from PAY_D_FIRST_COL on read a column.
 // A list column gives p0 = its head plane (p1 = NULL: the head reads as a U32 cell), off = its

@@ -1,0 +1,697 @@
+// Host side of the payload index (DESIGN.md sections 15, 17, 19): the storage of the columns, every hx_payload_* entry,
+// and what the lifecycle of the rows (lifecycle.hip) does to a column.  The kernels are in payload.hip and paytext.hip,
+// the splice of a list or text column in replace.hip.
+#include "index.hpp"
+
+namespace hx {
+
+using PayCol = hx_index::PayCol;
+
+PayCol& pay_col(hx_index* h, int32_t col) {
+  for (auto& c : h->pay)
+    if (c.id == col) return c;
+  throw Error("payload: unknown column " + std::to_string(col));
+}
+
+void pay_free(PayCol& c) {
+  for (void* q : {(void*)c.p0, (void*)c.p1, (void*)c.off, (void*)c.e0, (void*)c.e1})
+    if (q) (void)hipFree(q);
+  c.p0 = c.p1 = c.e0 = c.e1 = nullptr;
+  c.off = nullptr;
+  c.filled = c.cap = c.n_el = c.el_cap = 0;
+}
+
+// ---- what the lifecycle does to a column -----------------------------------------------------------------------------------
+void pay_truncate(hx_index* h, int64_t n_rows) {
+  for (auto& c : h->pay) {
+    if (c.csr() && c.filled > n_rows)      // (the elements past off[n_rows] are dead)
+      HX_HIP(hipMemcpy(&c.n_el, c.off + n_rows, 8, hipMemcpyDeviceToHost));
+    c.filled = std::min(c.filled, n_rows);
+  }
+}
+
+std::vector<PayMoved> pay_moved(hx_index* h, int64_t n) {
+  std::vector<PayMoved> cols;
+  for (auto& c : h->pay)
+    if (c.filled == n) cols.push_back({c.p0, c.p1, c.csr() ? c.off : nullptr, c.e0, c.e1, &c.n_el});
+  return cols;
+}
+
+void pay_retained(hx_index* h, int64_t n, int64_t count) {
+  for (size_t i = h->pay.size(); i-- > 0;) {
+    if (h->pay[i].filled == n) {
+      h->pay[i].filled = count;
+      continue;
+    }
+    pay_free(h->pay[i]);
+    h->pay.erase(h->pay.begin() + (long)i);
+  }
+}
+
+// ---- the word planes of doubles ----------------------------------------------------------------------------------------------
+// nan_refusal: what a NaN cell is refused with (NULL: the caller's cells are taken as they are)
+static void split_f64(const void* cells, int64_t n, std::vector<uint32_t>& lo, std::vector<uint32_t>& hi,
+                      const char* nan_refusal = nullptr) {
+  const uint64_t* v = (const uint64_t*)cells;
+  const double* d = (const double*)cells;
+  lo.resize((size_t)n);
+  hi.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    if (nan_refusal) HX_CHECK(d[i] == d[i], nan_refusal);
+    lo[(size_t)i] = (uint32_t)v[i];
+    hi[(size_t)i] = (uint32_t)(v[i] >> 32);
+  }
+}
+static void join_f64(const std::vector<uint32_t>& lo, const std::vector<uint32_t>& hi, void* cells) {
+  uint64_t* out = (uint64_t*)cells;
+  for (size_t i = 0; i < lo.size(); ++i) out[i] = ((uint64_t)hi[i] << 32) | lo[i];
+}
+
+// ---- growth ------------------------------------------------------------------------------------------------------------------
+// a device array of `want` entries that holds the first `keep` of `old` (the new one is made before the old one goes)
+template <typename T>
+static T* pay_grown(const T* old, int64_t keep, int64_t want) {
+  T* a = nullptr;
+  if (hipMalloc((void**)&a, (size_t)want * sizeof(T)) != hipSuccess) throw Error("payload: out of device memory");
+  if (keep > 0 && hipMemcpy(a, old, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess) {
+    (void)hipFree(a);
+    throw Error("payload: device copy failed");
+  }
+  return a;
+}
+
+// Room for `rows` rows and, in a list or text column, `els` words per element plane -- all or nothing: every new array is
+// allocated and filled before an old one is freed, and a failure leaves the column as it was.
+static void pay_reserve(hx_index* h, PayCol& c, int64_t rows, int64_t els) {
+  uint32_t *np0 = nullptr, *np1 = nullptr, *ne0 = nullptr, *ne1 = nullptr;
+  int64_t* noff = nullptr;
+  int64_t nc = c.cap, nec = c.el_cap;
+  try {
+    if (rows > c.cap || (c.csr() && !c.off)) {
+      nc = round_up(std::max<int64_t>(std::max(rows, c.cap * 2), h->cap), 256);
+      HX_HIP(hipDeviceSynchronize());
+      np0 = pay_grown(c.p0, c.filled, nc);
+      if (c.kind == HX_PAY_F64) np1 = pay_grown(c.p1, c.filled, nc);
+      if (c.csr()) noff = pay_grown(c.off, c.off ? c.filled + 1 : 0, nc + 1);
+    }
+    if (els > c.el_cap) {
+      nec = round_up(std::max<int64_t>(els, c.el_cap * 2), 256);
+      HX_HIP(hipDeviceSynchronize());
+      ne0 = pay_grown(c.e0, c.n_el, nec);
+      if (c.kind == HX_PAY_LIST_F64) ne1 = pay_grown(c.e1, c.n_el, nec);
+    }
+  } catch (...) {
+    for (void* q : {(void*)np0, (void*)np1, (void*)noff, (void*)ne0, (void*)ne1})
+      if (q) (void)hipFree(q);
+    throw;
+  }
+  if (np0) {
+    for (void* q : {(void*)c.p0, (void*)c.p1, (void*)c.off})
+      if (q) (void)hipFree(q);
+    c.p0 = np0;
+    c.p1 = np1;
+    c.off = noff;
+    c.cap = nc;
+  }
+  if (ne0) {
+    if (c.e0) (void)hipFree(c.e0);
+    if (c.e1) (void)hipFree(c.e1);
+    c.e0 = ne0;
+    c.e1 = ne1;
+    c.el_cap = nec;
+  }
+}
+
+// ---- list and text cells as a column stores them ---------------------------------------------------------------------------
+// The checked cells of n list rows: heads[n] as the head plane keeps them (missing / null / 0 = a list), off[n + 1] = the
+// rows' offsets in elements from `base`, and -- of doubles only: codes are stored as they come -- lo / hi = the elements'
+// word planes.  Refuses element counts that do not sum to n_values or pass `room`, NaNs and reserved codes.  Returns the
+// element count.
+static int64_t pay_list_pack(const uint32_t* heads_host, int64_t n, const void* values_host, int64_t n_values, int64_t base,
+                             int kind, int64_t room, std::vector<uint32_t>& heads, std::vector<int64_t>& off,
+                             std::vector<uint32_t>& lo, std::vector<uint32_t>& hi) {
+  heads.resize((size_t)n);
+  off.resize((size_t)n + 1);
+  int64_t total = 0;
+  off[0] = base;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    const bool is_list = hd < HX_PAY_U32_NULL;
+    heads[(size_t)i] = is_list ? 0u : hd;
+    if (is_list) total += hd;
+    HX_CHECK(total <= n_values, "payload: the element counts of the heads do not sum to n_values");
+    off[(size_t)i + 1] = base + total;
+  }
+  HX_CHECK(total == n_values, "payload: the element counts of the heads do not sum to n_values");
+  HX_CHECK(total <= room, "payload: a list column holds fewer than 2^31 elements");
+  if (kind == HX_PAY_LIST_F64) {
+    split_f64(values_host, total, lo, hi, "payload: a list element is a NaN");
+  } else {
+    const uint32_t* v = (const uint32_t*)values_host;
+    for (int64_t i = 0; i < total; ++i) HX_CHECK(v[i] < HX_PAY_U32_NULL, "payload: a list element is a reserved code");
+  }
+  return total;
+}
+
+// The checked cells of n text rows: off[n + 1] = the rows' offsets in 32-bit words from `base`, words = the rows' bytes
+// one after another, each row padded with zero bytes to a word.  Refuses lengths that do not sum to n_bytes.
+static void pay_text_pack(const uint32_t* heads_host, int64_t n, const void* bytes_host, int64_t n_bytes, int64_t base,
+                          std::vector<int64_t>& off, std::vector<uint32_t>& words) {
+  off.resize((size_t)n + 1);
+  off[0] = base;
+  int64_t total = 0, n_words = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    if (hd < HX_PAY_U32_NULL) {
+      total += hd;
+      n_words += ((int64_t)hd + 3) / 4;
+    }
+    HX_CHECK(total <= n_bytes, "payload: the byte lengths of the heads do not sum to n_bytes");
+    off[(size_t)i + 1] = base + n_words;
+  }
+  HX_CHECK(total == n_bytes, "payload: the byte lengths of the heads do not sum to n_bytes");
+  words.assign((size_t)n_words, 0u);
+  const uint8_t* src = (const uint8_t*)bytes_host;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    if (hd >= HX_PAY_U32_NULL || hd == 0u) continue;
+    std::memcpy((uint8_t*)words.data() + (size_t)(off[(size_t)i] - base) * 4, src, hd);
+    src += hd;
+  }
+}
+
+// Store the checked cells of rows [filled, filled + n) of a list or text column: heads[n] as the head plane keeps them,
+// off[n + 1] = the rows' offsets (off[0] = n_el), e0_host / e1_host = `total` new words per element plane (e1_host: the
+// high words of a HX_PAY_LIST_F64 column, NULL otherwise).  Every allocation comes before the column changes.
+static void pay_store_csr(hx_index* h, PayCol& c, const uint32_t* heads, const int64_t* off, int64_t n, const void* e0_host,
+                          const void* e1_host, int64_t total) {
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  if (n == 0) return;
+  h->set_device();
+  const int64_t want = c.filled + n, want_el = c.n_el + total;
+  pay_reserve(h, c, want, want_el);
+  // (the cells behind `filled` and the elements behind n_el are dead until `filled` moves: a failed copy changes nothing)
+  HX_HIP(hipMemcpy(c.p0 + c.filled, heads, (size_t)n * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(c.off + c.filled, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+  if (total > 0) {
+    HX_HIP(hipMemcpy(c.e0 + c.n_el, e0_host, (size_t)total * 4, hipMemcpyHostToDevice));
+    if (f64) HX_HIP(hipMemcpy(c.e1 + c.n_el, e1_host, (size_t)total * 4, hipMemcpyHostToDevice));
+  }
+  c.filled = want;
+  c.n_el = want_el;
+}
+
+// Replace the checked cells of m stored rows of a list or text column: heads[m] as the head plane keeps them, noff[m + 1] =
+// the new rows' offsets from 0, e0_host / e1_host = their `total` words per element plane.  The heads are scattered; offsets
+// and elements are spliced from the first replaced row on.  Every refusal and allocation comes before the column changes.
+static void pay_splice_csr(hx_index* h, PayCol& c, const int64_t* rows_host, int64_t m, const uint32_t* heads,
+                           const int64_t* noff, const void* e0_host, const void* e1_host, int64_t total, const char* who) {
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  if (m == 0) return;
+  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, who);
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  hipStream_t st = nullptr;
+  DevTmp rows_dev, heads_dev, noff_dev, n0, n1, t0, t1;
+  rows_dev.alloc((size_t)m * 4);
+  heads_dev.alloc((size_t)m * 4);
+  noff_dev.alloc((size_t)(m + 1) * 8);
+  n0.alloc((size_t)total * 4);
+  if (f64) n1.alloc((size_t)total * 4);
+  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(heads_dev.p, heads, (size_t)m * 4, hipMemcpyHostToDevice));
+  HX_HIP(hipMemcpy(noff_dev.p, noff, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+  if (total > 0) {
+    HX_HIP(hipMemcpy(n0.p, e0_host, (size_t)total * 4, hipMemcpyHostToDevice));
+    if (f64) HX_HIP(hipMemcpy(n1.p, e1_host, (size_t)total * 4, hipMemcpyHostToDevice));
+  }
+  // rows in front of the first replaced one keep their elements and offsets; the rest go the sparse CSR's way
+  SplicePlan sp;
+  splice_plan(sp, c.off, c.filled, *std::min_element(rows.begin(), rows.end()), (const uint32_t*)rows_dev.p, m,
+              (const int64_t*)noff_dev.p, st);
+  const int64_t want_el = sp.base + sp.moved;
+  HX_CHECK(want_el <= 0x7FFFFFFFll, c.text() ? "payload: a text column holds fewer than 2^31 words" : "payload: a list column holds fewer than 2^31 elements");
+  if (sp.moved > 0) {
+    t0.alloc((size_t)sp.moved * 4);
+    if (f64) t1.alloc((size_t)sp.moved * 4);
+  }
+  pay_reserve(h, c, c.filled, want_el);
+  // ---- the column changes ----
+  launch_scatter_u32(heads_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, st);
+  if (sp.moved > 0) {
+    launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e0, (const uint32_t*)n0.p,
+                          (uint32_t*)t0.p, st);
+    if (f64)
+      launch_csr_splice_u32(c.off + sp.f, sp.map(), (const int64_t*)noff_dev.p, sp.off(), sp.docs, c.e1,
+                            (const uint32_t*)n1.p, (uint32_t*)t1.p, st);
+    launch_copy_u32(t0.p, c.e0 + sp.base, sp.moved, st);
+    if (f64) launch_copy_u32(t1.p, c.e1 + sp.base, sp.moved, st);
+  }
+  launch_csr_new_indptr(c.off + sp.f, sp.off(), sp.docs, sp.base, st);
+  HX_HIP(hipDeviceSynchronize());
+  c.n_el = want_el;
+}
+
+// what hx_payload_debug_list / _text read of a stored row: its head and the offsets of its elements, o[0] and o[1]
+static void pay_row_span(hx_index* h, const PayCol& c, int64_t row, const void* out, int64_t cap, uint32_t* hd, int64_t o[2]) {
+  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
+  HX_CHECK(cap >= 0 && (out || cap == 0), "payload: bad output buffer");
+  h->set_device();
+  HX_HIP(hipMemcpy(hd, c.p0 + row, 4, hipMemcpyDeviceToHost));
+  HX_HIP(hipMemcpy(o, c.off + row, 16, hipMemcpyDeviceToHost));
+}
+
+}  // namespace hx
+
+extern "C" {
+
+// ---- payload index ---------------------------------------------------------------------------
+int hx_payload_create(hx_index* h, int32_t kind, int32_t* col) {
+  HX_TRY
+  HX_CHECK(h && col, "NULL argument");
+  HX_CHECK(kind == HX_PAY_U32 || kind == HX_PAY_F64 || kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64 ||
+               kind == HX_PAY_TEXT,
+           "payload: kind must be HX_PAY_U32, HX_PAY_F64, HX_PAY_LIST_U32, HX_PAY_LIST_F64 or HX_PAY_TEXT");
+  HX_CHECK((int)h->pay.size() < HX_PAY_MAX_COLUMNS, "payload: an index holds at most 64 columns");
+  hx_index::PayCol c;
+  c.id = h->pay_next_id++;
+  c.kind = kind;
+  h->pay.push_back(c);
+  *col = c.id;
+  HX_CATCH
+}
+
+int hx_payload_drop(hx_index* h, int32_t col) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  pay_free(c);
+  h->pay.erase(h->pay.begin() + (&c - h->pay.data()));
+  HX_CATCH
+}
+
+int hx_payload_rows(hx_index* h, int32_t col, int64_t* filled) {
+  HX_TRY
+  HX_CHECK(h && filled, "NULL argument");
+  *filled = pay_col(h, col).filled;
+  HX_CATCH
+}
+
+int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t n) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(n >= 0, "payload: n < 0");
+  HX_CHECK(cells_host || n == 0, "payload: cells are NULL");
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_append_lists (column kind)");
+  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_append_text (column kind)");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  if (n == 0) return 0;
+  h->set_device();
+  const int64_t want = c.filled + n;
+  pay_reserve(h, c, want, 0);          // (everything that can fail comes before the column changes)
+  if (c.kind != HX_PAY_F64) {
+    HX_HIP(hipMemcpy(c.p0 + c.filled, cells_host, (size_t)n * 4, hipMemcpyHostToDevice));
+  } else {
+    std::vector<uint32_t> lo, hi;
+    split_f64(cells_host, n, lo, hi);
+    HX_HIP(hipMemcpy(c.p0 + c.filled, lo.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HX_HIP(hipMemcpy(c.p1 + c.filled, hi.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  c.filled = want;
+  HX_CATCH
+}
+
+int hx_payload_append_lists(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* values_host,
+                            int64_t n_values) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_append_lists needs a list column (column kind)");
+  HX_CHECK(n >= 0 && n_values >= 0, "payload: n < 0");
+  HX_CHECK((heads_host || n == 0) && (values_host || n_values == 0), "payload: cells are NULL");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  // ---- every refusal and every allocation before the column changes ----
+  std::vector<uint32_t> heads, lo, hi;
+  std::vector<int64_t> off;
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  const int64_t total =
+      pay_list_pack(heads_host, n, values_host, n_values, c.n_el, c.kind, 0x7FFFFFFFll - c.n_el, heads, off, lo, hi);
+  pay_store_csr(h, c, heads.data(), off.data(), n, f64 ? (const void*)lo.data() : values_host, f64 ? hi.data() : nullptr, total);
+  HX_CATCH
+}
+
+// ---- the cells of rows that stay where they are (upsert by an existing id) --------------------
+int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const void* cells_host) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(m >= 0, "payload: m < 0");
+  HX_CHECK(m == 0 || (rows_host && cells_host), "payload: rows / cells are NULL");
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_replace_lists (column kind)");
+  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_replace_text (column kind)");
+  if (m == 0) return 0;
+  const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, "hx_payload_replace");
+  h->set_device();
+  HX_HIP(hipDeviceSynchronize());
+  const bool f64 = c.kind == HX_PAY_F64;
+  DevTmp rows_dev, lo_dev, hi_dev;
+  rows_dev.alloc((size_t)m * 4);
+  lo_dev.alloc((size_t)m * 4);
+  HX_HIP(hipMemcpy(rows_dev.p, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  if (!f64) {
+    HX_HIP(hipMemcpy(lo_dev.p, cells_host, (size_t)m * 4, hipMemcpyHostToDevice));
+  } else {
+    std::vector<uint32_t> lo, hi;
+    split_f64(cells_host, m, lo, hi);
+    hi_dev.alloc((size_t)m * 4);
+    HX_HIP(hipMemcpy(lo_dev.p, lo.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+    HX_HIP(hipMemcpy(hi_dev.p, hi.data(), (size_t)m * 4, hipMemcpyHostToDevice));
+  }
+  launch_scatter_u32(lo_dev.p, c.p0, (const uint32_t*)rows_dev.p, m, nullptr);
+  if (f64) launch_scatter_u32(hi_dev.p, c.p1, (const uint32_t*)rows_dev.p, m, nullptr);
+  HX_HIP(hipDeviceSynchronize());
+  HX_CATCH
+}
+
+int hx_payload_replace_lists(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                             const void* values_host, int64_t n_values) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_replace_lists needs a list column (column kind)");
+  HX_CHECK(m >= 0 && n_values >= 0, "payload: m < 0");
+  HX_CHECK((m == 0 || (rows_host && heads_host)) && (values_host || n_values == 0), "payload: rows / cells are NULL");
+  // ---- every refusal and every allocation before the column changes (the element count: once the splice is planned) ----
+  std::vector<uint32_t> heads, lo, hi;
+  std::vector<int64_t> noff;
+  const bool f64 = c.kind == HX_PAY_LIST_F64;
+  const int64_t total = pay_list_pack(heads_host, m, values_host, n_values, 0, c.kind, INT64_MAX, heads, noff, lo, hi);
+  pay_splice_csr(h, c, rows_host, m, heads.data(), noff.data(), f64 ? (const void*)lo.data() : values_host,
+                 f64 ? hi.data() : nullptr, total, "hx_payload_replace_lists");
+  HX_CATCH
+}
+
+int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* values_out, int64_t cap,
+                          int64_t* count) {
+  HX_TRY
+  HX_CHECK(h && head && count, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.list(), "payload: hx_payload_debug_list needs a list column (column kind)");
+  uint32_t hd = 0;
+  int64_t o[2] = {0, 0};
+  pay_row_span(h, c, row, values_out, cap, &hd, o);
+  const int64_t len = o[1] - o[0];
+  HX_CHECK(len >= 0 && o[0] >= 0 && o[1] <= c.n_el, "payload: corrupt list offsets");
+  *count = len;
+  *head = hd >= HX_PAY_U32_NULL ? hd : (uint32_t)len;
+  const int64_t k = std::min(len, cap);
+  if (k <= 0) return 0;
+  if (c.kind == HX_PAY_LIST_U32) {
+    HX_HIP(hipMemcpy(values_out, c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+  } else {
+    std::vector<uint32_t> lo((size_t)k), hi((size_t)k);
+    HX_HIP(hipMemcpy(lo.data(), c.e0 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+    HX_HIP(hipMemcpy(hi.data(), c.e1 + o[0], (size_t)k * 4, hipMemcpyDeviceToHost));
+    join_f64(lo, hi, values_out);
+  }
+  HX_CATCH
+}
+
+// ---- text columns (HX_PAY_TEXT) ----------------------------------------------------------------
+int hx_payload_append_text(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const void* bytes_host,
+                           int64_t n_bytes) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.text(), "payload: hx_payload_append_text needs a text column (column kind)");
+  HX_CHECK(n >= 0 && n_bytes >= 0, "payload: n < 0");
+  HX_CHECK((heads_host || n == 0) && (bytes_host || n_bytes == 0), "payload: cells are NULL");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  // ---- every refusal and every allocation before the column changes ----
+  std::vector<int64_t> off;
+  std::vector<uint32_t> words;
+  pay_text_pack(heads_host, n, bytes_host, n_bytes, c.n_el, off, words);
+  HX_CHECK(c.n_el + (int64_t)words.size() <= 0x7FFFFFFFll, "payload: a text column holds fewer than 2^31 words");
+  pay_store_csr(h, c, heads_host, off.data(), n, words.data(), nullptr, (int64_t)words.size());
+  HX_CATCH
+}
+
+int hx_payload_replace_text(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                            const void* bytes_host, int64_t n_bytes) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.text(), "payload: hx_payload_replace_text needs a text column (column kind)");
+  HX_CHECK(m >= 0 && n_bytes >= 0, "payload: m < 0");
+  HX_CHECK((m == 0 || (rows_host && heads_host)) && (bytes_host || n_bytes == 0), "payload: rows / cells are NULL");
+  std::vector<int64_t> noff;
+  std::vector<uint32_t> words;
+  pay_text_pack(heads_host, m, bytes_host, n_bytes, 0, noff, words);
+  pay_splice_csr(h, c, rows_host, m, heads_host, noff.data(), words.data(), nullptr, (int64_t)words.size(),
+                 "hx_payload_replace_text");
+  HX_CATCH
+}
+
+int hx_payload_debug_text(hx_index* h, int32_t col, int64_t row, uint32_t* head, void* bytes_out, int64_t cap,
+                          int64_t* count) {
+  HX_TRY
+  HX_CHECK(h && head && count, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.text(), "payload: hx_payload_debug_text needs a text column (column kind)");
+  uint32_t hd = 0;
+  int64_t o[2] = {0, 0};
+  pay_row_span(h, c, row, bytes_out, cap, &hd, o);
+  const int64_t len = hd < HX_PAY_U32_NULL ? (int64_t)hd : 0;
+  HX_CHECK(o[0] >= 0 && o[1] <= c.n_el && o[1] - o[0] == (len + 3) / 4, "payload: corrupt text offsets");
+  *head = hd;
+  *count = len;
+  const int64_t k = std::min(len, cap);
+  if (k <= 0) return 0;
+  std::vector<uint32_t> words((size_t)(k + 3) / 4);
+  HX_HIP(hipMemcpy(words.data(), c.e0 + o[0], words.size() * 4, hipMemcpyDeviceToHost));
+  std::memcpy(bytes_out, words.data(), (size_t)k);
+  HX_CATCH
+}
+
+int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host) {
+  HX_TRY
+  HX_CHECK(h && out_host, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(!c.list(), "payload: a list column takes hx_payload_debug_list (column kind)");
+  HX_CHECK(!c.text(), "payload: a text column takes hx_payload_debug_text (column kind)");
+  HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
+  h->set_device();
+  HX_HIP(hipMemcpy(out_host, c.p0 + row, 4, hipMemcpyDeviceToHost));
+  if (c.kind == HX_PAY_F64) HX_HIP(hipMemcpy((uint8_t*)out_host + 4, c.p1 + row, 4, hipMemcpyDeviceToHost));
+  HX_CATCH
+}
+
+int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets, int32_t n_sets,
+                    uint32_t* mask_dev, int64_t* n_kept, void* stream) {
+  HX_TRY
+  HX_CHECK(h && ops && (mask_dev || h->n == 0), "NULL argument");
+  HX_CHECK(n_ops >= 1 && n_ops <= HX_PAY_MAX_OPS, "payload: a program holds 1 to 4096 ops");
+  HX_CHECK(n_sets >= 0 && (sets || n_sets == 0), "payload: bad sets");
+  // ---- every refusal, before any device work ----
+  std::vector<PayOpDev> prog((size_t)n_ops);
+  std::vector<int8_t> set_kind((size_t)n_sets, 0);        // 0 = unused, 1 = uint32, 2 = double, 3 = a pattern blob
+  struct TextOp {                                         // one HX_PAY_TEXT_ALL: a k_payload_text launch + PAY_D_BITS
+    int at;
+    const hx_index::PayCol* c;
+    std::vector<PayTextPat> pats;
+    size_t pat_off = 0;
+  };
+  std::vector<TextOp> texts;
+  int depth = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    const hx_pay_op& o = ops[i];
+    PayOpDev d{0u, 0u, o.imm, nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
+    int pops = 0;
+    const hx_index::PayCol* c = nullptr;
+    const bool list_op = o.op >= HX_PAY_ANY_EQ && o.op <= HX_PAY_IS_EMPTY_LIST;
+    const bool reads_col = (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_GE) || list_op || o.op == HX_PAY_TEXT_ALL;
+    if (reads_col) {
+      c = &pay_col(h, o.col);
+      HX_CHECK(c->filled == h->n, "payload: column " + std::to_string(o.col) + " is not filled to the index's row count");
+      d.p0 = c->p0;
+      d.p1 = c->kind == HX_PAY_F64 ? c->p1 : nullptr;
+      if (c->list()) {                 // (filled == hx_count > 0 below: off is allocated; no element = never read)
+        d.off = c->off;
+        d.e0 = c->e0;
+        d.e1 = c->kind == HX_PAY_LIST_F64 ? c->e1 : nullptr;
+      }
+      HX_CHECK(!c->text() || (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_PRESENT) || o.op == HX_PAY_TEXT_ALL,
+               "payload: a text column takes IS_MISSING / IS_NULL / PRESENT / TEXT_ALL only");
+      HX_CHECK(!list_op || c->list(), "payload: ANY_EQ / ANY_IN / ANY_RANGE / IS_EMPTY_LIST need a list column");
+      HX_CHECK(!(o.op >= HX_PAY_EQ && o.op <= HX_PAY_GE) || !c->list(),
+               "payload: EQ / IN / LT / LE / GT / GE need a scalar column (a list column takes the ANY ops)");
+      HX_CHECK(o.op != HX_PAY_TEXT_ALL || c->text(),
+               "payload: unknown op " + std::to_string(o.op) + " for this column's kind: TEXT_ALL needs a text column");
+    }
+    const bool f64 = c && (c->kind == HX_PAY_F64 || c->kind == HX_PAY_LIST_F64);
+    switch (o.op) {
+      case HX_PAY_TRUE: d.op = PAY_D_TRUE; break;
+      case HX_PAY_FALSE: d.op = PAY_D_FALSE; break;
+      case HX_PAY_IS_MISSING: d.op = PAY_D_IS_MISSING; break;
+      case HX_PAY_IS_NULL: d.op = PAY_D_IS_NULL; break;
+      case HX_PAY_PRESENT: d.op = PAY_D_PRESENT; break;
+      case HX_PAY_EQ: d.op = f64 ? PAY_D_EQ_F64 : PAY_D_EQ_U32; break;
+      case HX_PAY_IN: d.op = f64 ? PAY_D_IN_F64 : PAY_D_IN_U32; break;
+      case HX_PAY_LT: d.op = PAY_D_LT; break;
+      case HX_PAY_LE: d.op = PAY_D_LE; break;
+      case HX_PAY_GT: d.op = PAY_D_GT; break;
+      case HX_PAY_GE: d.op = PAY_D_GE; break;
+      case HX_PAY_ROW_IN: d.op = PAY_D_ROW_IN; break;
+      case HX_PAY_AND: d.op = PAY_D_AND; pops = 2; break;
+      case HX_PAY_OR: d.op = PAY_D_OR; pops = 2; break;
+      case HX_PAY_NOT: d.op = PAY_D_NOT; pops = 1; break;
+      case HX_PAY_ANY_EQ: d.op = f64 ? PAY_D_ANY_EQ_F64 : PAY_D_ANY_EQ_U32; break;
+      case HX_PAY_ANY_IN: d.op = f64 ? PAY_D_ANY_IN_F64 : PAY_D_ANY_IN_U32; break;
+      case HX_PAY_ANY_RANGE: d.op = PAY_D_ANY_RANGE; break;
+      case HX_PAY_IS_EMPTY_LIST: d.op = PAY_D_IS_EMPTY_LIST; break;
+      case HX_PAY_TEXT_ALL: {          // the blob: uint32 P, uint32 len[P], the patterns' bytes one after another
+        HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
+        const hx_pay_set& ps = sets[o.imm];
+        HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == 3, "payload: one set used as values and as a pattern blob");
+        set_kind[(size_t)o.imm] = 3;
+        HX_CHECK(ps.vals && ps.n >= 4, "payload: a pattern blob starts with its pattern count");
+        const uint8_t* blob = (const uint8_t*)ps.vals;
+        uint32_t np = 0;
+        std::memcpy(&np, blob, 4);
+        HX_CHECK(np >= 1 && np <= HX_PAY_TEXT_MAX_WORDS, "payload: a pattern blob holds 1 to 32 patterns");
+        HX_CHECK(ps.n >= 4 + 4 * (int64_t)np, "payload: the pattern blob's size disagrees with its header");
+        TextOp t;
+        t.at = i;
+        t.c = c;
+        t.pats.assign(np, PayTextPat{});
+        int64_t at = 4 + 4 * (int64_t)np;
+        for (uint32_t k = 0; k < np; ++k) {
+          uint32_t len = 0;
+          std::memcpy(&len, blob + 4 + 4 * k, 4);
+          HX_CHECK(len >= 1 && len <= HX_PAY_TEXT_MAX_WORD_BYTES, "payload: a pattern holds 1 to 64 bytes");
+          HX_CHECK(at + len <= ps.n, "payload: the pattern blob's size disagrees with its header");
+          PayTextPat& pt = t.pats[k];
+          pt.len = len;
+          pt.fmask = len >= 4 ? 0xFFFFFFFFu : (1u << (8 * len)) - 1u;
+          std::memcpy(pt.w, blob + at, len);
+          at += len;
+        }
+        HX_CHECK(at == ps.n, "payload: the pattern blob's size disagrees with its header");
+        texts.push_back(std::move(t));
+        d.op = PAY_D_BITS;
+        d.p0 = nullptr;                // (not a column op on the device: the plane travels in imm)
+        d.off = nullptr;
+        d.e0 = nullptr;
+        break;
+      }
+      default: throw Error("payload: unknown op " + std::to_string(o.op));
+    }
+    if (o.op >= HX_PAY_LT && o.op <= HX_PAY_GE) HX_CHECK(f64, "payload: LT / LE / GT / GE need an F64 column");
+    if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(f64, "payload: ANY_RANGE needs an F64 list column");
+    if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN || o.op == HX_PAY_ANY_IN || o.op == HX_PAY_ANY_RANGE) {
+      HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
+      if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(sets[o.imm].n == 2, "payload: the set of ANY_RANGE holds exactly two doubles, lo <= hi");
+      const int8_t kind = f64 ? 2 : 1;
+      HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == kind, "payload: one set used as uint32 and as double");
+      set_kind[(size_t)o.imm] = kind;
+    }
+    HX_CHECK(depth >= pops, "payload: stack underflow at op " + std::to_string(i));
+    depth += 1 - pops;
+    HX_CHECK(depth <= HX_PAY_MAX_STACK, "payload: the stack exceeds 32 entries at op " + std::to_string(i));
+    prog[(size_t)i] = d;
+  }
+  HX_CHECK(depth == 1, "payload: the program must leave exactly one entry on the stack");
+  const size_t prog_bytes = (size_t)n_ops * sizeof(PayOpDev);
+  std::vector<size_t> set_off((size_t)n_sets, 0);
+  size_t bytes = prog_bytes;
+  for (int s = 0; s < n_sets; ++s) {
+    if (!set_kind[(size_t)s] || set_kind[(size_t)s] == 3) continue;   // (a pattern blob travels per op, checked above)
+    const int64_t m = sets[s].n;
+    HX_CHECK(m >= 0 && m <= 0xFFFFFFFFll && (sets[s].vals || m == 0), "payload: bad set");
+    bool ok = true;
+    if (set_kind[(size_t)s] == 1) {
+      const uint32_t* v = (const uint32_t*)sets[s].vals;
+      for (int64_t i = 1; i < m; ++i) ok &= v[i - 1] <= v[i];
+    } else {
+      const double* v = (const double*)sets[s].vals;
+      for (int64_t i = 0; i < m; ++i) ok &= v[i] == v[i] && (i == 0 || v[i - 1] <= v[i]);
+    }
+    HX_CHECK(ok, "payload: set " + std::to_string(s) + " is not sorted ascending");
+    set_off[(size_t)s] = bytes;
+    bytes += (size_t)round_up(std::max<int64_t>(m, 1) * (set_kind[(size_t)s] == 1 ? 4 : 8), 8);
+  }
+  for (auto& t : texts) {
+    t.pat_off = bytes;
+    bytes += (size_t)round_up((int64_t)(t.pats.size() * sizeof(PayTextPat)), 8);
+  }
+  const int64_t n = h->n;
+  if (n == 0) {
+    if (n_kept) *n_kept = 0;
+    return 0;
+  }
+  // ---- the program, its sets and its patterns: one pinned staging buffer, one copy ----
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  if (h->pay_ev_pending) {              // the device has taken the previous call's program
+    HX_HIP(hipEventSynchronize(h->pay_ev));
+    h->pay_ev_pending = false;
+  }
+  if (bytes > h->pay_pin_cap) {
+    if (h->pay_pin) HX_HIP(hipHostFree(h->pay_pin));
+    h->pay_pin = nullptr;
+    h->pay_pin_cap = 0;
+    const size_t want = (size_t)round_up((int64_t)bytes * 2, 4096);
+    HX_HIP(hipHostMalloc((void**)&h->pay_pin, want, hipHostMallocDefault));
+    h->pay_pin_cap = want;
+  }
+  if (!h->pay_ev) HX_HIP(hipEventCreateWithFlags(&h->pay_ev, hipEventDisableTiming));
+  uint8_t* dev = (uint8_t*)h->ws.get(WS_PAY_PROG, bytes);
+  // one packed verdict plane per TEXT_ALL, written by k_payload_text in front of the mask kernel
+  const int64_t plane_words = (n + 31) / 32;
+  uint32_t* planes = texts.empty() ? nullptr : (uint32_t*)h->ws.get(WS_PAY_PLANES, texts.size() * (size_t)plane_words * 4);
+  for (size_t t = 0; t < texts.size(); ++t) prog[(size_t)texts[t].at].imm = (uint64_t)(uintptr_t)(planes + t * (size_t)plane_words);
+  for (int i = 0; i < n_ops; ++i) {
+    PayOpDev& d = prog[(size_t)i];
+    if (d.op == PAY_D_ANY_RANGE) {     // (two doubles, checked above: the closed interval travels in the op itself)
+      const uint64_t* v = (const uint64_t*)sets[(size_t)d.imm].vals;
+      d.imm = v[0];
+      d.imm2 = v[1];
+      continue;
+    }
+    if (d.op != PAY_D_ROW_IN && d.op != PAY_D_IN_U32 && d.op != PAY_D_IN_F64 && d.op != PAY_D_ANY_IN_U32 &&
+        d.op != PAY_D_ANY_IN_F64)
+      continue;
+    const size_t s = (size_t)d.imm;
+    d.cnt = (uint32_t)sets[s].n;
+    d.imm = (uint64_t)(uintptr_t)(dev + set_off[s]);
+  }
+  std::memcpy(h->pay_pin, prog.data(), prog_bytes);
+  for (int s = 0; s < n_sets; ++s)
+    if (set_kind[(size_t)s] && set_kind[(size_t)s] != 3 && sets[s].n > 0)
+      std::memcpy(h->pay_pin + set_off[(size_t)s], sets[s].vals, (size_t)sets[s].n * (set_kind[(size_t)s] == 1 ? 4 : 8));
+  for (const auto& t : texts) std::memcpy(h->pay_pin + t.pat_off, t.pats.data(), t.pats.size() * sizeof(PayTextPat));
+  HX_HIP(hipMemcpyAsync(dev, h->pay_pin, bytes, hipMemcpyHostToDevice, st));
+  HX_HIP(hipEventRecord(h->pay_ev, st));
+  h->pay_ev_pending = true;
+  uint32_t* kept = nullptr;
+  if (n_kept) {
+    kept = (uint32_t*)h->ws.get(WS_PAY_KEPT, 4);
+    HX_HIP(hipMemsetAsync(kept, 0, 4, st));
+  }
+  for (size_t t = 0; t < texts.size(); ++t)
+    launch_payload_text(texts[t].c->p0, texts[t].c->off, texts[t].c->e0, n, (const PayTextPat*)(dev + texts[t].pat_off),
+                        (int)texts[t].pats.size(), planes + t * (size_t)plane_words, h->pay_grid, st);
+  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, h->pay_grid, st);
+  if (n_kept) {
+    uint32_t* pin = (uint32_t*)host_pin(h) + 14;
+    HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    *n_kept = pin[0];
+  }
+  HX_CATCH
+}
+
+}  // extern "C"
