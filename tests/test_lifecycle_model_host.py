@@ -1,0 +1,451 @@
+"""CPU: the lifecycle sequences of tests/lifecycle_model.py without a GPU.
+
+  * the driver (`apply`, `check`, `run`) on `FakeIndex`, a CPU index with HxIndex's method names that keeps the rows'
+    DATA (not their corpus numbers) and the model's inverted-index rule: a broken driver is found here;
+  * the coverage table of the committed (seed, profile) list, computed from the generator alone and asserted, so that
+    an edit of the op weights cannot thin the sequences silently;
+  * the brute-force restatement: after every op the model equals the state re-derived from the op log, row by row in
+    plain Python."""
+import numpy as np
+import pytest
+
+from rag_application_amd import filters as F
+from rag_application_amd import payload_index as PI
+from tests import lifecycle_model as L
+from tests.payload_helpers import U32_NULL
+
+
+# ---- a CPU index with HxIndex's method names ---------------------------------------------------------------------------
+class FakeParams:
+    def __init__(self, p, mode):
+        self.final_limit, self.mode = p["final_limit"], mode
+
+
+class FakeEngine:
+    HX_MODE_TREE, HX_MODE_H1 = 0, 1
+    HxError = RuntimeError
+
+    @staticmethod
+    def make_params(p, mode=0):
+        return FakeParams(p, mode)
+
+
+class FakeIndex(L.ModelPay):
+    """rows as data: X [n, dim], one (term ids, weights) or None per row; the lists are a plain numpy ranking (dense dot
+    product plus a fingerprint of the sparse vector), enough for `same` to tell two indexes apart"""
+    lens = None                                   # (set by the test: the pool's document lengths, for the Model inside)
+
+    def __init__(self, dim, ms):
+        super().__init__(0)
+        self.dim, self.msizes = dim, ms
+        self.X = np.zeros((0, dim), np.float32)
+        self.sp = []
+        self.inv = L.Model(FakeIndex.profile, np.zeros(1, np.int64))    # only its inverted-index rule is used
+        self.cand = L.PROFILES[FakeIndex.profile]["cand"]
+
+    def _sync(self):
+        """the Model inside sees document lengths only"""
+        m = self.inv
+        m.lens = np.array([0] + [len(v[0]) if v else 0 for v in self.sp], np.int64)
+        m.s = np.arange(1, len(self.sp) + 1)
+        m.x = np.zeros(len(self.sp), np.int64)
+        self.n = len(self.X)
+
+    def close(self):
+        pass
+
+    def count(self):
+        return len(self.X)
+
+    def stats(self):
+        self._sync()
+        return dict(nnz=self.inv.nnz(), n_segments=self.inv.n_segments(), cand8_row_error_max=0.0)
+
+    def dense_candidates(self):
+        return self.cand
+
+    def set_dense_candidates(self, kind):
+        self.cand = kind
+
+    @staticmethod
+    def _docs(ip, si, sv):
+        docs = []
+        for r in range(len(ip) - 1):
+            t = np.asarray(si[ip[r]:ip[r + 1]])
+            if len(np.unique(t)) != len(t):
+                raise RuntimeError("sparse indices must be unique within a vector")
+            docs.append((t.copy(), np.asarray(sv[ip[r]:ip[r + 1]]).copy()))
+        return docs
+
+    def add(self, dense, ip=None, si=None, sv=None):
+        if not np.isfinite(dense).all():
+            raise RuntimeError("dense rows must be finite")
+        docs = self._docs(ip, si, sv)
+        if not len(dense):
+            return
+        self.sp = [v if v is not None else (np.zeros(0, np.int32), np.zeros(0, np.float32)) for v in self.sp] + docs
+        self.X = np.concatenate([self.X, dense])
+        self._sync()
+        self.inv.sp_rows, self.inv.stale = len(self.X), True
+
+    def add_dense(self, dense):
+        self.X = np.concatenate([self.X, dense])
+        self.sp += [None] * len(dense)
+        self._sync()
+
+    def retain(self, keep):
+        n = len(self.X)
+        if len(keep) != n:
+            raise RuntimeError("mask_rows must equal the index's row count")
+        if keep.all():
+            return 0
+        self._sync()
+        super().retain(F.pack_rows(keep))
+        self.inv._retain(dict(keep=keep))
+        self.X, self.sp = self.X[keep], [v for v, k in zip(self.sp, keep) if k]
+        self._sync()
+        return n - len(self.X)
+
+    def replace(self, rows, dense, ip=None, si=None, sv=None):
+        rows = np.asarray(rows, np.int64)
+        if len(np.unique(rows)) != len(rows):
+            raise ValueError("rows must be unique")
+        if not len(rows):
+            return
+        self.X[rows] = dense
+        if ip is not None:
+            for r, d in zip(rows, self._docs(ip, si, sv)):
+                self.sp[int(r)] = d
+            if rows.max() >= self.inv.sp_rows:
+                self.sp = [v if v is not None else (np.zeros(0, np.int32), np.zeros(0, np.float32)) for v in self.sp]
+                self.inv.sp_rows = len(self.X)
+            self.inv.base = self.inv.tail = 0
+            self.inv.stale = True
+        self._sync()
+
+    def truncate(self, k):
+        m = self.inv
+        super().truncate(k)
+        if k == len(self.X) and m.sp_rows <= k:
+            return
+        self.X, self.sp = self.X[:k], self.sp[:k]
+        m.sp_rows, m.tail, m.stale = min(m.sp_rows, k), 0, True
+        if m.base > m.sp_rows:
+            m.base = 0
+        self._sync()
+
+    def finalize(self):
+        self._sync()
+        self.inv.finalize()
+        self.sp = [v if v is not None or r >= self.inv.sp_rows else (np.zeros(0, np.int32), np.zeros(0, np.float32))
+                   for r, v in enumerate(self.sp)]
+
+    def rebuild_sparse(self):
+        self.inv.base = self.inv.tail = 0
+        self.inv.stale = True
+        self.finalize()
+
+    saved = {}
+
+    def save(self, path):
+        FakeIndex.saved[path] = (self.X.copy(), list(self.sp), self.inv.sp_rows)
+
+    @classmethod
+    def load(cls, path):
+        X, sp, sp_rows = cls.saved[path]
+        ix = cls(X.shape[1], L.MS)
+        ix.X, ix.sp = X, sp
+        ix._sync()
+        ix.inv.sp_rows, ix.inv.stale = sp_rows, sp_rows > 0
+        return ix
+
+    def debug_row(self, which, row):
+        x = self.X[row]
+        return x if which == 0 else x[:64] if which == 1 else np.round(x * 100).astype(np.int8) if which < 6 else x[:1]
+
+    def hybrid_query_host(self, Q, qip, qsi, qsv, hp, mask=None):
+        self.finalize()
+        n, L_ = len(self.X), hp.final_limit
+        keep = np.ones(n, bool) if mask is None else np.asarray(mask, bool)
+        assert len(keep) == n
+        finger = np.array([float(v[1].sum()) + len(v[0]) if v else 0.0 for v in self.sp], np.float32)
+        rows = np.flatnonzero(keep)
+        s, i = np.full((len(Q), L_), -np.inf, np.float32), np.full((len(Q), L_), -1, np.int64)
+        c = np.zeros(len(Q), np.int32)
+        for b in range(len(Q)):
+            sc = (self.X[rows] @ Q[b] + (1 + hp.mode) * 1e-3 * finger[rows]).astype(np.float32)
+            top = np.lexsort((rows, -sc))[:L_]
+            c[b] = len(top)
+            s[b, :len(top)], i[b, :len(top)] = sc[top], rows[top]
+        return s, i, c
+
+    @staticmethod
+    def mask_host(mask):
+        return mask
+
+
+@pytest.fixture(scope="module")
+def lens(synth_tables):
+    return {name: L.pool_lens(name, synth_tables) for name in L.PROFILES}
+
+
+# ---- the driver on the fake ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed,profile", L.CASES)
+def test_driver_on_the_fake(synth_tables, tmp_path, seed, profile):
+    FakeIndex.profile = profile
+    L.run(FakeEngine, FakeIndex, seed, profile, synth_tables, tmp_path, oracle=False)
+
+
+def test_driver_reports_seed_step_and_log_and_notices_a_wrong_index(synth_tables, tmp_path):
+    """an index whose retain loses the last kept row's vector: the driver fails at the first retain that removes rows
+    and leaves some, and names the seed, the step and the ops so far"""
+    class Forgetful(FakeIndex):
+        def retain(self, keep):
+            removed = super().retain(keep)
+            if removed and len(self.X):
+                self.X[-1] = 0
+            return removed
+    FakeIndex.profile = "small"
+    ops = L.sequence(13, 30, "small", synth_tables)
+    first = next(i for i, op in enumerate(ops) if op["kind"] == "retain" and 0 < op["keep"].sum() < len(op["keep"]))
+    with pytest.raises(AssertionError, match=rf"seed 13 profile small step {first}: .*\nops so far: add\(") as e:
+        L.run(FakeEngine, Forgetful, 13, "small", synth_tables, tmp_path, oracle=False)
+    assert str(e.value).split("ops so far:")[1].split()[-2].startswith("retain(")
+
+
+# ---- the coverage table ----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def table(lens):
+    return coverage(L.CASES, lens)
+
+
+def coverage(cases, lens):
+    """what the sequences of `cases` cover, from the generator alone"""
+    t = dict(inv=set(), full=set(), dropped_by_retain=0, regrown=0, mid_save_loads=0, noops=set(), refused=set(),
+             touch=set(), pay=set(), segments=set(), dense_tail=set())
+    for seed, profile in cases:
+        n_ops = L.PROFILES[profile]["n_ops"]
+        ops, states = L.sequence(seed, n_ops, profile, lens=lens[profile], with_states=True)
+        m = L.Model(profile, lens[profile])
+        tail_searched, scanned_n = False, -1
+        for step, (op, st) in enumerate(zip(ops, states)):
+            k = op["kind"]
+            real = k
+            if k == "replace":
+                real = "replace_sparse" if op["sparse"] else "replace_dense"
+                if not len(op["rows"]):
+                    t["noops"].add("replace m=0")
+            if k == "retain" and op["keep"].all():
+                t["noops"].add("retain all")
+            if k == "truncate" and op["n"] == st["n"]:
+                t["noops"].add("truncate n")
+            noop = (k == "replace" and not len(op["rows"]) or k == "retain" and op["keep"].all() or
+                    k == "truncate" and op["n"] == st["n"])
+            if real in L.MUTATING:
+                t["inv"].add((real, st["inv"]))
+            if k in ("retain", "truncate", "replace") and not noop:
+                for key in st["full"]:
+                    t["full"].add((key, k))              # (an op that moves or rewrites rows under a full column)
+            if k == "truncate" and op["form"] in ("tail", "below_base") and st["inv"] == "base+tail":
+                t["cuts with a tail"] = t.get("cuts with a tail", set()) | {op["form"]}
+            if op.get("form") == "refill" and op["search"] and len(op["rows"]) > 1:
+                t["refills"] = t.get("refills", 0) + 1
+                # ... back to the count of the last scan, at least a tile of rows exchanged, the index not loaded since,
+                # and more rows than the first chunk of a scan, which passes every row (engine.hip geometry_sizes:
+                # 4096 with int8 candidates): only the chunks behind it prune by the maxima
+                if (m.n + len(op["rows"]) == scanned_n and len(op["rows"]) >= 256 and profile != "fp16_only"
+                        and scanned_n >= 3 * 4096):
+                    t["refills at the scanned count"] = t.get("refills at the scanned count", 0) + 1
+            if k == "retain" and st["lagging"] and not op["keep"].all():
+                t["dropped_by_retain"] += 1
+            if k == "save_load" and 0 < step < n_ops - 1:
+                t["mid_save_loads"] += 1
+            if k == "refused":
+                t["refused"].add(op["form"])
+            if k == "touch":
+                t["touch"].add(op["form"])
+            if k.startswith("pay_"):
+                t["pay"].add(k if k != "pay_append" else "pay_append_short" if len(op["cols"]) == 1 and
+                             len(op["cols"][0][1]) + len(m.pay.cols[m.keys[op["cols"][0][0]]]) < m.n else "pay_append_full")
+            if k in ("retain", "truncate", "replace"):
+                t[k + " forms"] = t.get(k + " forms", set()) | {op.get("form", real)}
+            before = (m.base, m.tail)
+            if profile == "trailing_dense" and m.sp_rows < m.n and real in L.MUTATING and not noop:
+                t["dense_tail"].add(real)             # (an op that meets rows without a sparse row, and changes something)
+                t["dense_tail"].add("searched" if tail_searched else "not searched")
+            m.apply(op)
+            if op["search"]:
+                m.finalize()
+            if k == "save_load":
+                scanned_n = -1
+            if op["search"] or k == "touch" and op["form"] == "search":
+                scanned_n = m.n                       # (the per-tile maxima of the scans are cached for this count)
+            tail_searched = m.sp_rows < m.n and (tail_searched or op["search"])   # (after finalize: it may pad the tail)
+            if profile == "segments":
+                if m.tail and m.tail != before[1]:
+                    t["segments"].add("tail built")
+                if m.base and m.base != before[0] and step:
+                    t["segments"].add("base rebuilt")
+                if m.base > L.SEG_DOCS:
+                    t["segments"].add("two base segments")
+        t["regrown"] += bool(m.regrown)
+    return t
+
+
+def test_coverage_table(table):
+    t = table
+    missing = [(k, s) for k in L.MUTATING for s in L.INV_STATES if (k, s) not in t["inv"]]
+    assert not missing, f"op kinds that never meet an inverted-index state: {missing}"
+    missing = [(key, k) for key in L.PAY_KEYS for k in ("retain", "truncate", "replace") if (key, k) not in t["full"]]
+    assert not missing, f"payload kinds never full at: {missing}"
+    assert t["dropped_by_retain"] >= 1
+    assert t["regrown"] >= 1, "no index is emptied and grown again"
+    assert t["mid_save_loads"] >= 2
+    assert t.get("cuts with a tail") == {"tail", "below_base"}, "no truncate into / below a base that has a tail"
+    assert t.get("refills at the scanned count", 0) >= 1, "no refill meets the cached per-tile maxima of a scan"
+    assert t.get("refills", 0) >= 3, "too few adds that bring the row count back to what it was before a delete"
+    assert t["noops"] == {"retain all", "replace m=0", "truncate n"}
+    assert t["refused"] == set(L.REFUSED_FORMS)
+    assert t["touch"] == set(L.TOUCH_FORMS)
+    assert t["pay"] == {"pay_create", "pay_drop", "pay_append_full", "pay_append_short", "pay_replace"}
+    assert t["retain forms"] == set(L.RETAIN_FORMS) and t["truncate forms"] == set(L.TRUNCATE_FORMS)
+    assert t["segments"] == {"tail built", "base rebuilt", "two base segments"}
+    assert t["dense_tail"] == set(L.MUTATING) | {"searched", "not searched"}, t["dense_tail"]
+
+
+def test_sequences_are_prefixes_of_longer_ones(lens):
+    a = L.sequence(3, 12, "small", lens=lens["small"])
+    b = L.sequence(3, 30, "small", lens=lens["small"])
+    assert [L.brief(x) for x in a] == [L.brief(x) for x in b[:12]]
+
+
+# ---- the brute-force restatement -----------------------------------------------------------------------------------------
+def replay(ops, profile, lens):
+    """the state after `ops`, re-derived from the log from scratch: Python lists, one row at a time"""
+    p = L.PROFILES[profile]
+    pays, pidx = L.payloads()
+    seg = int(p["env"].get("HX_DEBUG_SEG_DOCS", 32768))
+    rows, sp_rows, base, tail, stale = [], 0, 0, 0, False      # rows: [dense corpus row, sparse corpus row or None]
+    cols, ids, nxt = {}, {}, 0                                  # column id -> list of payload dicts; key -> column id
+
+    def nnz():
+        return sum(int(lens[s]) for _, s in rows[:sp_rows] if s is not None)
+
+    def finalize():
+        nonlocal sp_rows, base, tail, stale
+        if not stale:
+            return
+        if nnz() > 0:
+            sp_rows = max(sp_rows, len(rows))
+            limit = int(p["env"]["HX_DEBUG_TAIL_MIN"]) if "HX_DEBUG_TAIL_MIN" in p["env"] else max(base // 4, 2 ** 18)
+            if base == 0 or sp_rows - base > limit:
+                base, tail = sp_rows, 0
+            elif sp_rows > base:
+                tail = sp_rows - base if any(s is not None and lens[s] for _, s in rows[base:sp_rows]) else 0
+        else:
+            base = tail = 0
+        stale = False
+
+    for op in ops:
+        k = op["kind"]
+        if k == "add":
+            rows += [[int(r), int(r) if op["sparse"] else None] for r in op["rows"]]
+            if op["sparse"] and len(op["rows"]):
+                sp_rows, stale = len(rows), True
+        elif k == "retain" and not op["keep"].all():
+            n = len(rows)
+            for c in [c for c in cols if len(cols[c]) != n]:
+                del cols[c]
+            ids = {key: c for key, c in ids.items() if c in cols}
+            for c in cols:
+                cols[c] = [v for v, kp in zip(cols[c], op["keep"]) if kp]
+            if sp_rows:
+                sp_rows = sum(bool(kp) for kp in op["keep"][:sp_rows])
+            rows = [r for r, kp in zip(rows, op["keep"]) if kp]
+            base, tail, stale = 0, 0, True
+        elif k == "replace" and len(op["rows"]):
+            for r, new in zip(op["rows"], op["new"]):
+                rows[int(r)][0] = int(new)
+                if op["sparse"]:
+                    rows[int(r)][1] = int(new)
+            if op["sparse"]:
+                if max(op["rows"]) >= sp_rows:
+                    sp_rows = len(rows)
+                base, tail, stale = 0, 0, True
+        elif k == "truncate":
+            cut = op["n"]
+            for c in cols:
+                cols[c] = cols[c][:cut]
+            if not (cut == len(rows) and sp_rows <= cut):
+                rows = rows[:cut]
+                sp_rows = min(sp_rows, cut)
+                tail, stale = 0, True
+                if base > sp_rows:
+                    base = 0
+        elif k == "save_load":
+            cols, ids, nxt = {}, {}, 0
+            base, tail, stale = 0, 0, sp_rows > 0
+        elif k == "touch" and op["form"] != "set_dense_candidates":
+            if op["form"] == "rebuild_sparse":
+                base, tail, stale = 0, 0, True
+            finalize()
+        elif k == "pay_create":
+            cols[nxt], ids[op["key"]] = [], nxt
+            nxt += 1
+        elif k == "pay_drop":
+            del cols[ids.pop(op["key"])]
+        elif k == "pay_append":
+            for key, src in op["cols"]:
+                cols[ids[key]] += [pays[int(i)] for i in src]
+        elif k == "pay_replace":
+            for r, i in zip(op["rows"], op["src"]):
+                cols[ids[op["key"]]][int(r)] = pays[int(i)]
+        if op["search"]:
+            finalize()
+    return rows, sp_rows, (base, tail, stale), cols, ids, seg
+
+
+def decoded(pay, col, r):
+    kind = pay.kind_of(col)
+    if kind == L.PAY_TEXT:
+        return pay.payload_debug_text(col, r)
+    if kind in (L.PAY_LIST_U32, L.PAY_LIST_F64):
+        h, v = pay.payload_list(col, r, kind)
+        return h, np.asarray(v).tobytes()
+    return pay.payload_cell(col, r, kind)
+
+
+def encoded(key, payload):
+    """one payload's cell of `key` as the debug entries give it, through the encoder alone"""
+    _, pidx = L.payloads()
+    cells = pidx.encode(key, [payload])
+    if not isinstance(cells, tuple):
+        return int(cells[0])
+    h = int(cells[0][0])
+    if isinstance(cells[1], bytes):
+        return h, cells[1]
+    return (h if h >= U32_NULL else len(cells[1])), np.asarray(cells[1]).tobytes()
+
+
+@pytest.mark.parametrize("seed,profile", L.CASES)
+def test_model_equals_the_state_rederived_from_the_log(lens, seed, profile):
+    n_ops = L.PROFILES[profile]["n_ops"]
+    ops = L.sequence(seed, n_ops, profile, lens=lens[profile])
+    m = L.Model(profile, lens[profile])
+    for step, op in enumerate(ops):
+        m.apply(op)
+        if op["search"]:
+            m.finalize()
+        if profile == "segments" and step not in (0, n_ops - 1):
+            continue                                        # (40,000 rows one at a time: the ends only)
+        rows, sp_rows, inv, cols, ids, seg = replay(ops[:step + 1], profile, lens[profile])
+        what = (seed, profile, step, L.brief(op))
+        assert m.x.tolist() == [r[0] for r in rows], what
+        assert m.s.tolist() == [-1 if r[1] is None else r[1] for r in rows], what
+        assert (m.sp_rows, (m.base, m.tail, m.stale)) == (sp_rows, inv), what
+        assert m.n_segments() == -(-inv[0] // seg) - (-inv[1] // seg), what
+        assert m.keys == ids and set(m.pay.cols) == set(cols), what
+        for key, c in ids.items():
+            assert len(m.pay.cols[c]) == len(cols[c]), what + (key,)
+            for r in np.unique(np.linspace(0, len(cols[c]) - 1, 40).astype(int)) if cols[c] else []:
+                assert decoded(m.pay, c, int(r)) == encoded(key, cols[c][int(r)]), what + (key, int(r))
