@@ -613,6 +613,48 @@ int hx_hybrid_query_mmr_host(hx_index* h, const float* q_dense_host, const int64
                              int32_t candidates_limit, int32_t limit, float diversity, float* scores_host,
                              int64_t* ids_host, float* values_host, int32_t* counts_host);
 
+/* ---- payload facets -------------------------------------------
+ * Qdrant's facet(collection, key, facet_filter, limit, exact) (additive: the reference never calls it; parity unpinned, the
+ * semantics below are this project's statement of it): for every value of a keyword or bool field, the number of points a
+ * filter keeps that hold the value -- a list-valued field holds a value when some element equals it, and a point counts
+ * ONCE per value however often its list repeats it; missing, null and [] contribute nothing -- and of those the `limit`
+ * values with the largest counts, count descending, value ascending.  The engine sees codes: the caller keeps the
+ * dictionary and hands over the position of every code's value in sorted order.
+ *
+ * hx_payload_facet is the count.  col = an HX_PAY_U32 or HX_PAY_LIST_U32 column filled to hx_count; mask_dev = a packed
+ * row mask in the layout of hx_payload_mask, NULL = every row, otherwise mask_rows must equal hx_count;
+ *   counts_dev [n_codes] uint32   entry c = the kept rows holding code c; EVERY entry is written, zeros included;
+ *   stray_dev [1] uint64          the kept cells / elements (each one, repeats included) whose code is >= n_codes and below
+ *                                 HX_PAY_U32_NULL: the engine cannot know the caller's dictionary, a caller that sees a
+ *                                 non-zero stray knows its dictionary is out of step with the column.
+ * Everything is enqueued on `stream`; nothing is read back.  Refused before any device work, both outputs untouched: a
+ * NULL h, counts_dev or stray_dev, n_codes of 0 or above 0xFFFFFFFE, an unknown column, a column of another kind ("kind"
+ * in the message), a column not filled to hx_count, mask_rows != hx_count with a mask.
+ * n_codes <= HX_FACET_LDS_CODES is counted in a histogram per workgroup in LDS (64 KB: two workgroups per CU), anything
+ * above with global atomics; the counts are the same either way.
+ *
+ * hx_facet_top is the ranking: the at most `limit` codes of counts_dev [n_codes] with a non-zero count, each as a key
+ * count << 32 | (0xFFFFFFFF - rank), sorted descending -- rank = rank_dev[code], or the code itself when rank_dev is NULL.
+ * rank_dev [n_codes] uint32 is a permutation of [0, n_codes): the position of each code's value in sorted order, which is
+ * how the tie order "value ascending" reaches the device without a string crossing the ABI.  out_keys_dev [limit]: every
+ * slot is written, the slots past the hits are 0; *out_count_dev (int32) = the hits.  Everything is enqueued on `stream`;
+ * the scratch (8 bytes per code at most) is the index's.  Refused before any device work: a NULL h, counts_dev,
+ * out_keys_dev or out_count_dev, n_codes of 0 or above 0xFFFFFFFE, limit outside [1, 2048].
+ *
+ * hx_payload_facet_host is the whole call, host in, host out: mask_host NULL = every row; rank_host NULL or [n_codes];
+ * the two stages with scratch from the index, one synchronisation.  ranks_or_codes_host [limit] uint32 = the hits' ranks
+ * when rank_host is given, their codes when it is NULL; counts_host [limit] uint32 their counts; both 0 past *n_out
+ * (int32) hits; *stray_host as above (a caller that sees it non-zero discards the hits).  Refusals: those of the two
+ * stages, and a NULL output. */
+#define HX_FACET_LDS_CODES 16384
+int hx_payload_facet(hx_index* h, int32_t col, const uint32_t* mask_dev, int64_t mask_rows, uint32_t n_codes,
+                     uint32_t* counts_dev, uint64_t* stray_dev, void* stream);
+int hx_facet_top(hx_index* h, const uint32_t* counts_dev, uint32_t n_codes, const uint32_t* rank_dev, int32_t limit,
+                 uint64_t* out_keys_dev, int32_t* out_count_dev, void* stream);
+int hx_payload_facet_host(hx_index* h, int32_t col, const uint32_t* mask_host, int64_t mask_rows, uint32_t n_codes,
+                          const uint32_t* rank_host, int32_t limit, uint32_t* ranks_or_codes_host, uint32_t* counts_host,
+                          int32_t* n_out, uint64_t* stray_host);
+
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
  * Qdrant/bm25 :41, :123), batched (the reference's TODO :100): n texts -> CSR of (term id, weight)

@@ -115,6 +115,10 @@ _SIGS = {
     "hx_mmr": [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int64, _P, _P, _P, _P],
     "hx_hybrid_query_mmr_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, _P, _P, _P, _P],
+    "hx_payload_facet": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, _P, _P],
+    "hx_facet_top": [_P, _P, C.c_uint32, _P, C.c_int32, _P, _P, _P],
+    "hx_payload_facet_host": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),
+                              C.POINTER(C.c_uint64)],
     "hx_payload_create": [_P, C.c_int32, C.POINTER(C.c_int32)],
     "hx_payload_drop": [_P, C.c_int32],
     "hx_payload_append": [_P, C.c_int32, _P, C.c_int64],

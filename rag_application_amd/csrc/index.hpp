@@ -46,7 +46,8 @@ enum WsSlot {
   WS_SP_EXACT, WS_SP_ECNT, WS_SP_MM, WS_SP_FTAU, WS_SP_FOVF, WS_SP_QPARTS, WS_SP_SUM,
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
   WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
-  WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT
+  WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT,
+  WS_FACET_A, WS_FACET_B, WS_FACET_CNT, WS_FACET_COUNTS, WS_FACET_MASK, WS_FACET_RANK, WS_FACET_OUT
 };
 
 template <typename T>

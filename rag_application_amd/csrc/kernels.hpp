@@ -506,6 +506,28 @@ struct MmrArgs {
   int* out_counts;
 };
 void launch_mmr_select(const MmrArgs& a, int B, hipStream_t st);
+// ---- facet.hip: payload facets (hx_payload_facet / hx_facet_top) ---------------------------------
+// counts[c] += the rows r < n whose bit is set in mask (NULL: every row) and whose cell holds code c < n_codes: p0[r] == c
+// for a scalar column (off == NULL), some element of e0[off[r], off[r + 1]) == c for a list column -- a row counts once
+// per code.  *stray += the kept cells / elements with a code in [n_codes, HX_PAY_U32_NULL).  The caller zeroes both.
+struct FacetArgs {
+  const uint32_t* p0;
+  const int64_t* off;
+  const uint32_t* e0;
+  const uint32_t* mask;
+  int64_t n;
+  uint32_t n_codes;
+  uint32_t* counts;
+  unsigned long long* stray;
+};
+// grid_cap as launch_payload_mask takes it
+void launch_facet_count(const FacetArgs& a, int grid_cap, hipStream_t st);
+// The top stage's first pass: list s = the keys count << 32 | (0xFFFFFFFF - rank) (rank[c], or c when rank is NULL) of the
+// non-zero counters among codes [s * FACET_SLICE, (s + 1) * FACET_SLICE), 0 = an empty slot, lists[s * list_len ..]:
+// list_len <= 512 = the slice's best list_len keys, sorted; list_len = FACET_SLICE = all of them, in code order.
+constexpr int FACET_SLICE = 2048;
+void launch_facet_keys(const uint32_t* counts, uint32_t n_codes, const uint32_t* rank, uint64_t* lists, int list_len,
+                       hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

@@ -261,6 +261,65 @@ static void pay_row_span(hx_index* h, const PayCol& c, int64_t row, const void* 
   HX_HIP(hipMemcpy(o, c.off + row, 16, hipMemcpyDeviceToHost));
 }
 
+// ---- payload facets -------------------------------------------------------------------------------
+// every refusal of hx_payload_facet, before any device work
+static FacetArgs facet_args(hx_index* h, int32_t col, const uint32_t* mask, int64_t mask_rows, uint32_t n_codes) {
+  HX_CHECK(n_codes >= 1 && n_codes <= 0xFFFFFFFEu, "facet: n_codes out of range [1, 0xFFFFFFFE]");
+  const PayCol& c = pay_col(h, col);
+  HX_CHECK(c.kind == HX_PAY_U32 || c.kind == HX_PAY_LIST_U32,
+           "facet: the column kind must be HX_PAY_U32 or HX_PAY_LIST_U32 (keyword codes or bools)");
+  HX_CHECK(c.filled == h->n, "facet: the column is not filled to the index's row count (hx_count)");
+  HX_CHECK(!mask || mask_rows == h->n, "facet: mask_rows must equal the index's row count (hx_count)");
+  FacetArgs a{};
+  a.p0 = c.p0;
+  a.off = c.list() ? c.off : nullptr;
+  a.e0 = c.list() ? c.e0 : nullptr;
+  a.mask = mask;
+  a.n = h->n;
+  a.n_codes = n_codes;
+  return a;
+}
+static void facet_count_enqueue(hx_index* h, FacetArgs a, uint32_t* counts, uint64_t* stray, hipStream_t st) {
+  a.counts = counts;
+  a.stray = (unsigned long long*)stray;
+  HX_HIP(hipMemsetAsync(counts, 0, (size_t)a.n_codes * 4, st));
+  HX_HIP(hipMemsetAsync(stray, 0, 8, st));
+  launch_facet_count(a, h->pay_grid, st);
+}
+static void facet_top_check(uint32_t n_codes, int32_t limit) {
+  HX_CHECK(n_codes >= 1 && n_codes <= 0xFFFFFFFEu, "facet: n_codes out of range [1, 0xFFFFFFFE]");
+  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "facet: limit out of range [1, 2048]");
+}
+// The slices' lists (launch_facet_keys) merged by the compaction, at most CAND_CAP keys per merged list, until one list
+// is left: the top L of a union lies in the union of the top Ls.  A round turns k lists of `len`
+// keys into ceil(k / g) lists of `limit` keys, g = CAND_CAP / len.
+static void facet_top_enqueue(hx_index* h, const uint32_t* counts, uint32_t n_codes, const uint32_t* rank, int limit,
+                              uint64_t* out_keys, int32_t* out_count, hipStream_t st) {
+  int len = limit <= 512 ? limit : FACET_SLICE;
+  int64_t lists = ((int64_t)n_codes + FACET_SLICE - 1) / FACET_SLICE;
+  const int64_t g0 = CAND_CAP / len, g1 = CAND_CAP / limit;
+  const size_t keys = (size_t)std::max((lists + g0) * len, ((lists + g0 - 1) / g0 + g1) * limit);
+  uint64_t* cur = (uint64_t*)h->ws.get(WS_FACET_A, keys * 8);
+  uint64_t* nxt = (uint64_t*)h->ws.get(WS_FACET_B, keys * 8);
+  int* cnt = (int*)h->ws.get(WS_FACET_CNT, (size_t)((lists + g0 - 1) / g0) * 4);
+  launch_facet_keys(counts, n_codes, rank, cur, len, st);
+  for (;;) {
+    const int64_t g = CAND_CAP / len;
+    if (lists <= g) {
+      launch_compact(cur, (int)(lists * len), nullptr, 1, limit, 0, out_keys, limit, out_count, nullptr,
+                     (int)(lists * len), st);
+      return;
+    }
+    const int64_t groups = (lists + g - 1) / g;
+    if (groups * g > lists)              // the last group's missing lists read as empty
+      HX_HIP(hipMemsetAsync(cur + lists * len, 0, (size_t)(groups * g - lists) * len * 8, st));
+    launch_compact(cur, (int)(g * len), nullptr, (int)groups, limit, 0, nxt, limit, cnt, nullptr, (int)(g * len), st);
+    std::swap(cur, nxt);
+    lists = groups;
+    len = limit;
+  }
+}
+
 }  // namespace hx
 
 extern "C" {
@@ -690,6 +749,68 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
     HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     *n_kept = pin[0];
+  }
+  HX_CATCH
+}
+
+int hx_payload_facet(hx_index* h, int32_t col, const uint32_t* mask_dev, int64_t mask_rows, uint32_t n_codes,
+                     uint32_t* counts_dev, uint64_t* stray_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && counts_dev && stray_dev, "NULL argument");
+  const FacetArgs a = facet_args(h, col, mask_dev, mask_rows, n_codes);
+  h->set_device();
+  facet_count_enqueue(h, a, counts_dev, stray_dev, (hipStream_t)stream);
+  HX_CATCH
+}
+
+int hx_facet_top(hx_index* h, const uint32_t* counts_dev, uint32_t n_codes, const uint32_t* rank_dev, int32_t limit,
+                 uint64_t* out_keys_dev, int32_t* out_count_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && counts_dev && out_keys_dev && out_count_dev, "NULL argument");
+  facet_top_check(n_codes, limit);
+  h->set_device();
+  facet_top_enqueue(h, counts_dev, n_codes, rank_dev, limit, out_keys_dev, out_count_dev, (hipStream_t)stream);
+  HX_CATCH
+}
+
+int hx_payload_facet_host(hx_index* h, int32_t col, const uint32_t* mask_host, int64_t mask_rows, uint32_t n_codes,
+                          const uint32_t* rank_host, int32_t limit, uint32_t* ranks_or_codes_host, uint32_t* counts_host,
+                          int32_t* n_out, uint64_t* stray_host) {
+  HX_TRY
+  HX_CHECK(h && ranks_or_codes_host && counts_host && n_out && stray_host, "NULL argument");
+  facet_top_check(n_codes, limit);
+  FacetArgs a = facet_args(h, col, mask_host, mask_rows, n_codes);
+  h->set_device();
+  hipStream_t st = nullptr;
+  const size_t mask_bytes = (size_t)((h->n + 31) / 32) * 4;
+  if (mask_host && mask_bytes) {
+    uint32_t* m = (uint32_t*)h->ws.get(WS_FACET_MASK, mask_bytes);
+    HX_HIP(hipMemcpyAsync(m, mask_host, mask_bytes, hipMemcpyHostToDevice, st));
+    a.mask = m;
+  } else {
+    a.mask = nullptr;
+  }
+  uint32_t* rank = nullptr;
+  if (rank_host) {
+    rank = (uint32_t*)h->ws.get(WS_FACET_RANK, (size_t)n_codes * 4);
+    HX_HIP(hipMemcpyAsync(rank, rank_host, (size_t)n_codes * 4, hipMemcpyHostToDevice, st));
+  }
+  uint32_t* counts = (uint32_t*)h->ws.get(WS_FACET_COUNTS, (size_t)n_codes * 4);
+  // the results, one block and one copy: [limit keys | the hits (int32, in an 8-byte slot) | stray]
+  uint64_t* out = (uint64_t*)h->ws.get(WS_FACET_OUT, ((size_t)limit + 2) * 8);
+  facet_count_enqueue(h, a, counts, out + limit + 1, st);
+  facet_top_enqueue(h, counts, n_codes, rank, limit, out, (int32_t*)(out + limit), st);
+  std::vector<uint64_t> res((size_t)limit + 2);
+  HX_HIP(hipMemcpyAsync(res.data(), out, res.size() * 8, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  int32_t hits = 0;
+  std::memcpy(&hits, &res[(size_t)limit], 4);
+  *n_out = hits;
+  *stray_host = res[(size_t)limit + 1];
+  for (int32_t i = 0; i < limit; ++i) {
+    const uint64_t k = res[(size_t)i];
+    ranks_or_codes_host[i] = k ? 0xFFFFFFFFu - (uint32_t)k : 0u;
+    counts_host[i] = (uint32_t)(k >> 32);
   }
   HX_CATCH
 }

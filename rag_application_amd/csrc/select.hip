@@ -109,47 +109,7 @@ __global__ __launch_bounds__(NT) void k_compact(const uint64_t* __restrict__ key
 // is a bitonic run holding the best 64 E of both, sorted again by the last stages.  One barrier per round
 // instead of one per stage (66 at P = 2048).
 // ---------------------------------------------------------------------------------
-// The fold itself, for a block of exactly NW waves: src[0, n) (n <= NW * 64 E) -> wave 0 holds the best 64 E keys in v,
-// sorted (index lane * E + e); returns the number of non-empty keys.  Every thread of the block must call it.
-template <int NW, int E, typename LOAD>
-__device__ __forceinline__ int compact_top_core(LOAD&& load, int n, uint64_t (&v)[E], int lane, int w) {
-  constexpr int R = 64 * E;          // keys per wave
-  // a wave hands its run to its partner through slot w / 2: the only earlier reader of that slot is the wave itself
-  // (as the partner of wave w + 1 in the first round), so NW / 2 slots serve every round
-  __shared__ uint64_t buf[NW > 1 ? (NW / 2) * R : 1];
-  __shared__ int s_tot[NW];
-  int tot = 0;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {   // the order inside an unsorted run is free: coalesced loads
-    const int i = w * R + e * 64 + lane;
-    v[e] = i < n ? load(i) : 0ull;
-    tot += __popcll(__ballot(v[e] != 0ull));
-  }
-  if (n > w * R) w_sort<R>(v, lane);
-  if (NW > 1) {
-    if (lane == 0) s_tot[w] = tot;
-#pragma unroll
-    for (int s = 0; (1 << s) < NW; ++s) {
-      const int m = (2 << s) - 1;
-      if ((w & m) == (1 << s)) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) buf[(w >> 1) * R + lane * E + e] = v[e];
-      }
-      __syncthreads();   // also: every wave's loads have landed before any store below (in-place use)
-      const int pw = w + (1 << s);
-      if ((w & m) == 0 && n > pw * R) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) v[e] = k64max(v[e], buf[(pw >> 1) * R + (R - 1) - (lane * E + e)]);
-        w_merge<R, R / 2>(v, lane);
-      }
-    }
-    tot = 0;
-#pragma unroll
-    for (int x = 0; x < NW; ++x) tot += s_tot[x];
-  }
-  return tot;
-}
-
+// (the fold itself, compact_top_core, is in wsort.hpp: facet.hip folds the same way)
 template <int NW, int E>
 __global__ __launch_bounds__(NW * 64) void k_compact_top(const uint64_t* __restrict__ keys, int stride,
                                                          const int* __restrict__ in_cnt, int keep,

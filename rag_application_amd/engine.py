@@ -590,6 +590,70 @@ class HxIndex:
                                                      _ptr(counts)))
         return scores, ids, counts
 
+    # -- payload facets (hx.h: hx_payload_facet / hx_facet_top / hx_payload_facet_host) --------
+    def payload_facet(self, col: int, n_codes: int, mask: Optional[torch.Tensor] = None, counts=None, stray=None):
+        """How many kept rows hold each code below n_codes of the U32 or LIST_U32 column `col` (hx_payload_facet).  mask:
+        None = every row, or the packed words as payload_mask returns them (an int32 device tensor).  Returns (counts
+        [n_codes] int32 holding the uint32 counts, stray [1] int64: the kept cells / elements with a code at or above
+        n_codes).  counts / stray: the tensors to write (tests hand in sentinels).  Only enqueues work."""
+        n_codes = int(n_codes)
+        if not 0 <= n_codes <= 0xFFFFFFFF:
+            raise HxError("facet: n_codes out of range [1, 0xFFFFFFFE]")
+        rows = 0
+        if mask is not None:
+            mask = _need_cuda(mask, torch.int32, "mask")
+            rows = self.count()
+            if mask.shape[0] != (rows + 31) // 32:
+                raise ValueError(f"mask: {mask.shape[0]} words for {rows} rows")
+        if counts is None:
+            counts = torch.empty((n_codes if 1 <= n_codes <= 0xFFFFFFFE else 1,), dtype=torch.int32, device=self._tdev)
+        if stray is None:
+            stray = torch.empty((1,), dtype=torch.int64, device=self._tdev)
+        check(_lib.lib().hx_payload_facet(self._h, int(col), _ptr(mask), rows, n_codes, _ptr(counts),
+                                          _ptr(stray), _stream()))
+        return counts, stray
+
+    def facet_top(self, counts: torch.Tensor, limit: int, rank: Optional[torch.Tensor] = None, out=None, out_count=None):
+        """The at most `limit` codes of counts [n_codes] with a non-zero count (hx_facet_top): keys [limit] int64, each
+        count << 32 | (0xFFFFFFFF - rank), sorted descending, 0 past the hits, and the number of hits [1] int32.  rank:
+        None (a code ranks as itself) or the int32 device tensor [n_codes] holding the uint32 position of each code's
+        value in sorted order.  out / out_count: the tensors to write.  Only enqueues work."""
+        counts = _need_cuda(counts, torch.int32, "counts")
+        if rank is not None:
+            rank = _need_cuda(rank, torch.int32, "rank")
+            if rank.shape[0] != counts.shape[0]:
+                raise ValueError(f"rank: {rank.shape[0]} entries for {counts.shape[0]} codes")
+        L = int(limit)
+        if out is None:
+            out = torch.empty((L if 1 <= L <= 2048 else 1,), dtype=torch.int64, device=counts.device)
+        if out_count is None:
+            out_count = torch.empty((1,), dtype=torch.int32, device=counts.device)
+        check(_lib.lib().hx_facet_top(self._h, _ptr(counts), int(counts.shape[0]), _ptr(rank), L, _ptr(out),
+                                      _ptr(out_count), _stream()))
+        return out, out_count
+
+    def payload_facet_host(self, col: int, n_codes: int, limit: int, rank: Optional[np.ndarray] = None, mask=None):
+        """The whole facet, host in, host out (hx_payload_facet_host): the `limit` codes of the column with the largest
+        counts among the rows of `mask` (None, a bool array or packed np.uint32 words, as hybrid_query_host takes it).
+        rank: None, or np.uint32 [n_codes], the position of each code's value in sorted order.  Returns (ranks_or_codes
+        np.uint32 [hits] -- ranks when `rank` is given, codes otherwise --, counts np.uint32 [hits], stray: int)."""
+        n_codes, L = int(n_codes), int(limit)
+        if not 1 <= L <= 2048:
+            raise HxError("facet: limit out of range [1, 2048]")
+        if not 0 <= n_codes <= 0xFFFFFFFF:
+            raise HxError("facet: n_codes out of range [1, 0xFFFFFFFE]")
+        if rank is not None:
+            rank = np.ascontiguousarray(rank, dtype=np.uint32)
+            if rank.shape[0] != n_codes:
+                raise ValueError(f"rank: {rank.shape[0]} entries for {n_codes} codes")
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        first = np.empty((L,), dtype=np.uint32)
+        counts = np.empty((L,), dtype=np.uint32)
+        n_out, stray = C.c_int32(), C.c_uint64()
+        check(_lib.lib().hx_payload_facet_host(self._h, int(col), _ptr(words), rows, n_codes, _ptr(rank), L,
+                                               _ptr(first), _ptr(counts), C.byref(n_out), C.byref(stray)))
+        return first[:n_out.value], counts[:n_out.value], int(stray.value)
+
     # -- grouped search (hx.h: hx_group / hx_hybrid_query_groups_host; DESIGN.md section 20) -------------------------
     def group(self, col: int, keys: torch.Tensor, counts: Optional[torch.Tensor], n_groups: int, group_size: int):
         """The best n_groups groups of the ranked lists keys [B, stride] (+ counts [B], None = every slot), at most

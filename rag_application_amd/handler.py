@@ -24,6 +24,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from . import engine as _engine
+from . import faceting as _faceting
 from . import filters as _filters
 from . import grouping as _grouping
 from . import payload_index as _pindex
@@ -54,6 +55,14 @@ class PointGroup:
     of the group_by field its hits share (a str, a bool or an int), `hits` = its ScoredPoints, best first."""
     id: Any
     hits: List[ScoredPoint] = field(default_factory=list)
+
+
+@dataclass
+class FacetHit:
+    """One value of a facet (shape-compatible with qdrant_client.http.models.FacetValueHit): `value` = a value of the
+    faceted field (a str, a bool or an int), `count` = the points holding it."""
+    value: Any
+    count: int
 
 
 @dataclass
@@ -142,6 +151,40 @@ class _Collection:
                 pi.declined["engine refused"] = pi.declined.get("engine refused", 0) + 1
         pi.python_evals += 1
         return None
+
+    FACET_SCHEMAS = ("keyword", "bool", "keyword_list", "bool_list")
+
+    def facet(self, key: str, flt, limit: int):
+        """[(value, count)] of the field `key` over the rows `flt` keeps: at most `limit` values, count descending, then
+        value ascending (faceting.py states the rules).  A key with a live keyword / bool (or _list) column is counted
+        and ranked on the device (hx_payload_facet_host) under the packed mask of `flt`; everything else -- an unindexed
+        or poisoned key, another schema, a limit above 2048, an engine refusal, a stray code -- is counted by faceting.py
+        over the payloads under the same mask."""
+        _faceting.check_limit(limit)
+        if not isinstance(key, str) or not key:
+            raise ValueError("key must be a non-empty string (a payload key, dotted paths allowed)")
+        mask = self.row_mask(flt) if flt else None
+        pi = getattr(self, "pindex", None)
+        k = pi.keys.get(key) if pi is not None else None
+        if (k is not None and k.col is not None and k.schema in self.FACET_SCHEMAS and limit <= _faceting.MAX_LIMIT
+                and hasattr(self.index, "payload_facet_host")):
+            n_codes = len(k.codes) if k.elem == "keyword" else 2
+            try:
+                if n_codes == 0:                          # a keyword column that never saw a keyword: nothing to count
+                    pi.facet_device_calls += 1
+                    return []
+                if self.index.count() != len(self.ids):
+                    raise RuntimeError("the engine's row count differs from the payloads'")
+                first, counts, stray = self.index.payload_facet_host(k.col, n_codes, limit, rank=k.ranks(), mask=mask)
+                if stray == 0:
+                    pi.facet_device_calls += 1
+                    return [(k.value_at(r), c) for r, c in zip(first.tolist(), counts.tolist())]
+                logging.warning("facet on %r: %d cells outside the dictionary, Python path taken", key, stray)
+            except Exception as e:                        # never a wrong count: the walk over the payloads is always right
+                logging.warning("facet on %r: the device path failed, Python path taken: %s", key, e)
+        if pi is not None:
+            pi.facet_python_calls += 1
+        return _faceting.facet_top(_faceting.facet_counts(self.payloads, key, keep=mask), limit)
 
     def _poison(self, key: str) -> None:
         k = self.pindex.keys[key]
@@ -289,6 +332,8 @@ class QdrantHandler:
     _grouped_search = True
     # hybrid_search_mmr picks from the pool of ONE engine index, by the rows of that index
     _mmr_search = True
+    # facet counts the payload columns of ONE engine index, or this process's payloads
+    _facets = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -928,6 +973,36 @@ class QdrantHandler:
         except Exception as e:
             logging.error("delete_points(%s) failed: %s", user_id, e)
             raise
+
+    def _facet_sync(self, user_id, key, filters, limit):
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        return [FacetHit(value=v, count=c) for v, c in self._collections[str(user_id)].facet(key, filters, limit)]
+
+    async def facet(self, user_id: str, key: str, filters: Optional[Dict] = None, limit: int = 10,
+                    exact: bool = True) -> List[FacetHit]:
+        """Qdrant's facet(collection, key, facet_filter, limit, exact) (additive; parity unpinned): for every value of the
+        payload field `key` (a dotted path) the number of points `filters` keeps that hold it, and of those the `limit`
+        values with the largest counts -- count descending, then value ascending (bool < int < str between types).  A
+        list-valued field holds each of its elements, a point counts once per value; points without the field, with
+        None or [] there count nowhere; `str`, `bool` and `int` values are counted, everything else is ignored
+        (faceting.py states the rules).  `exact` is accepted and ignored: every count is exact.
+        A field with a live "keyword", "bool", "keyword_list" or "bool_list" payload index is counted and ranked by
+        kernels over the whole column (hx_payload_facet_host); a "number" key, an unindexed or
+        poisoned key, a limit above 2048 or an engine refusal is counted over the payloads in Python.  Both ways give
+        the same hits; `PayloadIndex.facet_device_calls` / `facet_python_calls` say which one ran.
+        A read call: it never raises -- an unknown collection or any error is logged and gives [] -- except on a
+        sharded collection, which refuses it with a ValueError as it refuses the other payload-column features."""
+        if not self._facets:
+            raise ValueError("facet is not supported on a sharded collection")
+        try:
+            if str(user_id) not in self._collections:
+                logging.warning("facet: no collection for %s", user_id)
+                return []
+            return await self._run(self._facet_sync, user_id, key, filters, limit)
+        except Exception as e:
+            logging.error("facet(%s, %r) failed: %s", user_id, key, e)
+            return []
 
     async def get_collection_chunk_count(self, user_id: str, filters: Optional[Dict] = None) -> int:
         try:

@@ -90,6 +90,8 @@ class _Key:
         self.col: Optional[int] = None     # the engine column; None = not live (poisoned, or its column was lost)
         self.codes: Dict[str, int] = {}    # keyword -> code
         self._names: List[str] = []        # code -> keyword, built when a grouped search asks (value_of)
+        self._ranks: Optional[np.ndarray] = None   # code -> position of its keyword in sorted order (ranks)
+        self._sorted: List[str] = []       # position -> keyword
 
     def value_of(self, code: int):
         """The stored value a cell of a "keyword" or "bool" column stands for: what a grouped search names a group by."""
@@ -98,6 +100,28 @@ class _Key:
         if len(self._names) != len(self.codes):           # codes are handed out in order and never taken back
             self._names = list(self.codes)
         return self._names[code]
+
+    def ranks(self) -> Optional[np.ndarray]:
+        """np.uint32 [len(codes)]: the position of each code's keyword in sorted order (Python's order on `str`) -- the
+        rank array of hx_facet_top, which carries the tie order "value ascending" onto the device.  Cached; built again
+        when the dictionary has grown (codes are never taken back).  None for a bool key: False = 0 < True = 1, a code
+        ranks as itself."""
+        if self.elem != "keyword":
+            return None
+        if self._ranks is None or self._ranks.shape[0] != len(self.codes):
+            names = list(self.codes)                          # (in code order: dicts keep insertion order)
+            order = sorted(range(len(names)), key=names.__getitem__)
+            r = np.empty(len(names), np.uint32)
+            r[order] = np.arange(len(names), dtype=np.uint32)
+            self._ranks, self._sorted = r, [names[i] for i in order]
+        return self._ranks
+
+    def value_at(self, rank: int):
+        """The keyword at a position of the sorted order `ranks` describes (a bool key: the code's value)."""
+        if self.elem != "keyword":
+            return bool(rank)
+        self.ranks()
+        return self._sorted[rank]
 
     @property
     def is_list(self) -> bool:
@@ -127,6 +151,8 @@ class PayloadIndex:
         self.python_evals = 0              # masks evaluated by the Python loop
         self.declined: Dict[str, int] = {}  # reason -> filters that did not compile
         self.group_device_calls = 0        # grouped searches served by hx_hybrid_query_groups_host
+        self.facet_device_calls = 0        # facets served by hx_payload_facet_host
+        self.facet_python_calls = 0        # facets counted by faceting.py over the payloads
 
     # -- definitions -----------------------------------------------------------------------------------------------
     def definitions(self) -> Dict[str, str]:

@@ -475,6 +475,7 @@ class ShardedHandler(QdrantHandler):
     _payload_indexes = False         # create_payload_index raises ValueError: payloads live on the front rank only
     _grouped_search = False          # hybrid_search_groups raises ValueError: nothing is sent to the ranks
     _mmr_search = False              # hybrid_search_mmr raises ValueError: nothing is sent to the ranks
+    _facets = False                  # facet raises ValueError: payload columns live in one engine index only
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
