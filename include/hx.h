@@ -613,6 +613,93 @@ int hx_hybrid_query_mmr_host(hx_index* h, const float* q_dense_host, const int64
                              int32_t candidates_limit, int32_t limit, float diversity, float* scores_host,
                              int64_t* ids_host, float* values_host, int32_t* counts_host);
 
+/* ---- late-interaction rerank -------------------------------------
+ * Qdrant's multivector with comparator=MAX_SIM used as the rescoring query over the hybrid prefetch (additive: the
+ * reference's "late interaction reranking" mean-pools one vector per text, qdrant_handler.py:379-382; parity unpinned, the
+ * semantics below are this project's statement of it).  Additive to the ABI: HX_ABI_VERSION stays 3.
+ *
+ * Token form.  A token is dim_t int8 values x8[k] and one fp32 scale s, s finite and s >= 0; dim_t is a multiple of 64 in
+ * [64, HX_TOKENS_MAX_DIM].  The HOST quantises, the engine only ever sees bytes (as with text columns); the rule is
+ * prep.hip's, in fp32: amax = max|x|, s = amax / 127, x8 = clip(rint(x * (127 / amax)), -127, 127); amax == 0 gives
+ * x8 = 0 and s = 0; non-finite input is refused by the quantiser.  Stored tokens and query tokens are quantised
+ * identically; a model that emits fewer dimensions zero-pads to a multiple of 64, which changes no dot product.
+ *
+ * Score of a query with tokens i < Tq, 1 <= Tq <= HX_MAXSIM_MAX_QTOKENS, against a row with tokens j < Td, Td >= 1:
+ *   1. I_ij = sum_k q8_i[k] * d8_j[k] in int32.  |I| <= 127^2 * 1024 < 2^24, so (float)I_ij is exact: that is why dim_t
+ *      stops at 1024;
+ *   2. m_i = max_j ((float)I_ij * sd_j): one fp32 multiply per pair, the max is order-free;
+ *   3. t_i = m_i * sq_i;
+ *   4. 64 slots: t_0 .. t_{Tq-1}, then +0.0f in every slot >= Tq;
+ *   5. the 64 slots are summed by the balanced pairwise tree in index order -- (t0 + t1), (t2 + t3), ..., then pairs of
+ *      those, six levels; every add is one fp32 add, round to nearest, nothing is fused;
+ *   6. + 0.0f at the end, so that -0 and +0 are one value.
+ * (The tree is the order the C/D layout of a 16-row MFMA tile gives without moving data: the registers of a lane, the lane
+ * groups, the four tiles.  On float32 numpy arrays it is a = a[0::2] + a[1::2], six times.)  The caller keeps
+ * |I| * sd * sq inside the finite range; the engine does not look.
+ * Not eligible: a 0 slot, a position at or past counts_dev[b], a key whose row is not in this index, a row whose cell is
+ * missing or null or holds no token (a point without the vector is not scored, as in Qdrant), a row whose bit is clear in
+ * eligible_dev.  Order: score descending, the smaller pool position first on a tie.
+ *
+ * Storage: HX_PAY_TOKENS, a sixth column kind, one state per row -- missing, null, or Td >= 0 tokens -- made by
+ * hx_payload_create_tokens (hx_payload_create refuses the kind: it has no width to give), dim_t fixed at creation.  On the
+ * device it is stored as a text column is: a head plane (uint32 per row: missing, null or Td), int64 offsets [filled + 1]
+ * counting 32-bit words, and one word plane.  Inside a row: Td x dim_t bytes (token j at byte j * dim_t), then Td fp32
+ * scales, then zero words up to a multiple of four -- a row is dim_t / 4 * Td + 4 * ceil(Td / 4) words, so every row, every
+ * token and the scales start on a 16-byte boundary.  hx_truncate, hx_retain_rows, hx_payload_drop and hx_destroy treat it as
+ * they treat a list or text column (a column that lags a retain is dropped).  Programs of hx_payload_mask may use
+ * IS_MISSING / IS_NULL / PRESENT / IS_EMPTY_LIST on it and nothing else.
+ *   hx_payload_append_tokens   the cells of rows [filled, filled + n): heads_host[i] = HX_PAY_U32_MISSING, HX_PAY_U32_NULL
+ *                              or Td; x8_host = the rows' tokens one after another, n_tokens x dim_t int8; scales_host
+ *                              [n_tokens] fp32.  Refused, with the column unchanged: filled + n > hx_count, counts that do
+ *                              not sum to n_tokens, a scale that is negative or not finite, a column of another kind
+ *                              ("kind" in the message; likewise the other append entries on a token column), a column that
+ *                              would hold 2^31 words or more.
+ *   hx_payload_replace_tokens  hx_payload_replace_text for a token column: the heads are scattered, offsets and words are
+ *                              spliced from the first replaced row on; the refusals of both.
+ *   hx_payload_debug_tokens    the logical content of one row, not its layout: *head = what append took for it, *count =
+ *                              its tokens, of which the first min(count, cap) go to x8_out [cap x dim_t] and scales_out
+ *                              [cap]; *dim_t (may be NULL) = the column's width.
+ *
+ * hx_maxsim is the stage.  keys_dev [B x stride] + counts_dev [B] is a pool as the hybrid entries hand it out (global ids);
+ * counts_dev NULL = all `stride` slots; eligible_dev NULL = every row.  q8_dev = the queries' tokens one after another,
+ * dim_t bytes each, 16-byte aligned; qscale_dev their scales; q_indptr_dev [B + 1] int64 = the first token of every query
+ * -- the device copy is what the kernel reads, q_indptr_host [B + 1] the same numbers for the check (nothing is read back).
+ *   out_keys_dev [B x limit]   slot t = make_key(MaxSim score, the input id) of the t-th best eligible position, 0 past
+ *                              them (hx_unpack turns that into (-inf, -1)); every slot is written;
+ *   out_counts_dev [B]         min(limit, eligible positions).
+ * Everything is enqueued on `stream`; nothing is read back.  Refused before any device work, every output untouched: a NULL
+ * argument (counts_dev and eligible_dev aside), B < 1, stride or limit outside [1, 2048], a query with 0 or more than
+ * HX_MAXSIM_MAX_QTOKENS tokens, an unknown column, a column that is not a token column ("kind" in the message), a column
+ * not filled to hx_count, eligible_rows != hx_count when eligible_dev is given.
+ *
+ * hx_hybrid_query_rerank_host is the whole call, host in, host out.  The plain query runs on a copy of *p with
+ * final_limit = the POOL size (the maxima of hx_hybrid_query_mmr_host, both modes; candidates_limit = 0 asks for the
+ * maximum); the pool is what that query returns -- in H1 the fused list with its fused scores, NOT re-scored.  mask_host /
+ * mask_root_only as hx_hybrid_query_mmr_host (a root-only mask becomes the eligibility plane; refused in H1).  Then
+ * hx_maxsim, the ids' map, the unpacking and the copy out.  q8_host / qscale_host / q_indptr_host: the query tokens as
+ * hx_maxsim takes them, on the host.  Outputs [B x limit], the slots past counts_host[b] (-inf, -1, -inf): scores_host =
+ * MaxSim, ids_host, first_scores_host = the score the pool carried.  Refusals: those of the plain call and of hx_maxsim. */
+#define HX_PAY_TOKENS 6
+#define HX_TOKENS_MAX_DIM 1024
+#define HX_MAXSIM_MAX_QTOKENS 64
+int hx_payload_create_tokens(hx_index* h, int32_t dim_t, int32_t* col);
+int hx_payload_append_tokens(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const int8_t* x8_host,
+                             const float* scales_host, int64_t n_tokens);
+int hx_payload_replace_tokens(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                              const int8_t* x8_host, const float* scales_host, int64_t n_tokens);
+int hx_payload_debug_tokens(hx_index* h, int32_t col, int64_t row, uint32_t* head, int8_t* x8_out, float* scales_out,
+                            int64_t cap, int64_t* count, int32_t* dim_t);
+int hx_maxsim(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+              const int8_t* q8_dev, const float* qscale_dev, const int64_t* q_indptr_dev, const int64_t* q_indptr_host,
+              const uint32_t* eligible_dev, int64_t eligible_rows, int32_t limit, uint64_t* out_keys_dev,
+              int32_t* out_counts_dev, void* stream);
+int hx_hybrid_query_rerank_host(hx_index* h, const float* q_dense_host, const int64_t* q_indptr_host,
+                                const int32_t* q_idx_host, const float* q_val_host, int32_t B, const hx_params* p,
+                                const uint32_t* mask_host, int64_t mask_rows, int32_t mask_root_only,
+                                int32_t candidates_limit, int32_t col, const int8_t* q8_host, const float* qscale_host,
+                                const int64_t* qtok_indptr_host, int32_t limit, float* scores_host, int64_t* ids_host,
+                                float* first_scores_host, int32_t* counts_host);
+
 /* ---- payload facets -------------------------------------------
  * Qdrant's facet(collection, key, facet_filter, limit, exact) (additive: the reference never calls it; parity unpinned, the
  * semantics below are this project's statement of it): for every value of a keyword or bool field, the number of points a

@@ -115,6 +115,14 @@ _SIGS = {
     "hx_mmr": [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_int64, _P, _P, _P, _P],
     "hx_hybrid_query_mmr_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, _P, _P, _P, _P],
+    "hx_payload_create_tokens": [_P, C.c_int32, C.POINTER(C.c_int32)],
+    "hx_payload_append_tokens": [_P, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64],
+    "hx_payload_replace_tokens": [_P, C.c_int32, _P, C.c_int64, _P, _P, _P, C.c_int64],
+    "hx_payload_debug_tokens": [_P, C.c_int32, C.c_int64, C.POINTER(C.c_uint32), _P, _P, C.c_int64, C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int32)],
+    "hx_maxsim": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
+    "hx_hybrid_query_rerank_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32, C.c_int32,
+                                    C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P],
     "hx_payload_facet": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, _P, _P],
     "hx_facet_top": [_P, _P, C.c_uint32, _P, C.c_int32, _P, _P, _P],
     "hx_payload_facet_host": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),

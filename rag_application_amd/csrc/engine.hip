@@ -2712,13 +2712,73 @@ struct MmrSpec {
   int32_t* counts_host;
 };
 
+// ---- late-interaction rerank ---------------------------------------------------------------------
+// every refusal of hx_maxsim, before any device work; returns the token column
+static const hx_index::PayCol& maxsim_check(hx_index* h, int32_t col, int32_t stride, int32_t B, const int64_t* q_indptr_host,
+                                            int32_t limit) {
+  HX_CHECK(B >= 1, "maxsim: B < 1");
+  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "maxsim: stride out of range [1, 2048]");
+  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "maxsim: limit out of range [1, 2048]");
+  HX_CHECK(q_indptr_host[0] == 0, "maxsim: the query token offsets start at 0");
+  for (int b = 0; b < B; ++b) {
+    const int64_t tq = q_indptr_host[b + 1] - q_indptr_host[b];
+    HX_CHECK(tq >= 1 && tq <= HX_MAXSIM_MAX_QTOKENS, "maxsim: a query holds 1 to 64 tokens");
+  }
+  const hx_index::PayCol& c = pay_col(h, col);
+  HX_CHECK(c.kind == HX_PAY_TOKENS, "maxsim: the column kind must be HX_PAY_TOKENS");
+  HX_CHECK(c.filled == h->n, "maxsim: the column is not filled to the index's row count (hx_count)");
+  return c;
+}
+// out_keys [B x limit] and out_counts [B] as hx_maxsim hands them out; first (may be NULL) = the scores the pool carried
+static void maxsim_enqueue(hx_index* h, const hx_index::PayCol& c, const uint64_t* keys, const uint64_t* ikeys, int stride,
+                           const int* counts, int B, const int8_t* q8, const float* qscale, const int64_t* q_indptr,
+                           const uint32_t* eligible, int limit, uint64_t* out_keys, int* out_counts, float* first,
+                           hipStream_t st) {
+  MaxsimArgs m{};
+  m.keys = keys;
+  m.ikeys = ikeys;
+  m.stride = stride;
+  m.counts = counts;
+  m.head = c.p0;
+  m.off = c.off;
+  m.words = c.e0;
+  m.dim_t = c.dim_t;
+  m.n_rows = h->n;
+  m.id_base = (uint32_t)h->id_base;
+  m.eligible = eligible;
+  m.q8 = q8;
+  m.qscale = qscale;
+  m.q_indptr = q_indptr;
+  m.pos_keys = (uint64_t*)h->ws.get(WS_MS_POS, (size_t)B * stride * 8);
+  if (h->n == 0) {                       // (no row, no column arrays: nothing is eligible)
+    HX_HIP(hipMemsetAsync(out_keys, 0, (size_t)B * limit * 8, st));
+    HX_HIP(hipMemsetAsync(out_counts, 0, (size_t)B * 4, st));
+    if (first) launch_fill_f32(first, (int64_t)B * limit, -__builtin_inff(), st);
+    return;
+  }
+  launch_maxsim_score(m, B, st);
+  launch_compact(m.pos_keys, stride, nullptr, B, std::min(limit, stride), 0, out_keys, limit, out_counts, nullptr, stride, st);
+  launch_maxsim_finish(keys, stride, out_keys, first, B, limit, st);
+}
+// what hx_hybrid_query_rerank_host adds to hx_hybrid_query_host
+struct RerankSpec {
+  int32_t root_only, candidates, col, limit;
+  const int8_t* q8_host;
+  const float* qscale_host;
+  const int64_t* qtok_indptr_host;
+  float* first_host;
+  int32_t* counts_host;
+};
+
 // hx_hybrid_query_host, its masked form (mask_host NULL = every row), its grouped form (grp NULL = the plain lists;
-// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots) and its
-// MMR form (mmr: the pool likewise, scores / ids receive the picks)
+// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots), its
+// MMR form (mmr: the pool likewise, scores / ids receive the picks) and its rerank form (rr: the pool likewise, scores /
+// ids receive the pool's rows in MaxSim order)
 static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
                               int32_t B, const hx_params* p_in, const uint32_t* mask_host, float* scores, int64_t* ids,
-                              int32_t* counts, const GroupSpec* grp = nullptr, const MmrSpec* mmr = nullptr) {
-  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr) && B > 0, "bad argument");
+                              int32_t* counts, const GroupSpec* grp = nullptr, const MmrSpec* mmr = nullptr,
+                              const RerankSpec* rr = nullptr) {
+  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr || rr) && B > 0, "bad argument");
   HX_CHECK(p_in != nullptr, "params is NULL");
   hx_params pool_params = *p_in;          // (the caller's params are never written)
   const hx_params* p = p_in;
@@ -2750,6 +2810,25 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     pool_params.final_limit = mmr->candidates ? mmr->candidates : (int32_t)pool_max;
     p = &pool_params;
     if (mmr->root_only) {
+      root_mask = mask_host;
+      mask_host = nullptr;
+    }
+  }
+  const hx_index::PayCol* tok = nullptr;
+  if (rr) {
+    HX_CHECK(rr->q8_host && rr->qscale_host && rr->qtok_indptr_host && rr->first_host && rr->counts_host, "bad argument");
+    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
+    HX_CHECK(rr->root_only == 0 || rr->root_only == 1, "rerank: mask_root_only must be 0 or 1");
+    HX_CHECK(!(mask_host && rr->root_only && p_in->mode == HX_MODE_H1),
+             "rerank: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
+    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
+    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
+    HX_CHECK(rr->candidates >= 0 && rr->candidates <= pool_max && pool_max >= 1,
+             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
+    pool_params.final_limit = rr->candidates ? rr->candidates : (int32_t)pool_max;
+    p = &pool_params;
+    tok = &maxsim_check(h, rr->col, pool_params.final_limit, B, rr->qtok_indptr_host, rr->limit);
+    if (rr->root_only) {
       root_mask = mask_host;
       mask_host = nullptr;
     }
@@ -2793,7 +2872,8 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
   float* dv = (float*)h->ws.get(WS_H_QV, (size_t)std::max<int64_t>(nnz, 1) * 4);
   uint64_t* ok = (uint64_t*)h->ws.get(WS_H_OUT, (size_t)B * L * 8);
   int* oc = (int*)h->ws.get(WS_H_OCNT, (size_t)B * 4);
-  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : mmr ? std::max(L, mmr->limit) : L;   // slots of a result
+  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : mmr ? std::max(L, mmr->limit)
+                                                                     : rr ? std::max(L, rr->limit) : L;   // slots of a result
   float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * OL * 4);
   int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * OL * 8);
   HX_HIP(hipMemcpyAsync(dq, qd, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
@@ -2853,6 +2933,35 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * ML * 8, hipMemcpyDeviceToHost, st));
     HX_HIP(hipMemcpyAsync(mmr->values_host, mv, (size_t)B * ML * 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipMemcpyAsync(mmr->counts_host, mn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
+  if (rr) {                              // the stage reads internal ids: before remap_out
+    const uint32_t* elig = nullptr;
+    if (root_mask) {
+      const int64_t nw = (h->n + 31) / 32;
+      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+      elig = dm;
+    }
+    const int RL = rr->limit;
+    const int64_t nt = rr->qtok_indptr_host[B];
+    int8_t* q8 = (int8_t*)h->ws.get(WS_MS_Q8, (size_t)nt * tok->dim_t);
+    float* qs = (float*)h->ws.get(WS_MS_QS, (size_t)nt * 4);
+    int64_t* qtip = (int64_t*)h->ws.get(WS_MS_QIP, (size_t)(B + 1) * 8);
+    HX_HIP(hipMemcpyAsync(q8, rr->q8_host, (size_t)nt * tok->dim_t, hipMemcpyHostToDevice, st));
+    HX_HIP(hipMemcpyAsync(qs, rr->qscale_host, (size_t)nt * 4, hipMemcpyHostToDevice, st));
+    HX_HIP(hipMemcpyAsync(qtip, rr->qtok_indptr_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    uint64_t* mk = (uint64_t*)h->ws.get(WS_MS_KEYS, (size_t)B * RL * 8);
+    float* mf = (float*)h->ws.get(WS_MS_FIRST, (size_t)B * RL * 4);
+    int* mn = (int*)h->ws.get(WS_MS_CNT, (size_t)B * 4);
+    maxsim_enqueue(h, *tok, ok, ok, L, oc, B, q8, qs, qtip, elig, RL, mk, mn, mf, st);
+    remap_out(h, mk, (int64_t)B * RL, st);
+    launch_unpack(mk, (int64_t)B * RL, osc, oid, st);
+    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * RL * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * RL * 8, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(rr->first_host, mf, (size_t)B * RL * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(rr->counts_host, mn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     return;
   }
@@ -2936,6 +3045,37 @@ int hx_hybrid_query_mmr_host(hx_index* h, const float* qd, const int64_t* qip, c
   HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
   const MmrSpec m{mask_root_only, candidates_limit, limit, diversity, values, counts};
   hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, &m);
+  HX_CATCH
+}
+
+int hx_maxsim(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+              const int8_t* q8_dev, const float* qscale_dev, const int64_t* q_indptr_dev, const int64_t* q_indptr_host,
+              const uint32_t* eligible_dev, int64_t eligible_rows, int32_t limit, uint64_t* out_keys_dev,
+              int32_t* out_counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && keys_dev && q8_dev && qscale_dev && q_indptr_dev && q_indptr_host && out_keys_dev && out_counts_dev,
+           "NULL argument");
+  const hx_index::PayCol& c = maxsim_check(h, col, stride, B, q_indptr_host, limit);
+  HX_CHECK(!eligible_dev || eligible_rows == h->n, "maxsim: eligible_rows must equal the index's row count (hx_count)");
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
+  maxsim_enqueue(h, c, keys_dev, ikeys, stride, counts_dev, B, q8_dev, qscale_dev, q_indptr_dev, eligible_dev, limit,
+                 out_keys_dev, out_counts_dev, nullptr, st);
+  HX_CATCH
+}
+
+int hx_hybrid_query_rerank_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
+                                int32_t mask_root_only, int32_t candidates_limit, int32_t col, const int8_t* q8_host,
+                                const float* qscale_host, const int64_t* qtok_indptr_host, int32_t limit, float* scores,
+                                int64_t* ids, float* first_scores, int32_t* counts) {
+  HX_TRY
+  HX_CHECK(h, "NULL argument");
+  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  const RerankSpec r{mask_root_only, candidates_limit, col, limit, q8_host, qscale_host, qtok_indptr_host, first_scores,
+                     counts};
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, nullptr, &r);
   HX_CATCH
 }
 

@@ -47,7 +47,8 @@ enum WsSlot {
   WS_ID_IN, WS_LONG_ROWS, WS_Q8S, WS_SQ, WS_EPSQ, WS_TREE_FLAG, WS_DONE,
   WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
   WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT,
-  WS_FACET_A, WS_FACET_B, WS_FACET_CNT, WS_FACET_COUNTS, WS_FACET_MASK, WS_FACET_RANK, WS_FACET_OUT
+  WS_FACET_A, WS_FACET_B, WS_FACET_CNT, WS_FACET_COUNTS, WS_FACET_MASK, WS_FACET_RANK, WS_FACET_OUT,
+  WS_MS_POS, WS_MS_KEYS, WS_MS_CNT, WS_MS_FIRST, WS_MS_Q8, WS_MS_QS, WS_MS_QIP
 };
 
 template <typename T>
@@ -208,6 +209,8 @@ struct hx_index {
   // offsets [filled + 1] into the element planes e0 (codes, or the low words of doubles) and e1 (the high words).
   // A text column (HX_PAY_TEXT) is stored the same way: p0 = the head plane (missing / null / the
   // row's byte length), off counts 32-bit words, e0 = the rows' bytes, each row padded with zero bytes to a word.
+  // A token column (HX_PAY_TOKENS) likewise: p0 = missing / null / the row's token count Td, e0 =
+  // per row Td x dim_t int8, then Td fp32 scales, then zero words up to a multiple of four words.
   struct PayCol {
     int id = 0, kind = 0;
     uint32_t* p0 = nullptr;
@@ -217,9 +220,11 @@ struct hx_index {
     uint32_t* e0 = nullptr;
     uint32_t* e1 = nullptr;
     int64_t n_el = 0, el_cap = 0;
+    int dim_t = 0;                    // HX_PAY_TOKENS: bytes of a token, fixed at creation
     bool list() const { return kind == HX_PAY_LIST_U32 || kind == HX_PAY_LIST_F64; }
     bool text() const { return kind == HX_PAY_TEXT; }
-    bool csr() const { return list() || text(); }      // offsets and element planes: what the lifecycle moves
+    bool tokens() const { return kind == HX_PAY_TOKENS; }
+    bool csr() const { return list() || text() || tokens(); }   // offsets and element planes: what the lifecycle moves
   };
   std::vector<PayCol> pay;
   int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap

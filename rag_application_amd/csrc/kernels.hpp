@@ -506,6 +506,33 @@ struct MmrArgs {
   int* out_counts;
 };
 void launch_mmr_select(const MmrArgs& a, int B, hipStream_t st);
+// ---- maxsim.hip: late-interaction rerank (hx_maxsim) ---------------------------------------------
+// Per query b: the pool keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same slots with
+// internal ids.  A position is eligible when its key is not 0, its row is in [0, n_rows), the row's head is a token count
+// >= 1 and (eligible != NULL) the row's bit is set.  A token row: word off[row] of `words` on, head[row] x dim_t bytes, then
+// head[row] fp32 scales (hx.h states the layout and the score).  q8 / qscale / q_indptr: the queries' tokens.
+// launch_maxsim_score writes pos_keys[b * stride + i] = orderable(score) << 32 | 0xFFFFFFFF - i, 0 for a position that is
+// not eligible (every slot); launch_maxsim_finish turns sorted position keys sorted[b * limit + t] (in place) into
+// make_key(score, the id of keys[.. + i]), first[b * limit + t] (may be NULL) = the score keys[.. + i] carried.
+struct MaxsimArgs {
+  const uint64_t* keys;
+  const uint64_t* ikeys;
+  int stride;              // 1 .. 2048
+  const int* counts;
+  const uint32_t* head;
+  const int64_t* off;
+  const uint32_t* words;
+  int dim_t;               // a multiple of 64 in [64, 1024]
+  int64_t n_rows;
+  uint32_t id_base;
+  const uint32_t* eligible;
+  const int8_t* q8;
+  const float* qscale;
+  const int64_t* q_indptr;
+  uint64_t* pos_keys;
+};
+void launch_maxsim_score(const MaxsimArgs& a, int B, hipStream_t st);
+void launch_maxsim_finish(const uint64_t* keys, int stride, uint64_t* sorted, float* first, int B, int limit, hipStream_t st);
 // ---- facet.hip: payload facets (hx_payload_facet / hx_facet_top) ---------------------------------
 // counts[c] += the rows r < n whose bit is set in mask (NULL: every row) and whose cell holds code c < n_codes: p0[r] == c
 // for a scalar column (off == NULL), some element of e0[off[r], off[r + 1]) == c for a list column -- a row counts once

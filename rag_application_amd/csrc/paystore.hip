@@ -180,6 +180,42 @@ static void pay_text_pack(const uint32_t* heads_host, int64_t n, const void* byt
   }
 }
 
+// words of a token row of td tokens: td x dim_t bytes, td scales, zero words up to a multiple of four (16 bytes)
+static int64_t pay_token_words(int64_t td, int dim_t) { return td * (dim_t / 4) + round_up(td, 4); }
+
+// The checked cells of n token rows (hx.h states the layout): off[n + 1] = the rows' offsets in 32-bit words from `base`,
+// words = the rows one after another.  Refuses counts that do not sum to n_tokens, a column of 2^31 words or more (before
+// a token is read) and a scale that is negative or not finite.
+static void pay_tokens_pack(const uint32_t* heads_host, int64_t n, const int8_t* x8, const float* scales, int64_t n_tokens,
+                            int dim_t, int64_t base, std::vector<int64_t>& off, std::vector<uint32_t>& words) {
+  off.resize((size_t)n + 1);
+  off[0] = base;
+  int64_t total = 0, n_words = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    if (hd < HX_PAY_U32_NULL) {
+      total += hd;
+      n_words += pay_token_words(hd, dim_t);
+    }
+    HX_CHECK(total <= n_tokens, "payload: the token counts of the heads do not sum to n_tokens");
+    off[(size_t)i + 1] = base + n_words;
+  }
+  HX_CHECK(total == n_tokens, "payload: the token counts of the heads do not sum to n_tokens");
+  HX_CHECK(base + n_words <= 0x7FFFFFFFll, "payload: a token column holds fewer than 2^31 words");
+  for (int64_t t = 0; t < total; ++t)
+    HX_CHECK(scales[t] >= 0.0f && scales[t] <= 3.402823466e38f, "payload: a token scale is negative or not finite");
+  words.assign((size_t)n_words, 0u);
+  int64_t t = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t hd = heads_host[i];
+    if (hd >= HX_PAY_U32_NULL || hd == 0u) continue;
+    uint8_t* row = (uint8_t*)(words.data() + (off[(size_t)i] - base));
+    std::memcpy(row, x8 + t * dim_t, (size_t)hd * dim_t);
+    std::memcpy(row + (size_t)hd * dim_t, scales + t, (size_t)hd * 4);
+    t += hd;
+  }
+}
+
 // Store the checked cells of rows [filled, filled + n) of a list or text column: heads[n] as the head plane keeps them,
 // off[n + 1] = the rows' offsets (off[0] = n_el), e0_host / e1_host = `total` new words per element plane (e1_host: the
 // high words of a HX_PAY_LIST_F64 column, NULL otherwise).  Every allocation comes before the column changes.
@@ -230,7 +266,9 @@ static void pay_splice_csr(hx_index* h, PayCol& c, const int64_t* rows_host, int
   splice_plan(sp, c.off, c.filled, *std::min_element(rows.begin(), rows.end()), (const uint32_t*)rows_dev.p, m,
               (const int64_t*)noff_dev.p, st);
   const int64_t want_el = sp.base + sp.moved;
-  HX_CHECK(want_el <= 0x7FFFFFFFll, c.text() ? "payload: a text column holds fewer than 2^31 words" : "payload: a list column holds fewer than 2^31 elements");
+  HX_CHECK(want_el <= 0x7FFFFFFFll, c.tokens() ? "payload: a token column holds fewer than 2^31 words"
+                                    : c.text() ? "payload: a text column holds fewer than 2^31 words"
+                                               : "payload: a list column holds fewer than 2^31 elements");
   if (sp.moved > 0) {
     t0.alloc((size_t)sp.moved * 4);
     if (f64) t1.alloc((size_t)sp.moved * 4);
@@ -366,6 +404,7 @@ int hx_payload_append(hx_index* h, int32_t col, const void* cells_host, int64_t 
   HX_CHECK(cells_host || n == 0, "payload: cells are NULL");
   HX_CHECK(!c.list(), "payload: a list column takes hx_payload_append_lists (column kind)");
   HX_CHECK(!c.text(), "payload: a text column takes hx_payload_append_text (column kind)");
+  HX_CHECK(!c.tokens(), "payload: a token column takes hx_payload_append_tokens (column kind)");
   HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
   if (n == 0) return 0;
   h->set_device();
@@ -411,6 +450,7 @@ int hx_payload_replace(hx_index* h, int32_t col, const int64_t* rows_host, int64
   HX_CHECK(m == 0 || (rows_host && cells_host), "payload: rows / cells are NULL");
   HX_CHECK(!c.list(), "payload: a list column takes hx_payload_replace_lists (column kind)");
   HX_CHECK(!c.text(), "payload: a text column takes hx_payload_replace_text (column kind)");
+  HX_CHECK(!c.tokens(), "payload: a token column takes hx_payload_replace_tokens (column kind)");
   if (m == 0) return 0;
   const std::vector<uint32_t> rows = replace_rows_checked(rows_host, m, c.filled, "hx_payload_replace");
   h->set_device();
@@ -535,12 +575,86 @@ int hx_payload_debug_text(hx_index* h, int32_t col, int64_t row, uint32_t* head,
   HX_CATCH
 }
 
+// ---- token columns (HX_PAY_TOKENS) -------------------------------------------------------------
+int hx_payload_create_tokens(hx_index* h, int32_t dim_t, int32_t* col) {
+  HX_TRY
+  HX_CHECK(h && col, "NULL argument");
+  HX_CHECK(dim_t >= 64 && dim_t <= HX_TOKENS_MAX_DIM && dim_t % 64 == 0,
+           "payload: dim_t must be a multiple of 64 in [64, 1024]");
+  HX_CHECK((int)h->pay.size() < HX_PAY_MAX_COLUMNS, "payload: an index holds at most 64 columns");
+  hx_index::PayCol c;
+  c.id = h->pay_next_id++;
+  c.kind = HX_PAY_TOKENS;
+  c.dim_t = dim_t;
+  h->pay.push_back(c);
+  *col = c.id;
+  HX_CATCH
+}
+
+int hx_payload_append_tokens(hx_index* h, int32_t col, const uint32_t* heads_host, int64_t n, const int8_t* x8_host,
+                             const float* scales_host, int64_t n_tokens) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.tokens(), "payload: hx_payload_append_tokens needs a token column (column kind)");
+  HX_CHECK(n >= 0 && n_tokens >= 0, "payload: n < 0");
+  HX_CHECK((heads_host || n == 0) && ((x8_host && scales_host) || n_tokens == 0), "payload: cells are NULL");
+  HX_CHECK(c.filled + n <= h->n, "payload: the cells reach past the index's row count (hx_count)");
+  // ---- every refusal and every allocation before the column changes ----
+  std::vector<int64_t> off;
+  std::vector<uint32_t> words;
+  pay_tokens_pack(heads_host, n, x8_host, scales_host, n_tokens, c.dim_t, c.n_el, off, words);
+  pay_store_csr(h, c, heads_host, off.data(), n, words.data(), nullptr, (int64_t)words.size());
+  HX_CATCH
+}
+
+int hx_payload_replace_tokens(hx_index* h, int32_t col, const int64_t* rows_host, int64_t m, const uint32_t* heads_host,
+                              const int8_t* x8_host, const float* scales_host, int64_t n_tokens) {
+  HX_TRY
+  HX_CHECK(h, "index is NULL");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.tokens(), "payload: hx_payload_replace_tokens needs a token column (column kind)");
+  HX_CHECK(m >= 0 && n_tokens >= 0, "payload: m < 0");
+  HX_CHECK((m == 0 || (rows_host && heads_host)) && ((x8_host && scales_host) || n_tokens == 0),
+           "payload: rows / cells are NULL");
+  std::vector<int64_t> noff;
+  std::vector<uint32_t> words;
+  pay_tokens_pack(heads_host, m, x8_host, scales_host, n_tokens, c.dim_t, 0, noff, words);
+  pay_splice_csr(h, c, rows_host, m, heads_host, noff.data(), words.data(), nullptr, (int64_t)words.size(),
+                 "hx_payload_replace_tokens");
+  HX_CATCH
+}
+
+int hx_payload_debug_tokens(hx_index* h, int32_t col, int64_t row, uint32_t* head, int8_t* x8_out, float* scales_out,
+                            int64_t cap, int64_t* count, int32_t* dim_t) {
+  HX_TRY
+  HX_CHECK(h && head && count, "NULL argument");
+  auto& c = pay_col(h, col);
+  HX_CHECK(c.tokens(), "payload: hx_payload_debug_tokens needs a token column (column kind)");
+  HX_CHECK(cap == 0 || scales_out, "payload: bad output buffer");
+  uint32_t hd = 0;
+  int64_t o[2] = {0, 0};
+  pay_row_span(h, c, row, x8_out, cap, &hd, o);
+  const int64_t td = hd < HX_PAY_U32_NULL ? (int64_t)hd : 0;
+  HX_CHECK(o[0] >= 0 && o[1] <= c.n_el && o[1] - o[0] == pay_token_words(td, c.dim_t), "payload: corrupt token offsets");
+  *head = hd;
+  *count = td;
+  if (dim_t) *dim_t = c.dim_t;
+  const int64_t k = std::min(td, cap);
+  if (k <= 0) return 0;
+  const uint8_t* base = (const uint8_t*)(c.e0 + o[0]);
+  HX_HIP(hipMemcpy(x8_out, base, (size_t)k * c.dim_t, hipMemcpyDeviceToHost));
+  HX_HIP(hipMemcpy(scales_out, base + (size_t)td * c.dim_t, (size_t)k * 4, hipMemcpyDeviceToHost));
+  HX_CATCH
+}
+
 int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host) {
   HX_TRY
   HX_CHECK(h && out_host, "NULL argument");
   auto& c = pay_col(h, col);
   HX_CHECK(!c.list(), "payload: a list column takes hx_payload_debug_list (column kind)");
   HX_CHECK(!c.text(), "payload: a text column takes hx_payload_debug_text (column kind)");
+  HX_CHECK(!c.tokens(), "payload: a token column takes hx_payload_debug_tokens (column kind)");
   HX_CHECK(row >= 0 && row < c.filled, "payload: row out of range");
   h->set_device();
   HX_HIP(hipMemcpy(out_host, c.p0 + row, 4, hipMemcpyDeviceToHost));
@@ -582,9 +696,12 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
         d.e0 = c->e0;
         d.e1 = c->kind == HX_PAY_LIST_F64 ? c->e1 : nullptr;
       }
+      if (c->tokens()) d.off = c->off;  // (IS_EMPTY_LIST: head 0 and no word; the words themselves are never read)
       HX_CHECK(!c->text() || (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_PRESENT) || o.op == HX_PAY_TEXT_ALL,
                "payload: a text column takes IS_MISSING / IS_NULL / PRESENT / TEXT_ALL only");
-      HX_CHECK(!list_op || c->list(), "payload: ANY_EQ / ANY_IN / ANY_RANGE / IS_EMPTY_LIST need a list column");
+      HX_CHECK(!c->tokens() || (o.op >= HX_PAY_IS_MISSING && o.op <= HX_PAY_PRESENT) || o.op == HX_PAY_IS_EMPTY_LIST,
+               "payload: a token column takes IS_MISSING / IS_NULL / PRESENT / IS_EMPTY_LIST only");
+      HX_CHECK(!list_op || c->list() || c->tokens(), "payload: ANY_EQ / ANY_IN / ANY_RANGE / IS_EMPTY_LIST need a list column");
       HX_CHECK(!(o.op >= HX_PAY_EQ && o.op <= HX_PAY_GE) || !c->list(),
                "payload: EQ / IN / LT / LE / GT / GE need a scalar column (a list column takes the ANY ops)");
       HX_CHECK(o.op != HX_PAY_TEXT_ALL || c->text(),

@@ -17,6 +17,8 @@ from .filters import pack_rows
 
 # payload index (hx.h): the column kinds; the cell codes and the ops of a program are in payload_index.py
 PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64, PAY_TEXT = 1, 2, 3, 4, 5
+PAY_TOKENS = 6                        # made by payload_create_tokens (hx.h: late-interaction rerank)
+MAXSIM_MAX_QTOKENS = 64
 
 SEARCH_PARAM_KEYS = ("matryoshka_64_limit", "matryoshka_128_limit", "matryoshka_256_limit",
                      "dense_limit", "quantized_limit", "sparse_limit", "final_limit", "hnsw_ef")
@@ -748,6 +750,139 @@ class HxIndex:
                                                   int(candidates_limit), L, float(diversity), _ptr(scores), _ptr(ids),
                                                   _ptr(values), _ptr(counts)))
         return scores, ids, values, counts
+
+    # -- late-interaction rerank (hx.h: HX_PAY_TOKENS / hx_maxsim / hx_hybrid_query_rerank_host) --
+    def payload_create_tokens(self, dim_t: int) -> int:
+        """A new empty token column of `dim_t` int8 values per token (hx_payload_create_tokens); returns its id."""
+        col = C.c_int32()
+        check(_lib.lib().hx_payload_create_tokens(self._h, int(dim_t), C.byref(col)))
+        return col.value
+
+    @staticmethod
+    def _token_cells(heads, x8, scales):
+        heads, x8, scales = np.ascontiguousarray(heads), np.ascontiguousarray(x8), np.ascontiguousarray(scales)
+        if (heads.dtype != np.uint32 or heads.ndim != 1 or x8.dtype != np.int8 or x8.ndim != 2
+                or scales.dtype != np.float32 or scales.ndim != 1):
+            raise TypeError("payload tokens: 1-d np.uint32 heads, [n_tokens, dim_t] np.int8 tokens, 1-d np.float32 scales")
+        if x8.shape[0] != scales.shape[0]:
+            raise ValueError(f"{x8.shape[0]} tokens but {scales.shape[0]} scales")
+        return heads, x8, scales
+
+    def _token_dim(self, col: int) -> int:
+        head, count, dim_t = C.c_uint32(), C.c_int64(), C.c_int32()
+        if self.payload_rows(col) == 0:
+            return 0                                          # (nothing stored: the engine checks the bytes it is given)
+        check(_lib.lib().hx_payload_debug_tokens(self._h, int(col), 0, C.byref(head), None, None, 0, C.byref(count),
+                                                 C.byref(dim_t)))
+        return dim_t.value
+
+    def payload_append_tokens(self, col: int, heads: np.ndarray, x8: np.ndarray, scales: np.ndarray) -> None:
+        """The cells of the next len(heads) rows of a token column (hx_payload_append_tokens): heads np.uint32 -- MISSING,
+        NULL or the row's token count --, x8 [n_tokens, dim_t] np.int8 the rows' tokens one after another, scales
+        [n_tokens] np.float32 (late_interaction.quantize_tokens makes both)."""
+        heads, x8, scales = self._token_cells(heads, x8, scales)
+        check(_lib.lib().hx_payload_append_tokens(self._h, int(col), _ptr(heads), heads.shape[0], _ptr(x8), _ptr(scales),
+                                                  x8.shape[0]))
+
+    def payload_replace_tokens(self, col: int, rows, heads: np.ndarray, x8: np.ndarray, scales: np.ndarray) -> None:
+        """New cells for the stored rows `rows` of a token column (hx_payload_replace_tokens), in the order of `rows`."""
+        rows = self._rows(rows)
+        heads, x8, scales = self._token_cells(heads, x8, scales)
+        if heads.shape[0] != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} rows but {heads.shape[0]} heads")
+        check(_lib.lib().hx_payload_replace_tokens(self._h, int(col), _ptr(rows), rows.shape[0], _ptr(heads), _ptr(x8),
+                                                   _ptr(scales), x8.shape[0]))
+
+    def payload_debug_tokens(self, col: int, row: int):
+        """One row of a token column (hx_payload_debug_tokens): (head, x8 [Td, dim_t] np.int8, scales [Td] np.float32) --
+        head = MISSING, NULL or the token count."""
+        head, count, dim_t = C.c_uint32(), C.c_int64(), C.c_int32()
+        check(_lib.lib().hx_payload_debug_tokens(self._h, int(col), int(row), C.byref(head), None, None, 0, C.byref(count),
+                                                 C.byref(dim_t)))
+        x8 = np.zeros((max(count.value, 1), dim_t.value), dtype=np.int8)
+        sc = np.zeros(max(count.value, 1), dtype=np.float32)
+        check(_lib.lib().hx_payload_debug_tokens(self._h, int(col), int(row), C.byref(head), _ptr(x8), _ptr(sc), count.value,
+                                                 C.byref(count), C.byref(dim_t)))
+        return head.value, x8[:count.value], sc[:count.value]
+
+    @staticmethod
+    def _query_tokens(q8, qscale, q_indptr):
+        q8, qscale = np.ascontiguousarray(q8), np.ascontiguousarray(qscale)
+        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
+        if q8.dtype != np.int8 or q8.ndim != 2 or qscale.dtype != np.float32 or qscale.ndim != 1 or q_indptr.ndim != 1:
+            raise TypeError("query tokens: [n_tokens, dim_t] np.int8, [n_tokens] np.float32 scales, [B + 1] offsets")
+        if q8.shape[0] != qscale.shape[0] or q_indptr.shape[0] < 2 or q_indptr[-1] != q8.shape[0]:
+            raise ValueError("query tokens: the offsets, the tokens and the scales disagree")
+        return q8, qscale, q_indptr
+
+    def maxsim(self, col: int, keys: torch.Tensor, counts: Optional[torch.Tensor], q8: np.ndarray, qscale: np.ndarray,
+               q_indptr: np.ndarray, limit: int, eligible=None, out=None, out_counts=None):
+        """The pools keys [B, stride] (+ counts [B], None = every slot) ordered by the MaxSim of the queries' tokens
+        against the rows' tokens in the token column `col` (hx_maxsim).  q8 [n_tokens, dim_t] np.int8 / qscale [n_tokens]
+        np.float32: the queries' tokens one after another, q_indptr [B + 1] the first token of every query.  eligible as
+        mmr takes it.  Returns (out_keys [B, limit] int64 carrying the MaxSim scores, 0 past the eligible positions;
+        counts [B] int32).  out / out_counts: the tensors to write (tests hand in sentinels).  Only enqueues work."""
+        keys = _need_cuda(keys, torch.int64, "keys")
+        if keys.dim() != 2:
+            raise HxError("keys must be a [B, stride] tensor")
+        if counts is not None:
+            counts = _need_cuda(counts, torch.int32, "counts")
+        q8, qscale, q_indptr = self._query_tokens(q8, qscale, q_indptr)
+        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        if q_indptr.shape[0] != B + 1:
+            raise ValueError(f"{q_indptr.shape[0] - 1} queries' tokens for {B} pools")
+        dim_t = self._token_dim(col)
+        if dim_t and q8.shape[1] != dim_t:
+            raise ValueError(f"query tokens of {q8.shape[1]} values for a column of {dim_t}")
+        slots = L if 1 <= L <= 2048 else 1                  # (the engine refuses; nothing huge is allocated)
+        words, rows = None, 0
+        if eligible is not None:
+            w, rows = self._mask(eligible)
+            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
+        dq8 = torch.from_numpy(q8.reshape(-1) if q8.size else np.zeros(16, np.int8)).to(keys.device)
+        dqs = torch.from_numpy(qscale if qscale.size else np.zeros(1, np.float32)).to(keys.device)
+        dip = torch.from_numpy(q_indptr).to(keys.device)
+        if out is None:
+            out = torch.empty((B, slots), dtype=torch.int64, device=keys.device)
+        if out_counts is None:
+            out_counts = torch.empty((B,), dtype=torch.int32, device=keys.device)
+        check(_lib.lib().hx_maxsim(self._h, int(col), _ptr(keys), stride, _ptr(counts), B, _ptr(dq8), _ptr(dqs), _ptr(dip),
+                                   _ptr(q_indptr), _ptr(words), rows, L, _ptr(out), _ptr(out_counts), _stream()))
+        return out, out_counts
+
+    def hybrid_query_rerank_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
+                                 params: HxParams, col: int, q8: np.ndarray, qscale: np.ndarray, qtok_indptr: np.ndarray,
+                                 limit: int, candidates_limit: int = 0, mask=None, mask_root_only: bool = False):
+        """hybrid_query_host followed by the MaxSim rerank of its pool (hx_hybrid_query_rerank_host): the query runs with
+        final_limit = the pool (candidates_limit = 0: the mode's whole pool; params.final_limit is not used), the pool's
+        rows that hold tokens come back ordered by MaxSim.  q8 / qscale / qtok_indptr as maxsim takes them; mask /
+        mask_root_only as hybrid_query_mmr_host.  Returns (scores [B, limit] float32 -- MaxSim --, ids [B, limit] int64,
+        first_scores [B, limit] float32 -- what the pool carried --, counts [B] int32), the slots past the counts
+        (-inf, -1, -inf)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
+        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
+        q8, qscale, qtok_indptr = self._query_tokens(q8, qscale, qtok_indptr)
+        B, L = q.shape[0], int(limit)
+        if qtok_indptr.shape[0] != B + 1:
+            raise ValueError(f"{qtok_indptr.shape[0] - 1} queries' tokens for {B} queries")
+        if not 1 <= L <= 2048:
+            raise HxError("maxsim: limit out of range [1, 2048]")
+        dim_t = self._token_dim(col)
+        if dim_t and q8.shape[1] != dim_t:
+            raise ValueError(f"query tokens of {q8.shape[1]} values for a column of {dim_t}")
+        scores = np.empty((B, L), dtype=np.float32)
+        ids = np.empty((B, L), dtype=np.int64)
+        first = np.empty((B, L), dtype=np.float32)
+        counts = np.empty((B,), dtype=np.int32)
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        check(_lib.lib().hx_hybrid_query_rerank_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
+                                                     C.byref(params), _ptr(words), rows, int(bool(mask_root_only)),
+                                                     int(candidates_limit), int(col), _ptr(q8), _ptr(qscale),
+                                                     _ptr(qtok_indptr), L, _ptr(scores), _ptr(ids), _ptr(first),
+                                                     _ptr(counts)))
+        return scores, ids, first, counts
 
 
 # -- index-free stages -------------------------------------------------------------------

@@ -27,6 +27,7 @@ from . import engine as _engine
 from . import faceting as _faceting
 from . import filters as _filters
 from . import grouping as _grouping
+from . import late_interaction as _late
 from . import payload_index as _pindex
 from ._lib import HX_MODE_H1, HX_MODE_TREE
 
@@ -74,6 +75,13 @@ class MmrPoint(ScoredPoint):
 
 
 @dataclass
+class RerankedPoint(ScoredPoint):
+    """One hit of hybrid_search_rerank: a ScoredPoint whose `score` is the MaxSim of the query's tokens against the
+    point's tokens and whose `first_score` is the score the point carried in the hybrid pool."""
+    first_score: float = 0.0
+
+
+@dataclass
 class SparseVector:
     """Shape-compatible with qdrant_client.http.models.SparseVector."""
     indices: List[int] = field(default_factory=list)
@@ -102,6 +110,7 @@ class _Collection:
         self.sparse_enabled = True
         self._masks: Dict[str, Any] = {}
         self.pindex: Optional[_pindex.PayloadIndex] = None
+        self.tokens: Optional[Dict[str, Any]] = None
 
     MASK_CACHE = 64   # filters whose row masks a collection keeps (least recently used first out): n / 8 bytes each
 
@@ -280,17 +289,118 @@ class _Collection:
                 logging.warning("payload index: replacing cells of %r failed, the key is dropped: %s", key, e)
             self._poison(key)
 
+    # -- token multivectors (late_interaction.py) ---------------------------------------------------
+    # self.tokens = None, or {"dim": the token width, "col": the engine column or None (dropped: rebuilt on next use),
+    # "cells": one entry per row, None (no vector) or (x8 [T, dim] int8, scales [T] float32)}: the quantised tokens stay on
+    # the host as the payloads do, the column is derived from them.
+    def create_token_index(self, dim: int) -> None:
+        if not hasattr(self.index, "payload_create_tokens"):
+            raise ValueError("this collection's engine index has no token columns")
+        dim = _late.check_dim(dim)
+        tk = getattr(self, "tokens", None)
+        if tk is not None:
+            if tk["dim"] != dim:
+                raise ValueError(f"the collection holds a token index of width {tk['dim']}")
+            return
+        self.tokens = {"dim": dim, "col": None, "cells": [None] * len(self.ids)}
+        self._token_column()
+
+    def token_cells_of(self, items) -> Optional[list]:
+        """The quantised token cells of chunks (None for a chunk without "token_embeddings"); None when the collection
+        has no token index and no chunk brings tokens.  Everything that can raise comes before the engine is touched."""
+        tk = getattr(self, "tokens", None)
+        have = [item.get("token_embeddings") is not None for item in items]
+        if tk is None:
+            if any(have):
+                raise ValueError('"token_embeddings" needs a token index: call create_token_index first')
+            return None
+        return [_late.quantize_tokens(_late.pad_dim(item["token_embeddings"], tk["dim"])) if h else None
+                for item, h in zip(items, have)]
+
+    def _token_column(self) -> int:
+        """The live token column, rebuilt from the host cells when there is none (never made, dropped by a delete it
+        lagged, or lost to an engine failure)."""
+        tk = self.tokens
+        if tk["col"] is not None:
+            try:
+                if self.index.payload_rows(tk["col"]) == len(self.ids):
+                    return tk["col"]
+                self.index.payload_drop(tk["col"])
+            except Exception:
+                pass                                       # (the engine dropped it)
+            tk["col"] = None
+        col = self.index.payload_create_tokens(tk["dim"])
+        try:
+            if tk["cells"]:
+                self.index.payload_append_tokens(col, *_late.pack_tokens(tk["cells"], tk["dim"])[:3])
+        except Exception:
+            self.index.payload_drop(col)
+            raise
+        tk["col"] = col
+        return col
+
+    def _token_fail(self, what: str, e: Exception) -> None:
+        logging.warning("token index: %s failed, the column is dropped and rebuilt on next use: %s", what, e)
+        tk = self.tokens
+        if tk["col"] is not None:
+            try:
+                self.index.payload_drop(tk["col"])
+            except Exception:
+                pass
+        tk["col"] = None
+
+    def append_token_cells(self, cells) -> None:
+        """The token cells of rows just added (`cells` from token_cells_of; None = no token index)."""
+        tk = getattr(self, "tokens", None)
+        if tk is None:
+            return
+        cells = cells if cells is not None else []
+        n0 = len(tk["cells"])
+        tk["cells"].extend(cells)
+        if tk["col"] is None:
+            return
+        try:
+            if self.index.payload_rows(tk["col"]) != n0:
+                raise RuntimeError("the column's row count differs from the cells'")
+            self.index.payload_append_tokens(tk["col"], *_late.pack_tokens(cells, tk["dim"])[:3])
+        except Exception as e:
+            self._token_fail("appending", e)
+
+    def replace_token_cells(self, rows, cells) -> None:
+        """The token cells of rows replaced in place (hx_payload_replace_tokens)."""
+        tk = getattr(self, "tokens", None)
+        if tk is None:
+            return
+        for r, c in zip(rows, cells):
+            tk["cells"][r] = c
+        if tk["col"] is None:
+            return
+        try:
+            self.index.payload_replace_tokens(tk["col"], np.asarray(rows, np.int64), *_late.pack_tokens(cells, tk["dim"])[:3])
+        except Exception as e:
+            self._token_fail("replacing", e)
+
     def close(self):
         self.index.close()
 
     # on-disk form (the reference asks Qdrant for on_disk storage, qdrant_handler.py:47-55, 62):
-    # <dir>/<user>.hx = the engine's file, <dir>/<user>.json = point ids + payloads
+    # <dir>/<user>.hx = the engine's file, <dir>/<user>.json = point ids + payloads, <dir>/<user>.tokens.npz = the
+    # quantised tokens of a collection with a token index (the JSON names the index)
     def save(self, base: str):
         self.index.save(base + ".hx")
+        tk = getattr(self, "tokens", None)
+        if tk is not None:
+            state = np.asarray([0 if c is None else 1 for c in tk["cells"]], np.uint8)
+            _, x8, sc, indptr = _late.pack_tokens(tk["cells"], tk["dim"])
+            with open(base + ".tokens.npz", "wb") as f:
+                np.savez(f, state=state, x8=x8, scales=sc, indptr=indptr)
+        elif os.path.exists(base + ".tokens.npz"):
+            os.remove(base + ".tokens.npz")
         with open(base + ".json", "w") as f:
             json.dump({"dim": self.dim, "msizes": list(self.msizes), "sparse_enabled": self.sparse_enabled,
                        "ids": self.ids, "payloads": self.payloads,
-                       "payload_indexes": self.pindex.definitions() if getattr(self, "pindex", None) else {}}, f)
+                       "payload_indexes": self.pindex.definitions() if getattr(self, "pindex", None) else {},
+                       "token_index": {"dim": tk["dim"]} if tk is not None else None}, f)
 
     @classmethod
     def load(cls, base: str, device: int, index_loader=None):
@@ -310,6 +420,18 @@ class _Collection:
         if hasattr(self.index, "payload_create"):
             for key, schema in (meta.get("payload_indexes") or {}).items():
                 self.create_payload_index(str(key), _pindex.schema_of(schema))
+        self.tokens = None
+        tdef = meta.get("token_index")
+        if tdef and hasattr(self.index, "payload_create_tokens"):
+            dim = _late.check_dim(int(tdef["dim"]))
+            with np.load(base + ".tokens.npz") as z:
+                state, x8, sc, indptr = z["state"], z["x8"], z["scales"], z["indptr"]
+            if state.shape[0] != len(self.ids) or indptr.shape[0] != len(self.ids) + 1 or x8.shape[1:] != (dim,):
+                raise ValueError("the token sidecar does not belong to this collection")
+            cells = [(np.ascontiguousarray(x8[indptr[r]:indptr[r + 1]]), np.ascontiguousarray(sc[indptr[r]:indptr[r + 1]]))
+                     if state[r] else None for r in range(len(self.ids))]
+            self.tokens = {"dim": dim, "col": None, "cells": cells}
+            self._token_column()
         return self
 
 
@@ -334,6 +456,8 @@ class QdrantHandler:
     _mmr_search = True
     # facet counts the payload columns of ONE engine index, or this process's payloads
     _facets = True
+    # token columns live in ONE engine index; hybrid_search_rerank reranks the pool of that index
+    _late_rerank = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -471,6 +595,7 @@ class QdrantHandler:
             payloads.append(emb_key_payload(item))
         if not dense:
             return 0
+        tcells = col.token_cells_of(items)                 # (quantised here: a refusal comes before the engine)
 
         def add():
             col.index.add(np.stack(dense), np.asarray(indptr, np.int64), np.asarray(idx, np.int32),
@@ -478,6 +603,7 @@ class QdrantHandler:
             col.ids.extend(ids)
             col.payloads.extend(payloads)
             col.append_payload_cells(payloads)
+            col.append_token_cells(tcells)
         await self._run(add)
         return len(dense)
 
@@ -546,6 +672,7 @@ class QdrantHandler:
         new = [k for k, p in enumerate(point_ids) if p is None or str(p) not in id_rows]
         rows = [id_rows[str(point_ids[k])] for k in old]
         payloads = [self._document_payload(item) for item in items]
+        tcells = col.token_cells_of(items)
         packed_new = pack(new) if new else None             # (everything that can raise in Python comes before the engine)
         packed_old = pack(old) if old else None
         n0 = len(col.ids)
@@ -555,6 +682,7 @@ class QdrantHandler:
             col.ids.extend(str(point_ids[k]) if point_ids[k] is not None else str(uuid.uuid4()) for k in new)
             col.payloads.extend(payloads[k] for k in new)
             col.append_payload_cells([payloads[k] for k in new])
+            col.append_token_cells([tcells[k] for k in new] if tcells is not None else None)
         if not old:
             return 0
         try:
@@ -564,11 +692,15 @@ class QdrantHandler:
                 col.index.truncate(n0)                      # (the payload columns are cut with the rows)
                 del col.ids[n0:]
                 del col.payloads[n0:]
+                if getattr(col, "tokens", None) is not None:
+                    del col.tokens["cells"][n0:]
                 col._idrows = None
             raise
         for r, k in zip(rows, old):
             col.payloads[r] = payloads[k]
         col.replace_payload_cells(rows, [payloads[k] for k in old])
+        if tcells is not None:
+            col.replace_token_cells(rows, [tcells[k] for k in old])
         col._masks.clear()                                  # a cached mask may be wrong for a replaced row
         return len(old)
 
@@ -895,6 +1027,94 @@ class QdrantHandler:
             logging.error("MMR hybrid search for %s failed: %s", user_id, e)
             return []
 
+    # ------------------------------------------------------------- late-interaction rerank
+    async def create_token_index(self, user_id: str, dim: int) -> None:
+        """Qdrant's multivector with comparator=MAX_SIM (additive): give the collection ONE token
+        column of `dim` values per token, a multiple of 64 in [64, 1024] (a model that emits fewer zero-pads; the handler
+        pads for it).  Points stored so far hold no tokens; store_document_vectors / upsert_points then take an optional
+        "token_embeddings" [T, d <= dim] per chunk, quantised on the host (late_interaction.quantize_tokens) and kept
+        beside the payloads.  Calling it again with the same width does nothing.  Raises ValueError for a bad or another
+        width, a sharded collection, or an engine index without token columns; KeyError for an unknown collection."""
+        try:
+            if not self._late_rerank:
+                raise ValueError("create_token_index is not supported on a sharded collection")
+            _late.check_dim(dim)
+            col = self._collections[str(user_id)]          # KeyError if absent: re-raised
+            await self._run(col.create_token_index, dim)
+        except Exception as e:
+            logging.error("create_token_index(%s, %r) failed: %s", user_id, dim, e)
+            raise
+
+    def _rerank_sync(self, user_id, dense_vectors, sparse_vectors, query_tokens, limit, candidates_limit, search_params,
+                     filters, mode, filter_stages):
+        if not self._late_rerank:
+            raise ValueError("hybrid_search_rerank is not supported on a sharded collection")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= 2048:
+            raise ValueError(f"limit must be an integer in [1, 2048], got {limit!r}")
+        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
+                                             or candidates_limit < 1):
+            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if mode not in ("tree", "h1"):
+            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+        root_filter = bool(filters) and filter_stages == "root"
+        if root_filter and mode != "tree":
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
+        hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
+        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
+        if pool_max < 1:
+            raise ValueError("the search_params leave an empty pool")
+        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        col = self._collections[str(user_id)]
+        tk = getattr(col, "tokens", None)
+        if tk is None:
+            raise ValueError("hybrid_search_rerank needs a token index: call create_token_index first")
+        if len(query_tokens) != len(sparse_vectors):
+            raise ValueError(f"{len(sparse_vectors)} queries but {len(query_tokens)} token lists")
+        q8, qs, qtip = _late.pack_queries(query_tokens, tk["dim"])      # ValueError: 0 or > 64 tokens, too wide, non-finite
+        q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
+        mask = None
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            mask = col.row_mask(filters)
+        scores, rows, first, counts = col.index.hybrid_query_rerank_host(
+            q, indptr, idx.astype(np.int32), val.astype(np.float32), hp, col._token_column(), q8, qs, qtip, limit,
+            candidates_limit=pool, mask=mask, mask_root_only=root_filter)
+        cids, cpay = col.ids, col.payloads
+        return [[RerankedPoint(id=cids[r], version=0, score=s, payload=cpay[r], first_score=f)
+                 for s, r, f in zip(sc[:n], rw[:n], fs[:n])]
+                for sc, rw, fs, n in zip(scores.tolist(), rows.tolist(), first.tolist(), counts.tolist())]
+
+    async def hybrid_search_rerank(self, user_id: str, dense_vectors, sparse_vectors, query_tokens, limit: int = 10,
+                                   candidates_limit: Optional[int] = 100,
+                                   search_params: Optional[Dict[str, Any]] = None, filters: Optional[Dict] = None,
+                                   mode: str = "tree", filter_stages: str = "root") -> List[List[RerankedPoint]]:
+        """Qdrant's hybrid + ColBERT recipe for B queries in one engine call (additive): the hybrid query is the prefetch,
+        the points of its POOL that hold tokens are rescored by MaxSim against query_tokens[b] -- a [Tq, d <= dim] float
+        array, 1 <= Tq <= 64, quantised as stored tokens are -- and the best `limit` come back, MaxSim descending, pool
+        order on a tie; include/hx.h states the arithmetic.  The pool is the ranked list the engine returns with
+        final_limit = the pool size, as hybrid_search_batch would (mode "tree": the root's re-scored union, min(dense_limit
+        + 10, 2048) rows; mode "h1": the fused list, min(dense_limit + sparse_limit, 2048)); candidates_limit asks for a
+        shorter pool, above the maximum it is clipped, None = the maximum.  search_params["final_limit"] must be there and
+        is NOT used.  A point stored without "token_embeddings" is not scored and never comes back.  filters /
+        filter_stages as in hybrid_search_mmr.  `score` = MaxSim, `first_score` = the score the pool carried.  All of it
+        runs on the device (hx_hybrid_query_rerank_host); there is no Python path.
+        Raises ValueError for arguments no search can serve (a limit outside [1, 2048], a candidates_limit below 1, a
+        query with no or more than 64 tokens or tokens wider than the index, a collection without a token index, mode
+        "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or filter clause); any other
+        failure is logged and gives [], as in every search."""
+        try:
+            return await self._run(self._rerank_sync, user_id, dense_vectors, sparse_vectors, query_tokens, limit,
+                                   candidates_limit, search_params, filters, mode, filter_stages)
+        except ValueError as ve:
+            logging.error("rerank hybrid search for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("rerank hybrid search for %s failed: %s", user_id, e)
+            return []
+
     async def rerank_with_colbert(self, query: str, documents: List[str], results: List[Dict],
                                   max_tokens: int) -> List[Dict]:
         """qdrant_handler.py:388-412: reorder by reranker indices; any failure keeps the order."""
@@ -946,6 +1166,8 @@ class QdrantHandler:
         col.index.retain(_filters.pack_rows(keep))
         col.ids = [i for i, k in zip(col.ids, keep) if k]
         col.payloads = [p for p, k in zip(col.payloads, keep) if k]
+        if getattr(col, "tokens", None) is not None:       # (the column was compacted with the rows, or dropped if it lagged)
+            col.tokens["cells"] = [c for c, k in zip(col.tokens["cells"], keep) if k]
         # the cached row masks speak of the old rows: dropped, not patched (a delete of k rows followed by an add of k
         # rows would pass the cache's `done != n` test with a stale mask)
         col._masks.clear()
