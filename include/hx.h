@@ -333,6 +333,14 @@ int hx_scan8_form(int32_t B, int64_t row_bytes, int32_t kind, int32_t* form);
 /* Waves that share the log appends of one scan launch over `tiles` 256-row tiles and nq_tiles query tiles (qs: the
  * query-stationary form): what the per-wave log capacity is planned by.  Host arithmetic only. */
 int hx_scan8_log_waves(int64_t tiles, int32_t nq_tiles, int32_t qs, double* waves);
+/* Diagnostic: the walk of workgroup `block` (0 .. 255) of one k_scan8q launch over the logical rows [row_begin, row_end)
+ * with nq_tiles query tiles (1, 2, 4, 8 or 16) and the tile permutation (perm_mul, perm_n; perm_n = 0: identity) -- the
+ * kernel's own cursor, run on the host; no index and no device are involved.
+ *  n_items      64-row items the workgroup scans (0: its stream has no rows);
+ *  tiles, rows  [cap] the physical 256-row tile and the first physical row of items 0 .. min(n_items, cap) - 1
+ *               (may be NULL when cap is 0). */
+int hx_scan8q_items(int64_t row_begin, int64_t row_end, int32_t nq_tiles, uint32_t perm_mul, uint32_t perm_n, int32_t block,
+                    int32_t cap, uint32_t* tiles, int64_t* rows, int32_t* n_items);
 int hx_sparse_wmax(hx_index* h, float* wmax, int32_t* nonpos);
 int hx_set_sparse_wmax(hx_index* h, float wmax);
 int hx_h1_nominate_async(hx_index* h, const float* q_dev, const int64_t* q_indptr_dev, const int32_t* q_idx_dev,

@@ -96,6 +96,8 @@ _SIGS = {
     "hx_dense_route": [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.POINTER(C.c_int32)] * 5,
     "hx_scan8_form": [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)],
     "hx_scan8_log_waves": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double)],
+    "hx_scan8q_items": [C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32),
+                        C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
     "hx_sparse_wmax": [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
     "hx_set_sparse_wmax": [_P, C.c_float],
     "hx_h1_nominate_async": [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P],

@@ -2382,6 +2382,30 @@ int hx_scan8_log_waves(int64_t tiles, int32_t nq_tiles, int32_t qs, double* wave
   HX_CATCH
 }
 
+int hx_scan8q_items(int64_t row_begin, int64_t row_end, int32_t nq_tiles, uint32_t perm_mul, uint32_t perm_n, int32_t block,
+                    int32_t cap, uint32_t* tiles, int64_t* rows, int32_t* n_items) {
+  HX_TRY
+  HX_CHECK(n_items && (cap == 0 || (tiles && rows)) && cap >= 0, "NULL argument");
+  HX_CHECK(row_begin >= 0 && (row_begin & 255) == 0 && row_end > row_begin && row_end < (1ll << 32),
+           "row_begin must be a multiple of 256 below row_end, rows below 2^32");
+  HX_CHECK(nq_tiles >= 1 && nq_tiles <= 16 && 32 % nq_tiles == 0, "nq_tiles must be 1, 2, 4, 8 or 16");
+  HX_CHECK(block >= 0 && block < 256, "block out of range [0, 256)");
+  HX_CHECK(perm_n < (1u << 24) && (perm_n == 0 || perm_mul < perm_n), "perm_mul < perm_n < 2^24");
+  // the kernel's own walk (kernels.hpp), on the host
+  Scan8qCursor cs;
+  cs.init(row_begin, row_end, nq_tiles, perm_mul, perm_n, block & 7, block >> 3);
+  *n_items = cs.n_items;
+  for (int j = 0; 2 * j < cs.n_items; ++j) {
+    if (j) cs.tile = cs.next_tile();
+    for (int odd = 0; odd < 2; ++odd)
+      if (2 * j + odd < cap) {
+        tiles[2 * j + odd] = cs.tile;
+        rows[2 * j + odd] = cs.row0() + odd * 64;
+      }
+  }
+  HX_CATCH
+}
+
 int hx_sparse_wmax(hx_index* h, float* wmax, int32_t* nonpos) {
   HX_TRY
   HX_CHECK(h && wmax && nonpos, "NULL argument");

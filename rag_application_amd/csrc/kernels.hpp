@@ -68,6 +68,41 @@ __host__ __device__ inline uint32_t scan_phys_tile(uint32_t t, uint32_t mul, uin
   r = r >= dn ? r - dn : r;
   return (uint32_t)r;
 }
+// The walk of one workgroup of k_scan8q (scan8.hip; its grid is always 256: 8 XCDs x 32 workgroups).  Workgroup
+// (xcd, i0) keeps query tile i0 mod nq and is stream i0 / nq of nstreams = 32 / nq; it scans the 128-row halves
+// u = stream + j * nstreams, j = 0, 1, ..., of its XCD's logical tiles (row_begin / 256 + (u >> 1) * 8 + xcd), each as a
+// PAIR of 64-row items.  nstreams is even, so u keeps its parity and the logical tile advances by 4 * nstreams per pair:
+// the physical tile advances by the constant step = (4 * nstreams * perm_mul) mod perm_n, one add and one conditional
+// subtract in 32-bit integers -- exact, and nothing but SALU inside the item loop.  The modulo itself is taken twice per
+// workgroup, for the start tile and for the step, in 64-bit integers (init runs in the kernel's prologue, where a
+// division costs nothing that shows; scan_phys_tile's fp64 form gives the same values and stays with the kernels that
+// take it once per twelve-phase item).  One code for the kernel and for the host (hx_scan8q_items).
+struct Scan8qCursor {
+  uint32_t tile;      // physical 256-row tile of the current pair
+  uint32_t step;      // added per pair
+  uint32_t wrap;      // perm_n, or 2^32 - 1 for the identity order (never reached)
+  uint32_t sub;       // first row of the pair's half inside its tile: 0 | 128
+  int n_items;        // 64-row items of this workgroup (even; 0: the stream has no rows)
+  __host__ __device__ static inline uint32_t mulmod(uint32_t t, uint32_t mul, uint32_t n) {
+    return n ? (uint32_t)(((uint64_t)t * (uint64_t)mul) % (uint64_t)n) : t;
+  }
+  __host__ __device__ inline void init(int64_t row_begin, int64_t row_end, int nq, uint32_t perm_mul, uint32_t perm_n,
+                                       int xcd, int i0) {
+    const int n_row_tiles = (int)((row_end - row_begin + 255) >> 8);
+    const int stream = i0 / nq, nstreams = 32 / nq;
+    const int halves_x = 2 * ((n_row_tiles - xcd + 7) >> 3);   // 128-row halves of this XCD's tiles
+    n_items = stream < halves_x ? 2 * ((halves_x - stream + nstreams - 1) / nstreams) : 0;
+    sub = (uint32_t)(stream & 1) * 128u;
+    wrap = perm_n ? perm_n : 0xFFFFFFFFu;
+    tile = mulmod((uint32_t)((row_begin >> 8) + (stream >> 1) * 8 + xcd), perm_mul, perm_n);
+    step = mulmod((uint32_t)(4 * nstreams), perm_mul, perm_n);
+  }
+  __host__ __device__ inline uint32_t next_tile() const {
+    const uint32_t p = tile + step;
+    return p >= wrap ? p - wrap : p;
+  }
+  __host__ __device__ inline int64_t row0() const { return (int64_t)tile * 256 + sub; }   // odd item of the pair: + 64
+};
 constexpr int SCAN8_WAVES = 256 * 8;   // waves of the largest scan8 grid
 constexpr int SCAN8_LOGCAP = 4096;      // most entries per wave log (expected: a few hundred per launch)
 #ifndef HX_S8_TS

@@ -694,10 +694,34 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
 // waves 0..3, as in k_scan8.
 // The thresholds of a lane's two query columns are constants of the launch and live in two registers; the row-scale
 // bound of an item is the one of its parent 256-row tile (still an upper bound of the half's rows).
+// The item loop is unrolled over the PAIR of items of a half (ring slots are constants) and walks with Scan8qCursor
+// (kernels.hpp): integer SALU once per pair, inside an M segment -- an item has three phases, not k_scan8's twelve, and
+// the fp64 tile modulo, its v_readfirstlane and the scale load at the head of every item's first L segment cost that
+// segment 850 cycles against 305 (profiles/scan8q_cursor.txt).
 // Log entries are k_scan8's: {query, first row} + MT words, one entry per passing column of a 64-row item;
 // k_scatter_log<.., QS> maps wave w of workgroup (xcd, i0) to queries qt * 256 + 32 w .. + 31.
 // DBG 2 (timing build, wrong results): no global_load_lds in the loop.
 constexpr int S8Q_SLAB = 8192;
+// Diagnostic build only (-DHX_S8Q_STAMP; scripts/s8q_stamps.py): waves 0 and 4 -- one per stagger group -- accumulate
+// s_memtime deltas around every barrier of the item loop, by phase position (first, middle, last phase of an item):
+//   [4 pos + 0] L segment   [4 pos + 1] the wait at the barrier behind it   [4 pos + 2] M segment   [4 pos + 3] its barrier
+//   [12] the tail of a last M segment, from the issue of its last MFMA to the end of the filter   [13] items
+// into a debug buffer of their own, summed over launches (never read by the kernel, never in a timed build).
+#ifdef HX_S8Q_STAMP
+constexpr int S8Q_NSTAMP = 16;
+__device__ unsigned long long g_s8q_stamps[256 * 2 * S8Q_NSTAMP];
+#define S8Q_STAMP_DECL unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_tf = 0, st_acc[S8Q_NSTAMP] = {};
+#define S8Q_STAMP(i) { const unsigned long long st_t1 = __builtin_amdgcn_s_memtime(); st_acc[i] += st_t1 - st_t0; st_t0 = st_t1; }
+#define S8Q_STAMP_TAIL_BEGIN st_tf = __builtin_amdgcn_s_memtime();
+#define S8Q_STAMP_TAIL_END { st_acc[12] += __builtin_amdgcn_s_memtime() - st_tf; st_acc[13] += 1; }
+#define S8Q_STAMP_FLUSH if (lane == 0 && (wave & 3) == 0) for (int i_ = 0; i_ < S8Q_NSTAMP; ++i_) g_s8q_stamps[(blockIdx.x * 2 + grp) * S8Q_NSTAMP + i_] += st_acc[i_];
+#else
+#define S8Q_STAMP_DECL
+#define S8Q_STAMP(i)
+#define S8Q_STAMP_TAIL_BEGIN
+#define S8Q_STAMP_TAIL_END
+#define S8Q_STAMP_FLUSH
+#endif
 template <int KT, int DBG, int KP>
 __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   constexpr int MT = 4, NT = 2, KS = 2;
@@ -716,19 +740,20 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   GF* g_rinv_q = (GF*)a.rinv_q;
   auto* g_ovf = (__attribute__((address_space(1))) int*)a.overflow;
 
-  const int64_t n_rows = a.row_end - a.row_begin;
-  const int n_row_tiles = (int)((n_rows + 255) >> 8);
   const int nq = a.nq_tiles;
   const int xcd = blockIdx.x & 7;
-  const int per_xcd = gridDim.x >> 3;
   const int i0 = blockIdx.x >> 3;
-  const int qt = i0 % nq, stream = i0 / nq, nstreams = per_xcd / nq;
-  const int halves_x = 2 * ((n_row_tiles - xcd + 7) >> 3);   // 128-row halves of this XCD's tiles
-  if (stream >= halves_x) {
+  const int qt = i0 % nq;
+  // ---- item cursor (scalar; kernels.hpp): its two modulos are taken here, nothing in flight ----------------
+  Scan8qCursor cs;
+  cs.init(a.row_begin, a.row_end, nq, a.perm_mul, a.perm_n, xcd, i0);
+  cs.tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)cs.tile);
+  cs.step = (uint32_t)__builtin_amdgcn_readfirstlane((int)cs.step);
+  if (cs.n_items == 0) {     // the stream has no rows
     if (lane == 0) a.hitcnt[blockIdx.x * 8 + wave] = 0;
     return;
   }
-  const int n_items = 2 * ((halves_x - stream + nstreams - 1) / nstreams);   // 64-row items of this workgroup
+  const int n_pairs = cs.n_items >> 1;   // 128-row halves of this workgroup, two 64-row items each
 
   // ---- the wave's query fragments and thresholds: plain loads, nothing else in flight ----------------------
   i32x4 qf[NT][KT][KS];
@@ -770,23 +795,15 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   uint32_t rd[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) rd[ks] = (uint32_t)r * 128 + (uint32_t)(((ks * 4 + hh) ^ swz) << 4);   // + mt * 2048
+  // the same for slots 8 on: a ds_read offset holds 16 bits, and the ring slots are constants of the unrolled item
+  // pair -- without a second base the compiler forms every such address with a VALU op at the head of the L segment
+  uint32_t rd_hi[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    rd_hi[ks] = rd[ks] + 8 * S8Q_SLAB;
+    asm volatile("" : "+v"(rd_hi[ks]));
+  }
 
-  // ---- item cursor (scalar): item k = 64-row part (k & 1) of half u = stream + (k >> 1) * nstreams ------
-  struct Item {
-    const uint8_t* p;   // first row of the item
-    int64_t row0;       // its physical row
-    int rt;             // its physical 256-row tile
-  };
-  auto item_at = [&](int k) __attribute__((always_inline)) {
-    const int u = stream + (k >> 1) * nstreams;
-    const int rt = (int)__builtin_amdgcn_readfirstlane(
-        (int)scan_phys_tile((uint32_t)((a.row_begin >> 8) + (u >> 1) * 8 + xcd), a.perm_mul, a.perm_n, a.perm_inv));
-    Item it;
-    it.rt = rt;
-    it.row0 = (int64_t)rt * 256 + (u & 1) * 128 + (k & 1) * 64;
-    it.p = a.A + it.row0 * a.row_bytes;
-    return it;
-  };
   auto stage = [&](const uint8_t* base, int kt, int slot) __attribute__((always_inline)) {
     // (the empty asm keeps `scalar base + zext(32-bit lane offset)` visible to instruction selection: see k_scan8)
     // (and the one on the base keeps the k-tile's 128 bytes a SCALAR add: folded into the lane offset it costs two 64-bit
@@ -850,40 +867,58 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
     }
   };
 
+  // ---- the pair in hand and the one behind it (all scalar) -------------------------------------------------
+  // An item's fixed part is the advance below, once per PAIR: an add, a compare and a select for the tile, the
+  // 64-bit row address, and the s_load of the tile's scale bound -- SALU and SMEM only, issued behind the first MFMA
+  // of the even item's first M segment (where SALU issue is free and the compiler's own lgkmcnt(0) for the
+  // fragments is already passed), and the load is waited for at the end of that segment: a whole segment to land, a
+  // whole item before the pair needs it, and never the first wait of an L segment.  The odd item is + 64 rows.
+  typedef __attribute__((address_space(4))) const float CF;   // constant address space + uniform index = s_load_dword
+  const int64_t item_bytes = a.row_bytes * 64;
+  int64_t row_c = cs.row0();                        // first physical row of the pair in hand
+  const uint8_t* p_c = a.A + row_c * a.row_bytes;
+  rxm = ((CF*)a.rinv_tile_max)[cs.tile];
+  int64_t row_n = row_c;                            // the next pair; past the last one the cursor does not advance:
+  const uint8_t* p_n = p_c;                         // its even item is re-loaded (never read)
+  float rxm_n = rxm;
+
   // ---- prologue: the KT slabs of item 0 ---------------------------------------------------------------------
-  Item cur = item_at(0);
 #pragma unroll
-  for (int kt = 0; kt < KT; ++kt) stage(cur.p, kt, kt);
+  for (int kt = 0; kt < KT; ++kt) stage(p_c, kt, kt);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (grp == 1) __builtin_amdgcn_s_barrier();   // the stagger
+  S8Q_STAMP_DECL
 
-  for (int k = 0; k < n_items; ++k) {
-    const Item nxt = item_at(k + 1 < n_items ? k + 1 : k);   // past the last item: re-load it (never read)
-    const int s_cur = (k & 1) * KT, s_nxt = KT - s_cur;
-    {
-      typedef __attribute__((address_space(4))) const float CF;   // constant address space + uniform index = s_load_dword
-      rxm = ((CF*)a.rinv_tile_max)[cur.rt];
-    }
+  // item 2 j + ODD: ring slots ODD * KT .., stages the item behind it into the other half of the ring
+  auto item = [&](auto odd_c, int j) __attribute__((always_inline)) {
+    constexpr int ODD = decltype(odd_c)::value;
+    constexpr int s_cur = ODD * KT, s_nxt = KT - s_cur;
+    const uint8_t* nxt_p = ODD ? p_n : p_c + item_bytes;
 #pragma unroll
     for (int kt = 0; kt < KT; kt += KP) {
+      const int pos = kt == 0 ? 0 : (kt + KP == KT ? 2 : 1);   // first, middle, last phase of the item (stamps)
+      (void)pos;
       // L segment
 #pragma unroll
       for (int kp = 0; kp < KP; ++kp) {
-        const uint8_t* s = lds + (s_cur + kt + kp) * S8Q_SLAB;
+        const bool hi = s_cur + kt + kp >= 8;   // (a constant once the loops are unrolled)
+        const uint8_t* s = lds + (s_cur + kt + kp - (hi ? 8 : 0)) * S8Q_SLAB;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-          for (int ks = 0; ks < KS; ++ks) af[kp][mt][ks] = *(const half8*)(s + rd[ks] + mt * 2048);
+          for (int ks = 0; ks < KS; ++ks) af[kp][mt][ks] = *(const half8*)(s + (hi ? rd_hi[ks] : rd[ks]) + mt * 2048);
       }
       __builtin_amdgcn_sched_barrier(0);
       if (!NO_GLDS) {
 #pragma unroll
-        for (int kp = 0; kp < KP; ++kp) stage(nxt.p, kt + kp, s_nxt + kt + kp);
+        for (int kp = 0; kp < KP; ++kp) stage(nxt_p, kt + kp, s_nxt + kt + kp);
       }
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(KT - KP) : "memory");
       __builtin_amdgcn_sched_barrier(0);
+      S8Q_STAMP(pos * 4 + 0)
       __builtin_amdgcn_s_barrier();
+      S8Q_STAMP(pos * 4 + 1)
       __builtin_amdgcn_sched_barrier(0);
       // M segment
       __builtin_amdgcn_s_setprio(1);
@@ -899,19 +934,47 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
               const i32x4 cin = (kt + kp == 0 && ks == 0) ? z : acc[mt][nt];
               acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[kp][mt][ks]), qf[nt][kt + kp][ks],
                                                                   cin, 0, 0, 0);
+              if (!ODD && kt == 0 && kp == 0 && ks == 0 && mt == 0 && nt == 0) {   // the advance (see above)
+                __builtin_amdgcn_sched_barrier(0);
+                const uint32_t t2 = cs.next_tile();
+                cs.tile = j + 1 < n_pairs ? t2 : cs.tile;
+                row_n = cs.row0();
+                p_n = a.A + row_n * a.row_bytes;
+                rxm_n = ((CF*)a.rinv_tile_max)[cs.tile];
+                asm volatile("" : "+s"(p_n));      // (the address is formed here, not where the odd item first stages)
+              }
             }
-      if (kt + KP == KT) filter(cur.row0);
+      if (!ODD && kt == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("; the next pair's scale bound has landed" ::"s"(rxm_n));
+      }
+      if (kt + KP == KT) {
+        S8Q_STAMP_TAIL_BEGIN
+        filter(row_c + ODD * 64);
+        S8Q_STAMP_TAIL_END
+        if (ODD) {             // the pair boundary
+          row_c = row_n;
+          p_c = p_n;
+          rxm = rxm_n;
+        }
+      }
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
+      S8Q_STAMP(pos * 4 + 2)
       __builtin_amdgcn_s_barrier();
+      S8Q_STAMP(pos * 4 + 3)
       __builtin_amdgcn_sched_barrier(0);
     }
-    cur = nxt;
+  };
+  for (int j = 0; j < n_pairs; ++j) {
+    item(std::integral_constant<int, 0>{}, j);
+    item(std::integral_constant<int, 1>{}, j);
   }
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the never-read tail loads
   if (grp == 0) __builtin_amdgcn_s_barrier();
   if (lane == 0) a.hitcnt[blockIdx.x * 8 + wave] = wpos;
+  S8Q_STAMP_FLUSH
 }
 
 // Logs -> per-query candidate buffers.  Every entry is a lane's column of one quadrant (see the
@@ -1070,6 +1133,7 @@ void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_
   static const int qs_kp = getenv("HX_DEBUG_S8Q_KP") ? atoi(getenv("HX_DEBUG_S8Q_KP")) : 2;   // diagnostics: k-tiles per phase, 1 | 2
   if (!a.no_qs && cap == 256 && (dbg == 0 || dbg == 12) && scan8_qs_form(kind, a.half_q, a.row_bytes, a.nq_tiles)) {
     g = 256;
+    HX_CHECK(((32 / a.nq_tiles) & 1) == 0, "scan8: the query-stationary walk needs an even number of streams per XCD");
 #ifdef HX_SCAN_DBG
     if (dbg == 12) hipLaunchKernelGGL((k_scan8q<6, 2, 2>), dim3(256), dim3(512), 0, st, a); else
 #endif
@@ -1126,3 +1190,10 @@ void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_
 }
 
 }  // namespace hx
+
+#ifdef HX_S8Q_STAMP
+// out_host[0, n) = the stamp sums since the library was loaded (diagnostic build only)
+extern "C" int hx_debug_s8q_stamps(unsigned long long* out_host, int n) {
+  return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(hx::g_s8q_stamps), (size_t)n * 8);
+}
+#endif

@@ -947,6 +947,17 @@ def scan8_log_waves(tiles: int, nq_tiles: int, qs: bool) -> float:
     return float(v.value)
 
 
+def scan8q_items(row_begin: int, row_end: int, nq_tiles: int, perm_mul: int, perm_n: int, block: int):
+    """The walk of workgroup `block` of a k_scan8q launch (hx_scan8q_items: the kernel's cursor on the host): (tiles,
+    rows), the physical 256-row tile and the first physical row of every 64-row item, in order.  No index, no device."""
+    n = C.c_int32()
+    check(_lib.lib().hx_scan8q_items(row_begin, row_end, nq_tiles, perm_mul, perm_n, block, 0, None, None, C.byref(n)))
+    tiles = (C.c_uint32 * max(n.value, 1))()
+    rows = (C.c_int64 * max(n.value, 1))()
+    check(_lib.lib().hx_scan8q_items(row_begin, row_end, nq_tiles, perm_mul, perm_n, block, n.value, tiles, rows, C.byref(n)))
+    return list(tiles[:n.value]), list(rows[:n.value])
+
+
 def h1_finish(reduced: torch.Tensor, world: int, B: int, lp: int, k3: int, dense_limit: int, sparse_limit: int,
               limit: int = 10, k: float = 2.0, rank_base: int = 0, nfail: Optional[torch.Tensor] = None):
     """reduced: the all-reduced (integer sum over the `world` ranks) result of h1_rescore_async.  Returns (keys [B, limit],
