@@ -708,6 +708,56 @@ int hx_hybrid_query_rerank_host(hx_index* h, const float* q_dense_host, const in
                                 const int64_t* qtok_indptr_host, int32_t limit, float* scores_host, int64_t* ids_host,
                                 float* first_scores_host, int32_t* counts_host);
 
+/* ---- recommend search ----------------------------------------------
+ * Qdrant's RecommendQuery(positive, negative, strategy) (additive: the reference never calls it; parity unpinned, the
+ * semantics below are this project's statement of it): the nearest points to given examples.  Additive to the ABI:
+ * HX_ABI_VERSION stays 3.
+ *
+ * A call carries R requests, 1 <= R <= HX_RECO_MAX_REQUESTS.  Request r has E_r examples, 1 <= E_r <=
+ * HX_RECO_MAX_EXAMPLES with E_r * dim_pad <= 32768 floats (dim_pad = dim rounded up to 64: 32 examples up to width
+ * 1024, 8 at width 4096), each with a sign, +1 positive or -1 negative.  An example is a STORED ROW -- a local row in
+ * [0, hx_count), as hx_replace_rows takes rows; its vector is the normalised fp32 row as stored, bit for bit -- or a RAW
+ * VECTOR of dim finite fp32 values, normalised by the rule every dense query is.  p_0 .. p_{P-1} are the positives in the
+ * order given, n_0 .. n_{N-1} the negatives in the order given; duplicates are allowed, a row may carry both signs.
+ * sim(x, e) = the spec dot product of the stored normalised row x and e over the padded width.  Every product, sum,
+ * difference and quotient below is one unfused fp32 operation, round to nearest; every final score gets + 0.0f, so that
+ * -0 and +0 are one value.
+ *   HX_RECO_AVERAGE     needs P >= 1.  pm[k] = (((p_0[k] + p_1[k]) + ...) + p_{P-1}[k]) / f32(P), nm likewise;
+ *                       q[k] = pm[k] + (pm[k] - nm[k]) when N >= 1, else pm[k].  q then IS a raw dense query: the list
+ *                       is what hx_search_dense(q, prefix = 0) returns with the excluded rows removed.
+ *   HX_RECO_BEST_SCORE  s+ = max_i sim(x, p_i) (-inf when P = 0), s- = max_j sim(x, n_j) (-inf when N = 0);
+ *                       score = s+ if s+ > s-, else -(s- * s-).
+ *   HX_RECO_SUM_SCORES  acc = +0.0f, then acc = acc + sim(x, p_i) in order, then acc = acc - sim(x, n_j) in order.
+ * A row is excluded when it is a stored example of the same request (either sign) or its bit is clear in the optional
+ * row mask (the layout of hx_hybrid_query_*_masked; mask_rows must equal hx_count; an example need not be kept by the
+ * mask).  Order: score descending, id ascending, as make_key(score, global id).  Request r gets min(limit, rows not
+ * excluded) keys, the slots past them are 0; an empty index gives counts 0.
+ *
+ * ex_indptr_host [R + 1]; ex_rows_host [E] = a local row, or -1 = the next raw vector of ex_vecs_host ([n_raw x dim]
+ * fp32, in the order of the -1 entries; may be NULL when there is none); ex_sign_host [E].
+ * Refused before any device work, every output untouched: a NULL argument (the mask and an unneeded ex_vecs_host
+ * aside), R, E_r, limit or the LDS bound out of range, a sign that is neither +1 nor -1, a row outside [0, hx_count), a
+ * non-finite raw element ("finite" in the message), HX_RECO_AVERAGE with P = 0, an unknown strategy, mask_rows !=
+ * hx_count with a mask.  hx_recommend synchronises `stream` (the dense stage's certificate; the scan's overflow word,
+ * read once behind the scan).  hx_recommend_host adds the unpacking and the copy out: scores_host / ids_host
+ * [R x limit], empty slots (-inf, -1); counts_host [R].
+ * HX_DEBUG_RECO_CHUNK0 (rows of the scan's first chunk) and HX_DEBUG_RECO_CAP (keys of a request's candidate buffer, at
+ * least 2 * limit) are read by hx_create, per index: tests. */
+#define HX_RECO_AVERAGE 0
+#define HX_RECO_BEST_SCORE 1
+#define HX_RECO_SUM_SCORES 2
+#define HX_RECO_MAX_REQUESTS 16
+#define HX_RECO_MAX_EXAMPLES 32
+#define HX_RECO_MAX_LIMIT 1024
+int hx_recommend(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host,
+                 const int64_t* ex_rows_host, const int8_t* ex_sign_host, const float* ex_vecs_host,
+                 const uint32_t* mask_dev, int64_t mask_rows, int32_t limit,
+                 uint64_t* keys_dev /* [R x limit] */, int32_t* counts_dev /* [R] */, void* stream);
+int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host,
+                      const int64_t* ex_rows_host, const int8_t* ex_sign_host, const float* ex_vecs_host,
+                      const uint32_t* mask_host, int64_t mask_rows, int32_t limit,
+                      float* scores_host, int64_t* ids_host, int32_t* counts_host);
+
 /* ---- payload facets -------------------------------------------
  * Qdrant's facet(collection, key, facet_filter, limit, exact) (additive: the reference never calls it; parity unpinned, the
  * semantics below are this project's statement of it): for every value of a keyword or bool field, the number of points a

@@ -1593,16 +1593,16 @@ void mask_rows_dev(hx_index* h, const uint32_t* mask_dev, uint32_t*& rows, uint3
   launch_mask_rows(mask_dev, h->n, blk, rows, count_dev, st);
 }
 
-// hybrid_query_dev restricted to the rows of mask_dev.  count_known >= 0: the caller counted the kept rows (the host
-// entry, from the host mask); otherwise the count is read back once through the pinned buffer.  Keys leave with
-// internal ids, as those of hybrid_query_dev.
-static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
-                             const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
-                             int* out_cnt, hipStream_t st) {
-  if (count_known == h->n) return hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
-  if (count_known == 0) return zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
+// The frame of a pre-filtered call (masked_query_dev below; the recommend call's average route): run() with the view of
+// the kept rows set up -- or plainly when the mask keeps every row; returns false, without calling run(), when it keeps
+// none.  count_known >= 0: the caller counted the kept rows (the host entry, from the host mask); otherwise the count is
+// read back once through the pinned buffer.  sparse: run() searches the sparse vectors too.
+template <typename F>
+static bool with_mask_view(hx_index* h, const uint32_t* mask_dev, int64_t count_known, bool sparse, hipStream_t st, F&& run) {
+  if (count_known == h->n) return run(), true;
+  if (count_known == 0) return false;
   // (sparse vectors of rows whose dense rows have not arrived: the mask has no bit for them)
-  HX_CHECK(h->nnz == 0 || h->sp_rows <= h->n, "masked query: sparse vectors are pending for rows not added yet");
+  HX_CHECK(!sparse || h->nnz == 0 || h->sp_rows <= h->n, "masked query: sparse vectors are pending for rows not added yet");
   uint32_t *rows = nullptr, *count_dev = nullptr;
   {
     ProfScope ps(h, st, 5, 0.0, 0.0);   // hx_prof slot 5: the mask's list and the gathers
@@ -1614,8 +1614,8 @@ static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
     HX_HIP(hipMemcpyAsync(pin, count_dev, 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     count = pin[0];
-    if (count == h->n) return hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
-    if (count == 0) return zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
+    if (count == h->n) return run(), true;
+    if (count == 0) return false;
   }
   auto& v = h->mv;
   if (count > v.cap) {            // the copies' buffers: the next power of two of the kept rows, kept across calls
@@ -1635,7 +1635,17 @@ static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, c
     ~Off() { h->mv.on = false; }
   } off{h};
   v.on = true;
-  hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st);
+  run();
+  return true;
+}
+
+// hybrid_query_dev restricted to the rows of mask_dev.  Keys leave with internal ids, as those of hybrid_query_dev.
+static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
+                             const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
+                             int* out_cnt, hipStream_t st) {
+  if (!with_mask_view(h, mask_dev, count_known, true, st,
+                      [&] { hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st); }))
+    zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
 }
 
 // RRF settings: k finite and positive with 2 / k finite -- a document's two contributions
@@ -1659,6 +1669,187 @@ static void check_params(const hx_params* p) {
                  ok(p->quantized_limit) && ok(p->rrf_limit),
              "limit out of range [1, 2048]");
   }
+}
+
+// ---------------------------------------------------------------------------------
+// recommend search (hx_recommend)
+// ---------------------------------------------------------------------------------
+// A call as the kernels take it: the examples request by request, positives first, each group in the order given.
+struct RecoCall {
+  std::vector<RecoReq> req;
+  std::vector<int64_t> src;       // per example: the stored row, or -1 - (index of the raw vector)
+  std::vector<uint32_t> excl;     // per request from excl0: its stored rows, ascending, unique
+  int n_raw = 0, max_excl = 0;
+};
+
+// every refusal of the call, before any device work
+static RecoCall reco_check(hx_index* h, int strategy, int R, const int64_t* indptr, const int64_t* rows, const int8_t* sign,
+                           const float* vecs, const void* mask, int64_t mask_rows, int limit) {
+  HX_CHECK(h && indptr && rows && sign, "NULL argument");
+  HX_CHECK(strategy == HX_RECO_AVERAGE || strategy == HX_RECO_BEST_SCORE || strategy == HX_RECO_SUM_SCORES,
+           "recommend: unknown strategy");
+  HX_CHECK(R >= 1 && R <= HX_RECO_MAX_REQUESTS, "recommend: requests out of range [1, 16]");
+  HX_CHECK(limit >= 1 && limit <= HX_RECO_MAX_LIMIT, "recommend: limit out of range [1, 1024]");
+  HX_CHECK(!mask || mask_rows == h->n, "recommend: mask_rows must equal the index's row count (hx_count)");
+  HX_CHECK(indptr[0] == 0, "recommend: bad example indptr");
+  RecoCall c;
+  for (int r = 0; r < R; ++r) {
+    const int64_t b = indptr[r], e = indptr[r + 1];
+    HX_CHECK(e - b >= 1 && e - b <= HX_RECO_MAX_EXAMPLES, "recommend: a request takes 1 to 32 examples");
+    HX_CHECK((e - b) * h->dim_pad <= RECO_LDS_FLOATS, "recommend: examples x padded width above 32768 floats");
+    RecoReq q{};
+    q.ex0 = (int)c.src.size();
+    q.excl0 = (int)c.excl.size();
+    q.slot = r;
+    std::vector<int64_t> raw_of((size_t)(e - b), -1);
+    for (int64_t i = b; i < e; ++i) {
+      HX_CHECK(sign[i] == 1 || sign[i] == -1, "recommend: a sign must be +1 or -1");
+      if (rows[i] == -1) {
+        HX_CHECK(vecs != nullptr, "NULL argument");
+        const float* v = vecs + (int64_t)c.n_raw * h->dim;
+        for (int k = 0; k < h->dim; ++k) HX_CHECK(std::isfinite(v[k]), "recommend: example vector values must be finite");
+        raw_of[(size_t)(i - b)] = c.n_raw++;
+      } else {
+        HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "recommend: example row out of range");
+        c.excl.push_back((uint32_t)rows[i]);
+      }
+    }
+    for (int s = 1; s >= -1; s -= 2)
+      for (int64_t i = b; i < e; ++i)
+        if (sign[i] == s) {
+          c.src.push_back(rows[i] == -1 ? -1 - raw_of[(size_t)(i - b)] : rows[i]);
+          if (s == 1) ++q.n_pos;
+        }
+    q.n_ex = (int)(e - b);
+    HX_CHECK(strategy != HX_RECO_AVERAGE || q.n_pos >= 1, "recommend: the average strategy needs a positive example");
+    std::sort(c.excl.begin() + q.excl0, c.excl.end());
+    c.excl.erase(std::unique(c.excl.begin() + q.excl0, c.excl.end()), c.excl.end());
+    q.n_excl = (int)c.excl.size() - q.excl0;
+    c.max_excl = std::max(c.max_excl, q.n_excl);
+    c.req.push_back(q);
+  }
+  return c;
+}
+
+// count_known: the kept rows of the mask when the caller counted them (the host entry), -1 otherwise.  Keys leave with
+// internal ids.  Synchronises `st`.
+static void recommend_dev(hx_index* h, int strategy, int R, const RecoCall& c_in, const float* vecs, const uint32_t* mask_dev,
+                          int64_t count_known, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
+  if (h->n == 0 || count_known == 0) {
+    zero_outputs(out_keys, out_cnt, R, L, st);
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
+  RecoCall c = c_in;
+  const int E = (int)c.src.size(), dp = h->dim_pad;
+  // The scan's launches: requests in order, as many as fit the LDS together -- the corpus is read once per launch.
+  std::vector<std::pair<int, int>> groups;   // [first request, end) and, in lds0, where each request's examples are staged
+  for (int r = 0, g0 = 0, used = 0; r < R; ++r) {
+    if ((int64_t)(used + c.req[r].n_ex) * dp > RECO_LDS_FLOATS) {
+      groups.push_back({g0, r});
+      g0 = r;
+      used = 0;
+    }
+    c.req[r].lds0 = used;
+    used += c.req[r].n_ex;
+    if (r == R - 1) groups.push_back({g0, R});
+  }
+  // one upload: the descriptors, the example sources, the excluded rows
+  const size_t o_src = round_up(R * sizeof(RecoReq), 16), o_excl = o_src + round_up((size_t)E * 8, 16);
+  const size_t meta_bytes = o_excl + c.excl.size() * 4 + 16;
+  std::vector<uint8_t> meta(meta_bytes, 0);
+  std::memcpy(meta.data(), c.req.data(), R * sizeof(RecoReq));
+  std::memcpy(meta.data() + o_src, c.src.data(), (size_t)E * 8);
+  if (!c.excl.empty()) std::memcpy(meta.data() + o_excl, c.excl.data(), c.excl.size() * 4);
+  uint8_t* meta_dev = (uint8_t*)h->ws.get(WS_RECO_META, meta_bytes);
+  HX_HIP(hipMemcpyAsync(meta_dev, meta.data(), meta_bytes, hipMemcpyHostToDevice, st));
+  const RecoReq* req_dev = (const RecoReq*)meta_dev;
+  const uint32_t* excl_dev = (const uint32_t*)(meta_dev + o_excl);
+  float* raw_n = nullptr;
+  if (c.n_raw) {   // raw vectors: the dense stage's query preparation (finite: checked on the host)
+    float* raw = (float*)h->ws.get(WS_RECO_RAW, (size_t)c.n_raw * h->dim * 4);
+    raw_n = (float*)h->ws.get(WS_RECO_RAWN, (size_t)c.n_raw * dp * 4);
+    HX_HIP(hipMemcpyAsync(raw, vecs, (size_t)c.n_raw * h->dim * 4, hipMemcpyHostToDevice, st));
+    launch_prep_queries_f(raw, h->dim, c.n_raw, c.n_raw, h->dim, dp, raw_n, nullptr, st);
+  }
+  float* X = (float*)h->ws.get(WS_RECO_X, (size_t)E * dp * 4);
+  launch_reco_examples(h->dense, raw_n, (const int64_t*)(meta_dev + o_src), E, dp, X, st);
+
+  if (strategy == HX_RECO_AVERAGE) {
+    // the dense stage, unchanged, for R queries and room for every stored example; then the examples are dropped
+    const int Lin = L + c.max_excl;
+    float* q = (float*)h->ws.get(WS_RECO_Q, (size_t)R * h->dim * 4);
+    uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_KEYS, (size_t)R * Lin * 8);
+    int* kcnt = (int*)h->ws.get(WS_RECO_KCNT, (size_t)R * 4);
+    launch_reco_average(X, req_dev, R, h->dim, dp, q, st);
+    const auto run = [&] { search_dense(h, q, R, 0, Lin, keys, kcnt, st); };
+    const bool any = mask_dev ? with_mask_view(h, mask_dev, count_known, false, st, run) : (run(), true);
+    if (any) launch_reco_drop(keys, Lin, kcnt, req_dev, excl_dev, (uint32_t)h->id_base, R, L, out_keys, out_cnt, st);
+    else zero_outputs(out_keys, out_cnt, R, L, st);
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
+
+  // BEST_SCORE / SUM_SCORES: the exhaustive scan in geometric chunks with a non-predictive threshold, as chunked_scan:
+  // the first chunk passes every row (tau = -inf), every compaction keeps the best L and sets tau to the exact L-th score
+  // so far.  A doubling chunk of an exchangeable corpus appends about L ln 2 keys; the buffer takes C - L.
+  int C = std::clamp(next_pow2(8 * L), 2048, CAND_CAP);
+  if (h->reco_cap) C = std::max(h->reco_cap, 2 * L);
+  const int64_t chunk0 = h->reco_chunk0 ? std::min(h->reco_chunk0, C) : C;
+  uint64_t* cand = (uint64_t*)h->ws.get(WS_RECO_CAND, (size_t)R * C * 8);
+  int* cnt = (int*)h->ws.get(WS_RECO_CNT, (size_t)R * 4);
+  int* ovf = (int*)h->ws.get(WS_RECO_OVF, (size_t)R * 4);
+  float* tau = (float*)h->ws.get(WS_RECO_TAU, (size_t)R * 4);
+  float* tau0 = (float*)h->ws.get(WS_RECO_TAU0, (size_t)R * 4);   // stays -inf: the redo's threshold
+  HX_HIP(hipMemsetAsync(cnt, 0, (size_t)R * 4, st));
+  HX_HIP(hipMemsetAsync(ovf, 0, (size_t)R * 4, st));
+  launch_fill_f32(tau, R, -__builtin_inff(), st);
+  launch_fill_f32(tau0, R, -__builtin_inff(), st);
+  RecoScanArgs a{};
+  a.dense = h->dense;
+  a.dim_pad = dp;
+  a.X = X;
+  a.excl = excl_dev;
+  a.mask = mask_dev;
+  a.strategy = strategy;
+  a.cand = cand;
+  a.cnt = cnt;
+  a.ovf = ovf;
+  a.cap = C;
+  a.id_base = (uint32_t)h->id_base;
+  const auto scan = [&](int g0, int g1, int64_t r0, int64_t r1, const float* t) {
+    a.req = req_dev + g0;
+    a.n_req = g1 - g0;
+    a.row_begin = r0;
+    a.row_end = r1;
+    a.tau = t;
+    launch_reco_scan(a, c.req[g1 - 1].lds0 + c.req[g1 - 1].n_ex, st);
+  };
+  for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
+    for (const auto& g : groups) scan(g.first, g.second, r0, r1, tau);
+    launch_compact(cand, C, cnt, R, L, 0, cand, C, cnt, tau, C, st);
+    r0 = r1;
+    r1 = std::min<int64_t>(h->n, 2 * r1);
+  }
+  // the overflow word, read once behind the scan
+  std::vector<int> flagged((size_t)R);
+  HX_HIP(hipMemcpyAsync(flagged.data(), ovf, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  // A request whose buffer overflowed (a corpus ordered so that every chunk beats the threshold): again in fixed chunks of
+  // C - L rows, every row appended, a compaction after each -- as exact_range_fallback; the same list by construction.
+  for (int r = 0; r < R; ++r) {
+    if (!flagged[(size_t)r]) continue;
+    c.req[r].lds0 = 0;
+    HX_HIP(hipMemcpyAsync(meta_dev + r * sizeof(RecoReq), &c.req[r], sizeof(RecoReq), hipMemcpyHostToDevice, st));
+    HX_HIP(hipMemsetAsync(cnt + r, 0, 4, st));
+    for (int64_t r0 = 0; r0 < h->n; r0 += C - L) {
+      scan(r, r + 1, r0, std::min<int64_t>(h->n, r0 + (C - L)), tau0);
+      launch_compact(cand + (int64_t)r * C, C, cnt + r, 1, L, 0, cand + (int64_t)r * C, C, cnt + r, nullptr, C, st);
+    }
+  }
+  HX_HIP(hipMemcpy2DAsync(out_keys, (size_t)L * 8, cand, (size_t)C * 8, (size_t)L * 8, (size_t)R, hipMemcpyDeviceToDevice, st));
+  HX_HIP(hipMemcpyAsync(out_cnt, cnt, (size_t)R * 4, hipMemcpyDeviceToDevice, st));
+  HX_HIP(hipStreamSynchronize(st));
 }
 
 }  // namespace hx
@@ -1716,6 +1907,8 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_TAIL_MIN")) h->tail_min_force = atoll(e);   // tests: force / forbid a tail index
   if (const char* e = getenv("HX_DEBUG_COMPACT_CHUNK")) h->compact_chunk = std::max<int64_t>(0, atoll(e));   // tests: many chunks
   if (const char* e = getenv("HX_DEBUG_PAY_GRID")) h->pay_grid = (int)std::clamp<long long>(atoll(e), 0, 1 << 20);   // tests: the grid-stride loop
+  if (const char* e = getenv("HX_DEBUG_RECO_CHUNK0")) h->reco_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the recommend scan's chunks
+  if (const char* e = getenv("HX_DEBUG_RECO_CAP")) h->reco_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);
     if (v >= 1 && v <= SCAN8_LOGCAP) h->scan_logcap = v;
@@ -3100,6 +3293,58 @@ int hx_hybrid_query_rerank_host(hx_index* h, const float* qd, const int64_t* qip
   const RerankSpec r{mask_root_only, candidates_limit, col, limit, q8_host, qscale_host, qtok_indptr_host, first_scores,
                      counts};
   hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, nullptr, &r);
+  HX_CATCH
+}
+
+int hx_recommend(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
+                 const int8_t* ex_sign_host, const float* ex_vecs_host, const uint32_t* mask_dev, int64_t mask_rows,
+                 int32_t limit, uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(keys_dev && counts_dev, "NULL argument");
+  const RecoCall c = reco_check(h, strategy, R, ex_indptr_host, ex_rows_host, ex_sign_host, ex_vecs_host, mask_dev, mask_rows,
+                                limit);
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  recommend_dev(h, strategy, R, c, ex_vecs_host, mask_dev, -1, limit, keys_dev, counts_dev, st);
+  remap_out(h, keys_dev, (int64_t)R * limit, st);
+  HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
+                      const int8_t* ex_sign_host, const float* ex_vecs_host, const uint32_t* mask_host, int64_t mask_rows,
+                      int32_t limit, float* scores_host, int64_t* ids_host, int32_t* counts_host) {
+  HX_TRY
+  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
+  const RecoCall c = reco_check(h, strategy, R, ex_indptr_host, ex_rows_host, ex_sign_host, ex_vecs_host, mask_host, mask_rows,
+                                limit);
+  h->set_device();
+  hipStream_t st = nullptr;
+  const int64_t n_out = (int64_t)R * limit;
+  uint32_t* mask_dev = nullptr;
+  int64_t kept = -1;
+  if (mask_host) {                      // the count from the host mask: no read-back
+    const int64_t nw = (h->n + 31) / 32;
+    kept = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+      uint32_t m = mask_host[w];
+      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
+      kept += __builtin_popcount(m);
+    }
+    mask_dev = (uint32_t*)h->ws.get(WS_RECO_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+    HX_HIP(hipMemcpyAsync(mask_dev, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+  }
+  uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_OUT, (size_t)n_out * 8);
+  int* cnt = (int*)h->ws.get(WS_RECO_OCNT, (size_t)R * 4);
+  float* sc = (float*)h->ws.get(WS_RECO_SC, (size_t)n_out * 4);
+  int64_t* id = (int64_t*)h->ws.get(WS_RECO_ID, (size_t)n_out * 8);
+  recommend_dev(h, strategy, R, c, ex_vecs_host, mask_dev, kept, limit, keys, cnt, st);
+  remap_out(h, keys, n_out, st);
+  launch_unpack(keys, n_out, sc, id, st);
+  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
   HX_CATCH
 }
 

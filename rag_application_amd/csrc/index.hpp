@@ -1,4 +1,4 @@
-// Internal to the three host files of libhx -- engine.hip, lifecycle.hip, paystore.hip (DESIGN.md section 3 says what
+// Internal to the host files of libhx -- engine.hip, lifecycle.hip, paystore.hip (DESIGN.md section 3 says what
 // each owns): the state of one collection (struct hx_index) and what one file calls in another.
 #pragma once
 #include "../../include/hx.h"
@@ -48,7 +48,9 @@ enum WsSlot {
   WS_M_MASK, WS_M_BLK, WS_M_ROWS, WS_M_FB, WS_ROWS_CHECK, WS_NOM_QBAD, WS_C_LEN, WS_PAY_PROG, WS_PAY_KEPT, WS_PAY_PLANES,
   WS_G_KEYS, WS_G_CODES, WS_G_CNT, WS_MMR_KEYS, WS_MMR_VAL, WS_MMR_CNT, WS_MMR_POOL, WS_MMR_PCNT,
   WS_FACET_A, WS_FACET_B, WS_FACET_CNT, WS_FACET_COUNTS, WS_FACET_MASK, WS_FACET_RANK, WS_FACET_OUT,
-  WS_MS_POS, WS_MS_KEYS, WS_MS_CNT, WS_MS_FIRST, WS_MS_Q8, WS_MS_QS, WS_MS_QIP
+  WS_MS_POS, WS_MS_KEYS, WS_MS_CNT, WS_MS_FIRST, WS_MS_Q8, WS_MS_QS, WS_MS_QIP,
+  WS_RECO_X, WS_RECO_RAW, WS_RECO_RAWN, WS_RECO_META, WS_RECO_Q, WS_RECO_KEYS, WS_RECO_KCNT, WS_RECO_CAND, WS_RECO_CNT,
+  WS_RECO_OVF, WS_RECO_TAU, WS_RECO_TAU0, WS_RECO_MASK, WS_RECO_OUT, WS_RECO_OCNT, WS_RECO_SC, WS_RECO_ID
 };
 
 template <typename T>
@@ -227,6 +229,8 @@ struct hx_index {
     bool csr() const { return list() || text() || tokens(); }   // offsets and element planes: what the lifecycle moves
   };
   std::vector<PayCol> pay;
+  int reco_chunk0 = 0;                // HX_DEBUG_RECO_CHUNK0 (tests): rows of the first chunk of the recommend scan, 0 = the buffer's capacity
+  int reco_cap = 0;                   // HX_DEBUG_RECO_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
   int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap
   int pay_next_id = 0;
   uint8_t* pay_pin = nullptr;

@@ -590,6 +590,49 @@ void launch_facet_count(const FacetArgs& a, int grid_cap, hipStream_t st);
 constexpr int FACET_SLICE = 2048;
 void launch_facet_keys(const uint32_t* counts, uint32_t n_codes, const uint32_t* rank, uint64_t* lists, int list_len,
                        hipStream_t st);
+// ---- reco.hip: recommend search (hx_recommend) ----------------------------------------------------
+// The examples of a call lie in one matrix X [E x dim_pad] of normalised fp32 rows, request by request, inside a request
+// the positives in the order given, then the negatives in the order given.
+constexpr int RECO_LDS_FLOATS = 32768;   // floats of staged examples per launch: 128 KB of LDS
+constexpr int RECO_MAX_EXCL = 32;        // stored examples of a request (HX_RECO_MAX_EXAMPLES)
+struct RecoReq {
+  int ex0, n_pos, n_ex;    // rows [ex0, ex0 + n_ex) of X; the first n_pos are positives
+  int excl0, n_excl;       // excl[excl0 ..]: the request's stored-example rows, ascending, unique
+  int slot;                // the request's index in the call: its candidate buffer, counter, threshold and flag
+  int lds0;                // first staged example of the request inside its scan launch
+};
+// X[i] = dense row src[i] (src[i] >= 0), or row -1 - src[i] of raw_n [n_raw x dim_pad] (prepared raw vectors)
+void launch_reco_examples(const float* dense, const float* raw_n, const int64_t* src, int E, int dim_pad, float* X,
+                          hipStream_t st);
+// q [R x dim] = the average-vector query of every request: p + (p - n) with p, n the example-order means (p when a
+// request has no negative); every operation one fp32 operation, the sums starting from the first example
+void launch_reco_average(const float* X, const RecoReq* req, int R, int dim, int dim_pad, float* q, hipStream_t st);
+// out[r * limit ..] = the first `limit` keys of in[r * in_stride ..] (in_cnt[r] of them) whose row is not in the
+// request's excl list, 0 past them; out_cnt[r] = their number
+void launch_reco_drop(const uint64_t* in, int in_stride, const int* in_cnt, const RecoReq* req, const uint32_t* excl,
+                      uint32_t id_base, int R, int limit, uint64_t* out, int* out_cnt, hipStream_t st);
+// The exhaustive scan of rows [row_begin, row_end) for the n_req requests req[0 .. n_req) (their examples fit
+// RECO_LDS_FLOATS together): a row that is not excluded and whose score is >= tau[slot] is appended to
+// cand[slot * cap + atomicAdd(cnt[slot])]; ovf[slot] = 1 when the buffer is full.
+struct RecoScanArgs {
+  const float* dense;      // the normalised fp32 rows, dim_pad floats each (a multiple of 64, at most 4096)
+  int dim_pad;
+  int64_t row_begin, row_end;
+  const float* X;
+  const RecoReq* req;      // device
+  int n_req;
+  const uint32_t* excl;    // device
+  const uint32_t* mask;    // packed row mask, NULL = every row
+  int strategy;            // HX_RECO_BEST_SCORE | HX_RECO_SUM_SCORES
+  const float* tau;
+  uint64_t* cand;
+  int* cnt;
+  int* ovf;
+  int cap;
+  uint32_t id_base;
+};
+// lds_examples = examples staged by the launch (sum of its requests' n_ex): sizes the LDS request and the grid
+void launch_reco_scan(const RecoScanArgs& a, int lds_examples, hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

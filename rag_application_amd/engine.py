@@ -751,6 +751,61 @@ class HxIndex:
                                                   _ptr(values), _ptr(counts)))
         return scores, ids, values, counts
 
+    # -- recommend search (hx.h: hx_recommend / hx_recommend_host) --------------------------------
+    def _reco_examples(self, requests):
+        """requests: per request a sequence of (example, sign) -- example = a local row (an int) or a vector of `dim`
+        numbers, sign = +1 | -1 -> (indptr int64 [R + 1], rows int64 [E] with -1 for a raw vector, signs int8 [E], vecs
+        float32 [n_raw, dim] or None), as hx_recommend takes them."""
+        indptr, rows, signs, vecs = [0], [], [], []
+        for req in requests:
+            for ex, sign in req:
+                if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+                    rows.append(int(ex))
+                else:
+                    v = np.asarray(ex, dtype=np.float32).reshape(-1)
+                    if v.shape[0] != self.dim:
+                        raise HxError(f"recommend: an example vector of {v.shape[0]} values, the index holds {self.dim}")
+                    rows.append(-1)
+                    vecs.append(v)
+                signs.append(int(sign))
+            indptr.append(len(rows))
+        return (np.asarray(indptr, np.int64), np.asarray(rows, np.int64).reshape(-1),
+                np.asarray(signs, np.int64).clip(-128, 127).astype(np.int8).reshape(-1),
+                np.ascontiguousarray(np.stack(vecs)) if vecs else None)
+
+    def recommend(self, requests, strategy: int, limit: int, mask=None, keys=None, counts=None):
+        """Points like given examples (hx_recommend): requests as _reco_examples takes them, strategy = RECO_AVERAGE |
+        RECO_BEST_SCORE | RECO_SUM_SCORES, mask = None or a row mask as hybrid_query takes it.  Returns (keys [R, limit]
+        int64, counts [R] int32) on the device (keys / counts: tensors to write into); the call synchronises."""
+        indptr, rows, signs, vecs = self._reco_examples(requests)
+        R, L = len(indptr) - 1, int(limit)
+        if keys is None or counts is None:
+            keys, counts = self._out(max(R, 1), L if 1 <= L <= 1024 else 1)   # (the engine refuses; nothing huge is allocated)
+        words, mrows = None, 0
+        if mask is not None:
+            if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
+                words, mrows = mask, self.count()
+            else:
+                packed, mrows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
+                words = torch.from_numpy(packed.view(np.int32)).to(keys.device)
+        check(_lib.lib().hx_recommend(self._h, int(strategy), R, _ptr(indptr), _ptr(rows), _ptr(signs), _ptr(vecs),
+                                      _ptr(words), mrows, L, _ptr(keys), _ptr(counts), _stream()))
+        return keys, counts
+
+    def recommend_host(self, requests, strategy: int, limit: int, mask=None):
+        """recommend, host in, host out (hx_recommend_host): (scores [R, limit] float32, ids [R, limit] int64, counts [R]
+        int32), the slots past a request's count (-inf, -1)."""
+        indptr, rows, signs, vecs = self._reco_examples(requests)
+        R, L = len(indptr) - 1, int(limit)
+        slots = L if 1 <= L <= 1024 else 1
+        scores = np.empty((max(R, 1), slots), dtype=np.float32)
+        ids = np.empty((max(R, 1), slots), dtype=np.int64)
+        counts = np.empty((max(R, 1),), dtype=np.int32)
+        words, mrows = (None, 0) if mask is None else self._mask(mask)
+        check(_lib.lib().hx_recommend_host(self._h, int(strategy), R, _ptr(indptr), _ptr(rows), _ptr(signs), _ptr(vecs),
+                                           _ptr(words), mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores[:R], ids[:R], counts[:R]
+
     # -- late-interaction rerank (hx.h: HX_PAY_TOKENS / hx_maxsim / hx_hybrid_query_rerank_host; DESIGN.md section 23) --
     def payload_create_tokens(self, dim_t: int) -> int:
         """A new empty token column of `dim_t` int8 values per token (hx_payload_create_tokens); returns its id."""

@@ -436,6 +436,8 @@ class _Collection:
 
 
 FILTER_STAGES = ("root", "all")
+RECO_MAX_LIMIT, RECO_MAX_REQUESTS, RECO_MAX_EXAMPLES = 1024, 16, 32   # HX_RECO_MAX_* of hx.h
+RECO_STRATEGIES = {"average_vector": 0, "best_score": 1, "sum_scores": 2}   # HX_RECO_AVERAGE / _BEST_SCORE / _SUM_SCORES
 MMR_MAX_LIMIT = 256                   # HX_MMR_MAX_LIMIT of hx.h: most hits hybrid_search_mmr picks per query
 
 
@@ -458,6 +460,8 @@ class QdrantHandler:
     _facets = True
     # token columns live in ONE engine index; hybrid_search_rerank reranks the pool of that index
     _late_rerank = True
+    # recommend scans the rows of ONE engine index and looks its examples up in this process's ids
+    _recommend = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -1127,6 +1131,97 @@ class QdrantHandler:
         except Exception as e:
             logging.error("reranker raised, order kept: %s", e)
             return results
+
+    # ------------------------------------------------------------------------ recommend
+    def _recommend_sync(self, user_id, requests, limit, filters):
+        if not self._recommend:
+            raise ValueError("recommend is not supported on a sharded collection")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= RECO_MAX_LIMIT:
+            raise ValueError(f"limit must be an integer in [1, {RECO_MAX_LIMIT}], got {limit!r}")
+        requests = list(requests)
+        if not 1 <= len(requests) <= RECO_MAX_REQUESTS:
+            raise ValueError(f"a recommend batch takes 1 to {RECO_MAX_REQUESTS} requests, got {len(requests)}")
+        col = self._collections[str(user_id)]
+        dim_pad = (col.dim + 63) // 64 * 64
+        id_rows = None
+        strategies, packed = set(), []
+        for req in requests:
+            positive, negative, strategy = req.get("positive"), req.get("negative"), req.get("strategy", "average_vector")
+            positive = [] if positive is None else list(positive)
+            negative = [] if negative is None else list(negative)
+            if strategy not in RECO_STRATEGIES:
+                raise ValueError(f"strategy must be one of {tuple(RECO_STRATEGIES)}, got {strategy!r}")
+            strategies.add(strategy)
+            examples = []
+            for group, sign in ((positive, 1), (negative, -1)):
+                for ex in group:
+                    if isinstance(ex, (str, int)) and not isinstance(ex, bool):   # a point id -> its stored row
+                        if id_rows is None:
+                            id_rows = col._id_rows()
+                            if id_rows is None:                      # an id held twice: the first row that holds it
+                                id_rows = {}
+                                for r, pid in enumerate(col.ids):
+                                    id_rows.setdefault(pid, r)
+                        if str(ex) not in id_rows:
+                            raise ValueError(f"recommend: unknown point id {ex!r}")
+                        examples.append((id_rows[str(ex)], sign))
+                    else:
+                        try:
+                            v = np.asarray(ex, dtype=np.float32).reshape(-1)
+                        except (TypeError, ValueError):
+                            raise ValueError("recommend: an example is a point id or a vector of numbers") from None
+                        if v.shape[0] != col.dim:
+                            raise ValueError(f"example dimension {v.shape[0]} != collection dimension {col.dim}")
+                        if not np.isfinite(v).all():
+                            raise ValueError("recommend: example vector values must be finite")
+                        examples.append((v, sign))
+            if not examples:
+                raise ValueError("recommend: a request needs at least one example")
+            if len(examples) > RECO_MAX_EXAMPLES or len(examples) * dim_pad > 32768:
+                raise ValueError(f"recommend: too many examples ({len(examples)}): at most {RECO_MAX_EXAMPLES}, and "
+                                 f"examples x padded width at most 32768 (width {dim_pad})")
+            if strategy == "average_vector" and not positive:
+                raise ValueError("recommend: the average_vector strategy needs a positive example")
+            packed.append(examples)
+        if len(strategies) != 1:
+            raise ValueError("recommend_batch: one strategy per batch")
+        mask = None
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            mask = col.row_mask(filters)
+        scores, rows, counts = col.index.recommend_host(packed, RECO_STRATEGIES[strategies.pop()], limit, mask=mask)
+        cids, cpay = col.ids, col.payloads
+        return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+                for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist())]
+
+    async def recommend_batch(self, user_id: str, requests, limit: int = 10,
+                              filters: Optional[Dict] = None) -> List[List[ScoredPoint]]:
+        """Qdrant's RecommendQuery for up to 16 requests in one engine call (additive).  A request
+        is a dict {"positive": [...], "negative": [...], "strategy": "average_vector" | "best_score" | "sum_scores"}; an
+        example is a point id (looked up in the collection, it becomes a stored row) or a vector of `dim` numbers.  All
+        requests of a batch share one strategy.  The examples given as point ids are never returned; `filters` keeps
+        only the rows the filter keeps (through the payload index where there is one) -- an example need not pass it.
+        `score` is the strategy's score (include/hx.h states the arithmetic).  All of it runs on the device
+        (hx_recommend_host); there is no Python path.  Raises ValueError for arguments no search can serve (an unknown
+        point id or strategy, no example, average_vector without a positive, too many examples, a limit outside [1,
+        1024], a vector of the wrong length or with a non-finite element, a sharded collection); any other failure is
+        logged and gives [], as in every search."""
+        try:
+            return await self._run(self._recommend_sync, user_id, requests, limit, filters)
+        except ValueError as ve:
+            logging.error("recommend for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("recommend for %s failed: %s", user_id, e)
+            return []
+
+    async def recommend(self, user_id: str, positive, negative=None, strategy: str = "average_vector", limit: int = 10,
+                        filters: Optional[Dict] = None) -> List[ScoredPoint]:
+        """One request of recommend_batch: the `limit` points most like the positive examples and least like the
+        negative ones, the examples themselves left out."""
+        res = await self.recommend_batch(user_id, [{"positive": positive, "negative": negative, "strategy": strategy}],
+                                         limit=limit, filters=filters)
+        return res[0] if res else []
 
     # ------------------------------------------------------------------------ collections
     async def get_all_containers(self) -> List[str]:

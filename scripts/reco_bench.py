@@ -1,0 +1,123 @@
+"""Diagnostic: recommend search (hx_recommend) on a 10M x 768 synthetic corpus (hx_synth_fill, dense
+rows only).  ms per call, median [min-max] of 20 after 3 warm-up calls:
+  scan strategies   HIP events around hx_recommend for best_score and sum_scores with 1 / 3 / 32 stored examples per
+                    request and R = 1 / 16 requests, limit 10: the span holds k_reco_scan's launches (one per chunk and
+                    per group of requests whose examples share the LDS) and the compactions between them; GB/s by the
+                    cost model rows * row_bytes per launch group (the fp32 matrix is read once per group);
+  k_scan            the dense stage's int8 candidate scan for 1 and 16 queries in the same session (hx_profile, slot 3:
+                    its own cost model, rows * row_bytes + B * row_bytes over 768-byte rows), the stream the figure above
+                    is set beside;
+  average_vector    the whole call (wall clock, hx_recommend_host): example matrix, query, dense stage, drop.
+Not part of bench.py.  argv: [rows (default 10M)] [--label TEXT].  Output: one table on stdout (kept as
+profiles/reco_*.txt)."""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from rag_application_amd import engine as eng, synth  # noqa: E402
+
+LABEL = sys.argv[sys.argv.index("--label") + 1] if "--label" in sys.argv else ""
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--") and a != LABEL]
+N = int(ARGS[0]) if ARGS else 10_000_000
+DIM, LIMIT, REPS, WARM = 768, 10, 20, 3
+AVERAGE, BEST_SCORE, SUM_SCORES = 0, 1, 2
+
+
+def spread(ts):
+    return f"{np.median(ts):9.3f} [{np.min(ts):.3f}-{np.max(ts):.3f}]"
+
+
+def events(fn):
+    for _ in range(WARM):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(REPS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return ts
+
+
+def wall(fn):
+    for _ in range(WARM):
+        fn()
+    ts = []
+    for _ in range(REPS):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def requests(rng, R, E):
+    """R requests of E stored examples, two thirds of them positive"""
+    return [[(int(r), 1 if k % 3 else -1) if E > 1 else (int(r), 1) for k, r in enumerate(rng.choice(N, E, replace=False))]
+            for _ in range(R)]
+
+
+def groups(reqs):
+    """launch groups of a batch: requests in order while their examples fit 32768 floats (engine.hip deals them so)"""
+    g, used = 1, 0
+    for rq in reqs:
+        if (used + len(rq)) * DIM > 32768:
+            g, used = g + 1, 0
+        used += len(rq)
+    return g
+
+
+def main():
+    ix = eng.HxIndex(DIM, ())
+    ix.reserve(N)
+    ix.synth_fill(N, synth.SEED_CORPUS)
+    print(f"recommend search, {N} rows x {DIM}, limit {LIMIT}; ms per call, median [min-max] of {REPS} after {WARM} warm-up "
+          f"calls; {torch.cuda.get_device_name(0)}; {LABEL}")
+    rng = np.random.default_rng(24)
+    row_bytes = DIM * 4
+    for strategy, name in ((BEST_SCORE, "best_score"), (SUM_SCORES, "sum_scores")):
+        print(f"\n{name}: hx_recommend by HIP events (k_reco_scan's launches and the compactions between them)")
+        for R in (1, 16):
+            for E in (1, 3, 32):
+                reqs = requests(rng, R, E)
+                keys, cnt = ix.recommend(reqs, strategy, LIMIT)
+                ms = events(lambda: ix.recommend(reqs, strategy, LIMIT, keys=keys, counts=cnt))
+                g = groups(reqs)
+                gbs = g * N * row_bytes / (np.median(ms) * 1e-3) / 1e9
+                print(f"  R = {R:2d}, {E:2d} examples each, {g:2d} launch group(s)   {spread(ms)}   {gbs:7.1f} GB/s of rows * "
+                      f"row_bytes per group; {np.median(ms) / (R * E):8.3f} ms per (request, example)")
+    print("\nk_scan, the dense stage's int8 candidate scan, same session (hx_profile slot 3, its own cost model)")
+    for B in (1, 16):
+        q = eng.synth_queries_dense(DIM, 0, B, synth.SEED_QUERY)
+        for _ in range(WARM):
+            ix.search_dense(q, LIMIT)
+        ix.profile(True)
+        ix.profile_read()
+        for _ in range(REPS):
+            ix.search_dense(q, LIMIT)
+        p = ix.profile_read()
+        ix.profile(False)
+        s = p["scan_cand8"]
+        gbs = s["bytes"] / (s["ms"] * 1e-3) / 1e9 if s["ms"] > 0 else 0.0
+        print(f"  B = {B:2d}: {s['launches']} launches, {s['ms'] / max(s['launches'], 1):.3f} ms per launch, {gbs:7.1f} GB/s")
+    print("\naverage_vector: the whole call, wall clock (hx_recommend_host)")
+    for R in (1, 16):
+        for E in (1, 3, 32):
+            reqs = requests(rng, R, E)
+            ms = wall(lambda: ix.recommend_host(reqs, AVERAGE, LIMIT))
+            print(f"  R = {R:2d}, {E:2d} examples each   {spread(ms)}")
+    for strategy, name in ((BEST_SCORE, "best_score"), (SUM_SCORES, "sum_scores")):
+        reqs = requests(rng, 1, 3)
+        print(f"  for comparison, {name}, R = 1, 3 examples, whole host call   {spread(wall(lambda: ix.recommend_host(reqs, strategy, LIMIT)))}")
+    ix.close()
+
+
+if __name__ == "__main__":
+    main()
