@@ -800,6 +800,52 @@ int hx_payload_facet_host(hx_index* h, int32_t col, const uint32_t* mask_host, i
                           const uint32_t* rank_host, int32_t limit, uint32_t* ranks_or_codes_host, uint32_t* counts_host,
                           int32_t* n_out, uint64_t* stray_host);
 
+/* ---- scroll -----------------------------------------------------
+ * Qdrant's scroll(collection, scroll_filter, limit, offset, order_by) (additive: the reference never calls it; parity
+ * unpinned, the semantics below are this project's statement of it): the points a filter keeps, page by page, in row
+ * order (the insertion order every tie of this project uses) or in the order of a number field.
+ *
+ * hx_scroll_rows is the page in row order: the first `limit` local rows r >= start_row whose bit is set in mask_dev (a
+ * packed row mask in the layout of hx_payload_mask; NULL = every row, otherwise mask_rows must equal hx_count),
+ * ascending.  out_rows_dev [limit] uint32: every slot is written, 0 past *out_count_dev (int32) hits.
+ *
+ * hx_payload_order is the ordered page: col = an HX_PAY_F64 column filled to hx_count.  The ORDER VALUE of a cell x is
+ * x + 0.0 (-0.0 orders as 0.0); as an integer, with b the 64 bits of x + 0.0:  u = b ^ (b >> 63 ? ~0 : 1 << 63), and
+ * s = u for HX_ORDER_ASC, ~u for HX_ORDER_DESC.  The order is (s ascending, row ascending) in BOTH directions.  A row is
+ * eligible when its mask bit is set (or there is no mask), its cell is neither HX_PAY_F64_MISSING nor HX_PAY_F64_NULL
+ * (any other bit pattern, another NaN included, orders by its s), and
+ *   HX_ORDER_HAS_START   s(cell) >= s(start_from): the cell is >= start_from ascending, <= start_from descending;
+ *   HX_ORDER_HAS_AFTER   (s(cell), row) > (s(after_value), after_row) as a pair: the row lies strictly after the cursor.
+ *                        The engine compares the pair and never looks at the cell of after_row (after_row may be any
+ *                        value >= 0, past hx_count included).
+ * The outputs are the best `limit` eligible rows in that order: out_rows_dev [limit] uint32 the rows, out_bits_dev
+ * [limit] uint64 the STORED cells of those rows (a stored -0.0 comes back as -0.0), *out_count_dev (int32) the hits;
+ * every slot is written, 0 past the hits.  The result is exact and the same bits on every run.
+ *
+ * Both entries only enqueue work on `stream` (scratch from the index); nothing is read back.  Refused before any device
+ * work, the outputs untouched: a NULL h or a NULL output, limit outside [1, HX_SCROLL_MAX_LIMIT], mask_rows != hx_count
+ * with a mask, start_row outside [0, hx_count], an unknown column, a column of another kind ("kind" in the message), a
+ * column not filled to hx_count, a direction other than 0 or 1, flag bits other than the two above, a NaN start_from /
+ * after_value or a negative after_row when its flag is set.  An empty index gives 0 hits.
+ *
+ * The _host forms are the whole call, host in, host out: mask_host NULL = every row; the mask goes up, the kernels run
+ * and the page comes back behind one synchronisation, scratch from the index.  Same refusals. */
+#define HX_ORDER_ASC 0
+#define HX_ORDER_DESC 1
+#define HX_ORDER_HAS_START 1
+#define HX_ORDER_HAS_AFTER 2
+#define HX_SCROLL_MAX_LIMIT 2048
+int hx_scroll_rows(hx_index* h, const uint32_t* mask_dev, int64_t mask_rows, int64_t start_row, int32_t limit,
+                   uint32_t* out_rows_dev, int32_t* out_count_dev, void* stream);
+int hx_payload_order(hx_index* h, int32_t col, const uint32_t* mask_dev, int64_t mask_rows, int32_t direction,
+                     int32_t flags, double start_from, double after_value, int64_t after_row, int32_t limit,
+                     uint32_t* out_rows_dev, uint64_t* out_bits_dev, int32_t* out_count_dev, void* stream);
+int hx_scroll_rows_host(hx_index* h, const uint32_t* mask_host, int64_t mask_rows, int64_t start_row, int32_t limit,
+                        uint32_t* out_rows_host, int32_t* out_count_host);
+int hx_payload_order_host(hx_index* h, int32_t col, const uint32_t* mask_host, int64_t mask_rows, int32_t direction,
+                          int32_t flags, double start_from, double after_value, int64_t after_row, int32_t limit,
+                          uint32_t* out_rows_host, uint64_t* out_bits_host, int32_t* out_count_host);
+
 /* ---- sparse text provider (host cores) ---------------------------------------
  * EmbeddingHandler.encode_sparse (app/core/embedding/embedding_handler.py:101-142 -> fastembed
  * Qdrant/bm25 :41, :123), batched (the reference's TODO :100): n texts -> CSR of (term id, weight)

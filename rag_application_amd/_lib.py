@@ -131,6 +131,12 @@ _SIGS = {
     "hx_facet_top": [_P, _P, C.c_uint32, _P, C.c_int32, _P, _P, _P],
     "hx_payload_facet_host": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32),
                               C.POINTER(C.c_uint64)],
+    "hx_scroll_rows": [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P],
+    "hx_payload_order": [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_int32,
+                         _P, _P, _P, _P],
+    "hx_scroll_rows_host": [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.POINTER(C.c_int32)],
+    "hx_payload_order_host": [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int64,
+                              C.c_int32, _P, _P, C.POINTER(C.c_int32)],
     "hx_payload_create": [_P, C.c_int32, C.POINTER(C.c_int32)],
     "hx_payload_drop": [_P, C.c_int32],
     "hx_payload_append": [_P, C.c_int32, _P, C.c_int64],

@@ -50,7 +50,8 @@ enum WsSlot {
   WS_FACET_A, WS_FACET_B, WS_FACET_CNT, WS_FACET_COUNTS, WS_FACET_MASK, WS_FACET_RANK, WS_FACET_OUT,
   WS_MS_POS, WS_MS_KEYS, WS_MS_CNT, WS_MS_FIRST, WS_MS_Q8, WS_MS_QS, WS_MS_QIP,
   WS_RECO_X, WS_RECO_RAW, WS_RECO_RAWN, WS_RECO_META, WS_RECO_Q, WS_RECO_KEYS, WS_RECO_KCNT, WS_RECO_CAND, WS_RECO_CNT,
-  WS_RECO_OVF, WS_RECO_TAU, WS_RECO_TAU0, WS_RECO_MASK, WS_RECO_OUT, WS_RECO_OCNT, WS_RECO_SC, WS_RECO_ID
+  WS_RECO_OVF, WS_RECO_TAU, WS_RECO_TAU0, WS_RECO_MASK, WS_RECO_OUT, WS_RECO_OCNT, WS_RECO_SC, WS_RECO_ID,
+  WS_SCROLL_WORK, WS_SCROLL_MASK, WS_SCROLL_OUT
 };
 
 template <typename T>

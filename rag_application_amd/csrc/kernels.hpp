@@ -633,6 +633,45 @@ struct RecoScanArgs {
 };
 // lds_examples = examples staged by the launch (sum of its requests' n_ex): sizes the LDS request and the grid
 void launch_reco_scan(const RecoScanArgs& a, int lds_examples, hipStream_t st);
+// ---- scroll.hip: scroll (hx_scroll_rows / hx_payload_order) --------------------------------------
+// "The first m rows of a predicate, in row order" over contiguous row slices, one per workgroup: a count per slice, an
+// exclusive prefix over the slices, and an emit that places a row at prefix + its rank inside the slice.
+constexpr int FIRST_MAX_SLICES = 1024;     // slices of one call: what the one-workgroup prefix takes
+constexpr int ORDER_BINS = 2048;           // counters of one radix pass
+constexpr int ORDER_PASSES = 6;            // digits of 11 / 11 / 10 bits over the high word, then over the low word
+struct OrderState {
+  uint64_t prefix;         // the digits of the threshold T chosen so far (after the last pass: T)
+  uint32_t need;           // rows still to take among those that match the prefix (after the last pass: rows with s == T)
+  uint32_t all;            // fewer than `limit` rows are eligible: every one is taken
+  uint32_t total;          // eligible rows (written by the first pick)
+  uint32_t n_less;         // cursor of the rows with s < T (all: of every eligible row) in the candidate arrays
+};
+struct OrderArgs {
+  const uint32_t* lo;      // the column's planes
+  const uint32_t* hi;
+  const uint32_t* mask;    // packed row mask, NULL = every row
+  int64_t n;
+  int desc;                // HX_ORDER_DESC
+  int has_start, has_after;
+  uint64_t s_start, s_after;   // the order keys s of start_from / after_value
+  int64_t after_row;
+  int limit;
+  uint32_t* hist;          // [ORDER_PASSES x ORDER_BINS]
+  OrderState* st;
+  uint64_t* cand_s;        // [HX_SCROLL_MAX_LIMIT] the chosen rows' keys and rows, unsorted
+  uint32_t* cand_row;
+  uint32_t* slice_cnt;     // [FIRST_MAX_SLICES] rows with s == T per slice
+  uint32_t* slice_pre;     // ... and their exclusive prefix
+};
+// slices of a call over n rows under the grid cap of launch_payload_mask (0 = none), and the rows of one slice
+int first_slices(int64_t n, int grid_cap, int64_t* slice_rows);
+// out_rows [limit] = the first `limit` rows r in [start_row, n) whose mask bit is set (mask NULL: every row), 0 past
+// them; *out_count = their number.  slice_cnt / slice_pre: FIRST_MAX_SLICES words each.
+void launch_scroll_rows(const uint32_t* mask, int64_t n, int64_t start_row, int limit, uint32_t* slice_cnt,
+                        uint32_t* slice_pre, uint32_t* out_rows, int32_t* out_count, int grid_cap, hipStream_t st);
+// the whole ordered selection (hx.h states it): out_rows / out_bits [limit], *out_count
+void launch_payload_order(const OrderArgs& a, uint32_t* out_rows, uint64_t* out_bits, int32_t* out_count, int grid_cap,
+                          hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

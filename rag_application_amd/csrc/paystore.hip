@@ -358,6 +358,104 @@ static void facet_top_enqueue(hx_index* h, const uint32_t* counts, uint32_t n_co
   }
 }
 
+// ---- scroll -----------------------------------------------------------------------------------------
+// every refusal of hx_scroll_rows, before any device work
+static void scroll_check(hx_index* h, const uint32_t* mask, int64_t mask_rows, int64_t start_row, int32_t limit) {
+  HX_CHECK(limit >= 1 && limit <= HX_SCROLL_MAX_LIMIT, "scroll: limit out of range [1, 2048]");
+  HX_CHECK(!mask || mask_rows == h->n, "scroll: mask_rows must equal the index's row count (hx_count)");
+  HX_CHECK(start_row >= 0 && start_row <= h->n, "scroll: start_row out of range [0, hx_count]");
+}
+// the order key s of a bound (hx.h)
+static uint64_t order_s(double x, int desc) {
+  x += 0.0;
+  uint64_t b;
+  std::memcpy(&b, &x, 8);
+  const uint64_t u = b ^ ((b >> 63) ? ~0ull : 0x8000000000000000ull);
+  return desc ? ~u : u;
+}
+// every refusal of hx_payload_order, before any device work; the scratch pointers are the caller's to fill
+static OrderArgs order_args(hx_index* h, int32_t col, const uint32_t* mask, int64_t mask_rows, int32_t direction,
+                            int32_t flags, double start_from, double after_value, int64_t after_row, int32_t limit) {
+  scroll_check(h, mask, mask_rows, 0, limit);
+  const PayCol& c = pay_col(h, col);
+  HX_CHECK(c.kind == HX_PAY_F64, "scroll: the column kind must be HX_PAY_F64 (numbers)");
+  HX_CHECK(c.filled == h->n, "scroll: the column is not filled to the index's row count (hx_count)");
+  HX_CHECK(direction == HX_ORDER_ASC || direction == HX_ORDER_DESC, "scroll: direction must be HX_ORDER_ASC or HX_ORDER_DESC");
+  HX_CHECK((flags & ~(HX_ORDER_HAS_START | HX_ORDER_HAS_AFTER)) == 0, "scroll: unknown flag bits");
+  const bool has_start = flags & HX_ORDER_HAS_START, has_after = flags & HX_ORDER_HAS_AFTER;
+  HX_CHECK(!has_start || start_from == start_from, "scroll: start_from is a NaN");
+  HX_CHECK(!has_after || after_value == after_value, "scroll: after_value is a NaN");
+  HX_CHECK(!has_after || after_row >= 0, "scroll: after_row is negative");
+  OrderArgs a{};
+  a.lo = c.p0;
+  a.hi = c.p1;
+  a.mask = mask;
+  a.n = h->n;
+  a.desc = direction;
+  a.has_start = has_start;
+  a.has_after = has_after;
+  a.s_start = has_start ? order_s(start_from, direction) : 0ull;
+  a.s_after = has_after ? order_s(after_value, direction) : 0ull;
+  a.after_row = has_after ? after_row : 0;
+  a.limit = limit;
+  return a;
+}
+// the scratch of both calls, one block: [histograms | state | candidate keys | candidate rows | slice counts | prefixes]
+struct ScrollWork {
+  uint32_t* hist;
+  OrderState* st;
+  uint64_t* cand_s;
+  uint32_t *cand_row, *slice_cnt, *slice_pre;
+};
+static ScrollWork scroll_work(hx_index* h) {
+  const size_t hist = (size_t)ORDER_PASSES * ORDER_BINS * 4, state = 64, cs = (size_t)HX_SCROLL_MAX_LIMIT * 8,
+               cr = (size_t)HX_SCROLL_MAX_LIMIT * 4, sl = (size_t)FIRST_MAX_SLICES * 4;
+  uint8_t* p = (uint8_t*)h->ws.get(WS_SCROLL_WORK, hist + state + cs + cr + 2 * sl);
+  ScrollWork w;
+  w.hist = (uint32_t*)p;
+  w.st = (OrderState*)(p + hist);
+  w.cand_s = (uint64_t*)(p + hist + state);
+  w.cand_row = (uint32_t*)(p + hist + state + cs);
+  w.slice_cnt = (uint32_t*)(p + hist + state + cs + cr);
+  w.slice_pre = w.slice_cnt + FIRST_MAX_SLICES;
+  return w;
+}
+static void scroll_rows_enqueue(hx_index* h, const uint32_t* mask, int64_t start_row, int32_t limit, uint32_t* out_rows,
+                                int32_t* out_count, hipStream_t st) {
+  if (h->n == 0) {
+    HX_HIP(hipMemsetAsync(out_rows, 0, (size_t)limit * 4, st));
+    HX_HIP(hipMemsetAsync(out_count, 0, 4, st));
+    return;
+  }
+  const ScrollWork w = scroll_work(h);
+  launch_scroll_rows(mask, h->n, start_row, limit, w.slice_cnt, w.slice_pre, out_rows, out_count, h->pay_grid, st);
+}
+static void order_enqueue(hx_index* h, OrderArgs a, uint32_t* out_rows, uint64_t* out_bits, int32_t* out_count,
+                          hipStream_t st) {
+  if (h->n == 0) {
+    HX_HIP(hipMemsetAsync(out_rows, 0, (size_t)a.limit * 4, st));
+    HX_HIP(hipMemsetAsync(out_bits, 0, (size_t)a.limit * 8, st));
+    HX_HIP(hipMemsetAsync(out_count, 0, 4, st));
+    return;
+  }
+  const ScrollWork w = scroll_work(h);
+  a.hist = w.hist;
+  a.st = w.st;
+  a.cand_s = w.cand_s;
+  a.cand_row = w.cand_row;
+  a.slice_cnt = w.slice_cnt;
+  a.slice_pre = w.slice_pre;
+  launch_payload_order(a, out_rows, out_bits, out_count, h->pay_grid, st);
+}
+// the host forms' mask on the device (NULL: every row), and their result block [bits: limit x 8 | rows: limit x 4 | count]
+static const uint32_t* scroll_mask_up(hx_index* h, const uint32_t* mask_host, hipStream_t st) {
+  const size_t mask_bytes = (size_t)((h->n + 31) / 32) * 4;
+  if (!mask_host || !mask_bytes) return nullptr;
+  uint32_t* m = (uint32_t*)h->ws.get(WS_SCROLL_MASK, mask_bytes);
+  HX_HIP(hipMemcpyAsync(m, mask_host, mask_bytes, hipMemcpyHostToDevice, st));
+  return m;
+}
+
 }  // namespace hx
 
 extern "C" {
@@ -929,6 +1027,67 @@ int hx_payload_facet_host(hx_index* h, int32_t col, const uint32_t* mask_host, i
     ranks_or_codes_host[i] = k ? 0xFFFFFFFFu - (uint32_t)k : 0u;
     counts_host[i] = (uint32_t)(k >> 32);
   }
+  HX_CATCH
+}
+
+// ---- scroll --------------------------------------------------------------------------------------
+int hx_scroll_rows(hx_index* h, const uint32_t* mask_dev, int64_t mask_rows, int64_t start_row, int32_t limit,
+                   uint32_t* out_rows_dev, int32_t* out_count_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && out_rows_dev && out_count_dev, "NULL argument");
+  scroll_check(h, mask_dev, mask_rows, start_row, limit);
+  h->set_device();
+  scroll_rows_enqueue(h, mask_dev, start_row, limit, out_rows_dev, out_count_dev, (hipStream_t)stream);
+  HX_CATCH
+}
+
+int hx_payload_order(hx_index* h, int32_t col, const uint32_t* mask_dev, int64_t mask_rows, int32_t direction,
+                     int32_t flags, double start_from, double after_value, int64_t after_row, int32_t limit,
+                     uint32_t* out_rows_dev, uint64_t* out_bits_dev, int32_t* out_count_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && out_rows_dev && out_bits_dev && out_count_dev, "NULL argument");
+  const OrderArgs a = order_args(h, col, mask_dev, mask_rows, direction, flags, start_from, after_value, after_row, limit);
+  h->set_device();
+  order_enqueue(h, a, out_rows_dev, out_bits_dev, out_count_dev, (hipStream_t)stream);
+  HX_CATCH
+}
+
+int hx_scroll_rows_host(hx_index* h, const uint32_t* mask_host, int64_t mask_rows, int64_t start_row, int32_t limit,
+                        uint32_t* out_rows_host, int32_t* out_count_host) {
+  HX_TRY
+  HX_CHECK(h && out_rows_host && out_count_host, "NULL argument");
+  scroll_check(h, mask_host, mask_rows, start_row, limit);
+  h->set_device();
+  hipStream_t st = nullptr;
+  const uint32_t* mask = scroll_mask_up(h, mask_host, st);
+  uint32_t* out = (uint32_t*)h->ws.get(WS_SCROLL_OUT, ((size_t)limit * 3 + 2) * 4);
+  scroll_rows_enqueue(h, mask, start_row, limit, out, (int32_t*)(out + limit), st);
+  std::vector<uint32_t> res((size_t)limit + 1);
+  HX_HIP(hipMemcpyAsync(res.data(), out, res.size() * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  std::memcpy(out_rows_host, res.data(), (size_t)limit * 4);
+  *out_count_host = (int32_t)res[(size_t)limit];
+  HX_CATCH
+}
+
+int hx_payload_order_host(hx_index* h, int32_t col, const uint32_t* mask_host, int64_t mask_rows, int32_t direction,
+                          int32_t flags, double start_from, double after_value, int64_t after_row, int32_t limit,
+                          uint32_t* out_rows_host, uint64_t* out_bits_host, int32_t* out_count_host) {
+  HX_TRY
+  HX_CHECK(h && out_rows_host && out_bits_host && out_count_host, "NULL argument");
+  OrderArgs a = order_args(h, col, mask_host, mask_rows, direction, flags, start_from, after_value, after_row, limit);
+  h->set_device();
+  hipStream_t st = nullptr;
+  a.mask = scroll_mask_up(h, mask_host, st);
+  // the results, one block and one copy: [limit cells | limit rows | the hits]
+  uint32_t* out = (uint32_t*)h->ws.get(WS_SCROLL_OUT, ((size_t)limit * 3 + 2) * 4);
+  order_enqueue(h, a, out + 2 * (size_t)limit, (uint64_t*)out, (int32_t*)(out + 3 * (size_t)limit), st);
+  std::vector<uint32_t> res((size_t)limit * 3 + 1);
+  HX_HIP(hipMemcpyAsync(res.data(), out, res.size() * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  std::memcpy(out_bits_host, res.data(), (size_t)limit * 8);
+  std::memcpy(out_rows_host, res.data() + 2 * (size_t)limit, (size_t)limit * 4);
+  *out_count_host = (int32_t)res[3 * (size_t)limit];
   HX_CATCH
 }
 

@@ -656,6 +656,89 @@ class HxIndex:
                                                _ptr(first), _ptr(counts), C.byref(n_out), C.byref(stray)))
         return first[:n_out.value], counts[:n_out.value], int(stray.value)
 
+    # -- scroll (hx.h: hx_scroll_rows / hx_payload_order and their _host forms) ----------------
+    def _dev_mask(self, mask):
+        """(mask, mask_rows) of a device call: None = every row, else the packed words as payload_mask returns them."""
+        if mask is None:
+            return None, 0
+        mask = _need_cuda(mask, torch.int32, "mask")
+        rows = self.count()
+        if mask.shape[0] != (rows + 31) // 32:
+            raise ValueError(f"mask: {mask.shape[0]} words for {rows} rows")
+        return mask, rows
+
+    def scroll_rows(self, limit: int, start_row: int = 0, mask: Optional[torch.Tensor] = None, out=None, out_count=None):
+        """The first `limit` rows r >= start_row whose mask bit is set, ascending (hx_scroll_rows).  Returns (rows [limit]
+        int32 holding the uint32 rows, 0 past the hits; count [1] int32).  out / out_count: the tensors to write (tests
+        hand in sentinels).  Only enqueues work."""
+        L = int(limit)
+        mask, rows = self._dev_mask(mask)
+        if out is None:
+            out = torch.empty((L if 1 <= L <= 2048 else 1,), dtype=torch.int32, device=self._tdev)
+        if out_count is None:
+            out_count = torch.empty((1,), dtype=torch.int32, device=self._tdev)
+        check(_lib.lib().hx_scroll_rows(self._h, _ptr(mask), rows, int(start_row), L, _ptr(out), _ptr(out_count),
+                                        _stream()))
+        return out, out_count
+
+    @staticmethod
+    def _order_bounds(start_from, after):
+        flags = (1 if start_from is not None else 0) | (2 if after is not None else 0)
+        av, ar = after if after is not None else (0.0, 0)
+        return flags, float(start_from if start_from is not None else 0.0), float(av), int(ar)
+
+    def payload_order(self, col: int, limit: int, desc: bool = False, start_from: Optional[float] = None,
+                      after=None, mask: Optional[torch.Tensor] = None, out=None, out_bits=None, out_count=None,
+                      direction: Optional[int] = None, flags: Optional[int] = None):
+        """The best `limit` eligible rows of the F64 column `col` in the order (value in the direction, row ascending)
+        (hx_payload_order; hx.h states eligibility): start_from = an inclusive bound, after = (value, row), the cursor
+        the page lies strictly after.  Returns (rows [limit] int32 holding the uint32 rows, bits [limit] int64 holding
+        the stored cells, count [1] int32), zeros past the hits.  direction / flags: raw values instead of the ones
+        derived (tests).  Only enqueues work."""
+        L = int(limit)
+        mask, rows = self._dev_mask(mask)
+        fl, sf, av, ar = self._order_bounds(start_from, after)
+        n = L if 1 <= L <= 2048 else 1
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int32, device=self._tdev)
+        if out_bits is None:
+            out_bits = torch.empty((n,), dtype=torch.int64, device=self._tdev)
+        if out_count is None:
+            out_count = torch.empty((1,), dtype=torch.int32, device=self._tdev)
+        check(_lib.lib().hx_payload_order(self._h, int(col), _ptr(mask), rows,
+                                          int(desc) if direction is None else int(direction),
+                                          fl if flags is None else int(flags), sf, av, ar, L, _ptr(out), _ptr(out_bits),
+                                          _ptr(out_count), _stream()))
+        return out, out_bits, out_count
+
+    def scroll_rows_host(self, limit: int, start_row: int = 0, mask=None) -> np.ndarray:
+        """hx_scroll_rows, host in, host out: mask None, a bool array or packed np.uint32 words (as hybrid_query_host
+        takes it).  Returns the rows, np.uint32 [hits]."""
+        L = int(limit)
+        if not 1 <= L <= 2048:
+            raise HxError("scroll: limit out of range [1, 2048]")
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        out = np.empty((L,), dtype=np.uint32)
+        n_out = C.c_int32()
+        check(_lib.lib().hx_scroll_rows_host(self._h, _ptr(words), rows, int(start_row), L, _ptr(out), C.byref(n_out)))
+        return out[:n_out.value]
+
+    def payload_order_host(self, col: int, limit: int, desc: bool = False, start_from: Optional[float] = None,
+                           after=None, mask=None):
+        """hx_payload_order, host in, host out.  Returns (rows np.uint32 [hits], bits np.uint64 [hits]: the stored
+        cells)."""
+        L = int(limit)
+        if not 1 <= L <= 2048:
+            raise HxError("scroll: limit out of range [1, 2048]")
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        fl, sf, av, ar = self._order_bounds(start_from, after)
+        out = np.empty((L,), dtype=np.uint32)
+        bits = np.empty((L,), dtype=np.uint64)
+        n_out = C.c_int32()
+        check(_lib.lib().hx_payload_order_host(self._h, int(col), _ptr(words), rows, int(desc), fl, sf, av, ar, L,
+                                               _ptr(out), _ptr(bits), C.byref(n_out)))
+        return out[:n_out.value], bits[:n_out.value]
+
     # -- grouped search (hx.h: hx_group / hx_hybrid_query_groups_host; DESIGN.md section 20) -------------------------
     def group(self, col: int, keys: torch.Tensor, counts: Optional[torch.Tensor], n_groups: int, group_size: int):
         """The best n_groups groups of the ranked lists keys [B, stride] (+ counts [B], None = every slot), at most

@@ -29,6 +29,7 @@ from . import filters as _filters
 from . import grouping as _grouping
 from . import late_interaction as _late
 from . import payload_index as _pindex
+from . import scrolling as _scrolling
 from ._lib import HX_MODE_H1, HX_MODE_TREE
 
 
@@ -64,6 +65,23 @@ class FacetHit:
     faceted field (a str, a bool or an int), `count` = the points holding it."""
     value: Any
     count: int
+
+
+@dataclass
+class Record:
+    """One point of scroll / retrieve (shape-compatible with qdrant_client.http.models.Record): `order_value` = the
+    value an ordered scroll placed the point by (a number; a datetime's integer microseconds since the epoch), None
+    otherwise."""
+    id: str
+    payload: Optional[Dict[str, Any]] = None
+    vector: Optional[Any] = None
+    shard_key: Optional[Any] = None
+    order_value: Optional[Any] = None
+
+    def dict(self):
+        return asdict(self)
+
+    model_dump = dict
 
 
 @dataclass
@@ -194,6 +212,86 @@ class _Collection:
         if pi is not None:
             pi.facet_python_calls += 1
         return _faceting.facet_top(_faceting.facet_counts(self.payloads, key, keep=mask), limit)
+
+    SCROLL_SCHEMAS = ("number", "datetime")
+
+    def _row_of(self, point_id) -> int:
+        """The row of a point id (the first one, should two rows share it); ValueError for an id the collection does not
+        hold."""
+        rows = self._id_rows()
+        try:
+            r = rows.get(point_id) if rows is not None else self.ids.index(point_id)
+        except (TypeError, ValueError):
+            r = None
+        if r is None:
+            raise ValueError(f"offset: the collection holds no point with id {point_id!r}")
+        return r
+
+    def scroll(self, flt, limit: int, offset=None, order_by=None):
+        """([(row, order value or None)], next_page_offset) of one page of `limit` points (scrolling.py states the
+        rules).  No order_by: the kept rows from the row of the id `offset` on (hx_scroll_rows_host).  order_by on a key
+        with a live "number" / "datetime" column: the ordered page under the packed mask of `flt` (hx_payload_order_host),
+        continued after the cursor offset = {"value": v, "id": point_id}.  Everything else -- an unindexed or poisoned
+        key, another schema, a bound no double holds, an engine refusal -- is walked by scrolling.py over the payloads
+        under the same mask.  One more point than the page is asked for: it says whether anything follows."""
+        _scrolling.check_limit(limit, _scrolling.MAX_LIMIT - 1)
+        n = len(self.ids)
+        pi = getattr(self, "pindex", None)
+        device = hasattr(self.index, "scroll_rows_host")
+        if order_by is None:
+            start = 0 if offset is None else self._row_of(offset)
+            mask = self.row_mask(flt) if flt else None
+            rows = None
+            if device:
+                try:
+                    if self.index.count() != n:
+                        raise RuntimeError("the engine's row count differs from the payloads'")
+                    rows = self.index.scroll_rows_host(limit + 1, start, mask=mask).tolist()
+                    if pi is not None:
+                        pi.scroll_device_calls += 1
+                except Exception as e:                    # never a wrong page: the walk over the mask is always right
+                    logging.warning("scroll: the device path failed, Python path taken: %s", e)
+            if rows is None:
+                if pi is not None:
+                    pi.scroll_python_calls += 1
+                rows = _scrolling.scroll_rows(n, mask, start, limit + 1)
+            nxt = self.ids[rows[limit]] if len(rows) > limit else None
+            return [(r, None) for r in rows[:limit]], nxt
+        key, desc, start_from = _scrolling.check_order_by(order_by)
+        after = None
+        if offset is not None:
+            if not isinstance(offset, dict) or set(offset) != {"value", "id"}:
+                raise ValueError('offset of an ordered scroll must be {"value": ..., "id": ...} (a next_page_offset)')
+            av = _scrolling.order_value(offset["value"])
+            if av is None:
+                raise ValueError("offset: value must be a number that is not a NaN, a datetime or an RFC 3339 string")
+            after = (av, self._row_of(offset["id"]))
+        mask = self.row_mask(flt) if flt else None
+        k = pi.keys.get(key) if pi is not None else None
+        hits = None
+        if device and k is not None and k.col is not None and k.schema in self.SCROLL_SCHEMAS:
+            sf = None if start_from is None else _pindex.exact_double(start_from)
+            af = None if after is None else _pindex.exact_double(after[0])
+            if (start_from is None or sf is not None) and (after is None or af is not None):
+                try:
+                    if self.index.count() != n:
+                        raise RuntimeError("the engine's row count differs from the payloads'")
+                    rows, _ = self.index.payload_order_host(k.col, limit + 1, desc=desc, start_from=sf,
+                                                            after=None if after is None else (af, after[1]), mask=mask)
+                    # the order value as the payload holds it (an int stays an int): what the Python path returns
+                    hits = [(r, _scrolling.order_value(_filters._get(self.payloads[r], key))) for r in rows.tolist()]
+                    pi.scroll_device_calls += 1
+                except Exception as e:
+                    logging.warning("scroll by %r: the device path failed, Python path taken: %s", key, e)
+                    hits = None
+        if hits is None:
+            if pi is not None:
+                pi.scroll_python_calls += 1
+            hits = _scrolling.ordered_rows(self.payloads, key, desc, keep=mask, start_from=start_from, after=after,
+                                           limit=limit + 1)
+        page = hits[:limit]
+        nxt = {"value": page[-1][1], "id": self.ids[page[-1][0]]} if len(hits) > limit else None
+        return page, nxt
 
     def _poison(self, key: str) -> None:
         k = self.pindex.keys[key]
@@ -462,6 +560,8 @@ class QdrantHandler:
     _late_rerank = True
     # recommend scans the rows of ONE engine index and looks its examples up in this process's ids
     _recommend = True
+    # scroll pages the rows of ONE engine index and the ids and payloads this process holds
+    _scroll = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -557,6 +657,9 @@ class QdrantHandler:
         Text fields (the reference's `content`, `file_description`, `document_summary`, `context`) take the opt-in schema
         "text": a value is then None or a `str`, and `match text` on the field is evaluated on the device (DESIGN.md
         section 19); any other value makes the field stay on the Python path.
+        Datetime fields (the chat messages' `timestamp`) take the opt-in schema "datetime": a value is then None, a
+        `datetime.datetime` or an RFC 3339 string, stored as its microseconds since the epoch; the field serves ordered
+        scrolls, filters on it stay on the Python path.
         Raises ValueError for a bad schema, a sharded collection, or an engine index without payload (list, text) columns;
         KeyError for an unknown collection."""
         try:
@@ -1320,6 +1423,75 @@ class QdrantHandler:
         except Exception as e:
             logging.error("facet(%s, %r) failed: %s", user_id, key, e)
             return []
+
+    def _scroll_sync(self, user_id, filters, limit, offset, order_by, with_payload):
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        col = self._collections[str(user_id)]
+        page, nxt = col.scroll(filters, limit, offset, order_by)
+        return [Record(id=col.ids[r], payload=col.payloads[r] if with_payload else None, order_value=v)
+                for r, v in page], nxt
+
+    async def scroll(self, user_id: str, filters: Optional[Dict] = None, limit: int = 10, offset=None, order_by=None,
+                     with_payload: bool = True):
+        """Qdrant's scroll(collection, scroll_filter, limit, offset, order_by) (additive; parity unpinned): one page of
+        at most `limit` points `filters` keeps, as (records, next_page_offset); next_page_offset is None when nothing
+        follows, otherwise what the next call takes as `offset`.
+        Without order_by the points come in insertion order, `offset` is a point id (the page starts there, inclusive)
+        and next_page_offset is the id of the first point after the page.
+        order_by = {"key": K, "direction": "asc" | "desc", "start_from": v} (or the bare key) orders by the number or
+        datetime field K -- an int or float that is no bool and no NaN, a datetime, or an RFC 3339 string; every other
+        point is left out -- then by insertion order in BOTH directions; start_from is inclusive.  Qdrant has no cursor
+        here; this project's is next_page_offset = {"value": the last record's order_value, "id": its id}: the next page
+        continues strictly after that pair, so chained pages neither repeat nor lose a point however many share a value.
+        Each record's `order_value` is the number it was placed by (a datetime's microseconds since the epoch).
+        A key with a live "number" or "datetime" payload index is selected by kernels over the whole column
+        (hx_payload_order_host), a plain scroll by hx_scroll_rows_host; an unindexed or poisoned
+        key or an engine refusal is walked over the payloads in Python.  Both ways give the same pages;
+        `PayloadIndex.scroll_device_calls` / `scroll_python_calls` say which one ran.
+        Raises ValueError for arguments no scroll can serve (a limit outside [1, 2047], a malformed order_by or offset,
+        an offset id the collection does not hold, a sharded collection); an unknown collection gives ([], None), any
+        other failure is logged and gives ([], None), as in every read call."""
+        if not self._scroll:
+            raise ValueError("scroll is not supported on a sharded collection")
+        _scrolling.check_limit(limit, _scrolling.MAX_LIMIT - 1)
+        if order_by is not None:
+            _scrolling.check_order_by(order_by)
+        try:
+            if str(user_id) not in self._collections:
+                logging.warning("scroll: no collection for %s", user_id)
+                return [], None
+            return await self._run(self._scroll_sync, user_id, filters, limit, offset, order_by, with_payload)
+        except ValueError as ve:
+            logging.error("scroll for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("scroll(%s) failed: %s", user_id, e)
+            return [], None
+
+    async def retrieve(self, user_id: str, point_ids, with_payload: bool = True) -> List[Record]:
+        """Qdrant's retrieve(collection, ids) (additive): the points with the given ids, in the order asked, unknown ids
+        skipped -- what a caller does next with a page's ids.  Host only: ids and payloads never cross the C ABI.  An
+        unknown collection gives []; a sharded collection refuses with a ValueError."""
+        if not self._scroll:
+            raise ValueError("retrieve is not supported on a sharded collection")
+        if isinstance(point_ids, (str, bytes)) or not hasattr(point_ids, "__iter__"):
+            raise ValueError("point_ids must be a list of point ids")
+        col = self._collections.get(str(user_id))
+        if col is None:
+            logging.warning("retrieve: no collection for %s", user_id)
+            return []
+
+        def fetch():
+            out = []
+            for p in point_ids:
+                try:
+                    r = col._row_of(p)
+                except ValueError:
+                    continue
+                out.append(Record(id=col.ids[r], payload=col.payloads[r] if with_payload else None))
+            return out
+        return await self._run(fetch)
 
     async def get_collection_chunk_count(self, user_id: str, filters: Optional[Dict] = None) -> int:
         try:

@@ -2,7 +2,7 @@
 
 Qdrant's `create_payload_index(collection, field_name, field_schema)`, the engine's way.  A `PayloadIndex` belongs to
 one collection.  It knows the indexed keys (dotted paths as `filters._get` reads them), each key's schema
-("keyword" | "number" | "bool"), the keyword dictionaries (str -> code) and the ids of the engine columns
+("keyword" | "number" | "bool" | "datetime"), the keyword dictionaries (str -> code) and the ids of the engine columns
 (hx.h: hx_payload_*).  It does two things:
 
   encode(key, payloads)   the cells of some rows of one key -- or None when a value POISONS the key;
@@ -27,7 +27,13 @@ The text schema ("text") is opt-in too: a row's value is m
 UTF-8 bytes of `value.lower()`; anything else (a number, a bool, a list, a dict, a string with a lone surrogate) poisons
 the key.  `match text` on such a key compiles to one TEXT_ALL over the distinct words of `str(text).lower().split()`,
 each as UTF-8 bytes: UTF-8 is self-synchronising, so a byte-substring test on the two encodings is Python's `w in hay`
-on the code points.  Lower-casing and splitting stay Python's; the engine only sees bytes."""
+on the code points.  Lower-casing and splitting stay Python's; the engine only sees bytes.
+
+The datetime schema ("datetime") exists for ordered scrolls: a row's value is missing, None, a
+`datetime.datetime` or a `str` that parses as RFC 3339 (scrolling.datetime_micros), stored as an F64 cell holding the
+integer microseconds since the epoch -- exact while |us| <= 2^53; anything else (a number, an unparsable string, a value
+outside that range) poisons the key.  The compiler DECLINES every condition on such a key: `filters.matches` compares the
+payload's own value, not its microseconds, and the masks stay what it gives."""
 from __future__ import annotations
 
 import math
@@ -37,6 +43,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import filters as _filters
+from . import scrolling as _scrolling
 
 # hx.h
 PAY_U32, PAY_F64, PAY_LIST_U32, PAY_LIST_F64, PAY_TEXT = 1, 2, 3, 4, 5
@@ -50,7 +57,7 @@ TEXT_MAX_COLUMN_WORDS = 0x7FFFFFFF      # a text column holds fewer than 2^31 32
 
 SCHEMAS = {"keyword": "keyword", "number": "number", "integer": "number", "float": "number", "bool": "bool",
            "keyword_list": "keyword_list", "number_list": "number_list", "integer_list": "number_list",
-           "float_list": "number_list", "bool_list": "bool_list", "text": "text"}
+           "float_list": "number_list", "bool_list": "bool_list", "text": "text", "datetime": "datetime"}
 _CLAUSES = ("must", "should", "must_not")
 _MAX_KEYWORDS = U32_NULL            # codes 0 .. 0xFFFFFFFD
 
@@ -141,7 +148,7 @@ class _Key:
             return PAY_TEXT
         if self.is_list:
             return PAY_LIST_F64 if self.elem == "number" else PAY_LIST_U32
-        return PAY_F64 if self.schema == "number" else PAY_U32
+        return PAY_F64 if self.schema in ("number", "datetime") else PAY_U32
 
 
 class PayloadIndex:
@@ -153,6 +160,8 @@ class PayloadIndex:
         self.group_device_calls = 0        # grouped searches served by hx_hybrid_query_groups_host
         self.facet_device_calls = 0        # facets served by hx_payload_facet_host
         self.facet_python_calls = 0        # facets counted by faceting.py over the payloads
+        self.scroll_device_calls = 0       # scrolls served by hx_scroll_rows_host / hx_payload_order_host
+        self.scroll_python_calls = 0       # scrolls walked by scrolling.py over the payloads
 
     # -- definitions -----------------------------------------------------------------------------------------------
     def definitions(self) -> Dict[str, str]:
@@ -176,6 +185,24 @@ class PayloadIndex:
             return self._encode_lists(k, key, payloads)
         if k.is_text:
             return self._encode_text(key, payloads)
+        if k.schema == "datetime":
+            vals = np.zeros(n, np.float64)
+            special = []
+            for r, p in enumerate(payloads):
+                v = get(p, key)
+                if v is missing:
+                    special.append((r, F64_MISSING))
+                elif v is None:
+                    special.append((r, F64_NULL))
+                else:
+                    us = _scrolling.datetime_micros(v)
+                    if us is None or abs(us) > 2 ** 53:
+                        return None
+                    vals[r] = float(us)
+            cells = vals.view(np.uint64).copy()
+            for r, bits in special:
+                cells[r] = bits
+            return cells
         if k.schema == "number":
             vals = np.zeros(n, np.float64)
             special: List[Tuple[int, int]] = []
@@ -372,6 +399,8 @@ class PayloadIndex:
             raise _Decline("unindexed key")
         if k.col is None:
             raise _Decline("poisoned key")
+        if k.schema == "datetime":
+            raise _Decline("datetime key")
         return k
 
     def _condition(self, c, ops, sets, id_rows):

@@ -478,6 +478,7 @@ class ShardedHandler(QdrantHandler):
     _facets = False                  # facet raises ValueError: payload columns live in one engine index only
     _late_rerank = False             # create_token_index / hybrid_search_rerank raise ValueError: token columns likewise
     _recommend = False               # recommend / recommend_batch raise ValueError: nothing is sent to the ranks
+    _scroll = False                  # scroll / retrieve raise ValueError: the rows of a collection lie in several indexes
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
