@@ -676,15 +676,32 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
 //
 // Schedule.  One phase = KP slabs (KP consecutive k-tiles of the item; shipped: 2), 16 KP MFMAs (4 row tiles x 2 query
 // tiles x 2 k-steps per slab) into 32 accumulator registers.
-//     L segment : ds_read the 8 KP A fragments of the phase's slabs, stage the same k-tiles of the NEXT item (KP pieces),
-//                 counted wait
+//     L segment : ds_read the 8 KP A fragments of the phase's slabs; in an item's FIRST phase the threshold filter of the
+//                 item the wave finished just before (below); stage the same k-tiles of the NEXT item (KP pieces),
+//                 counted wait; the log stores of that filter, if a column passed
 //     barrier
-//     M segment : the 16 KP MFMAs; behind the last phase of an item its threshold filter
+//     M segment : the 16 KP MFMAs and nothing else (once per pair the scalar advance): it ends with its last MFMA,
+//                 s_setprio 0 and the barrier
 //     barrier
-// Phase shapes measured on the 10M x 768 step, one box, six alternations (profiles/scan8_qs.txt; HX_DEBUG_S8Q_KP picks
-// one for diagnostics): one slab per phase 9.03 ms -- twice k_scan8's barriers per MAC, and a 256-cycle M segment is too
-// short a cover for its partner's L segment: the kernel alone took what k_scan8 takes; two slabs 8.86 ms (k_scan8's 32
-// MFMAs per phase and barriers per MAC, 218 VGPRs); three slabs 8.88 ms at 250 VGPRs -- no better, no headroom.
+// The deferred filter.  An item's accumulators stay where they are until the first MFMA of the wave's next item
+// overwrites them, one L segment later.  That segment is bound by its LDS reads and leaves the VALU idle, and its group
+// has some 265 cycles of slack at the barrier behind it; behind the item's last MFMA the same ten dependent VALU
+// instructions, the MFMA result latency and -- on a hit -- five stores held the matrix pipe of the SIMD empty, the
+// partner wave standing at the barrier (210-275 cycles of barrier wait per item, profiles/scan8q_cursor.txt).  So the
+// reduction and the compare run behind the issue of the next L segment's ds_reads, and the log stores behind its counted
+// wait, just ahead of the barrier: stores count in vmcnt, and issued AHEAD of the stage loads they make vmcnt(KT - KP)
+// wait for their acks and for the previous phase's pieces (measured: slower than the parent, profiles/scan8q_defer.txt;
+// -DHX_S8Q_LOG_EARLY=1 builds that placement).  Behind the wait they are the youngest vmcnt entries of the NEXT
+// phase's wait, which is the same count as before and so waits for at least what it waited for: no counted wait is
+// loosened.  The filter sees the finished item's own first row and the scale bound of its own parent tile: an even
+// item is filtered inside its pair (row_c, rxm), an odd one after the pair boundary, from the copies taken there
+// (row_p, rxm_p).  Item 0 has nothing pending; the last item of the walk is filtered behind the loop, before hitcnt is
+// written.  224 VGPRs (the fragments of the next phase are live beside the accumulators), no scratch.
+// Phase shapes measured on the 10M x 768 step, one box, six alternations (profiles/scan8_qs.txt; HX_DEBUG_S8Q_KP=1
+// picks the other one for diagnostics): one slab per phase 9.03 ms -- twice k_scan8's barriers per MAC, and a 256-cycle
+// M segment is too short a cover for its partner's L segment: the kernel alone took what k_scan8 takes; two slabs
+// 8.86 ms (k_scan8's 32 MFMAs per phase and barriers per MAC).  (Three slabs per phase were 8.88 ms at 250 VGPRs and
+// do not fit the deferred filter's registers: no longer built.)
 // (128 ROWS per phase would need 64 accumulator + 64 fragment registers beside the 96 of the queries.)
 // The ring is 2 KT slots, slot = (item & 1) * KT + kt.  RAW: the wait of a phase leaves KT - KP pieces in flight (the
 // slabs behind those of the NEXT phase), so the next phase's slabs are in LDS, for every wave of the group, before the
@@ -701,11 +718,16 @@ __global__ __launch_bounds__(512, 2) void k_scan8(ScanArgs a) {
 // Log entries are k_scan8's: {query, first row} + MT words, one entry per passing column of a 64-row item;
 // k_scatter_log<.., QS> maps wave w of workgroup (xcd, i0) to queries qt * 256 + 32 w .. + 31.
 // DBG 2 (timing build, wrong results): no global_load_lds in the loop.
+// DBG 3 (timing build, wrong results): no filter at all, the accumulators kept alive where the filter would read them.
 constexpr int S8Q_SLAB = 8192;
+#ifndef HX_S8Q_LOG_EARLY
+#define HX_S8Q_LOG_EARLY 0    // 1: the log stores of a deferred filter directly behind its compare, ahead of the segment's
+#endif                        // stage loads (measured against 0 in profiles/scan8q_defer.txt; 0 ships)
 // Diagnostic build only (-DHX_S8Q_STAMP; scripts/s8q_stamps.py): waves 0 and 4 -- one per stagger group -- accumulate
 // s_memtime deltas around every barrier of the item loop, by phase position (first, middle, last phase of an item):
 //   [4 pos + 0] L segment   [4 pos + 1] the wait at the barrier behind it   [4 pos + 2] M segment   [4 pos + 3] its barrier
-//   [12] the tail of a last M segment, from the issue of its last MFMA to the end of the filter   [13] items
+//   [12] the deferred filter inside an item's first L segment: its decision, and behind the counted wait its log stores
+//   (both are part of that L segment's stamp too)   [13] items
 // into a debug buffer of their own, summed over launches (never read by the kernel, never in a timed build).
 #ifdef HX_S8Q_STAMP
 constexpr int S8Q_NSTAMP = 16;
@@ -713,13 +735,15 @@ __device__ unsigned long long g_s8q_stamps[256 * 2 * S8Q_NSTAMP];
 #define S8Q_STAMP_DECL unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_tf = 0, st_acc[S8Q_NSTAMP] = {};
 #define S8Q_STAMP(i) { const unsigned long long st_t1 = __builtin_amdgcn_s_memtime(); st_acc[i] += st_t1 - st_t0; st_t0 = st_t1; }
 #define S8Q_STAMP_TAIL_BEGIN st_tf = __builtin_amdgcn_s_memtime();
-#define S8Q_STAMP_TAIL_END { st_acc[12] += __builtin_amdgcn_s_memtime() - st_tf; st_acc[13] += 1; }
+#define S8Q_STAMP_TAIL_END st_acc[12] += __builtin_amdgcn_s_memtime() - st_tf;
+#define S8Q_STAMP_ITEM st_acc[13] += 1;
 #define S8Q_STAMP_FLUSH if (lane == 0 && (wave & 3) == 0) for (int i_ = 0; i_ < S8Q_NSTAMP; ++i_) g_s8q_stamps[(blockIdx.x * 2 + grp) * S8Q_NSTAMP + i_] += st_acc[i_];
 #else
 #define S8Q_STAMP_DECL
 #define S8Q_STAMP(i)
 #define S8Q_STAMP_TAIL_BEGIN
 #define S8Q_STAMP_TAIL_END
+#define S8Q_STAMP_ITEM
 #define S8Q_STAMP_FLUSH
 #endif
 template <int KT, int DBG, int KP>
@@ -727,6 +751,7 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   constexpr int MT = 4, NT = 2, KS = 2;
   static_assert(KT % KP == 0 && KT / KP >= 2, "a phase is KP slabs of one item");
   constexpr bool NO_GLDS = DBG == 2;
+  constexpr bool NO_FILTER = DBG == 3;
   __shared__ __attribute__((aligned(1024))) uint8_t lds[2 * KT * S8Q_SLAB];
 
   const int tid = threadIdx.x;
@@ -825,26 +850,38 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   float rxm = 0.f;
 
   // lane owns query column r of each of the NT tiles and rows 4 hh + e of each of the MT row tiles
-  auto filter = [&](int64_t row0) __attribute__((always_inline)) {
+  // The filter of a finished item, in two halves (see "Schedule"): the decision -- the column maxima of the item's
+  // accumulators against the thresholds, under the scale bound rx of the item's OWN parent tile -- and the log entries
+  // of the passing columns, first row row0 of that item.
+  float fm[NT];
+  auto filter_decide = [&](float rx) __attribute__((always_inline)) {
+    if constexpr (NO_FILTER) {       // timing build: no filter at all (the accumulators are kept alive)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) asm volatile("" ::"v"(acc[mt][nt]));
+      return false;
+    }
     auto imax3 = [](int x, int y, int z) __attribute__((always_inline)) {
       const int t = x > y ? x : y;
       return t > z ? t : z;
     };
-    float m[NT];
     bool any = false;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       int im = acc[0][nt][0];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) im = imax3(imax3(im, acc[mt][nt][0], acc[mt][nt][1]), acc[mt][nt][2], acc[mt][nt][3]);
-      m[nt] = im > 0 ? (float)im * rxm : 0.f;    // (k_scan8's bound: f32(max dot) * max row scale of the parent tile)
-      any |= (m[nt] >= tau_r[nt]);
+      fm[nt] = im > 0 ? (float)im * rx : 0.f;    // (k_scan8's bound: f32(max dot) * max row scale of the parent tile)
+      any |= (fm[nt] >= tau_r[nt]);
     }
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(any) == 0ull, 1)) return;
+    return __builtin_amdgcn_ballot_w64(any) != 0ull;
+  };
+  auto filter_log = [&](int64_t row0) __attribute__((always_inline)) {
     const int64_t rowq = row0 + 4 * hh;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      const bool hit = m[nt] >= tau_r[nt];
+      const bool hit = fm[nt] >= tau_r[nt];
       const uint64_t mask = __builtin_amdgcn_ballot_w64(hit);
       if (mask == 0ull) continue;
       const int idx = wpos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
@@ -881,6 +918,10 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
   int64_t row_n = row_c;                            // the next pair; past the last one the cursor does not advance:
   const uint8_t* p_n = p_c;                         // its even item is re-loaded (never read)
   float rxm_n = rxm;
+  // the finished odd item of the pair BEHIND the one in hand, whose filter is still due: saved at the pair boundary,
+  // where row_c and rxm move on (a finished even item is filtered inside its own pair: row_c and rxm are still its own)
+  int64_t row_p = row_c;
+  float rxm_p = rxm;
 
   // ---- prologue: the KT slabs of item 0 ---------------------------------------------------------------------
 #pragma unroll
@@ -910,11 +951,27 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
           for (int ks = 0; ks < KS; ++ks) af[kp][mt][ks] = *(const half8*)(s + (hi ? rd_hi[ks] : rd[ks]) + mt * 2048);
       }
       __builtin_amdgcn_sched_barrier(0);
+      // the deferred filter of the item finished just before this one (item 0 has none): the decision runs on the
+      // VALU while the reads above are in flight
+      bool pend_hit = false;
+      if (kt == 0 && (ODD || j > 0)) {
+        S8Q_STAMP_TAIL_BEGIN
+        pend_hit = filter_decide(ODD ? rxm : rxm_p);
+        if (HX_S8Q_LOG_EARLY && __builtin_expect(pend_hit, 0)) filter_log(ODD ? row_c : row_p);
+        S8Q_STAMP_TAIL_END
+        __builtin_amdgcn_sched_barrier(0);
+      }
       if (!NO_GLDS) {
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp) stage(nxt_p, kt + kp, s_nxt + kt + kp);
       }
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(KT - KP) : "memory");
+      if (!HX_S8Q_LOG_EARLY && kt == 0) {     // the log stores behind the counted wait: no stage load waits for a store
+        __builtin_amdgcn_sched_barrier(0);
+        S8Q_STAMP_TAIL_BEGIN
+        if (__builtin_expect(pend_hit, 0)) filter_log(ODD ? row_c : row_p);
+        S8Q_STAMP_TAIL_END
+      }
       __builtin_amdgcn_sched_barrier(0);
       S8Q_STAMP(pos * 4 + 0)
       __builtin_amdgcn_s_barrier();
@@ -948,11 +1005,11 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("; the next pair's scale bound has landed" ::"s"(rxm_n));
       }
-      if (kt + KP == KT) {
-        S8Q_STAMP_TAIL_BEGIN
-        filter(row_c + ODD * 64);
-        S8Q_STAMP_TAIL_END
+      if (kt + KP == KT) {     // the item's filter is left to the wave's next L segment
+        S8Q_STAMP_ITEM
         if (ODD) {             // the pair boundary
+          row_p = row_c + 64;
+          rxm_p = rxm;
           row_c = row_n;
           p_c = p_n;
           rxm = rxm_n;
@@ -970,6 +1027,7 @@ __global__ __launch_bounds__(512, 2) void k_scan8q(ScanArgs a) {
     item(std::integral_constant<int, 0>{}, j);
     item(std::integral_constant<int, 1>{}, j);
   }
+  if (n_pairs > 0 && filter_decide(rxm_p)) filter_log(row_p);   // the last item of the walk (an odd one)
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the never-read tail loads
   if (grp == 0) __builtin_amdgcn_s_barrier();
@@ -1129,16 +1187,18 @@ void launch_scan8(const ScanArgs& a, int kind, hipStream_t st, hipEvent_t after_
 #else
   constexpr int dbg = 0;
 #endif
-  // HX_SCAN_DBG 12 (timing build): the query-stationary form without its global_load_lds; every other value times k_scan8
+  // HX_SCAN_DBG (timing builds) 12: the query-stationary form without its global_load_lds, 13: without its filter; every
+  // other value times k_scan8
   static const int qs_kp = getenv("HX_DEBUG_S8Q_KP") ? atoi(getenv("HX_DEBUG_S8Q_KP")) : 2;   // diagnostics: k-tiles per phase, 1 | 2
-  if (!a.no_qs && cap == 256 && (dbg == 0 || dbg == 12) && scan8_qs_form(kind, a.half_q, a.row_bytes, a.nq_tiles)) {
+  if (!a.no_qs && cap == 256 && (dbg == 0 || dbg == 12 || dbg == 13) &&
+      scan8_qs_form(kind, a.half_q, a.row_bytes, a.nq_tiles)) {
     g = 256;
     HX_CHECK(((32 / a.nq_tiles) & 1) == 0, "scan8: the query-stationary walk needs an even number of streams per XCD");
 #ifdef HX_SCAN_DBG
     if (dbg == 12) hipLaunchKernelGGL((k_scan8q<6, 2, 2>), dim3(256), dim3(512), 0, st, a); else
+    if (dbg == 13) hipLaunchKernelGGL((k_scan8q<6, 3, 2>), dim3(256), dim3(512), 0, st, a); else
 #endif
     if (qs_kp == 1) hipLaunchKernelGGL((k_scan8q<6, 0, 1>), dim3(256), dim3(512), 0, st, a);
-    else if (qs_kp == 3) hipLaunchKernelGGL((k_scan8q<6, 0, 3>), dim3(256), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((k_scan8q<6, 0, 2>), dim3(256), dim3(512), 0, st, a);
     HX_HIP(hipGetLastError());
     if (after_kernel) HX_HIP(hipEventRecord(after_kernel, st));

@@ -42,4 +42,4 @@ for g in (0, 1):
     for pos, pn in enumerate(("first phase", "middle phases", "last phase")):
         row = "  ".join("%s %7.1f" % (names[i], per[:, pos * 4 + i].mean()) for i in range(4))
         print("  %-13s %s   sum %7.1f" % (pn, row, per[:, pos * 4:pos * 4 + 4].sum(1).mean()))
-    print("  tail of the last M segment (last MFMA issued -> filter done): %.1f cycles per item" % (s[:, 12] / n[:, 0]).mean())
+    print("  deferred filter inside the first L segment (decision + log stores): %.1f cycles per item" % (s[:, 12] / n[:, 0]).mean())
