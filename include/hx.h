@@ -488,7 +488,25 @@ int hx_payload_replace_text(hx_index* h, int32_t col, const int64_t* rows_host, 
  *                                         within the row's byte length); false on a missing or null row
  * Its set is a pattern blob: hx_pay_set.vals points at bytes, n = their number; uint32 P, then uint32 len[P], then the
  * patterns' bytes one after another, 1 <= P <= HX_PAY_TEXT_MAX_WORDS, 1 <= len <= HX_PAY_TEXT_MAX_WORD_BYTES.  Every
- * other column op is refused on a text column, TEXT_ALL on every other column. */
+ * other column op is refused on a text column, TEXT_ALL on every other column.
+ * Nested blocks: list columns that hold ONE element per object of an array of objects, so that
+ * position i of every such column speaks of the same object ("aligned": equal heads and offsets for every row)
+ *   HX_PAY_NESTED  col imm = m            col = a list column, the block's ANCHOR (its offsets say which element positions
+ *                                         a row owns); the next m ops, 1 <= m <= HX_PAY_NESTED_MAX_OPS, are ELEMENT ops.
+ *                                         Pushes ONE entry on the row stack: some element position of the row makes the
+ *                                         element program true.  False on a missing, null or empty row.
+ *   element ops: HX_PAY_TRUE / _FALSE / _AND / _OR / _NOT on a per-ELEMENT boolean stack (at most HX_PAY_MAX_STACK deep,
+ *                exactly one entry at the end), and
+ *   HX_PAY_EL_EQ  col imm                 the element of `col` at this position == imm (as ANY_EQ compares)
+ *   HX_PAY_EL_IN  col imm = set index     ... is in the set
+ *   HX_PAY_EL_RANGE  col imm = set index  HX_PAY_LIST_F64 only; the set is exactly two doubles lo <= hi: lo <= x <= hi
+ * The columns of a block's EL ops (at most HX_PAY_NESTED_MAX_COLS distinct ones; the anchor counts only when an EL op
+ * reads it) must be list columns filled to hx_count that hold as many elements as the anchor: that equality, checked on
+ * the host, keeps every element read in bounds.  Alignment proper is the caller's contract (hx_payload_same_offsets
+ * checks it): over columns of equal totals but different offsets a block evaluates positions, in bounds, that belong
+ * to other rows. */
+#define HX_PAY_NESTED_MAX_OPS 64
+#define HX_PAY_NESTED_MAX_COLS 8
 #define HX_PAY_TRUE 0
 #define HX_PAY_FALSE 1
 #define HX_PAY_IS_MISSING 2
@@ -509,6 +527,10 @@ int hx_payload_replace_text(hx_index* h, int32_t col, const int64_t* rows_host, 
 #define HX_PAY_ANY_RANGE 17
 #define HX_PAY_IS_EMPTY_LIST 18
 #define HX_PAY_TEXT_ALL 19
+#define HX_PAY_NESTED 20
+#define HX_PAY_EL_EQ 21
+#define HX_PAY_EL_IN 22
+#define HX_PAY_EL_RANGE 23
 typedef struct hx_pay_op {
   int32_t op;
   int32_t col;
@@ -528,9 +550,16 @@ typedef struct hx_pay_set {
  * no pattern, more than HX_PAY_TEXT_MAX_WORDS, an empty one or one above HX_PAY_TEXT_MAX_WORD_BYTES, a set index out of
  * range, a set that is not ascending, more than
  * HX_PAY_MAX_OPS ops, a stack that would exceed HX_PAY_MAX_STACK entries or underflow or does not end with exactly one
- * entry. */
+ * entry.  Of a nested block: m out of range or past the program's end, a row op inside a block or an EL op outside
+ * one, a block column that is not a list column or not filled to hx_count, more than HX_PAY_NESTED_MAX_COLS distinct
+ * columns, columns of unequal element totals, EL_RANGE on a U32 column or with a set of other than two entries, a set of
+ * mixed kind, an element stack that underflows, passes HX_PAY_MAX_STACK entries or does not end at one. */
 int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_pay_set* sets_host, int32_t n_sets,
                     uint32_t* mask_dev, int64_t* n_kept, void* stream);
+/* *same = 1 when two list columns are aligned: both filled to the same row count, with equal heads and equal offsets
+ * for every row (compared on the device; the call synchronises), else 0.  Refused: an unknown column, a column that is
+ * not a list column ("kind" in the message). */
+int hx_payload_same_offsets(hx_index* h, int32_t col_a, int32_t col_b, int32_t* same);
 /* copy one cell to the host (4 bytes of a U32 column, 8 of an F64 column), as hx_debug_row does for vectors; refused on
  * a list or text column */
 int hx_payload_debug_cell(hx_index* h, int32_t col, int64_t row, void* out_host);

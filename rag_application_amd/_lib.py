@@ -142,6 +142,7 @@ _SIGS = {
     "hx_payload_append": [_P, C.c_int32, _P, C.c_int64],
     "hx_payload_rows": [_P, C.c_int32, C.POINTER(C.c_int64)],
     "hx_payload_mask": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.POINTER(C.c_int64), _P],
+    "hx_payload_same_offsets": [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
     "hx_payload_debug_cell": [_P, C.c_int32, C.c_int64, _P],
     "hx_payload_append_lists": [_P, C.c_int32, _P, C.c_int64, _P, C.c_int64],
     "hx_payload_replace": [_P, C.c_int32, _P, C.c_int64, _P],

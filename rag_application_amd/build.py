@@ -18,6 +18,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("sprescore.hip", "sprescore.o", ()), ("mask.hip", "mask.o", ()), ("compact.hip", "compact.o", ()),
            ("replace.hip", "replace.o", ()),
            ("payload.hip", "payload.o", ()), ("paytext.hip", "paytext.o", ()),
+           ("paynested.hip", "paynested.o", ()),
            ("group.hip", "group.o", ()), ("mmr.hip", "mmr.o", ()), ("maxsim.hip", "maxsim.o", ()),
            ("facet.hip", "facet.o", ()), ("reco.hip", "reco.o", ()), ("scroll.hip", "scroll.o", ()),
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),

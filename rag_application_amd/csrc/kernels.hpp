@@ -498,6 +498,32 @@ struct PayTextPat {
 // allocated to a multiple of four words).  grid_cap as launch_payload_mask takes it.
 void launch_payload_text(const uint32_t* head, const int64_t* off, const uint32_t* text, int64_t n, const PayTextPat* pats,
                          int n_pats, uint32_t* plane, int grid_cap, hipStream_t st);
+// ---- paynested.hip: HX_PAY_NESTED -------------------------------------------------------------
+// One ELEMENT op as the kernel reads it: slot = which of the block's distinct columns it reads; a set as a device
+// pointer in imm with cnt entries, EL_RANGE's closed interval in imm / imm2 (the bits of two doubles).
+enum PayElOp : uint32_t {
+  PAY_E_TRUE = 0, PAY_E_FALSE, PAY_E_AND, PAY_E_OR, PAY_E_NOT, PAY_E_EQ_U32, PAY_E_IN_U32, PAY_E_EQ_F64, PAY_E_IN_F64,
+  PAY_E_RANGE
+};
+struct PayElOpDev {
+  uint32_t op, slot, cnt, pad;
+  uint64_t imm, imm2;
+};
+constexpr int PAY_NESTED_COLS = 8;    // HX_PAY_NESTED_MAX_COLS
+// the element planes of a block's distinct columns (e1 = the high words of doubles or NULL), slots [0, n_cols)
+struct PayNestedCols {
+  const uint32_t* e0[PAY_NESTED_COLS];
+  const uint32_t* e1[PAY_NESTED_COLS];
+  int n_cols;
+};
+// plane[ceil(n / 32)] (the mask's layout, bits at or past n zero): bit r = some element position in
+// [off[r], off[r + 1]) makes the element program (1 to 64 ops, leaving one entry) true.  off = the anchor's int64 offsets
+// [n + 1]; every plane of `cols` (a table in device memory) holds at least off[n] elements.  grid_cap as launch_payload_mask takes it.
+void launch_payload_nested(const int64_t* off, int64_t n, const PayNestedCols* cols, const PayElOpDev* prog, int n_ops,
+                           uint32_t* plane, int grid_cap, hipStream_t st);
+// *same (the caller sets it to 1) becomes 0 when head_a[r] != head_b[r] for a row r < n or off_a[r] != off_b[r] for r <= n
+void launch_payload_same_offsets(const uint32_t* head_a, const uint32_t* head_b, const int64_t* off_a, const int64_t* off_b,
+                                 int64_t n, uint32_t* same, hipStream_t st);
 // ---- group.hip: grouped search (hx_group) ------------------------------------------------------
 constexpr uint32_t HX_GROUP_MISSING = 0xFFFFFFFFu, HX_GROUP_NULL = 0xFFFFFFFEu;   // HX_PAY_U32_MISSING / _NULL of hx.h
 // Per query b: the ranked list keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same

@@ -1,6 +1,6 @@
-// Host side of the payload index (DESIGN.md sections 15, 17, 19): the storage of the columns, every hx_payload_* entry,
-// and what the lifecycle of the rows (lifecycle.hip) does to a column.  The kernels are in payload.hip and paytext.hip,
-// the splice of a list or text column in replace.hip.
+// Host side of the payload index (DESIGN.md sections 15, 17, 19, 26): the storage of the columns, every hx_payload_* entry,
+// and what the lifecycle of the rows (lifecycle.hip) does to a column.  The kernels are in payload.hip, paytext.hip and
+// paynested.hip, the splice of a list or text column in replace.hip.
 #include "index.hpp"
 
 namespace hx {
@@ -776,10 +776,93 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
     size_t pat_off = 0;
   };
   std::vector<TextOp> texts;
-  int depth = 0;
+  struct NestedOp {                                       // one HX_PAY_NESTED: a k_payload_nested launch + PAY_D_BITS
+    int at;
+    const int64_t* off;
+    PayNestedCols cols;
+    std::vector<PayElOpDev> ops;                          // (an IN op: imm = the set's index until the sets are placed)
+    size_t op_off = 0;
+  };
+  std::vector<NestedOp> nests;
+  auto use_set = [&](uint64_t idx, int8_t kind) {
+    HX_CHECK(idx < (uint64_t)n_sets, "payload: set index out of range");
+    HX_CHECK(set_kind[(size_t)idx] == 0 || set_kind[(size_t)idx] == kind, "payload: one set used as uint32 and as double");
+    set_kind[(size_t)idx] = kind;
+  };
+  int depth = 0, n_dev = 0;                               // n_dev = ops of the device program: a nested block becomes one
   for (int i = 0; i < n_ops; ++i) {
     const hx_pay_op& o = ops[i];
     PayOpDev d{0u, 0u, o.imm, nullptr, nullptr, nullptr, nullptr, nullptr, 0ull};
+    if (o.op == HX_PAY_NESTED) {       // 
+      const hx_index::PayCol& a = pay_col(h, o.col);
+      HX_CHECK(a.list(), "payload: the anchor of a nested block must be a list column (column kind)");
+      HX_CHECK(a.filled == h->n, "payload: column " + std::to_string(o.col) + " is not filled to the index's row count");
+      HX_CHECK(o.imm >= 1 && o.imm <= HX_PAY_NESTED_MAX_OPS, "payload: a nested block holds 1 to 64 element ops");
+      const int m = (int)o.imm;
+      HX_CHECK(i + m < n_ops, "payload: a nested block runs past the program's end");
+      NestedOp nb;
+      nb.at = n_dev;
+      nb.off = a.off;
+      nb.cols = PayNestedCols{};
+      int32_t ids[HX_PAY_NESTED_MAX_COLS];
+      int edepth = 0;
+      for (int j = 1; j <= m; ++j) {
+        const hx_pay_op& e = ops[i + j];
+        PayElOpDev ed{0u, 0u, 0u, 0u, e.imm, 0ull};
+        int epops = 0;
+        bool ef64 = false;
+        if (e.op >= HX_PAY_EL_EQ && e.op <= HX_PAY_EL_RANGE) {
+          const hx_index::PayCol& c = pay_col(h, e.col);
+          HX_CHECK(c.list(), "payload: EL_EQ / EL_IN / EL_RANGE need a list column (column kind)");
+          HX_CHECK(c.filled == h->n, "payload: column " + std::to_string(e.col) + " is not filled to the index's row count");
+          HX_CHECK(c.n_el == a.n_el, "payload: the columns of a nested block hold different numbers of elements");
+          ef64 = c.kind == HX_PAY_LIST_F64;
+          int slot = 0;
+          while (slot < nb.cols.n_cols && ids[slot] != e.col) ++slot;
+          if (slot == nb.cols.n_cols) {
+            HX_CHECK(slot < HX_PAY_NESTED_MAX_COLS, "payload: a nested block reads at most 8 distinct columns");
+            ids[slot] = e.col;
+            nb.cols.e0[slot] = c.e0;
+            nb.cols.e1[slot] = ef64 ? c.e1 : nullptr;
+            ++nb.cols.n_cols;
+          }
+          ed.slot = (uint32_t)slot;
+        }
+        switch (e.op) {
+          case HX_PAY_TRUE: ed.op = PAY_E_TRUE; break;
+          case HX_PAY_FALSE: ed.op = PAY_E_FALSE; break;
+          case HX_PAY_AND: ed.op = PAY_E_AND; epops = 2; break;
+          case HX_PAY_OR: ed.op = PAY_E_OR; epops = 2; break;
+          case HX_PAY_NOT: ed.op = PAY_E_NOT; epops = 1; break;
+          case HX_PAY_EL_EQ: ed.op = ef64 ? PAY_E_EQ_F64 : PAY_E_EQ_U32; break;
+          case HX_PAY_EL_IN:
+            ed.op = ef64 ? PAY_E_IN_F64 : PAY_E_IN_U32;
+            use_set(e.imm, ef64 ? 2 : 1);
+            break;
+          case HX_PAY_EL_RANGE:
+            HX_CHECK(ef64, "payload: EL_RANGE needs an F64 list column");
+            ed.op = PAY_E_RANGE;
+            use_set(e.imm, 2);
+            HX_CHECK(sets[e.imm].n == 2, "payload: the set of EL_RANGE holds exactly two doubles, lo <= hi");
+            break;
+          default: throw Error("payload: op " + std::to_string(e.op) + " is a row op inside a nested block");
+        }
+        HX_CHECK(edepth >= epops, "payload: element stack underflow at op " + std::to_string(i + j));
+        edepth += 1 - epops;
+        HX_CHECK(edepth <= HX_PAY_MAX_STACK, "payload: the element stack exceeds 32 entries at op " + std::to_string(i + j));
+        nb.ops.push_back(ed);
+      }
+      HX_CHECK(edepth == 1, "payload: the element program must leave exactly one entry on its stack");
+      nests.push_back(std::move(nb));
+      d.op = PAY_D_BITS;
+      ++depth;
+      HX_CHECK(depth <= HX_PAY_MAX_STACK, "payload: the stack exceeds 32 entries at op " + std::to_string(i));
+      prog[(size_t)n_dev++] = d;
+      i += m;
+      continue;
+    }
+    HX_CHECK(!(o.op >= HX_PAY_EL_EQ && o.op <= HX_PAY_EL_RANGE),
+             "payload: op " + std::to_string(o.op) + " is an element op outside a nested block");
     int pops = 0;
     const hx_index::PayCol* c = nullptr;
     const bool list_op = o.op >= HX_PAY_ANY_EQ && o.op <= HX_PAY_IS_EMPTY_LIST;
@@ -838,7 +921,7 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
         HX_CHECK(np >= 1 && np <= HX_PAY_TEXT_MAX_WORDS, "payload: a pattern blob holds 1 to 32 patterns");
         HX_CHECK(ps.n >= 4 + 4 * (int64_t)np, "payload: the pattern blob's size disagrees with its header");
         TextOp t;
-        t.at = i;
+        t.at = n_dev;
         t.c = c;
         t.pats.assign(np, PayTextPat{});
         int64_t at = 4 + 4 * (int64_t)np;
@@ -866,19 +949,16 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
     if (o.op >= HX_PAY_LT && o.op <= HX_PAY_GE) HX_CHECK(f64, "payload: LT / LE / GT / GE need an F64 column");
     if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(f64, "payload: ANY_RANGE needs an F64 list column");
     if (o.op == HX_PAY_IN || o.op == HX_PAY_ROW_IN || o.op == HX_PAY_ANY_IN || o.op == HX_PAY_ANY_RANGE) {
-      HX_CHECK(o.imm < (uint64_t)n_sets, "payload: set index out of range");
+      use_set(o.imm, f64 ? 2 : 1);
       if (o.op == HX_PAY_ANY_RANGE) HX_CHECK(sets[o.imm].n == 2, "payload: the set of ANY_RANGE holds exactly two doubles, lo <= hi");
-      const int8_t kind = f64 ? 2 : 1;
-      HX_CHECK(set_kind[(size_t)o.imm] == 0 || set_kind[(size_t)o.imm] == kind, "payload: one set used as uint32 and as double");
-      set_kind[(size_t)o.imm] = kind;
     }
     HX_CHECK(depth >= pops, "payload: stack underflow at op " + std::to_string(i));
     depth += 1 - pops;
     HX_CHECK(depth <= HX_PAY_MAX_STACK, "payload: the stack exceeds 32 entries at op " + std::to_string(i));
-    prog[(size_t)i] = d;
+    prog[(size_t)n_dev++] = d;
   }
   HX_CHECK(depth == 1, "payload: the program must leave exactly one entry on the stack");
-  const size_t prog_bytes = (size_t)n_ops * sizeof(PayOpDev);
+  const size_t prog_bytes = (size_t)n_dev * sizeof(PayOpDev);
   std::vector<size_t> set_off((size_t)n_sets, 0);
   size_t bytes = prog_bytes;
   for (int s = 0; s < n_sets; ++s) {
@@ -900,6 +980,10 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
   for (auto& t : texts) {
     t.pat_off = bytes;
     bytes += (size_t)round_up((int64_t)(t.pats.size() * sizeof(PayTextPat)), 8);
+  }
+  for (auto& b : nests) {
+    b.op_off = bytes;
+    bytes += b.ops.size() * sizeof(PayElOpDev) + sizeof(PayNestedCols);   // (the column table behind the element ops)
   }
   const int64_t n = h->n;
   if (n == 0) {
@@ -923,11 +1007,28 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
   }
   if (!h->pay_ev) HX_HIP(hipEventCreateWithFlags(&h->pay_ev, hipEventDisableTiming));
   uint8_t* dev = (uint8_t*)h->ws.get(WS_PAY_PROG, bytes);
-  // one packed verdict plane per TEXT_ALL, written by k_payload_text in front of the mask kernel
+  // one packed verdict plane per TEXT_ALL and per NESTED, written by k_payload_text and
+  // k_payload_nested (section 26) in front of the mask kernel
   const int64_t plane_words = (n + 31) / 32;
-  uint32_t* planes = texts.empty() ? nullptr : (uint32_t*)h->ws.get(WS_PAY_PLANES, texts.size() * (size_t)plane_words * 4);
+  const size_t n_planes = texts.size() + nests.size();
+  uint32_t* planes = n_planes ? (uint32_t*)h->ws.get(WS_PAY_PLANES, n_planes * (size_t)plane_words * 4) : nullptr;
+  uint32_t* nplanes = planes + texts.size() * (size_t)plane_words;
   for (size_t t = 0; t < texts.size(); ++t) prog[(size_t)texts[t].at].imm = (uint64_t)(uintptr_t)(planes + t * (size_t)plane_words);
-  for (int i = 0; i < n_ops; ++i) {
+  for (size_t t = 0; t < nests.size(); ++t) {
+    prog[(size_t)nests[t].at].imm = (uint64_t)(uintptr_t)(nplanes + t * (size_t)plane_words);
+    for (auto& e : nests[t].ops) {
+      if (e.op == PAY_E_RANGE) {
+        const uint64_t* v = (const uint64_t*)sets[(size_t)e.imm].vals;
+        e.imm2 = v[1];
+        e.imm = v[0];
+      } else if (e.op == PAY_E_IN_U32 || e.op == PAY_E_IN_F64) {
+        const size_t s = (size_t)e.imm;
+        e.cnt = (uint32_t)sets[s].n;
+        e.imm = (uint64_t)(uintptr_t)(dev + set_off[s]);
+      }
+    }
+  }
+  for (int i = 0; i < n_dev; ++i) {
     PayOpDev& d = prog[(size_t)i];
     if (d.op == PAY_D_ANY_RANGE) {     // (two doubles, checked above: the closed interval travels in the op itself)
       const uint64_t* v = (const uint64_t*)sets[(size_t)d.imm].vals;
@@ -947,6 +1048,10 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
     if (set_kind[(size_t)s] && set_kind[(size_t)s] != 3 && sets[s].n > 0)
       std::memcpy(h->pay_pin + set_off[(size_t)s], sets[s].vals, (size_t)sets[s].n * (set_kind[(size_t)s] == 1 ? 4 : 8));
   for (const auto& t : texts) std::memcpy(h->pay_pin + t.pat_off, t.pats.data(), t.pats.size() * sizeof(PayTextPat));
+  for (const auto& b : nests) {
+    std::memcpy(h->pay_pin + b.op_off, b.ops.data(), b.ops.size() * sizeof(PayElOpDev));
+    std::memcpy(h->pay_pin + b.op_off + b.ops.size() * sizeof(PayElOpDev), &b.cols, sizeof(PayNestedCols));
+  }
   HX_HIP(hipMemcpyAsync(dev, h->pay_pin, bytes, hipMemcpyHostToDevice, st));
   HX_HIP(hipEventRecord(h->pay_ev, st));
   h->pay_ev_pending = true;
@@ -958,13 +1063,43 @@ int hx_payload_mask(hx_index* h, const hx_pay_op* ops, int32_t n_ops, const hx_p
   for (size_t t = 0; t < texts.size(); ++t)
     launch_payload_text(texts[t].c->p0, texts[t].c->off, texts[t].c->e0, n, (const PayTextPat*)(dev + texts[t].pat_off),
                         (int)texts[t].pats.size(), planes + t * (size_t)plane_words, h->pay_grid, st);
-  launch_payload_mask((const PayOpDev*)dev, n_ops, n, mask_dev, kept, h->pay_grid, st);
+  for (size_t t = 0; t < nests.size(); ++t)
+    launch_payload_nested(nests[t].off, n,
+                          (const PayNestedCols*)(dev + nests[t].op_off + nests[t].ops.size() * sizeof(PayElOpDev)),
+                          (const PayElOpDev*)(dev + nests[t].op_off), (int)nests[t].ops.size(),
+                          nplanes + t * (size_t)plane_words, h->pay_grid, st);
+  launch_payload_mask((const PayOpDev*)dev, n_dev, n, mask_dev, kept, h->pay_grid, st);
   if (n_kept) {
     uint32_t* pin = (uint32_t*)host_pin(h) + 14;
     HX_HIP(hipMemcpyAsync(pin, kept, 4, hipMemcpyDeviceToHost, st));
     HX_HIP(hipStreamSynchronize(st));
     *n_kept = pin[0];
   }
+  HX_CATCH
+}
+
+int hx_payload_same_offsets(hx_index* h, int32_t col_a, int32_t col_b, int32_t* same) {
+  HX_TRY
+  HX_CHECK(h && same, "NULL argument");
+  const auto& a = pay_col(h, col_a);
+  const auto& b = pay_col(h, col_b);
+  HX_CHECK(a.list() && b.list(), "payload: hx_payload_same_offsets compares two list columns (column kind)");
+  if (a.filled != b.filled || a.n_el != b.n_el) {
+    *same = 0;
+    return 0;
+  }
+  if (a.filled == 0 || a.id == b.id) {
+    *same = 1;
+    return 0;
+  }
+  h->set_device();
+  uint32_t* flag = (uint32_t*)h->ws.get(WS_PAY_KEPT, 4);
+  const uint32_t one = 1u;
+  HX_HIP(hipMemcpy(flag, &one, 4, hipMemcpyHostToDevice));
+  launch_payload_same_offsets(a.p0, b.p0, a.off, b.off, a.filled, flag, nullptr);
+  uint32_t out = 0u;
+  HX_HIP(hipMemcpy(&out, flag, 4, hipMemcpyDeviceToHost));
+  *same = (int32_t)out;
   HX_CATCH
 }
 

@@ -565,6 +565,13 @@ class HxIndex:
                                          C.byref(kept) if want_count else None, _stream()))
         return mask[:nw], (kept.value if want_count else None)
 
+    def payload_same_offsets(self, col_a: int, col_b: int) -> bool:
+        """Whether two list columns are element-aligned (hx_payload_same_offsets): filled alike, with equal heads and
+        equal offsets for every row -- what the columns of one nested block must be.  Synchronises."""
+        same = C.c_int32()
+        check(_lib.lib().hx_payload_same_offsets(self._h, int(col_a), int(col_b), C.byref(same)))
+        return bool(same.value)
+
     @staticmethod
     def mask_host(mask: torch.Tensor) -> np.ndarray:
         """A device mask of payload_mask as packed np.uint32 words (what filters.row_mask returns)."""

@@ -17,7 +17,21 @@ Qdrant is absent from the image, so the condition semantics are restated from it
   {"is_empty": {"key": k}}               k missing, None or []
   {"is_null": {"key": k}}                k present with value None
   {"has_id": [ids]}                      the point id is listed
+  {"nested": {"key": a, "filter": f}}    payload[a] is a list and ONE of its elements that is a dict passes the Filter
+                                         f, whose keys are relative to that element
 Keys may be dotted paths ("chunk_metadata.page").
+
+Arrays of objects (the reference stores `entities` and `relationships` so: entity_relation_extractor.py:235-301).  A
+path step `name[]` projects over the list at `name`: when the dict holds the literal key "name[]" that key is read, as
+ever (the literal wins); otherwise, when `name` holds a `list`, the rest of the path is read from every element that is
+a dict and the values found are collected, in element order, into a new list -- elements that are not dicts or lack the
+path contribute nothing, so the result may be [] -- and when `name` is missing, None or not a list the key is missing.
+A final `name[]` with no step behind it is the list itself.  match / range / is_empty / is_null then see that list as
+they see a stored list: {"key": "entities[].entity_type", "match": {"value": "PERSON"}} = some entity is a PERSON.
+Conditions on two projections may be met by DIFFERENT elements; `nested` asks ONE element to meet its whole filter.  Its
+key is a dotted path (a trailing "[]" is accepted and ignored); it is false when the value is missing, None, not a
+list, empty or holds no dict.  A `nested` inside its filter is `matches` recursing on the element; a `has_id` anywhere
+inside it raises ValueError (an element has no id).
 
 `row_mask` evaluates a filter over every stored row at once, as the packed row mask of the engine's
 pre-filtered query (include/hx.h: hx_hybrid_query_*_masked): the filter then applies to every stage,
@@ -34,9 +48,17 @@ _MISSING = object()
 
 def _get(payload: Dict[str, Any], key: str):
     cur: Any = payload
-    for part in str(key).split("."):
+    parts = str(key).split(".")
+    for i, part in enumerate(parts):
         if isinstance(cur, dict) and part in cur:
             cur = cur[part]
+        elif isinstance(cur, dict) and part.endswith("[]") and type(cur.get(part[:-2], _MISSING)) is list:
+            arr = cur[part[:-2]]
+            if i + 1 == len(parts):
+                return arr
+            rest = ".".join(parts[i + 1:])
+            found = (_get(el, rest) for el in arr if isinstance(el, dict))
+            return [v for v in found if v is not _MISSING]
         else:
             return _MISSING
     return cur
@@ -71,9 +93,39 @@ def _range(value, r: Dict[str, Any]) -> bool:
     return value is not _MISSING and any(ok(x) for x in _values(value))
 
 
+def _refuse_has_id(flt) -> None:
+    """ValueError when a has_id condition occurs anywhere inside the filter of a `nested` condition."""
+    if not isinstance(flt, dict):
+        return
+    for clause in ("must", "should", "must_not"):
+        for c in _as_list(flt.get(clause)):
+            if not isinstance(c, dict):
+                continue
+            if "has_id" in c:
+                raise ValueError("has_id inside a nested filter: an element has no id")
+            _refuse_has_id(c)                             # (a sub-filter)
+            if isinstance(c.get("nested"), dict):
+                _refuse_has_id(c["nested"].get("filter"))
+
+
+def _nested(c: Dict[str, Any], payload: Dict[str, Any]) -> bool:
+    nd = c["nested"]
+    if not isinstance(nd, dict) or "key" not in nd:
+        raise ValueError(f"unsupported filter condition: {c}")
+    flt = nd.get("filter")
+    _refuse_has_id(flt)
+    key = str(nd["key"])
+    v = _get(payload, key[:-2] if key.endswith("[]") else key)
+    if type(v) is not list:
+        return False
+    return any(matches(el, flt) for el in v if isinstance(el, dict))
+
+
 def _condition(c: Dict[str, Any], payload: Dict[str, Any], point_id) -> bool:
     if any(k in c for k in ("must", "should", "must_not")):
         return matches(payload, c, point_id)
+    if "nested" in c:
+        return _nested(c, payload)
     if "has_id" in c:
         return point_id in c["has_id"]
     if "is_empty" in c:

@@ -193,7 +193,8 @@ class _Collection:
         mask = self.row_mask(flt) if flt else None
         pi = getattr(self, "pindex", None)
         k = pi.keys.get(key) if pi is not None else None
-        if (k is not None and k.col is not None and k.schema in self.FACET_SCHEMAS and limit <= _faceting.MAX_LIMIT
+        if (k is not None and k.col is not None and k.schema in self.FACET_SCHEMAS and not k.array
+                and limit <= _faceting.MAX_LIMIT
                 and hasattr(self.index, "payload_facet_host")):
             n_codes = len(k.codes) if k.elem == "keyword" else 2
             try:
@@ -269,7 +270,7 @@ class _Collection:
         mask = self.row_mask(flt) if flt else None
         k = pi.keys.get(key) if pi is not None else None
         hits = None
-        if device and k is not None and k.col is not None and k.schema in self.SCROLL_SCHEMAS:
+        if device and k is not None and k.col is not None and k.schema in self.SCROLL_SCHEMAS and not k.array:
             sf = None if start_from is None else _pindex.exact_double(start_from)
             af = None if after is None else _pindex.exact_double(after[0])
             if (start_from is None or sf is not None) and (after is None or af is not None):
@@ -314,7 +315,9 @@ class _Collection:
             self._poison(key)
         elif len(pi.keys) >= _pindex.MAX_COLUMNS:
             raise ValueError(f"a collection takes at most {_pindex.MAX_COLUMNS} payload indexes")
-        k = _pindex._Key(schema)
+        k = _pindex._Key(schema, key)                     # (ValueError for a malformed array key "A[].f")
+        if k.array and not hasattr(self.index, "payload_same_offsets"):
+            raise ValueError("this collection's engine index has no nested blocks")
         if k.is_list and not hasattr(self.index, "payload_append_lists"):
             raise ValueError("this collection's engine index has no list columns")
         if k.is_text and not hasattr(self.index, "payload_append_text"):
@@ -326,10 +329,23 @@ class _Collection:
         col = self.index.payload_create(k.kind)
         try:
             self._append_cells(k, col, cells)
+            if k.array and not self._aligned(key, col):
+                logging.warning("payload index: %r is not aligned with its siblings, the key is dropped", key)
+                self.index.payload_drop(col)
+                return False
         except Exception:
             self.index.payload_drop(col)
             raise
         k.col = col
+        return True
+
+    def _aligned(self, key: str, col: int) -> bool:
+        """Whether the new column of an array key has the heads and offsets of a live key of the same parent
+        (hx_payload_same_offsets; one check when a second key of a parent goes live: a nested block needs it)."""
+        parent = self.pindex.keys[key].array[0]
+        for name, other in self.pindex.keys.items():
+            if name != key and other.col is not None and other.array and other.array[0] == parent:
+                return self.index.payload_same_offsets(other.col, col)
         return True
 
     def _append_cells(self, k, col: int, cells) -> None:
@@ -354,9 +370,10 @@ class _Collection:
         pi = getattr(self, "pindex", None)
         if pi is None:
             return
+        heads_of: Dict[str, np.ndarray] = {}              # one heads array per array parent and batch
         for key in pi.live_keys():
             try:
-                cells = pi.encode(key, payloads)
+                cells = pi.encode(key, payloads, heads_of)
                 if cells is not None:
                     self._append_cells(pi.keys[key], pi.keys[key].col, cells)
                     continue
@@ -371,10 +388,11 @@ class _Collection:
         if pi is None:
             return
         rows = np.asarray(rows, np.int64)
+        heads_of: Dict[str, np.ndarray] = {}
         for key in pi.live_keys():
             k = pi.keys[key]
             try:
-                cells = pi.encode(key, payloads)
+                cells = pi.encode(key, payloads, heads_of)
                 if cells is not None:
                     if k.is_list:
                         self.index.payload_replace_lists(k.col, rows, cells[0], cells[1])
@@ -650,7 +668,7 @@ class QdrantHandler:
         then evaluated by one kernel over the collection's columns instead of a Python loop over its payloads
         (payload_index.py); the results are the same.  Returns True when the field is live, False when a stored value is
         not of the schema (a list, a dict, another type, NaN, an int beyond 2^53): such a field stays on the Python path.
-        List-valued fields (the reference's `languages`, `entities`, `relationships`) take the opt-in schemas
+        List-valued fields (the reference's `languages`; lists of scalars) take the opt-in schemas
         "keyword_list" | "number_list" ("integer_list" / "float_list") | "bool_list": a value is then None, a list of
         values of the element schema or one such value (the one-element list); a tuple, a nested list or dict, a None
         element or an element of another type makes the field stay on the Python path.
@@ -660,8 +678,13 @@ class QdrantHandler:
         Datetime fields (the chat messages' `timestamp`) take the opt-in schema "datetime": a value is then None, a
         `datetime.datetime` or an RFC 3339 string, stored as its microseconds since the epoch; the field serves ordered
         scrolls, filters on it stay on the Python path.
-        Raises ValueError for a bad schema, a sharded collection, or an engine index without payload (list, text) columns;
-        KeyError for an unknown collection."""
+        Arrays of objects (the reference's `entities` and `relationships`) take array keys: `field_name` = "A[].f" with
+        exactly one "[]" and the schema "keyword" | "number" | "bool" indexes the field `f` of the objects of the array
+        `A`; {"key": "A[].f", ...} (some object matches) and {"nested": {"key": "A", "filter": ...}} (ONE object meets the
+        whole filter) are then evaluated on the device.  A value of another type, or -- under
+        "number" -- an object without the field, makes the key stay on the Python path; the other keys of `A` go on.
+        Raises ValueError for a bad schema, a malformed array key, a sharded collection, or an engine index without payload
+        (list, text) columns; KeyError for an unknown collection."""
         try:
             if not self._payload_indexes:
                 raise ValueError("create_payload_index is not supported on a sharded collection")
@@ -992,7 +1015,7 @@ class QdrantHandler:
             reason = "group by an unindexed key"
         elif k.col is None:
             reason = "group by a poisoned key"
-        elif k.schema not in ("keyword", "bool"):
+        elif k.schema not in ("keyword", "bool") or k.array:
             reason = "group by a key of another schema"
         elif root_filter:
             reason = "group with a root filter"

@@ -33,7 +33,24 @@ The datetime schema ("datetime") exists for ordered scroll
 `datetime.datetime` or a `str` that parses as RFC 3339 (scrolling.datetime_micros), stored as an F64 cell holding the
 integer microseconds since the epoch -- exact while |us| <= 2^53; anything else (a number, an unparsable string, a value
 outside that range) poisons the key.  The compiler DECLINES every condition on such a key: `filters.matches` compares the
-payload's own value, not its microseconds, and the masks stay what it gives."""
+payload's own value, not its microseconds, and the masks stay what it gives.
+
+Array keys ("A[].f" with schema "keyword" | "number" | "bool") index one field of the objects of an
+array of objects: exactly one "[]", `A` and `f` dotted paths without one.  The key is stored as an ordinary list column
+that holds ONE element per object of `A`, so every key "A[].*" of one parent has the same heads and offsets (they are
+"element-aligned").  A row's head: `A` missing or not a list -> MISSING, None -> NULL, a list -> len(A).  Element i is the
+cell of A[i][f] when that value is of the schema; for a keyword or bool key it is the reserved code ABSENT when A[i] is
+not a dict, lacks `f` or holds None there (no string maps to it: such a key's dictionary holds one code fewer); a value
+of another type, a list or a dict poisons the key.  For a NUMBER key an absent or None field poisons the key too: the
+engine refuses NaN elements, so there is no spare double.  A payload whose dict holds the literal key "A[]" (which
+filters._get prefers) poisons the key.
+A plain condition on "A[].f" compiles to the list ops (ABSENT lies in no set); is_empty / is_null on it are declined
+(aligned storage cannot tell "no object has f" from []), and so is a None among the constants of its match.
+{"nested": {"key": A, "filter": F}} compiles to ONE nested block (hx.h: HX_PAY_NESTED) when every leaf of F is a match
+value / any / except or a range on a key f whose "A[].f" is live, joined by must / should / must_not and sub-filters; at
+element level `except` is "not ABSENT and not in the set".  Everything else declines: is_empty, is_null, match text, a
+nested inside, an unindexed or poisoned f, more than 64 element ops or 8 distinct columns, and a parent in which some
+stored array held an element that is not a dict (the oracle skips such an element, a position cannot)."""
 from __future__ import annotations
 
 import math
@@ -52,6 +69,9 @@ F64_MISSING, F64_NULL = 0x7FF80000FFFFFFFF, 0x7FF80000FFFFFFFE
 MAX_STACK, MAX_OPS, MAX_COLUMNS = 32, 4096, 64
 (TRUE, FALSE, IS_MISSING, IS_NULL, PRESENT, EQ, IN, LT, LE, GT, GE, ROW_IN, AND, OR, NOT, ANY_EQ, ANY_IN, ANY_RANGE,
  IS_EMPTY_LIST, TEXT_ALL) = range(20)
+NESTED, EL_EQ, EL_IN, EL_RANGE = 20, 21, 22, 23
+NESTED_MAX_OPS, NESTED_MAX_COLS = 64, 8
+ABSENT = 0xFFFFFFFD                     # host-side: the element of an array key whose object lacks the field
 TEXT_MAX_WORDS, TEXT_MAX_WORD_BYTES = 32, 64
 TEXT_MAX_COLUMN_WORDS = 0x7FFFFFFF      # a text column holds fewer than 2^31 32-bit words
 
@@ -87,13 +107,27 @@ def exact_double(v) -> Optional[float]:
     return f if f == v else None
 
 
+def split_array_key(key) -> Optional[Tuple[str, str]]:
+    """(A, f) of an array key "A[].f", None for a key without "[]"; ValueError for any other use of "[]"."""
+    if not isinstance(key, str) or "[]" not in key:
+        return None
+    a, sep, f = key.partition("[].")
+    if not sep or "[]" in a or "[]" in f or not all(a.split(".")) or not all(f.split(".")):
+        raise ValueError(f'an array key is "A[].f" with exactly one "[]", A and f dotted paths, got {key!r}')
+    return a, f
+
+
 class _Decline(Exception):
     pass
 
 
 class _Key:
-    def __init__(self, schema: str):
+    def __init__(self, schema: str, key: Optional[str] = None):
         self.schema = schema
+        self.array = split_array_key(key)  # (A, f) of an array key "A[].f": stored as a list column, one element per object
+        if self.array and schema not in ("keyword", "number", "bool"):
+            raise ValueError(f"an array key takes the schema keyword, number (integer, float) or bool, got {schema!r}")
+        self.nondict = False               # an array key: some stored array held an element that is not a dict
         self.col: Optional[int] = None     # the engine column; None = not live (poisoned, or its column was lost)
         self.codes: Dict[str, int] = {}    # keyword -> code
         self._names: List[str] = []        # code -> keyword, built when a grouped search asks (value_of)
@@ -132,11 +166,11 @@ class _Key:
 
     @property
     def is_list(self) -> bool:
-        return self.schema.endswith("_list")
+        return self.schema.endswith("_list") or self.array is not None
 
     @property
     def elem(self) -> str:             # the schema of a cell, or of a list's elements
-        return self.schema[:-5] if self.is_list else self.schema
+        return self.schema[:-5] if self.schema.endswith("_list") else self.schema
 
     @property
     def is_text(self) -> bool:
@@ -174,13 +208,16 @@ class PayloadIndex:
         return [k for k, v in self.keys.items() if v.col is not None]
 
     # -- encoder ---------------------------------------------------------------------------------------------------
-    def encode(self, key: str, payloads) -> Optional[np.ndarray]:
+    def encode(self, key: str, payloads, heads_of: Optional[Dict[str, np.ndarray]] = None) -> Optional[np.ndarray]:
         """The cells of `payloads` for `key` (np.uint32 codes or np.uint64 bit patterns of doubles), or None when a
         value poisons the key.  Keywords met for the first time get the next code; a poisoned call leaves the
-        dictionary with codes no row uses, which is harmless."""
+        dictionary with codes no row uses, which is harmless.  heads_of: parent -> heads, shared by the array keys of
+        one parent over one batch."""
         k = self.keys[key]
         get, missing = _filters._get, _filters._MISSING
         n = len(payloads)
+        if k.array:
+            return self._encode_array(k, payloads, heads_of)
         if k.is_list:
             return self._encode_lists(k, key, payloads)
         if k.is_text:
@@ -298,6 +335,67 @@ class PayloadIndex:
         return heads, np.array(vals, np.float64 if elem == "number" else np.uint32)
 
     @staticmethod
+    def array_heads(parent: str, payloads) -> Optional[np.ndarray]:
+        """The heads of an array parent `A` over a batch: MISSING (missing or not a list), NULL (None) or len(A); None
+        when a payload holds the literal key "A[]", which filters._get reads instead."""
+        get, missing = _filters._get, _filters._MISSING
+        up, _, last = parent.rpartition(".")
+        heads = np.empty(len(payloads), np.uint32)
+        for r, p in enumerate(payloads):
+            holder = get(p, up) if up else p
+            if isinstance(holder, dict) and (last + "[]") in holder:
+                return None
+            v = get(p, parent)
+            heads[r] = U32_NULL if v is None else len(v) if type(v) is list else U32_MISSING
+        return heads
+
+    def _encode_array(self, k: _Key, payloads, heads_of):
+        """(heads, values) of an array key "A[].f" for hx_payload_append_lists: ONE element per object of A (the module
+        docstring states the rules), or None when a value poisons the key."""
+        get, missing = _filters._get, _filters._MISSING
+        parent, field = k.array
+        heads = heads_of.get(parent) if heads_of is not None else None
+        if heads is None:
+            heads = self.array_heads(parent, payloads)
+            if heads is None:
+                return None
+            if heads_of is not None:
+                heads_of[parent] = heads
+        elem, codes = k.elem, k.codes
+        vals: List[Any] = []
+        for r, p in enumerate(payloads):
+            if heads[r] >= U32_NULL:
+                continue
+            for el in get(p, parent):
+                x = get(el, field) if isinstance(el, dict) else missing
+                if not isinstance(el, dict):
+                    k.nondict = True
+                if x is missing or x is None:
+                    if elem == "number":
+                        return None
+                    vals.append(ABSENT)
+                elif elem == "keyword":
+                    if type(x) is not str:
+                        return None
+                    c = codes.get(x)
+                    if c is None:
+                        if len(codes) >= ABSENT:          # codes 0 .. ABSENT - 1
+                            return None
+                        c = codes[x] = len(codes)
+                    vals.append(c)
+                elif elem == "bool":
+                    if not isinstance(x, bool):
+                        return None
+                    vals.append(1 if x else 0)
+                else:
+                    if isinstance(x, bool) or not isinstance(x, (int, float)) or x != x:
+                        return None
+                    if isinstance(x, int) and abs(x) > 2 ** 53:
+                        return None
+                    vals.append(float(x))
+        return heads, np.array(vals, np.float64 if elem == "number" else np.uint32)
+
+    @staticmethod
     def _encode_text(key: str, payloads):
         """(heads, data) of a text key for hx_payload_append_text -- heads: np.uint32, MISSING / NULL / the row's byte
         length; data: the rows' bytes one after another (bytes) -- or None when a value poisons the key: anything that is
@@ -348,8 +446,12 @@ class PayloadIndex:
             self._filter(flt, ops, sets, id_rows)
             if len(ops) > MAX_OPS:
                 raise _Decline("program too long")
-            depth = 0
-            for op, _, _ in ops:
+            depth, skip = 0, 0
+            for op, _, imm in ops:
+                if skip:                              # (the element ops of a nested block: counted by _nested)
+                    skip -= 1
+                    continue
+                skip = imm if op == NESTED else 0
                 depth += -1 if op in (AND, OR) else 0 if op == NOT else 1
                 if depth > MAX_STACK:
                     raise _Decline("stack deeper than 32")
@@ -359,7 +461,8 @@ class PayloadIndex:
             return None
         return ops, sets
 
-    def _filter(self, flt, ops, sets, id_rows):
+    def _filter(self, flt, ops, sets, id_rows, cond=None):
+        cond = cond or self._condition
         if not flt:
             ops.append((TRUE, 0, 0))
             return
@@ -369,19 +472,19 @@ class PayloadIndex:
             raise _Decline("unknown clause in a nested filter")      # (matches raises only where evaluation reaches it)
         terms = 0
         for c in _filters._as_list(flt.get("must")):
-            self._condition(c, ops, sets, id_rows)
+            cond(c, ops, sets, id_rows)
             if terms:
                 ops.append((AND, 0, 0))
             terms += 1
         for c in _filters._as_list(flt.get("must_not")):
-            self._condition(c, ops, sets, id_rows)
+            cond(c, ops, sets, id_rows)
             ops.append((NOT, 0, 0))
             if terms:
                 ops.append((AND, 0, 0))
             terms += 1
         should = _filters._as_list(flt.get("should"))
         for i, c in enumerate(should):
-            self._condition(c, ops, sets, id_rows)
+            cond(c, ops, sets, id_rows)
             if i:
                 ops.append((OR, 0, 0))
         if should:
@@ -408,6 +511,8 @@ class PayloadIndex:
             raise _Decline("condition is not a dict")
         if any(k in c for k in _CLAUSES):
             return self._filter(c, ops, sets, id_rows)
+        if "nested" in c:
+            return self._nested(c["nested"], ops, sets)
         if "has_id" in c:
             listed = c["has_id"]
             if not isinstance(listed, (list, tuple)) or id_rows is None:
@@ -431,6 +536,8 @@ class PayloadIndex:
             if not isinstance(c[what], dict) or "key" not in c[what]:
                 raise _Decline(what + " form")
             k = self._key(c[what]["key"])
+            if k.array:
+                raise _Decline(what + " on an array key")
             if what == "is_empty":
                 ops.extend([(IS_MISSING, k.col, 0), (IS_NULL, k.col, 0), (OR, 0, 0)])
                 if k.is_list:
@@ -487,6 +594,11 @@ class PayloadIndex:
             raise _Decline("match is not a dict")
         if k.is_text:
             return self._match_text(k, m, ops, sets)
+        if k.array:                                   # (a None field is collected by the projection, and stored as ABSENT)
+            form = next((f for f in ("value", "any", "except") if f in m), None)
+            if form and (m[form] is None or (form != "value" and isinstance(m[form], (list, tuple))
+                                             and any(e is None for e in m[form]))):
+                raise _Decline("None in a match on an array key")
         if "value" in m:
             v = m["value"]
             if v is not None and not isinstance(v, (str, bool, int, float)):
@@ -559,10 +671,90 @@ class PayloadIndex:
         if not terms:
             ops.append((PRESENT, k.col, 0))
 
-    def _range_any(self, k: _Key, r, ops, sets):
+    # -- nested blocks -------------------------------------------------------------------------
+    def _nested(self, nd, ops, sets):
+        """{"key": A, "filter": F} as one nested block: NESTED anchor m, then the m element ops of F."""
+        if not isinstance(nd, dict) or not isinstance(nd.get("key"), str):
+            raise _Decline("nested form")
+        parent = nd["key"][:-2] if nd["key"].endswith("[]") else nd["key"]
+        if "[]" in parent:
+            raise _Decline("nested key with an inner []")
+        siblings = [k for name, k in self.keys.items() if k.array and k.array[0] == parent and k.col is not None]
+        if not siblings:
+            raise _Decline("unindexed key")
+        if any(k.nondict for k in siblings):
+            raise _Decline("nested over an array that holds a non-object element")
+        eops: List[Tuple[int, int, int]] = []
+
+        def cond(c, o, s, id_rows):
+            if not isinstance(c, dict):
+                raise _Decline("condition is not a dict")
+            if any(name in c for name in _CLAUSES):
+                return self._filter(c, o, s, None, cond)
+            if "nested" in c:
+                raise _Decline("nested inside a nested filter")
+            if "has_id" in c:
+                raise _Decline("has_id inside a nested filter")      # (filters.matches raises)
+            if "is_empty" in c or "is_null" in c:
+                raise _Decline(("is_empty" if "is_empty" in c else "is_null") + " inside a nested filter")
+            if "key" in c and isinstance(c["key"], str) and "[]" not in c["key"]:
+                k = self._key(parent + "[]." + c["key"])
+                if "match" in c:
+                    return self._el_match(k, c["match"], o, s)
+                if "range" in c:
+                    return self._el_range(k, c["range"], o, s)
+            raise _Decline("unsupported condition")
+
+        self._filter(nd.get("filter"), eops, sets, None, cond)
+        if len(eops) > NESTED_MAX_OPS:
+            raise _Decline("nested filter with more than 64 element ops")
+        cols = {col for op, col, _ in eops if op in (EL_EQ, EL_IN, EL_RANGE)}
+        if len(cols) > NESTED_MAX_COLS:
+            raise _Decline("nested filter over more than 8 columns")
+        depth = 0
+        for op, _, _ in eops:
+            depth += -1 if op in (AND, OR) else 0 if op == NOT else 1
+            if depth > MAX_STACK:
+                raise _Decline("stack deeper than 32")
+        anchor = next((k.col for k in siblings if k.col in cols), siblings[0].col)
+        ops.append((NESTED, anchor, len(eops)))
+        ops.extend(eops)
+
+    def _el_match(self, k: _Key, m, ops, sets):
+        """filters._match on ONE element: a missing or None field (ABSENT) matches nothing, `except` included."""
+        if not isinstance(m, dict):
+            raise _Decline("match is not a dict")
+        if "value" in m:
+            v = m["value"]
+            if v is not None and not isinstance(v, (str, bool, int, float)):
+                raise _Decline("match value of an unsupported type")
+            cell = self._cell_of(k, v)
+            ops.append((FALSE, 0, 0) if cell is None else (EL_EQ, k.col, cell))
+        elif "any" in m:
+            sets.append(self._set_of(k, m["any"]))
+            ops.append((EL_IN, k.col, len(sets) - 1))
+        elif "except" in m:
+            sets.append(self._set_of(k, m["except"]))
+            ops.extend([(EL_IN, k.col, len(sets) - 1), (NOT, 0, 0)])
+            if k.elem != "number":                    # (a number key holds no ABSENT)
+                ops.extend([(EL_EQ, k.col, ABSENT), (NOT, 0, 0), (AND, 0, 0)])
+        elif "text" in m:
+            raise _Decline("match text inside a nested filter")
+        else:
+            raise _Decline("unsupported match")
+
+    def _el_range(self, k: _Key, r, ops, sets):
+        if not isinstance(r, dict):
+            raise _Decline("range is not a dict")
+        if k.elem != "number":                        # (filters._range: only numbers that are not bools are in a range)
+            ops.append((FALSE, 0, 0))
+            return
+        self._range_any(k, r, ops, sets, EL_RANGE)
+
+    def _range_any(self, k: _Key, r, ops, sets, op=ANY_RANGE):
         """filters._range over a list: ONE element meets every bound, so the bounds become one closed interval [lo, hi]
-        and one ANY_RANGE op.  A strict bound moves to the neighbouring double (every stored number is a double, so
-        x > b is x >= nextafter(b, +inf) exactly; +-0 and the subnormals included)."""
+        and one ANY_RANGE op (EL_RANGE inside a nested block).  A strict bound moves to the neighbouring double (every
+        stored number is a double, so x > b is x >= nextafter(b, +inf) exactly; +-0 and the subnormals included)."""
         lo, hi = -math.inf, math.inf
         for name in ("gt", "gte", "lt", "lte"):
             b = r.get(name)
@@ -594,4 +786,4 @@ class PayloadIndex:
             ops.append((FALSE, 0, 0))
             return
         sets.append(np.array([lo, hi], np.float64))
-        ops.append((ANY_RANGE, k.col, len(sets) - 1))
+        ops.append((op, k.col, len(sets) - 1))
