@@ -885,6 +885,98 @@ int hx_bm25_embed_batch(const char* const* texts, const int64_t* lens, int64_t n
                         double avg_len, int32_t threads, int64_t* indptr, int32_t* idx, double* val,
                         int64_t cap, int32_t* flags);
 
+/* ---- score-boosting search -----------------------------------------
+ * Qdrant's FormulaQuery ("score boosting") as the rescoring query over the hybrid prefetch (additive: the reference calls
+ * query_points without it; parity unpinned, the semantics below are this project's statement of it).  Additive to the ABI:
+ * HX_ABI_VERSION stays 3.
+ *
+ * A formula arrives as a POSTFIX PROGRAM over a stack of doubles, evaluated once per pool position.  Every operation is
+ * ONE IEEE double operation, round to nearest, never fused.  `imm` = the bits of a double unless said otherwise:
+ *   HX_F_CONST        push imm;
+ *   HX_F_SCORE        push (double) of the fp32 score of the pool key at this position;
+ *   HX_F_VAR          arg = an HX_PAY_F64 column: push the row's cell, imm (the default) when the cell is
+ *                     HX_PAY_F64_MISSING or HX_PAY_F64_NULL;
+ *   HX_F_COND         arg = a condition plane in [0, n_planes): push 1.0 when the row's bit is set in it, else 0.0;
+ *   HX_F_ADD / _MUL   pop b, pop a, push a + b / a * b;
+ *   HX_F_NEG / _ABS   the sign bit of the top entry flipped / cleared;
+ *   HX_F_DIV          pop b, pop a; b == 0.0 (either zero): push imm (by_zero_default; a NaN when there is none);
+ *                     otherwise push a / b;
+ *   HX_F_SQRT         sqrt(a), a NaN for a negative a (-0.0 gives -0.0);
+ *   HX_F_EXP          hx_exp(a), below;
+ *   HX_F_LIN_DECAY    pop d, t = 1.0 - imm * abs(d), push t < 0.0 ? 0.0 : t (a NaN stays a NaN);
+ *                     imm = (1 - midpoint) / scale, computed by the caller;
+ *   HX_F_EXP_DECAY    pop d, push hx_exp(imm * abs(d)); imm = ln(midpoint) / scale;
+ *   HX_F_GAUSS_DECAY  pop d, push hx_exp(imm * (d * d)); imm = ln(midpoint) / (scale * scale).
+ * A decay's d = x - target is compiled as x, target, NEG, ADD.
+ * hx_exp(x), the project's own exponential: a NaN gives that NaN; x > 709.0 gives +inf; x < -708.0 gives 0.0 (so no
+ * subnormal ever comes out of the ldexp); otherwise k = rint(x * 1.4426950408889634), r = (x - k *
+ * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10, p = Horner's rule from degree 13 down over the
+ * coefficients (double)(1.0 / i!), every step p = p * r + c_i as two roundings, and the result is ldexp(p, (int)k).
+ *
+ * The VALUE of a position is the stack's last entry rounded to fp32 (round to nearest even; out of range = +-inf), then
+ * + 0.0f (-0 and +0 are one value).  Eligible positions are those of hx_mmr: not a 0 slot, before counts_dev[b], a key
+ * whose row is in this index, a row whose bit is set in eligible_dev.  An eligible position whose value is not finite is
+ * DROPPED and counted in out_dropped_dev.  With a score_threshold that is not a NaN, positions whose value is < the
+ * threshold are cut too (not counted).  The survivors are ordered by value descending, then pool position ascending (a
+ * constant formula returns the pool in its own order); the first `limit` come out.
+ *
+ * hx_formula is the stage.  ops_host [n_ops] is read before the call returns.  planes_dev = a HOST array of n_planes
+ * device pointers to packed row masks of plane_rows rows each (NULL when n_planes = 0).  keys_dev [B x stride] +
+ * counts_dev [B] is a pool as the hybrid entries hand it out (global ids); counts_dev NULL = all `stride` slots;
+ * eligible_dev NULL = every row.
+ *   out_keys_dev [B x limit]   slot t = make_key(value, the id of the input key of hit t); 0 past the hits;
+ *   out_pos_dev [B x limit]    the pool position of hit t; -1 past the hits;
+ *   out_counts_dev [B]         hits;    out_dropped_dev [B]   positions dropped.
+ * Everything is enqueued on `stream`; nothing is read back.  Refused before any device work, every output untouched: a
+ * NULL argument (counts_dev and eligible_dev aside; planes_dev when n_planes = 0), B < 1, stride or limit outside [1,
+ * 2048], n_ops outside [1, HX_FORMULA_MAX_OPS], n_planes outside [0, HX_FORMULA_MAX_PLANES], a program that underflows
+ * its stack, holds more than HX_FORMULA_MAX_STACK entries at some point or does not end with exactly one entry, an
+ * unknown op, an unknown column, a column that is not HX_PAY_F64 or not filled to hx_count, a plane index outside [0,
+ * n_planes), an HX_F_VAR default that is a NaN, plane_rows != hx_count when n_planes > 0, eligible_rows != hx_count when
+ * eligible_dev is given. */
+#define HX_F_CONST 0
+#define HX_F_SCORE 1
+#define HX_F_VAR 2
+#define HX_F_COND 3
+#define HX_F_ADD 4
+#define HX_F_MUL 5
+#define HX_F_NEG 6
+#define HX_F_ABS 7
+#define HX_F_DIV 8
+#define HX_F_SQRT 9
+#define HX_F_EXP 10
+#define HX_F_LIN_DECAY 11
+#define HX_F_EXP_DECAY 12
+#define HX_F_GAUSS_DECAY 13
+#define HX_FORMULA_MAX_OPS 256
+#define HX_FORMULA_MAX_STACK 16
+#define HX_FORMULA_MAX_PLANES 8
+typedef struct hx_formula_op {
+  int32_t op;
+  int32_t arg;
+  uint64_t imm;
+} hx_formula_op;
+int hx_formula(hx_index* h, const hx_formula_op* ops_host, int32_t n_ops, const uint32_t* const* planes_dev,
+               int32_t n_planes, int64_t plane_rows, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev,
+               int32_t B, int32_t limit, float score_threshold, const uint32_t* eligible_dev, int64_t eligible_rows,
+               uint64_t* out_keys_dev, int32_t* out_pos_dev, int32_t* out_counts_dev, int32_t* out_dropped_dev,
+               void* stream);
+/* The whole boosted query, host in, host out.  The plain query runs on a copy of *p with final_limit = the POOL size, as
+ * in hx_hybrid_query_mmr_host (candidates_limit, mask_host and mask_root_only mean what they mean there), but the pool
+ * keeps the scores its mode hands out -- HX_MODE_TREE: the dense cosines of the root's re-scored union; HX_MODE_H1: the
+ * fused RRF scores; there is no extra re-score.  planes_host = n_planes host row masks of hx_count rows each (packed),
+ * uploaded as the condition planes.  Then hx_formula over the pool on the device, the ids' map, the unpacking and the
+ * copy out.  Outputs [B x limit] in rank order: scores_host = the values, ids_host, base_scores_host = the score the
+ * pool carried at the hit's position; (-inf, -1, -inf) past the hits; counts_host [B], dropped_host [B].  Refusals:
+ * those of the plain call, of hx_hybrid_query_mmr_host on its pool and mask, and of hx_formula. */
+int hx_hybrid_query_formula_host(hx_index* h, const float* q_dense_host, const int64_t* q_indptr_host,
+                                 const int32_t* q_idx_host, const float* q_val_host, int32_t B, const hx_params* p,
+                                 const uint32_t* mask_host, int64_t mask_rows, int32_t mask_root_only,
+                                 int32_t candidates_limit, const hx_formula_op* ops_host, int32_t n_ops,
+                                 const uint32_t* const* planes_host, int32_t n_planes, int32_t limit,
+                                 float score_threshold, float* scores_host, int64_t* ids_host, float* base_scores_host,
+                                 int32_t* counts_host, int32_t* dropped_host);
+
 /* ---- persistence ------------------------------------------------------------
  * The reference asks Qdrant for on-disk vectors (qdrant_handler.py:47-55, 62: on_disk=True,
  * memmap_threshold).  hx_save writes the collection to one file (stored vectors as they stand plus

@@ -53,6 +53,10 @@ class HxPayOp(C.Structure):
     _fields_ = [("op", C.c_int32), ("col", C.c_int32), ("imm", C.c_uint64)]
 
 
+class HxFormulaOp(C.Structure):
+    _fields_ = [("op", C.c_int32), ("arg", C.c_int32), ("imm", C.c_uint64)]
+
+
 class HxPaySet(C.Structure):
     _fields_ = [("vals", C.c_void_p), ("n", C.c_int64)]
 
@@ -125,6 +129,10 @@ _SIGS = {
     "hx_maxsim": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
     "hx_hybrid_query_rerank_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32, C.c_int32,
                                     C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P],
+    "hx_formula": [_P, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P,
+                   C.c_int64, _P, _P, _P, _P, _P],
+    "hx_hybrid_query_formula_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32,
+                                     C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P],
     "hx_recommend": [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
     "hx_recommend_host": [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
     "hx_payload_facet": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, _P, _P],

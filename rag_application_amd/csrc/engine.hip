@@ -2987,15 +2987,59 @@ struct RerankSpec {
   int32_t* counts_host;
 };
 
+// ---- score-boosting search ------------------------------------------------------------------------
+// the checks of hx_formula on its sizes, before any device work (formula_lower holds those on the program)
+static void formula_check(int32_t stride, int32_t B, int32_t limit) {
+  HX_CHECK(B >= 1, "formula: B < 1");
+  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "formula: stride out of range [1, 2048]");
+  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "formula: limit out of range [1, 2048]");
+}
+// f: lowered by formula_lower; planes: n_planes device planes; out_base may be NULL
+static void formula_enqueue(hx_index* h, FormulaArgs& f, const uint32_t* const* planes, int n_planes, const uint64_t* keys,
+                            const uint64_t* ikeys, int stride, const int* counts, int B, int limit, float threshold,
+                            const uint32_t* eligible, uint64_t* out_keys, int* out_pos, float* out_base, int* out_counts,
+                            int* out_dropped, hipStream_t st) {
+  for (int i = 0; i < n_planes; ++i) f.planes[i] = planes[i];
+  f.keys = keys;
+  f.ikeys = ikeys;
+  f.counts = counts;
+  f.eligible = eligible;
+  f.out_keys = out_keys;
+  f.out_pos = out_pos;
+  f.out_base = out_base;
+  f.out_counts = out_counts;
+  f.out_dropped = out_dropped;
+  f.n_rows = h->n;
+  f.id_base = (uint32_t)h->id_base;
+  f.stride = stride;
+  f.limit = limit;
+  f.threshold = threshold;
+  f.has_threshold = threshold == threshold;
+  launch_formula(f, B, st);
+}
+// what hx_hybrid_query_formula_host adds to hx_hybrid_query_host
+struct FormulaSpec {
+  int32_t root_only, candidates, limit;
+  const hx_formula_op* ops;
+  int32_t n_ops;
+  const uint32_t* const* planes_host;
+  int32_t n_planes;
+  float threshold;
+  float* base_host;
+  int32_t* counts_host;
+  int32_t* dropped_host;
+};
+
 // hx_hybrid_query_host, its masked form (mask_host NULL = every row), its grouped form (grp NULL = the plain lists;
 // otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots), its
-// MMR form (mmr: the pool likewise, scores / ids receive the picks) and its rerank form (rr: the pool likewise, scores /
-// ids receive the pool's rows in MaxSim order)
+// MMR form (mmr: the pool likewise, scores / ids receive the picks), its rerank form (rr: the pool likewise, scores /
+// ids receive the pool's rows in MaxSim order) and its boosted form (fm: the pool likewise, scores / ids receive the
+// pool's rows in the order of the formula's values)
 static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
                               int32_t B, const hx_params* p_in, const uint32_t* mask_host, float* scores, int64_t* ids,
                               int32_t* counts, const GroupSpec* grp = nullptr, const MmrSpec* mmr = nullptr,
-                              const RerankSpec* rr = nullptr) {
-  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr || rr) && B > 0, "bad argument");
+                              const RerankSpec* rr = nullptr, const FormulaSpec* fm = nullptr) {
+  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr || rr || fm) && B > 0, "bad argument");
   HX_CHECK(p_in != nullptr, "params is NULL");
   hx_params pool_params = *p_in;          // (the caller's params are never written)
   const hx_params* p = p_in;
@@ -3050,6 +3094,28 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
       mask_host = nullptr;
     }
   }
+  FormulaArgs fargs{};
+  if (fm) {
+    HX_CHECK(fm->base_host && fm->counts_host && fm->dropped_host, "bad argument");
+    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
+    HX_CHECK(fm->root_only == 0 || fm->root_only == 1, "formula: mask_root_only must be 0 or 1");
+    HX_CHECK(!(mask_host && fm->root_only && p_in->mode == HX_MODE_H1),
+             "formula: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
+    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
+    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
+    HX_CHECK(fm->candidates >= 0 && fm->candidates <= pool_max && pool_max >= 1,
+             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
+    pool_params.final_limit = fm->candidates ? fm->candidates : (int32_t)pool_max;
+    p = &pool_params;
+    formula_check(pool_params.final_limit, B, fm->limit);
+    formula_lower(h, fm->ops, fm->n_ops, fm->n_planes, fargs);
+    HX_CHECK(fm->n_planes == 0 || fm->planes_host, "NULL argument");
+    for (int i = 0; i < fm->n_planes; ++i) HX_CHECK(fm->planes_host[i] != nullptr, "NULL argument");
+    if (fm->root_only) {
+      root_mask = mask_host;
+      mask_host = nullptr;
+    }
+  }
   check_params(p);
   h->set_device();
   hipStream_t st = nullptr;
@@ -3090,7 +3156,8 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
   uint64_t* ok = (uint64_t*)h->ws.get(WS_H_OUT, (size_t)B * L * 8);
   int* oc = (int*)h->ws.get(WS_H_OCNT, (size_t)B * 4);
   const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : mmr ? std::max(L, mmr->limit)
-                                                                     : rr ? std::max(L, rr->limit) : L;   // slots of a result
+                                                                     : rr ? std::max(L, rr->limit)
+                                                                     : fm ? std::max(L, fm->limit) : L;   // slots of a result
   float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * OL * 4);
   int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * OL * 8);
   HX_HIP(hipMemcpyAsync(dq, qd, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
@@ -3182,6 +3249,39 @@ static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, 
     HX_HIP(hipStreamSynchronize(st));
     return;
   }
+  if (fm) {                              // the stage reads internal ids: before remap_out
+    const int64_t nw = (h->n + 31) / 32;
+    const uint32_t* elig = nullptr;
+    if (root_mask) {
+      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+      elig = dm;
+    }
+    const uint32_t* planes[HX_FORMULA_MAX_PLANES] = {};
+    if (fm->n_planes) {
+      uint32_t* dp = (uint32_t*)h->ws.get(WS_FORMULA_PLANES, (size_t)fm->n_planes * std::max<int64_t>(nw, 1) * 4);
+      for (int i = 0; i < fm->n_planes; ++i) {
+        if (nw) HX_HIP(hipMemcpyAsync(dp + (int64_t)i * nw, fm->planes_host[i], (size_t)nw * 4, hipMemcpyHostToDevice, st));
+        planes[i] = dp + (int64_t)i * nw;
+      }
+    }
+    const int FL = fm->limit;
+    uint64_t* fk = (uint64_t*)h->ws.get(WS_FORMULA_KEYS, (size_t)B * FL * 8);
+    int* fp = (int*)h->ws.get(WS_FORMULA_POS, (size_t)B * FL * 4);
+    float* fb = (float*)h->ws.get(WS_FORMULA_BASE, (size_t)B * FL * 4);
+    int* fn = (int*)h->ws.get(WS_FORMULA_CNT, (size_t)B * 4);
+    int* fd = (int*)h->ws.get(WS_FORMULA_DROP, (size_t)B * 4);
+    formula_enqueue(h, fargs, planes, fm->n_planes, ok, ok, L, oc, B, FL, fm->threshold, elig, fk, fp, fb, fn, fd, st);
+    remap_out(h, fk, (int64_t)B * FL, st);
+    launch_unpack(fk, (int64_t)B * FL, osc, oid, st);
+    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * FL * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * FL * 8, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(fm->base_host, fb, (size_t)B * FL * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(fm->counts_host, fn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipMemcpyAsync(fm->dropped_host, fd, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
   remap_out(h, ok, (int64_t)B * L, st);
   launch_unpack(ok, (int64_t)B * L, osc, oid, st);
   HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * L * 4, hipMemcpyDeviceToHost, st));
@@ -3262,6 +3362,43 @@ int hx_hybrid_query_mmr_host(hx_index* h, const float* qd, const int64_t* qip, c
   HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
   const MmrSpec m{mask_root_only, candidates_limit, limit, diversity, values, counts};
   hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, &m);
+  HX_CATCH
+}
+
+int hx_formula(hx_index* h, const hx_formula_op* ops_host, int32_t n_ops, const uint32_t* const* planes_dev,
+               int32_t n_planes, int64_t plane_rows, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev,
+               int32_t B, int32_t limit, float score_threshold, const uint32_t* eligible_dev, int64_t eligible_rows,
+               uint64_t* out_keys_dev, int32_t* out_pos_dev, int32_t* out_counts_dev, int32_t* out_dropped_dev,
+               void* stream) {
+  HX_TRY
+  HX_CHECK(h && ops_host && keys_dev && out_keys_dev && out_pos_dev && out_counts_dev && out_dropped_dev, "NULL argument");
+  formula_check(stride, B, limit);
+  FormulaArgs f{};
+  formula_lower(h, ops_host, n_ops, n_planes, f);
+  HX_CHECK(n_planes == 0 || planes_dev, "NULL argument");
+  for (int i = 0; i < n_planes; ++i) HX_CHECK(planes_dev[i] != nullptr, "NULL argument");
+  HX_CHECK(n_planes == 0 || plane_rows == h->n, "formula: plane_rows must equal the index's row count (hx_count)");
+  HX_CHECK(!eligible_dev || eligible_rows == h->n, "formula: eligible_rows must equal the index's row count (hx_count)");
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
+  formula_enqueue(h, f, planes_dev, n_planes, keys_dev, ikeys, stride, counts_dev, B, limit, score_threshold, eligible_dev,
+                  out_keys_dev, out_pos_dev, nullptr, out_counts_dev, out_dropped_dev, st);
+  HX_CATCH
+}
+
+int hx_hybrid_query_formula_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
+                                 int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
+                                 int32_t mask_root_only, int32_t candidates_limit, const hx_formula_op* ops_host,
+                                 int32_t n_ops, const uint32_t* const* planes_host, int32_t n_planes, int32_t limit,
+                                 float score_threshold, float* scores, int64_t* ids, float* base_scores, int32_t* counts,
+                                 int32_t* dropped) {
+  HX_TRY
+  HX_CHECK(h, "NULL argument");
+  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  const FormulaSpec f{mask_root_only, candidates_limit, limit, ops_host, n_ops, planes_host, n_planes, score_threshold,
+                      base_scores, counts, dropped};
+  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, nullptr, nullptr, &f);
   HX_CATCH
 }
 

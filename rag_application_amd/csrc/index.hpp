@@ -51,7 +51,8 @@ enum WsSlot {
   WS_MS_POS, WS_MS_KEYS, WS_MS_CNT, WS_MS_FIRST, WS_MS_Q8, WS_MS_QS, WS_MS_QIP,
   WS_RECO_X, WS_RECO_RAW, WS_RECO_RAWN, WS_RECO_META, WS_RECO_Q, WS_RECO_KEYS, WS_RECO_KCNT, WS_RECO_CAND, WS_RECO_CNT,
   WS_RECO_OVF, WS_RECO_TAU, WS_RECO_TAU0, WS_RECO_MASK, WS_RECO_OUT, WS_RECO_OCNT, WS_RECO_SC, WS_RECO_ID,
-  WS_SCROLL_WORK, WS_SCROLL_MASK, WS_SCROLL_OUT
+  WS_SCROLL_WORK, WS_SCROLL_MASK, WS_SCROLL_OUT,
+  WS_FORMULA_PLANES, WS_FORMULA_KEYS, WS_FORMULA_POS, WS_FORMULA_BASE, WS_FORMULA_CNT, WS_FORMULA_DROP
 };
 
 template <typename T>
@@ -302,6 +303,10 @@ struct SplicePlan {
 };
 void splice_plan(SplicePlan& s, const int64_t* indptr, int64_t total, int64_t f, const uint32_t* rows_dev, int64_t m,
                  const int64_t* new_indptr_dev, hipStream_t st);
+
+// ---- formula.hip: every refusal of hx_formula that concerns the program (before any device work), and the program and
+// its columns as the kernel's arguments hold them
+void formula_lower(hx_index* h, const hx_formula_op* ops, int32_t n_ops, int32_t n_planes, FormulaArgs& a);
 
 // ---- paystore.hip: a payload column as the engine and the lifecycle see it ------------------------------------------------
 hx_index::PayCol& pay_col(hx_index* h, int32_t col);      // throws for an unknown id

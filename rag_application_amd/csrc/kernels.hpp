@@ -698,6 +698,41 @@ void launch_scroll_rows(const uint32_t* mask, int64_t n, int64_t start_row, int 
 // the whole ordered selection (hx.h states it): out_rows / out_bits [limit], *out_count
 void launch_payload_order(const OrderArgs& a, uint32_t* out_rows, uint64_t* out_bits, int32_t* out_count, int grid_cap,
                           hipStream_t st);
+// ---- formula.hip: score-boosting search (hx_formula) ------------------------------------------------
+// Per query b: the pool keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same slots with
+// internal ids.  A position is eligible by the rule of MmrArgs.  The program travels in the kernel arguments (3.7 KB of
+// the 4 KB a launch takes; uniform reads): op[i] / arg[i] / imm[i] of hx_formula_op, a VAR's arg = its entry of col_lo /
+// col_hi (the low and high words of the column's doubles), a COND's arg = its entry of planes (packed row masks).
+// out_keys [B x limit] = make_key(value, the id of keys[.. + i]), 0 past the hits; out_pos = i, -1 past them; out_base
+// (may be NULL) = the score keys[.. + i] carried, -inf past them; out_counts [B] = hits; out_dropped [B] = eligible
+// positions whose value was not finite.
+constexpr int FORMULA_MAX_OPS = 256, FORMULA_MAX_COLS = 64, FORMULA_MAX_PLANES = 8;   // HX_FORMULA_* / HX_PAY_MAX_COLUMNS
+struct FormulaArgs {
+  const uint64_t* keys;
+  const uint64_t* ikeys;
+  const int* counts;
+  const uint32_t* eligible;
+  uint64_t* out_keys;
+  int* out_pos;
+  float* out_base;
+  int* out_counts;
+  int* out_dropped;
+  int64_t n_rows;
+  uint32_t id_base;
+  int stride;              // 1 .. 2048
+  int limit;               // 1 .. 2048
+  int n_ops;               // 1 .. 256
+  float threshold;
+  int has_threshold;
+  const uint32_t* planes[FORMULA_MAX_PLANES];
+  const uint32_t* col_lo[FORMULA_MAX_COLS];
+  const uint32_t* col_hi[FORMULA_MAX_COLS];
+  uint64_t imm[FORMULA_MAX_OPS];
+  uint8_t op[FORMULA_MAX_OPS];
+  uint8_t arg[FORMULA_MAX_OPS];
+};
+static_assert(sizeof(FormulaArgs) <= 4096, "the program travels in the kernel arguments");
+void launch_formula(const FormulaArgs& a, int B, hipStream_t st);
 // compact.hip, a list column's elements: dst[off[j] + k] = src[indptr[rows[j]] + k] for the m kept rows (one 4-byte plane)
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);

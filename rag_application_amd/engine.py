@@ -841,6 +841,87 @@ class HxIndex:
                                                   _ptr(values), _ptr(counts)))
         return scores, ids, values, counts
 
+    # -- score-boosting search (hx.h: hx_formula / hx_hybrid_query_formula_host) -----------------
+    @staticmethod
+    def _formula_ops(ops):
+        arr = (_lib.HxFormulaOp * max(len(ops), 1))()
+        for k, (op, arg, imm) in enumerate(ops):
+            arr[k].op, arr[k].arg, arr[k].imm = int(op), int(arg), int(imm) & 0xFFFFFFFFFFFFFFFF
+        return arr
+
+    def formula(self, ops, keys: torch.Tensor, counts: Optional[torch.Tensor], limit: int, planes=(),
+                score_threshold: Optional[float] = None, eligible=None, out=None):
+        """The pools keys [B, stride] (+ counts [B], None = every slot) ranked again by the value the postfix program
+        `ops` -- (op, arg, imm) triples, imm an int holding the bits of a double -- gives every position (hx_formula).
+        planes: the condition planes, row masks as hybrid_query_host takes them; eligible: None or one more such mask;
+        score_threshold None = no cut.  out: None, or the four output tensors to write into.  Returns (out_keys [B, limit]
+        int64, 0 past the hits; positions [B, limit] int32, -1 past them; counts [B] int32; dropped [B] int32).  Only
+        enqueues work."""
+        keys = _need_cuda(keys, torch.int64, "keys")
+        if keys.dim() != 2:
+            raise HxError("keys must be a [B, stride] tensor")
+        if counts is not None:
+            counts = _need_cuda(counts, torch.int32, "counts")
+        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        slots = L if 1 <= L <= 2048 else 1                  # (the engine refuses; nothing huge is allocated)
+        dev_planes, rows = [], 0
+        for m in planes:
+            w, rows = self._mask(m)
+            dev_planes.append(torch.from_numpy(w.view(np.int32)).to(keys.device))
+        parr = (C.c_void_p * max(len(dev_planes), 1))(*[t.data_ptr() for t in dev_planes])
+        words, erows = None, 0
+        if eligible is not None:
+            w, erows = self._mask(eligible)
+            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
+        if out is None:
+            out = (torch.empty((B, slots), dtype=torch.int64, device=keys.device),
+                   torch.empty((B, slots), dtype=torch.int32, device=keys.device),
+                   torch.empty((B,), dtype=torch.int32, device=keys.device),
+                   torch.empty((B,), dtype=torch.int32, device=keys.device))
+        okeys, opos, ocnt, odrop = out
+        thr = float("nan") if score_threshold is None else float(score_threshold)
+        check(_lib.lib().hx_formula(self._h, self._formula_ops(ops), len(ops), parr if dev_planes else None,
+                                    len(dev_planes), rows, _ptr(keys), stride, _ptr(counts), B, L, thr, _ptr(words), erows,
+                                    _ptr(okeys), _ptr(opos), _ptr(ocnt), _ptr(odrop), _stream()))
+        return okeys, opos, ocnt, odrop
+
+    def hybrid_query_formula_host(self, q: np.ndarray, q_indptr: np.ndarray, q_idx: np.ndarray, q_val: np.ndarray,
+                                  params: HxParams, ops, limit: int, planes=(), score_threshold: Optional[float] = None,
+                                  candidates_limit: int = 0, mask=None, mask_root_only: bool = False):
+        """hybrid_query_host followed by the formula stage over its pool (hx_hybrid_query_formula_host): the query runs
+        with final_limit = the pool (candidates_limit = 0: the mode's whole pool; params.final_limit is not used) and keeps
+        the scores its mode hands out; the best `limit` positions by the program's value come back.  ops / planes /
+        score_threshold as `formula` takes them, mask / mask_root_only as hybrid_query_mmr_host.  Returns (scores
+        [B, limit] float32 -- the values --, ids [B, limit] int64, base_scores [B, limit] float32 -- the scores the pool
+        carried --, counts [B] int32, dropped [B] int32); the slots past the hits (-inf, -1, -inf)."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
+        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
+        B, L = q.shape[0], int(limit)
+        if not 1 <= L <= 2048:
+            raise HxError("formula: limit out of range [1, 2048]")
+        host_planes = []
+        for m in planes:
+            w, rows = self._mask(m)
+            if rows != self.count():
+                raise HxError("formula: a condition plane must hold one bit per row of the index (hx_count)")
+            host_planes.append(w)
+        parr = (C.c_void_p * max(len(host_planes), 1))(*[w.ctypes.data for w in host_planes])
+        scores = np.empty((B, L), dtype=np.float32)
+        ids = np.empty((B, L), dtype=np.int64)
+        base = np.empty((B, L), dtype=np.float32)
+        counts = np.empty((B,), dtype=np.int32)
+        dropped = np.empty((B,), dtype=np.int32)
+        words, rows = (None, 0) if mask is None else self._mask(mask)
+        thr = float("nan") if score_threshold is None else float(score_threshold)
+        check(_lib.lib().hx_hybrid_query_formula_host(
+            self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B, C.byref(params), _ptr(words), rows,
+            int(bool(mask_root_only)), int(candidates_limit), self._formula_ops(ops), len(ops),
+            parr if host_planes else None, len(host_planes), L, thr, _ptr(scores), _ptr(ids), _ptr(base), _ptr(counts),
+            _ptr(dropped)))
+        return scores, ids, base, counts, dropped
+
     # -- recommend search (hx.h: hx_recommend / hx_recommend_host; DESIGN.md section 24) --------------------------------
     def _reco_examples(self, requests):
         """requests: per request a sequence of (example, sign) -- example = a local row (an int) or a vector of `dim`

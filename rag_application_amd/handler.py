@@ -23,6 +23,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
+from . import boosting as _boosting
 from . import engine as _engine
 from . import faceting as _faceting
 from . import filters as _filters
@@ -97,6 +98,13 @@ class RerankedPoint(ScoredPoint):
     """One hit of hybrid_search_rerank: a ScoredPoint whose `score` is the MaxSim of the query's tokens against the
     point's tokens and whose `first_score` is the score the point carried in the hybrid pool."""
     first_score: float = 0.0
+
+
+@dataclass
+class BoostedPoint(ScoredPoint):
+    """One hit of hybrid_search_boost: a ScoredPoint whose `score` is the value the formula gave the point and whose
+    `base_score` is the score the point carried in the hybrid pool (the formula's "$score")."""
+    base_score: float = 0.0
 
 
 @dataclass
@@ -555,6 +563,7 @@ FILTER_STAGES = ("root", "all")
 RECO_MAX_LIMIT, RECO_MAX_REQUESTS, RECO_MAX_EXAMPLES = 1024, 16, 32   # HX_RECO_MAX_* of hx.h
 RECO_STRATEGIES = {"average_vector": 0, "best_score": 1, "sum_scores": 2}   # HX_RECO_AVERAGE / _BEST_SCORE / _SUM_SCORES
 MMR_MAX_LIMIT = 256                   # HX_MMR_MAX_LIMIT of hx.h: most hits hybrid_search_mmr picks per query
+BOOST_MAX_LIMIT = _boosting.MAX_LIMIT  # most hits hybrid_search_boost returns per query (hx.h: hx_formula)
 
 
 class QdrantHandler:
@@ -576,6 +585,8 @@ class QdrantHandler:
     _facets = True
     # token columns live in ONE engine index; hybrid_search_rerank reranks the pool of that index
     _late_rerank = True
+    # hybrid_search_boost values the pool of ONE engine index by the payload columns of that index
+    _boost_search = True
     # recommend scans the rows of ONE engine index and looks its examples up in this process's ids
     _recommend = True
     # scroll pages the rows of ONE engine index and the ids and payloads this process holds
@@ -1243,6 +1254,128 @@ class QdrantHandler:
             raise
         except Exception as e:
             logging.error("rerank hybrid search for %s failed: %s", user_id, e)
+            return []
+
+    # ---------------------------------------------------------------------- score boosting
+    def _boost_sync(self, user_id, dense_vectors, sparse_vectors, formula, defaults, limit, candidates_limit,
+                    score_threshold, search_params, filters, mode, filter_stages):
+        if not self._boost_search:
+            raise ValueError("hybrid_search_boost is not supported on a sharded collection")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= BOOST_MAX_LIMIT:
+            raise ValueError(f"limit must be an integer in [1, {BOOST_MAX_LIMIT}], got {limit!r}")
+        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
+                                             or candidates_limit < 1):
+            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
+        if score_threshold is not None and (isinstance(score_threshold, bool)
+                                            or not isinstance(score_threshold, (int, float))
+                                            or score_threshold != score_threshold):
+            raise ValueError(f"score_threshold must be a number that is not a NaN or None, got {score_threshold!r}")
+        if defaults is not None and not isinstance(defaults, dict):
+            raise ValueError("defaults must be a dict (variable -> value) or None")
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        if mode not in ("tree", "h1"):
+            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+        root_filter = bool(filters) and filter_stages == "root"
+        if root_filter and mode != "tree":
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
+        defaults = defaults or {}
+        _boosting.check(formula, defaults)                 # ValueError: a formula no evaluation can serve
+        hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
+        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
+        if pool_max < 1:
+            raise ValueError("the search_params leave an empty pool")
+        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        col = self._collections[str(user_id)]
+        q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
+        idx, val = idx.astype(np.int32), val.astype(np.float32)
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        cids, cpay = col.ids, col.payloads
+        pi = getattr(col, "pindex", None)
+        prog = _boosting.compile(formula, defaults, pi, col._id_rows)
+        if prog is None:
+            reason = "formula declined"
+        elif not hasattr(col.index, "hybrid_query_formula_host"):
+            reason = "boost on an index without the formula query"
+        else:
+            reason = None
+        if reason is None:
+            try:
+                if prog[1] and col.index.count() != len(cids):
+                    raise RuntimeError("the engine's row count differs from the payloads'")
+                planes = [col.row_mask(f) for f in prog[1]]
+                mask = col.row_mask(filters) if filters else None
+                scores, rows, base, counts, dropped = col.index.hybrid_query_formula_host(
+                    q, indptr, idx, val, hp, prog[0], limit, planes=planes, score_threshold=score_threshold,
+                    candidates_limit=pool, mask=mask, mask_root_only=root_filter)
+                for b, d in enumerate(dropped.tolist()):
+                    if d:
+                        logging.warning("boosted search: query %d dropped %d points whose value was not finite", b, d)
+                if pi is not None:
+                    pi.boost_device_calls += 1
+                return [[BoostedPoint(id=cids[r], version=0, score=s, payload=cpay[r], base_score=f)
+                         for s, r, f in zip(sc[:n], rw[:n], bs[:n])]
+                        for sc, rw, bs, n in zip(scores.tolist(), rows.tolist(), base.tolist(), counts.tolist())]
+            except Exception as e:                          # never a wrong rank: the walk over the payloads is always right
+                logging.warning("boosted search: the device path failed, Python path taken: %s", e)
+                reason = "engine refused"
+        logging.warning("boosted search takes the Python path: %s", reason)
+        if pi is not None and reason != "formula declined":  # (compile counted its own reason)
+            pi.declined[reason] = pi.declined.get(reason, 0) + 1
+        hp.final_limit = pool
+        if filters and not root_filter:
+            scores, rows, counts = col.index.hybrid_query_host(q, indptr, idx, val, hp, mask=col.row_mask(filters))
+        else:
+            scores, rows, counts = col.index.hybrid_query_host(q, indptr, idx, val, hp)
+        out = []
+        for b, (sc, rw, n) in enumerate(zip(scores.tolist(), rows.tolist(), counts.tolist())):
+            values = []
+            for s, r in zip(sc[:n], rw[:n]):
+                if root_filter and not _filters.matches(cpay[r], filters, cids[r]):
+                    values.append(None)                     # the root's filter: the point is not eligible
+                else:
+                    values.append(_boosting.value_f32(_boosting.evaluate(formula, defaults, s, cpay[r], cids[r])))
+            hits, dropped = _boosting.rank(values, limit, score_threshold)
+            if dropped:
+                logging.warning("boosted search: query %d dropped %d points whose value was not finite", b, dropped)
+            out.append([BoostedPoint(id=cids[rw[i]], version=0, score=float(values[i]), payload=cpay[rw[i]],
+                                     base_score=sc[i]) for i in hits])
+        return out
+
+    async def hybrid_search_boost(self, user_id: str, dense_vectors, sparse_vectors, formula, defaults=None,
+                                  limit: int = 10, candidates_limit: Optional[int] = 100,
+                                  score_threshold: Optional[float] = None,
+                                  search_params: Optional[Dict[str, Any]] = None, filters: Optional[Dict] = None,
+                                  mode: str = "tree", filter_stages: str = "root") -> List[List[BoostedPoint]]:
+        """Qdrant's FormulaQuery ("score boosting") for B queries in one engine call (additive): the hybrid query is the
+        prefetch, every point of its POOL is valued by `formula` -- an expression over "$score" (the score the pool
+        carried: mode "tree" the dense cosine, mode "h1" the fused RRF score), payload variables with `defaults`,
+        conditions, sum / mult / neg / abs / div / sqrt / exp / pow / ln / log10, datetime / datetime_key and the three
+        decays; boosting.py states the grammar and the arithmetic -- and the best `limit` come back, value descending, pool
+        order on a tie.  A point whose value is not finite (a NaN, an infinity) is dropped, and the query logs a warning
+        with the count; score_threshold cuts the points whose value lies under it.  The pool is the ranked list the
+        engine returns with final_limit = the pool size, as in hybrid_search_mmr; candidates_limit asks for a shorter
+        pool, above the maximum it is clipped, None = the maximum.  search_params["final_limit"] must be there and is
+        NOT used.  filters / filter_stages as in hybrid_search_mmr.  `score` = the value, `base_score` = the pool's score.
+        A formula that compiles (boosting.compile: its variables have live "number" / "datetime" payload indexes, its
+        conditions compile, no pow / ln / log10) is valued and ranked by one kernel over the pool on the device
+        (hx_hybrid_query_formula_host), each condition one row mask of the collection's mask cache; everything else walks
+        the pool's payloads in Python (boosting.evaluate), logs a warning and counts itself in the payload index's
+        `declined`.  Both ways give the same hits.
+        Raises ValueError for arguments no search can serve (a limit outside [1, 2048], a candidates_limit below 1, a
+        score_threshold that is no number, a malformed formula, a variable without a default, a scale <= 0, a midpoint
+        outside (0, 1), mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or filter
+        clause); any other failure is logged and gives [], as in every search."""
+        try:
+            return await self._run(self._boost_sync, user_id, dense_vectors, sparse_vectors, formula, defaults, limit,
+                                   candidates_limit, score_threshold, search_params, filters, mode, filter_stages)
+        except ValueError as ve:
+            logging.error("boosted hybrid search for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("boosted hybrid search for %s failed: %s", user_id, e)
             return []
 
     async def rerank_with_colbert(self, query: str, documents: List[str], results: List[Dict],

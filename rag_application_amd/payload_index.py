@@ -196,6 +196,7 @@ class PayloadIndex:
         self.facet_python_calls = 0        # facets counted by faceting.py over the payloads
         self.scroll_device_calls = 0       # scrolls served by hx_scroll_rows_host / hx_payload_order_host
         self.scroll_python_calls = 0       # scrolls walked by scrolling.py over the payloads
+        self.boost_device_calls = 0        # boosted searches served by hx_hybrid_query_formula_host
 
     # -- definitions -----------------------------------------------------------------------------------------------
     def definitions(self) -> Dict[str, str]:

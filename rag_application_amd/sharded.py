@@ -477,6 +477,7 @@ class ShardedHandler(QdrantHandler):
     _mmr_search = False              # hybrid_search_mmr raises ValueError: nothing is sent to the ranks
     _facets = False                  # facet raises ValueError: payload columns live in one engine index only
     _late_rerank = False             # create_token_index / hybrid_search_rerank raise ValueError: token columns likewise
+    _boost_search = False            # hybrid_search_boost raises ValueError: nothing is sent to the ranks
     _recommend = False               # recommend / recommend_batch raise ValueError: nothing is sent to the ranks
     _scroll = False                  # scroll / retrieve raise ValueError: the rows of a collection lie in several indexes
 
