@@ -787,6 +787,33 @@ int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* e
                       const uint32_t* mask_host, int64_t mask_rows, int32_t limit,
                       float* scores_host, int64_t* ids_host, int32_t* counts_host);
 
+/* ---- distance matrix search ------------------------------------------
+ * Qdrant's search_matrix_pairs / search_matrix_offsets (additive: the reference never calls them; parity unpinned, the
+ * semantics below are this project's statement of them): for every point of a sample, its nearest neighbours among the
+ * OTHER points of the sample.  Additive to the ABI: HX_ABI_VERSION stays 3.
+ *
+ * The sample is S distinct local rows r_0 .. r_{S-1} in [0, hx_count), in any order, 1 <= S <= HX_MATRIX_MAX_SAMPLE.
+ * sim(a, b) = the spec dot product of the stored normalised fp32 rows a and b over the padded width, as hx_recommend
+ * defines it: every product and sum one unfused fp32 operation, the result + 0.0f.  sim(a, b) and sim(b, a) are the same
+ * bits.  The candidates of r_i are the r_j, j != i, with sim(r_i, r_j) >= score_threshold (a finite fp32, or -inf =
+ * none).  Of them the best `limit` are kept, 1 <= limit <= HX_MATRIX_MAX_LIMIT: score descending, id ascending, as
+ * make_key(sim, global id of r_j) -- the keys hx_recommend hands out.  Output row i belongs to r_i in the order given:
+ * counts[i] = min(limit, candidates of r_i), the slots past it are 0.  S = 1 gives one row with count 0.
+ * The engine reads the S sample rows only: the cost depends on S, dim and limit, never on hx_count.  There is no mask:
+ * the caller has chosen the rows.
+ *
+ * Refused before any device work, every output untouched: a NULL argument, S or limit out of range, a row outside
+ * [0, hx_count), a row listed twice, a NaN threshold.  hx_search_matrix synchronises `stream`.  hx_search_matrix_host
+ * adds the unpacking and the copy out: scores_host / ids_host [S x limit], empty slots (-inf, -1); counts_host [S].
+ * HX_DEBUG_MATRIX_SCAN_ONLY=1 (read by hx_create, per index: diagnostics) stops a call behind the scan kernel and zeroes
+ * the outputs, so that the scan can be timed alone. */
+#define HX_MATRIX_MAX_SAMPLE 4096
+#define HX_MATRIX_MAX_LIMIT 1024
+int hx_search_matrix(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
+                     uint64_t* keys_dev /* [S x limit] */, int32_t* counts_dev /* [S] */, void* stream);
+int hx_search_matrix_host(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
+                          float* scores_host, int64_t* ids_host /* [S x limit] */, int32_t* counts_host);
+
 /* ---- payload facets -------------------------------------------
  * Qdrant's facet(collection, key, facet_filter, limit, exact) (additive: the reference never calls it; parity unpinned, the
  * semantics below are this project's statement of it): for every value of a keyword or bool field, the number of points a

@@ -1852,6 +1852,45 @@ static void recommend_dev(hx_index* h, int strategy, int R, const RecoCall& c_in
   HX_HIP(hipStreamSynchronize(st));
 }
 
+// ---------------------------------------------------------------------------------
+// distance matrix search (hx_search_matrix)
+// ---------------------------------------------------------------------------------
+// every refusal of the call, before any device work; the sample as the kernels take it
+static std::vector<uint32_t> matrix_check(hx_index* h, const int64_t* rows, int S, int limit, float threshold) {
+  HX_CHECK(h, "NULL argument");
+  HX_CHECK(S >= 1 && S <= HX_MATRIX_MAX_SAMPLE, "search_matrix: sample out of range [1, 4096]");
+  HX_CHECK(limit >= 1 && limit <= HX_MATRIX_MAX_LIMIT, "search_matrix: limit out of range [1, 1024]");
+  HX_CHECK(rows, "NULL argument");
+  HX_CHECK(!std::isnan(threshold), "search_matrix: the score threshold is NaN");
+  std::vector<uint32_t> r((size_t)S);
+  for (int i = 0; i < S; ++i) {
+    HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "search_matrix: sample row out of range");
+    r[(size_t)i] = (uint32_t)rows[i];
+  }
+  std::vector<uint32_t> sorted = r;
+  std::sort(sorted.begin(), sorted.end());
+  HX_CHECK(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), "search_matrix: a sample row is listed twice");
+  return r;
+}
+
+// Keys leave with internal ids.  Synchronises `st` (the row list is uploaded from this frame).
+static void search_matrix_dev(hx_index* h, const std::vector<uint32_t>& rows, int L, float threshold, uint64_t* out_keys,
+                              int* out_cnt, hipStream_t st) {
+  const int S = (int)rows.size();
+  MatrixArgs a{};
+  a.dense = h->dense;
+  a.S = S;
+  a.dim_pad = h->dim_pad;
+  uint32_t* rows_dev = (uint32_t*)h->ws.get(WS_MATRIX_ROWS, (size_t)S * 4);
+  HX_HIP(hipMemcpyAsync(rows_dev, rows.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
+  a.rows = rows_dev;
+  a.plane = (float*)h->ws.get(WS_MATRIX_PLANE, (size_t)S * S * 4);   // 64 MB at the cap, sized by S, freed with the index
+  launch_matrix_scan(a, st);
+  if (h->matrix_scan_only) zero_outputs(out_keys, out_cnt, S, L, st);
+  else launch_matrix_select(a, threshold, (uint32_t)h->id_base, L, out_keys, out_cnt, st);
+  HX_HIP(hipStreamSynchronize(st));
+}
+
 }  // namespace hx
 
 // =================================================================================
@@ -1909,6 +1948,7 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_PAY_GRID")) h->pay_grid = (int)std::clamp<long long>(atoll(e), 0, 1 << 20);   // tests: the grid-stride loop
   if (const char* e = getenv("HX_DEBUG_RECO_CHUNK0")) h->reco_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the recommend scan's chunks
   if (const char* e = getenv("HX_DEBUG_RECO_CAP")) h->reco_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
+  if (const char* e = getenv("HX_DEBUG_MATRIX_SCAN_ONLY")) h->matrix_scan_only = atoi(e) != 0;             // diagnostics: the matrix scan's own time
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);
     if (v >= 1 && v <= SCAN8_LOGCAP) h->scan_logcap = v;
@@ -3481,6 +3521,41 @@ int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* e
   HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
   HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_search_matrix(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
+                     uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(keys_dev && counts_dev, "NULL argument");
+  const std::vector<uint32_t> rows = matrix_check(h, rows_host, S, limit, score_threshold);
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  search_matrix_dev(h, rows, limit, score_threshold, keys_dev, counts_dev, st);
+  remap_out(h, keys_dev, (int64_t)S * limit, st);
+  HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_search_matrix_host(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
+                          float* scores_host, int64_t* ids_host, int32_t* counts_host) {
+  HX_TRY
+  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
+  const std::vector<uint32_t> rows = matrix_check(h, rows_host, S, limit, score_threshold);
+  h->set_device();
+  hipStream_t st = nullptr;
+  const int64_t n_out = (int64_t)S * limit;
+  uint64_t* keys = (uint64_t*)h->ws.get(WS_MATRIX_OUT, (size_t)n_out * 8);
+  int* cnt = (int*)h->ws.get(WS_MATRIX_OCNT, (size_t)S * 4);
+  float* sc = (float*)h->ws.get(WS_MATRIX_SC, (size_t)n_out * 4);
+  int64_t* id = (int64_t*)h->ws.get(WS_MATRIX_ID, (size_t)n_out * 8);
+  search_matrix_dev(h, rows, limit, score_threshold, keys, cnt, st);
+  remap_out(h, keys, n_out, st);
+  launch_unpack(keys, n_out, sc, id, st);
+  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)S * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipStreamSynchronize(st));
   HX_CATCH
 }

@@ -659,6 +659,23 @@ struct RecoScanArgs {
 };
 // lds_examples = examples staged by the launch (sum of its requests' n_ex): sizes the LDS request and the grid
 void launch_reco_scan(const RecoScanArgs& a, int lds_examples, hipStream_t st);
+// ---- matrix.hip: distance matrix search (hx_search_matrix) ----------------------------------------
+// The sample is S local rows, rows[0 .. S) on the device; nothing but those rows of `dense` is read.
+struct MatrixArgs {
+  const float* dense;      // the normalised fp32 rows, dim_pad floats each (a multiple of 64, at most 4096)
+  const uint32_t* rows;    // device [S]: the sample's local rows, distinct
+  int S;                   // 1 .. HX_MATRIX_MAX_SAMPLE
+  int dim_pad;
+  float* plane;            // [S x S] plane[i * S + j] = sim(rows[i], rows[j]) (the diagonal included)
+};
+// staged rows of one workgroup of k_matrix_scan at this width: 48 KB of LDS up to width 1024, eight rows above
+int matrix_tile_rows(int dim_pad);
+// plane = every sim of the sample: spec_dot in wave_spec_dot's order, + 0.0f
+void launch_matrix_scan(const MatrixArgs& a, hipStream_t st);
+// Row i of the plane -> out_keys[i * limit ..] = the best `limit` of make_key(plane[i * S + j], id_base + rows[j]) over
+// j != i with plane[i * S + j] >= threshold, descending, 0 past them; out_counts[i] = their number
+void launch_matrix_select(const MatrixArgs& a, float threshold, uint32_t id_base, int limit, uint64_t* out_keys,
+                          int* out_counts, hipStream_t st);
 // ---- scroll.hip: scroll (hx_scroll_rows / hx_payload_order) --------------------------------------
 // "The first m rows of a predicate, in row order" over contiguous row slices, one per workgroup: a count per slice, an
 // exclusive prefix over the slices, and an emit that places a row at prefix + its rank inside the slice.

@@ -977,6 +977,35 @@ class HxIndex:
                                            _ptr(words), mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores[:R], ids[:R], counts[:R]
 
+    # -- distance matrix search (hx.h: hx_search_matrix / hx_search_matrix_host) ----------------------
+    @staticmethod
+    def _matrix_args(rows, limit, score_threshold):
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        S, L = int(rows.shape[0]), int(limit)
+        thr = float("-inf") if score_threshold is None else float(score_threshold)
+        # (the engine refuses a bad S or limit; nothing huge is allocated for the outputs of a refused call)
+        return rows, S, L, thr, (max(S, 1) if S <= 4096 else 1), (L if 1 <= L <= 1024 else 1)
+
+    def search_matrix(self, rows, limit: int, score_threshold=None, keys=None, counts=None):
+        """For every local row of the sample `rows` (distinct, any order) its nearest neighbours among the other rows of
+        the sample (hx_search_matrix): score_threshold = None or the smallest sim a neighbour may have.  Returns (keys
+        [S, limit] int64, counts [S] int32) on the device (keys / counts: tensors to write into); the call synchronises."""
+        rows, S, L, thr, out_rows, out_cols = self._matrix_args(rows, limit, score_threshold)
+        if keys is None or counts is None:
+            keys, counts = self._out(out_rows, out_cols)
+        check(_lib.lib().hx_search_matrix(self._h, _ptr(rows), S, L, thr, _ptr(keys), _ptr(counts), _stream()))
+        return keys, counts
+
+    def search_matrix_host(self, rows, limit: int, score_threshold=None):
+        """search_matrix, host out (hx_search_matrix_host): (scores [S, limit] float32, ids [S, limit] int64, counts [S]
+        int32), the slots past a row's count (-inf, -1)."""
+        rows, S, L, thr, out_rows, out_cols = self._matrix_args(rows, limit, score_threshold)
+        scores = np.empty((out_rows, out_cols), dtype=np.float32)
+        ids = np.empty((out_rows, out_cols), dtype=np.int64)
+        counts = np.empty((out_rows,), dtype=np.int32)
+        check(_lib.lib().hx_search_matrix_host(self._h, _ptr(rows), S, L, thr, _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores[:S], ids[:S], counts[:S]
+
     # -- late-interaction rerank (hx.h: HX_PAY_TOKENS / hx_maxsim / hx_hybrid_query_rerank_host; DESIGN.md section 23) --
     def payload_create_tokens(self, dim_t: int) -> int:
         """A new empty token column of `dim_t` int8 values per token (hx_payload_create_tokens); returns its id."""

@@ -29,8 +29,10 @@ from . import faceting as _faceting
 from . import filters as _filters
 from . import grouping as _grouping
 from . import late_interaction as _late
+from . import matrix as _matrix
 from . import payload_index as _pindex
 from . import scrolling as _scrolling
+from .matrix import MatrixOffsets, MatrixPair
 from ._lib import HX_MODE_H1, HX_MODE_TREE
 
 
@@ -591,6 +593,8 @@ class QdrantHandler:
     _recommend = True
     # scroll pages the rows of ONE engine index and the ids and payloads this process holds
     _scroll = True
+    # search_matrix_pairs / _offsets compare rows of ONE engine index with each other
+    _matrix_search = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -1481,6 +1485,90 @@ class QdrantHandler:
         res = await self.recommend_batch(user_id, [{"positive": positive, "negative": negative, "strategy": strategy}],
                                          limit=limit, filters=filters)
         return res[0] if res else []
+
+    # ------------------------------------------------------------------------ distance matrix
+    def _search_matrix_sync(self, user_id, sample, limit, filters, point_ids, seed, score_threshold):
+        """(the sample's point ids, scores [S, limit], neighbours as sample positions [S, limit], counts [S]) of one
+        engine call, or None when fewer than two points are sampled"""
+        if not self._matrix_search:
+            raise ValueError("search_matrix is not supported on a sharded collection")
+        if isinstance(sample, bool) or not isinstance(sample, int) or not 1 <= sample <= _matrix.MAX_SAMPLE:
+            raise ValueError(f"sample must be an integer in [1, {_matrix.MAX_SAMPLE}], got {sample!r}")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= _matrix.MAX_LIMIT:
+            raise ValueError(f"limit must be an integer in [1, {_matrix.MAX_LIMIT}], got {limit!r}")
+        if score_threshold is not None:
+            try:
+                score_threshold = float(score_threshold)
+            except (TypeError, ValueError):
+                raise ValueError(f"score_threshold must be a number, got {score_threshold!r}") from None
+            if score_threshold != score_threshold:
+                raise ValueError("score_threshold must not be NaN")
+        col = self._collections[str(user_id)]
+        n = len(col.ids)
+        mask = None
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            mask = col.row_mask(filters)
+        if point_ids is not None:                          # exactly these points, in the order given
+            point_ids = list(point_ids)
+            if len(point_ids) > _matrix.MAX_SAMPLE:
+                raise ValueError(f"search_matrix: at most {_matrix.MAX_SAMPLE} point ids, got {len(point_ids)}")
+            id_rows = col._id_rows()
+            if id_rows is None:                            # an id held twice: the first row that holds it
+                id_rows = {}
+                for r, pid in enumerate(col.ids):
+                    id_rows.setdefault(pid, r)
+            rows, seen = [], set()
+            for pid in point_ids:
+                if isinstance(pid, bool) or not isinstance(pid, (str, int)) or str(pid) not in id_rows:
+                    raise ValueError(f"search_matrix: unknown point id {pid!r}")
+                r = id_rows[str(pid)]
+                if r in seen:
+                    raise ValueError(f"search_matrix: point id {pid!r} is listed twice")
+                seen.add(r)
+                if mask is None or (int(mask[r >> 5]) >> (r & 31)) & 1:
+                    rows.append(r)
+            rows = np.asarray(rows, dtype=np.int64)
+        else:
+            rows = _matrix.choose_rows(mask, n, sample, seed)
+        if len(rows) < 2:
+            return None
+        scores, nbr_rows, counts = col.index.search_matrix_host(rows, limit, score_threshold)
+        ids = [col.ids[r] for r in rows.tolist()]
+        return ids, scores, _matrix.neighbour_positions(rows.tolist(), nbr_rows, counts), counts
+
+    async def _search_matrix(self, user_id, sample, limit, filters, point_ids, seed, score_threshold):
+        try:
+            return await self._run(self._search_matrix_sync, user_id, sample, limit, filters, point_ids, seed,
+                                   score_threshold)
+        except ValueError as ve:
+            logging.error("search_matrix for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:                             # logged, an empty response: as in every search
+            logging.error("search_matrix for %s failed: %s", user_id, e)
+            return None
+
+    async def search_matrix_pairs(self, user_id: str, sample: int = 10, limit: int = 3, filters: Optional[Dict] = None,
+                                  point_ids=None, seed=None, score_threshold=None) -> List[MatrixPair]:
+        """Qdrant's search_matrix_pairs (additive): a sample of at most `sample` of the points
+        `filters` keeps (matrix.choose_rows: `seed` makes it repeatable) -- or exactly the points `point_ids` names, in
+        that order, less those the filter drops -- and for each sample point, in sample order, its `limit` nearest
+        neighbours among the other sample points, best first, as MatrixPair(a, b, score); `score_threshold` keeps only
+        neighbours that score at least that.  Symmetric pairs are not merged.  One engine call on the device
+        (hx_search_matrix_host) that reads the sample's rows only; there is no Python path.  Fewer than two sample points
+        give [].  Raises ValueError for arguments no search can serve (sample outside [1, 4096], limit outside [1, 1024],
+        a NaN threshold, an unknown or repeated point id, more than 4096 point ids, a sharded collection); any other
+        failure is logged and gives [], as in every search."""
+        res = await self._search_matrix(user_id, sample, limit, filters, point_ids, seed, score_threshold)
+        return [] if res is None else _matrix.pairs(*res)
+
+    async def search_matrix_offsets(self, user_id: str, sample: int = 10, limit: int = 3, filters: Optional[Dict] = None,
+                                    point_ids=None, seed=None, score_threshold=None) -> MatrixOffsets:
+        """search_matrix_pairs in Qdrant's offsets form: MatrixOffsets(offsets_row, offsets_col, scores, ids), entry k
+        saying that ids[offsets_col[k]] is a neighbour of ids[offsets_row[k]]; `ids` = the sample in sample order.  Fewer
+        than two sample points give an empty response."""
+        res = await self._search_matrix(user_id, sample, limit, filters, point_ids, seed, score_threshold)
+        return MatrixOffsets([], [], [], []) if res is None else _matrix.offsets(*res)
 
     # ------------------------------------------------------------------------ collections
     async def get_all_containers(self) -> List[str]:
