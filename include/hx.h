@@ -787,6 +787,54 @@ int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* e
                       const uint32_t* mask_host, int64_t mask_rows, int32_t limit,
                       float* scores_host, int64_t* ids_host, int32_t* counts_host);
 
+/* ---- discovery and context search ------------------------------------
+ * Qdrant's DiscoverQuery(target, context = [ContextPair(positive, negative), ...]) and its target-less sibling
+ * ContextQuery (additive: the reference never calls them; parity unpinned, the semantics below are this project's
+ * statement of them): every context pair cuts the space in two, and the answer comes from the cell that agrees with the
+ * most pairs -- nearest the target there (discovery), or anywhere in it (context).  Additive to the ABI: HX_ABI_VERSION
+ * stays 3.
+ *
+ * A call carries R requests, 1 <= R <= HX_RECO_MAX_REQUESTS.  Request r has an optional target and P_r context pairs;
+ * its examples are the target first (when has_target_host[r] = 1), then pos_0, neg_0, pos_1, neg_1, ...: E_r = has_target
+ * + 2 P_r of them, 1 <= E_r <= HX_RECO_MAX_EXAMPLES (a target and 15 pairs, or 16 pairs) with E_r * dim_pad <= 32768
+ * floats.  P_r >= 1 without a target, P_r >= 0 with one.  An example is a stored row or a raw vector of dim finite fp32
+ * values, exactly as in hx_recommend: the same normalisation, sim(x, e) = the spec dot product over the padded width.
+ * Every operation below is one unfused fp32 operation, round to nearest; the division is the correctly rounded one.
+ *   fast_sigmoid(v) = v / (1.0f + |v|).
+ *   With a target (discovery): rank = +0.0f; for each pair in order rank = rank + c, c = +1.0f if sim(x, pos) >
+ *     sim(x, neg), -1.0f if it is less, 0.0f if they are equal.  score = rank + 0.5f * (fast_sigmoid(sim(x, target)) +
+ *     1.0f), then + 0.0f.
+ *   Without a target (context): acc = +0.0f; for each pair in order acc = acc + fast_sigmoid(min((sim(x, pos) -
+ *     sim(x, neg)) - 0x1p-23f, 0.0f)).  score = acc + 0.0f: exactly +0 for a row on the positive side of every pair.
+ * A row is excluded when it is a stored example of the same request or its bit is clear in the optional row mask (the
+ * layout and rules of hx_recommend; an example need not be kept by the mask).  Order: make_key(score, global id)
+ * descending -- score descending, id ascending; among the (many) rows a context search scores +0 the smallest ids win.
+ * Request r gets min(limit, rows not excluded) keys, the slots past them are 0; 1 <= limit <= HX_RECO_MAX_LIMIT; an empty
+ * index gives counts 0.
+ *
+ * ex_indptr_host [R + 1]; ex_rows_host [E] = a local row, or -1 = the next raw vector of ex_vecs_host ([n_raw x dim]
+ * fp32, in the order of the -1 entries; may be NULL when there is none); has_target_host [R] of 0 | 1.
+ * Refused before any device work, every output untouched: a NULL argument (the mask and an unneeded ex_vecs_host
+ * aside), R, E_r, limit or the LDS bound out of range, a request with neither target nor pair, a pair without its
+ * negative, has_target neither 0 nor 1, a row outside [0, hx_count), a non-finite raw element ("finite" in the message),
+ * mask_rows != hx_count with a mask.  hx_discover synchronises `stream` (the scan's overflow word, read once behind the
+ * scan).  hx_discover_host adds the unpacking and the copy out: scores_host / ids_host [R x limit], empty slots
+ * (-inf, -1); counts_host [R].
+ * The scan appends a row when its KEY beats the limit-th best key so far, so rows that tie the limit-th score cost
+ * nothing; rows ordered so that every chunk beats the threshold overflow a request's buffer, and the request is redone in
+ * fixed chunks -- the same list.  hx_discover_redone: how many requests of this index took that redo so far.
+ * HX_DEBUG_DISCOVER_CHUNK0 (rows of the scan's first chunk) and HX_DEBUG_DISCOVER_CAP (keys of a request's candidate
+ * buffer, at least 2 * limit) are read by hx_create, per index: tests. */
+int hx_discover(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
+                const float* ex_vecs_host, const int32_t* has_target_host,
+                const uint32_t* mask_dev, int64_t mask_rows, int32_t limit,
+                uint64_t* keys_dev /* [R x limit] */, int32_t* counts_dev /* [R] */, void* stream);
+int hx_discover_host(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
+                     const float* ex_vecs_host, const int32_t* has_target_host,
+                     const uint32_t* mask_host, int64_t mask_rows, int32_t limit,
+                     float* scores_host, int64_t* ids_host, int32_t* counts_host);
+int hx_discover_redone(hx_index* h, int64_t* requests);
+
 /* ---- distance matrix search ------------------------------------------
  * Qdrant's search_matrix_pairs / search_matrix_offsets (additive: the reference never calls them; parity unpinned, the
  * semantics below are this project's statement of them): for every point of a sample, its nearest neighbours among the

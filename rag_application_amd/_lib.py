@@ -135,6 +135,9 @@ _SIGS = {
                                      C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P, _P, _P],
     "hx_recommend": [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
     "hx_recommend_host": [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
+    "hx_discover": [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
+    "hx_discover_host": [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P, _P, _P],
+    "hx_discover_redone": [_P, C.POINTER(C.c_int64)],
     "hx_search_matrix": [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P],
     "hx_search_matrix_host": [_P, _P, C.c_int32, C.c_int32, C.c_float, _P, _P, _P],
     "hx_payload_facet": [_P, C.c_int32, _P, C.c_int64, C.c_uint32, _P, _P, _P],

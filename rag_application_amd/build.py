@@ -21,7 +21,8 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("paynested.hip", "paynested.o", ()),
            ("group.hip", "group.o", ()), ("mmr.hip", "mmr.o", ()), ("maxsim.hip", "maxsim.o", ()),
            ("formula.hip", "formula.o", ()),
-           ("facet.hip", "facet.o", ()), ("reco.hip", "reco.o", ()), ("matrix.hip", "matrix.o", ()),
+           ("facet.hip", "facet.o", ()), ("reco.hip", "reco.o", ()), ("discover.hip", "discover.o", ()),
+           ("matrix.hip", "matrix.o", ()),
            ("scroll.hip", "scroll.o", ()),
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),
            ("paystore.hip", "paystore.o", ()), ("bm25.cpp", "bm25.o", ())]

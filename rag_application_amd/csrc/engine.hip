@@ -1853,6 +1853,160 @@ static void recommend_dev(hx_index* h, int strategy, int R, const RecoCall& c_in
 }
 
 // ---------------------------------------------------------------------------------
+// discovery and context search (hx_discover)
+// ---------------------------------------------------------------------------------
+// every refusal of the call, before any device work.  The examples keep the order given (the target, then the pairs);
+// RecoReq.n_pos = 1 when the request has a target.
+static RecoCall discover_check(hx_index* h, int R, const int64_t* indptr, const int64_t* rows, const float* vecs,
+                               const int32_t* has_target, const void* mask, int64_t mask_rows, int limit) {
+  HX_CHECK(h && indptr && rows && has_target, "NULL argument");
+  HX_CHECK(R >= 1 && R <= HX_RECO_MAX_REQUESTS, "discover: requests out of range [1, 16]");
+  HX_CHECK(limit >= 1 && limit <= HX_RECO_MAX_LIMIT, "discover: limit out of range [1, 1024]");
+  HX_CHECK(!mask || mask_rows == h->n, "discover: mask_rows must equal the index's row count (hx_count)");
+  HX_CHECK(indptr[0] == 0, "discover: bad example indptr");
+  RecoCall c;
+  for (int r = 0; r < R; ++r) {
+    const int64_t b = indptr[r], e = indptr[r + 1];
+    HX_CHECK(has_target[r] == 0 || has_target[r] == 1, "discover: has_target must be 0 or 1");
+    HX_CHECK(e - b >= 1, "discover: a request needs a target or a context pair");
+    HX_CHECK(e - b <= HX_RECO_MAX_EXAMPLES, "discover: a request takes at most 32 examples (the target and two per pair)");
+    HX_CHECK((e - b - has_target[r]) % 2 == 0, "discover: context examples come in pairs (positive, negative)");
+    HX_CHECK((e - b) * h->dim_pad <= RECO_LDS_FLOATS, "discover: examples x padded width above 32768 floats");
+    RecoReq q{};
+    q.ex0 = (int)c.src.size();
+    q.excl0 = (int)c.excl.size();
+    q.slot = r;
+    q.n_pos = has_target[r];
+    q.n_ex = (int)(e - b);
+    for (int64_t i = b; i < e; ++i) {
+      if (rows[i] == -1) {
+        HX_CHECK(vecs != nullptr, "NULL argument");
+        const float* v = vecs + (int64_t)c.n_raw * h->dim;
+        for (int k = 0; k < h->dim; ++k) HX_CHECK(std::isfinite(v[k]), "discover: example vector values must be finite");
+        c.src.push_back(-1 - (int64_t)c.n_raw++);
+      } else {
+        HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "discover: example row out of range");
+        c.src.push_back(rows[i]);
+        c.excl.push_back((uint32_t)rows[i]);
+      }
+    }
+    std::sort(c.excl.begin() + q.excl0, c.excl.end());
+    c.excl.erase(std::unique(c.excl.begin() + q.excl0, c.excl.end()), c.excl.end());
+    q.n_excl = (int)c.excl.size() - q.excl0;
+    c.max_excl = std::max(c.max_excl, q.n_excl);
+    c.req.push_back(q);
+  }
+  return c;
+}
+
+// count_known: the kept rows of the mask when the caller counted them (the host entry), -1 otherwise.  Keys leave with
+// internal ids.  Synchronises `st`.
+static void discover_dev(hx_index* h, int R, const RecoCall& c_in, const float* vecs, const uint32_t* mask_dev,
+                         int64_t count_known, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
+  if (h->n == 0 || count_known == 0) {
+    zero_outputs(out_keys, out_cnt, R, L, st);
+    HX_HIP(hipStreamSynchronize(st));
+    return;
+  }
+  RecoCall c = c_in;
+  const int E = (int)c.src.size(), dp = h->dim_pad;
+  // the scan's launches, the upload and the example matrix: as recommend_dev makes them
+  std::vector<std::pair<int, int>> groups;
+  for (int r = 0, g0 = 0, used = 0; r < R; ++r) {
+    if ((int64_t)(used + c.req[r].n_ex) * dp > RECO_LDS_FLOATS) {
+      groups.push_back({g0, r});
+      g0 = r;
+      used = 0;
+    }
+    c.req[r].lds0 = used;
+    used += c.req[r].n_ex;
+    if (r == R - 1) groups.push_back({g0, R});
+  }
+  const size_t o_src = round_up(R * sizeof(RecoReq), 16), o_excl = o_src + round_up((size_t)E * 8, 16);
+  const size_t meta_bytes = o_excl + c.excl.size() * 4 + 16;
+  std::vector<uint8_t> meta(meta_bytes, 0);
+  std::memcpy(meta.data(), c.req.data(), R * sizeof(RecoReq));
+  std::memcpy(meta.data() + o_src, c.src.data(), (size_t)E * 8);
+  if (!c.excl.empty()) std::memcpy(meta.data() + o_excl, c.excl.data(), c.excl.size() * 4);
+  uint8_t* meta_dev = (uint8_t*)h->ws.get(WS_RECO_META, meta_bytes);
+  HX_HIP(hipMemcpyAsync(meta_dev, meta.data(), meta_bytes, hipMemcpyHostToDevice, st));
+  const RecoReq* req_dev = (const RecoReq*)meta_dev;
+  const uint32_t* excl_dev = (const uint32_t*)(meta_dev + o_excl);
+  float* raw_n = nullptr;
+  if (c.n_raw) {
+    float* raw = (float*)h->ws.get(WS_RECO_RAW, (size_t)c.n_raw * h->dim * 4);
+    raw_n = (float*)h->ws.get(WS_RECO_RAWN, (size_t)c.n_raw * dp * 4);
+    HX_HIP(hipMemcpyAsync(raw, vecs, (size_t)c.n_raw * h->dim * 4, hipMemcpyHostToDevice, st));
+    launch_prep_queries_f(raw, h->dim, c.n_raw, c.n_raw, h->dim, dp, raw_n, nullptr, st);
+  }
+  float* X = (float*)h->ws.get(WS_RECO_X, (size_t)E * dp * 4);
+  launch_reco_examples(h->dense, raw_n, (const int64_t*)(meta_dev + o_src), E, dp, X, st);
+
+  // The exhaustive scan in geometric chunks with a non-predictive threshold ON THE KEY: the first chunk, at most the
+  // buffer's capacity, passes every row (tau_key = 0); every compaction keeps the best L, sorted, and k_discover_tau sets
+  // tau_key to the L-th of them.  Chunks ascend in row order, so a later row that ties the L-th score has a larger id, a
+  // smaller key, and is not appended: a collection of tied scores appends what one of distinct scores appends.
+  int C = std::clamp(next_pow2(8 * L), 2048, CAND_CAP);
+  if (h->discover_cap) C = std::max(h->discover_cap, 2 * L);
+  const int64_t chunk0 = h->discover_chunk0 ? std::min(h->discover_chunk0, C) : C;
+  uint64_t* cand = (uint64_t*)h->ws.get(WS_RECO_CAND, (size_t)R * C * 8);
+  int* cnt = (int*)h->ws.get(WS_RECO_CNT, (size_t)R * 4);
+  int* ovf = (int*)h->ws.get(WS_RECO_OVF, (size_t)R * 4);
+  uint64_t* tau = (uint64_t*)h->ws.get(WS_DISC_TAU, (size_t)R * 8);
+  uint64_t* tau0 = (uint64_t*)h->ws.get(WS_DISC_TAU0, (size_t)R * 8);   // stays 0: the redo's threshold
+  HX_HIP(hipMemsetAsync(cnt, 0, (size_t)R * 4, st));
+  HX_HIP(hipMemsetAsync(ovf, 0, (size_t)R * 4, st));
+  HX_HIP(hipMemsetAsync(tau, 0, (size_t)R * 8, st));
+  HX_HIP(hipMemsetAsync(tau0, 0, (size_t)R * 8, st));
+  DiscoverScanArgs a{};
+  a.dense = h->dense;
+  a.dim_pad = dp;
+  a.X = X;
+  a.excl = excl_dev;
+  a.mask = mask_dev;
+  a.cand = cand;
+  a.cnt = cnt;
+  a.ovf = ovf;
+  a.cap = C;
+  a.id_base = (uint32_t)h->id_base;
+  const auto scan = [&](int g0, int g1, int64_t r0, int64_t r1, const uint64_t* t) {
+    a.req = req_dev + g0;
+    a.n_req = g1 - g0;
+    a.row_begin = r0;
+    a.row_end = r1;
+    a.tau_key = t;
+    launch_discover_scan(a, c.req[g1 - 1].lds0 + c.req[g1 - 1].n_ex, st);
+  };
+  for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
+    for (const auto& g : groups) scan(g.first, g.second, r0, r1, tau);
+    launch_compact(cand, C, cnt, R, L, 0, cand, C, cnt, nullptr, C, st);
+    launch_discover_tau(cand, C, cnt, R, L, tau, st);
+    r0 = r1;
+    r1 = std::min<int64_t>(h->n, 2 * r1);
+  }
+  // the overflow word, read once behind the scan
+  std::vector<int> flagged((size_t)R);
+  HX_HIP(hipMemcpyAsync(flagged.data(), ovf, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  // A request whose buffer overflowed (rows ordered so that every chunk beats the threshold): again in fixed chunks of
+  // C - L rows, every row appended, a compaction after each -- the same list by construction.
+  for (int r = 0; r < R; ++r) {
+    if (!flagged[(size_t)r]) continue;
+    ++h->discover_redone;
+    c.req[r].lds0 = 0;
+    HX_HIP(hipMemcpyAsync(meta_dev + r * sizeof(RecoReq), &c.req[r], sizeof(RecoReq), hipMemcpyHostToDevice, st));
+    HX_HIP(hipMemsetAsync(cnt + r, 0, 4, st));
+    for (int64_t r0 = 0; r0 < h->n; r0 += C - L) {
+      scan(r, r + 1, r0, std::min<int64_t>(h->n, r0 + (C - L)), tau0);
+      launch_compact(cand + (int64_t)r * C, C, cnt + r, 1, L, 0, cand + (int64_t)r * C, C, cnt + r, nullptr, C, st);
+    }
+  }
+  HX_HIP(hipMemcpy2DAsync(out_keys, (size_t)L * 8, cand, (size_t)C * 8, (size_t)L * 8, (size_t)R, hipMemcpyDeviceToDevice, st));
+  HX_HIP(hipMemcpyAsync(out_cnt, cnt, (size_t)R * 4, hipMemcpyDeviceToDevice, st));
+  HX_HIP(hipStreamSynchronize(st));
+}
+
+// ---------------------------------------------------------------------------------
 // distance matrix search (hx_search_matrix)
 // ---------------------------------------------------------------------------------
 // every refusal of the call, before any device work; the sample as the kernels take it
@@ -1948,6 +2102,8 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_PAY_GRID")) h->pay_grid = (int)std::clamp<long long>(atoll(e), 0, 1 << 20);   // tests: the grid-stride loop
   if (const char* e = getenv("HX_DEBUG_RECO_CHUNK0")) h->reco_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the recommend scan's chunks
   if (const char* e = getenv("HX_DEBUG_RECO_CAP")) h->reco_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
+  if (const char* e = getenv("HX_DEBUG_DISCOVER_CHUNK0")) h->discover_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the discover scan's chunks
+  if (const char* e = getenv("HX_DEBUG_DISCOVER_CAP")) h->discover_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
   if (const char* e = getenv("HX_DEBUG_MATRIX_SCAN_ONLY")) h->matrix_scan_only = atoi(e) != 0;             // diagnostics: the matrix scan's own time
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);
@@ -3522,6 +3678,65 @@ int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* e
   HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
   HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_discover(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host, const float* ex_vecs_host,
+                const int32_t* has_target_host, const uint32_t* mask_dev, int64_t mask_rows, int32_t limit,
+                uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(keys_dev && counts_dev, "NULL argument");
+  const RecoCall c = discover_check(h, R, ex_indptr_host, ex_rows_host, ex_vecs_host, has_target_host, mask_dev, mask_rows,
+                                    limit);
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  discover_dev(h, R, c, ex_vecs_host, mask_dev, -1, limit, keys_dev, counts_dev, st);
+  remap_out(h, keys_dev, (int64_t)R * limit, st);
+  HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_discover_host(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
+                     const float* ex_vecs_host, const int32_t* has_target_host, const uint32_t* mask_host, int64_t mask_rows,
+                     int32_t limit, float* scores_host, int64_t* ids_host, int32_t* counts_host) {
+  HX_TRY
+  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
+  const RecoCall c = discover_check(h, R, ex_indptr_host, ex_rows_host, ex_vecs_host, has_target_host, mask_host, mask_rows,
+                                    limit);
+  h->set_device();
+  hipStream_t st = nullptr;
+  const int64_t n_out = (int64_t)R * limit;
+  uint32_t* mask_dev = nullptr;
+  int64_t kept = -1;
+  if (mask_host) {                      // the count from the host mask: no read-back
+    const int64_t nw = (h->n + 31) / 32;
+    kept = 0;
+    for (int64_t w = 0; w < nw; ++w) {
+      uint32_t m = mask_host[w];
+      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
+      kept += __builtin_popcount(m);
+    }
+    mask_dev = (uint32_t*)h->ws.get(WS_RECO_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
+    HX_HIP(hipMemcpyAsync(mask_dev, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+  }
+  uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_OUT, (size_t)n_out * 8);
+  int* cnt = (int*)h->ws.get(WS_RECO_OCNT, (size_t)R * 4);
+  float* sc = (float*)h->ws.get(WS_RECO_SC, (size_t)n_out * 4);
+  int64_t* id = (int64_t*)h->ws.get(WS_RECO_ID, (size_t)n_out * 8);
+  discover_dev(h, R, c, ex_vecs_host, mask_dev, kept, limit, keys, cnt, st);
+  remap_out(h, keys, n_out, st);
+  launch_unpack(keys, n_out, sc, id, st);
+  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipStreamSynchronize(st));
+  HX_CATCH
+}
+
+int hx_discover_redone(hx_index* h, int64_t* requests) {
+  HX_TRY
+  HX_CHECK(h && requests, "NULL argument");
+  *requests = h->discover_redone;
   HX_CATCH
 }
 

@@ -53,7 +53,8 @@ enum WsSlot {
   WS_RECO_OVF, WS_RECO_TAU, WS_RECO_TAU0, WS_RECO_MASK, WS_RECO_OUT, WS_RECO_OCNT, WS_RECO_SC, WS_RECO_ID,
   WS_SCROLL_WORK, WS_SCROLL_MASK, WS_SCROLL_OUT,
   WS_FORMULA_PLANES, WS_FORMULA_KEYS, WS_FORMULA_POS, WS_FORMULA_BASE, WS_FORMULA_CNT, WS_FORMULA_DROP,
-  WS_MATRIX_ROWS, WS_MATRIX_PLANE, WS_MATRIX_OUT, WS_MATRIX_OCNT, WS_MATRIX_SC, WS_MATRIX_ID
+  WS_MATRIX_ROWS, WS_MATRIX_PLANE, WS_MATRIX_OUT, WS_MATRIX_OCNT, WS_MATRIX_SC, WS_MATRIX_ID,
+  WS_DISC_TAU, WS_DISC_TAU0
 };
 
 template <typename T>
@@ -234,6 +235,9 @@ struct hx_index {
   std::vector<PayCol> pay;
   int reco_chunk0 = 0;                // HX_DEBUG_RECO_CHUNK0 (tests): rows of the first chunk of the recommend scan, 0 = the buffer's capacity
   int reco_cap = 0;                   // HX_DEBUG_RECO_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
+  int discover_chunk0 = 0;            // HX_DEBUG_DISCOVER_CHUNK0 (tests): rows of the first chunk of the discover scan, 0 = the buffer's capacity
+  int discover_cap = 0;               // HX_DEBUG_DISCOVER_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
+  int64_t discover_redone = 0;        // hx_discover_redone: requests that went through the overflow redo
   bool matrix_scan_only = false;      // HX_DEBUG_MATRIX_SCAN_ONLY (scripts/matrix_bench.py): hx_search_matrix stops behind k_matrix_scan, the outputs zeroed
   int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap
   int pay_next_id = 0;

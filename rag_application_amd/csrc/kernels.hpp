@@ -659,6 +659,30 @@ struct RecoScanArgs {
 };
 // lds_examples = examples staged by the launch (sum of its requests' n_ex): sizes the LDS request and the grid
 void launch_reco_scan(const RecoScanArgs& a, int lds_examples, hipStream_t st);
+// ---- discover.hip: discovery and context search (hx_discover) ------------------------------------
+// The examples lie in reco.hip's matrix X; a request's are its target (RecoReq.n_pos = 1) or none (n_pos = 0), then
+// pos_0, neg_0, pos_1, neg_1, ...  The exhaustive scan of rows [row_begin, row_end) for the n_req requests
+// req[0 .. n_req): a row that is not excluded and whose KEY make_key(score, id_base + row) is > tau_key[slot] is appended
+// to cand[slot * cap + atomicAdd(cnt[slot])]; ovf[slot] = 1 when the buffer is full.
+struct DiscoverScanArgs {
+  const float* dense;      // the normalised fp32 rows, dim_pad floats each (a multiple of 64, at most 4096)
+  int dim_pad;
+  int64_t row_begin, row_end;
+  const float* X;
+  const RecoReq* req;      // device
+  int n_req;
+  const uint32_t* excl;    // device
+  const uint32_t* mask;    // packed row mask, NULL = every row
+  const uint64_t* tau_key; // per slot: the limit-th best key so far, 0 = none yet (every key passes)
+  uint64_t* cand;
+  int* cnt;
+  int* ovf;
+  int cap;
+  uint32_t id_base;
+};
+void launch_discover_scan(const DiscoverScanArgs& a, int lds_examples, hipStream_t st);
+// tau_key[r] = cand[r * cap + limit - 1] when cnt[r] >= limit (lists sorted by launch_compact), else 0; R <= 64
+void launch_discover_tau(const uint64_t* cand, int cap, const int* cnt, int R, int limit, uint64_t* tau_key, hipStream_t st);
 // ---- matrix.hip: distance matrix search (hx_search_matrix) ----------------------------------------
 // The sample is S local rows, rows[0 .. S) on the device; nothing but those rows of `dense` is read.
 struct MatrixArgs {

@@ -977,6 +977,70 @@ class HxIndex:
                                            _ptr(words), mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores[:R], ids[:R], counts[:R]
 
+    # -- discovery and context search (hx.h: hx_discover / hx_discover_host) --------------------------
+    def _discover_examples(self, requests):
+        """requests: per request (target | None, [(pos, neg), ...]) -- an example = a local row (an int) or a vector of
+        `dim` numbers -> (indptr int64 [R + 1], rows int64 [E] with -1 for a raw vector, vecs float32 [n_raw, dim] or
+        None, has_target int32 [R]), as hx_discover takes them: the target first, then pos_0, neg_0, pos_1, ..."""
+        indptr, rows, vecs, has_target = [0], [], [], []
+        for target, pairs in requests:
+            flat = [] if target is None else [target]
+            for pair in pairs:
+                pos, neg = pair
+                flat += [pos, neg]
+            for ex in flat:
+                if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+                    rows.append(int(ex))
+                else:
+                    v = np.asarray(ex, dtype=np.float32).reshape(-1)
+                    if v.shape[0] != self.dim:
+                        raise HxError(f"discover: an example vector of {v.shape[0]} values, the index holds {self.dim}")
+                    rows.append(-1)
+                    vecs.append(v)
+            has_target.append(0 if target is None else 1)
+            indptr.append(len(rows))
+        return (np.asarray(indptr, np.int64), np.asarray(rows, np.int64).reshape(-1),
+                np.ascontiguousarray(np.stack(vecs)) if vecs else None, np.asarray(has_target, np.int32).reshape(-1))
+
+    def discover(self, requests, limit: int, mask=None, keys=None, counts=None):
+        """Discovery (a target and context pairs) and context search (pairs only) in one exact scan (hx_discover):
+        requests as _discover_examples takes them, mask = None or a row mask as hybrid_query takes it.  Returns (keys
+        [R, limit] int64, counts [R] int32) on the device (keys / counts: tensors to write into); the call synchronises."""
+        indptr, rows, vecs, has_target = self._discover_examples(requests)
+        R, L = len(indptr) - 1, int(limit)
+        if keys is None or counts is None:
+            keys, counts = self._out(max(R, 1), L if 1 <= L <= 1024 else 1)   # (the engine refuses; nothing huge is allocated)
+        words, mrows = None, 0
+        if mask is not None:
+            if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
+                words, mrows = mask, self.count()
+            else:
+                packed, mrows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
+                words = torch.from_numpy(packed.view(np.int32)).to(keys.device)
+        check(_lib.lib().hx_discover(self._h, R, _ptr(indptr), _ptr(rows), _ptr(vecs), _ptr(has_target), _ptr(words), mrows,
+                                     L, _ptr(keys), _ptr(counts), _stream()))
+        return keys, counts
+
+    def discover_host(self, requests, limit: int, mask=None):
+        """discover, host in, host out (hx_discover_host): (scores [R, limit] float32, ids [R, limit] int64, counts [R]
+        int32), the slots past a request's count (-inf, -1)."""
+        indptr, rows, vecs, has_target = self._discover_examples(requests)
+        R, L = len(indptr) - 1, int(limit)
+        slots = L if 1 <= L <= 1024 else 1
+        scores = np.empty((max(R, 1), slots), dtype=np.float32)
+        ids = np.empty((max(R, 1), slots), dtype=np.int64)
+        counts = np.empty((max(R, 1),), dtype=np.int32)
+        words, mrows = (None, 0) if mask is None else self._mask(mask)
+        check(_lib.lib().hx_discover_host(self._h, R, _ptr(indptr), _ptr(rows), _ptr(vecs), _ptr(has_target), _ptr(words),
+                                          mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
+        return scores[:R], ids[:R], counts[:R]
+
+    def discover_redone(self) -> int:
+        """requests of this index that overflowed their candidate buffer and were redone in fixed chunks, so far"""
+        n = C.c_int64(0)
+        check(_lib.lib().hx_discover_redone(self._h, C.byref(n)))
+        return int(n.value)
+
     # -- distance matrix search (hx.h: hx_search_matrix / hx_search_matrix_host; DESIGN.md section 28) ----------------------
     @staticmethod
     def _matrix_args(rows, limit, score_threshold):

@@ -591,6 +591,8 @@ class QdrantHandler:
     _boost_search = True
     # recommend scans the rows of ONE engine index and looks its examples up in this process's ids
     _recommend = True
+    # discover scans the rows of ONE engine index and looks its examples up in this process's ids
+    _discover = True
     # scroll pages the rows of ONE engine index and the ids and payloads this process holds
     _scroll = True
     # search_matrix_pairs / _offsets compare rows of ONE engine index with each other
@@ -1484,6 +1486,97 @@ class QdrantHandler:
         negative ones, the examples themselves left out."""
         res = await self.recommend_batch(user_id, [{"positive": positive, "negative": negative, "strategy": strategy}],
                                          limit=limit, filters=filters)
+        return res[0] if res else []
+
+    # ------------------------------------------------------------------------ discovery / context
+    def _discover_sync(self, user_id, requests, limit, filters):
+        if not self._discover:
+            raise ValueError("discover is not supported on a sharded collection")
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= RECO_MAX_LIMIT:
+            raise ValueError(f"limit must be an integer in [1, {RECO_MAX_LIMIT}], got {limit!r}")
+        requests = list(requests)
+        if not 1 <= len(requests) <= RECO_MAX_REQUESTS:
+            raise ValueError(f"a discover batch takes 1 to {RECO_MAX_REQUESTS} requests, got {len(requests)}")
+        col = self._collections[str(user_id)]
+        dim_pad = (col.dim + 63) // 64 * 64
+        id_rows = None
+
+        def example(ex):
+            nonlocal id_rows
+            if isinstance(ex, (str, int)) and not isinstance(ex, bool):   # a point id -> its stored row
+                if id_rows is None:
+                    id_rows = col._id_rows()
+                    if id_rows is None:                      # an id held twice: the first row that holds it
+                        id_rows = {}
+                        for r, pid in enumerate(col.ids):
+                            id_rows.setdefault(pid, r)
+                if str(ex) not in id_rows:
+                    raise ValueError(f"discover: unknown point id {ex!r}")
+                return id_rows[str(ex)]
+            try:
+                v = np.asarray(ex, dtype=np.float32).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError("discover: an example is a point id or a vector of numbers") from None
+            if v.shape[0] != col.dim:
+                raise ValueError(f"example dimension {v.shape[0]} != collection dimension {col.dim}")
+            if not np.isfinite(v).all():
+                raise ValueError("discover: example vector values must be finite")
+            return v
+
+        packed = []
+        for req in requests:
+            target, context = req.get("target"), req.get("context")
+            if context is not None and not isinstance(context, (list, tuple)):
+                raise ValueError('discover: context is a list of pairs {"positive": x, "negative": y}')
+            context = [] if context is None else list(context)
+            pairs = []
+            for pair in context:
+                if not isinstance(pair, dict) or set(pair) != {"positive", "negative"} \
+                        or pair["positive"] is None or pair["negative"] is None:
+                    raise ValueError('discover: a context pair is {"positive": x, "negative": y}')
+                pairs.append((example(pair["positive"]), example(pair["negative"])))
+            if target is None and not pairs:
+                raise ValueError("discover: a request needs a target or a context pair")
+            n_ex = (target is not None) + 2 * len(pairs)
+            if n_ex > RECO_MAX_EXAMPLES or n_ex * dim_pad > 32768:
+                raise ValueError(f"discover: too many examples ({n_ex}, the target and two per pair): at most "
+                                 f"{RECO_MAX_EXAMPLES}, and examples x padded width at most 32768 (width {dim_pad})")
+            packed.append((None if target is None else example(target), pairs))
+        mask = None
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+            mask = col.row_mask(filters)
+        scores, rows, counts = col.index.discover_host(packed, limit, mask=mask)
+        cids, cpay = col.ids, col.payloads
+        return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+                for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist())]
+
+    async def discover_batch(self, user_id: str, requests, limit: int = 10,
+                             filters: Optional[Dict] = None) -> List[List[ScoredPoint]]:
+        """Qdrant's DiscoverQuery / ContextQuery for up to 16 requests in one engine call (additive; DESIGN.md section
+        29).  A request is a dict {"target": x | None, "context": [{"positive": x, "negative": y}, ...]}; x and y are each
+        a point id (looked up in the collection, it becomes a stored row) or a vector of `dim` numbers.  With a target
+        (discovery) the hits come from the cell that agrees with the most pairs, nearest the target first; without one
+        (context search) `score` is 0 for every point on the positive side of every pair and negative elsewhere, equal
+        scores in the order the points were stored.  Examples given as point ids are never returned; `filters` keeps only
+        the rows the filter keeps -- an example need not pass it.  include/hx.h states the arithmetic.  All of it runs on
+        the device (hx_discover_host); there is no Python path.  Raises ValueError for arguments no search can serve (an
+        unknown point id, neither target nor pair, a malformed pair, too many examples, a limit outside [1, 1024], a
+        vector of the wrong length or with a non-finite element, a sharded collection); any other failure is logged and
+        gives [], as in every search."""
+        try:
+            return await self._run(self._discover_sync, user_id, requests, limit, filters)
+        except ValueError as ve:
+            logging.error("discover for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("discover for %s failed: %s", user_id, e)
+            return []
+
+    async def discover(self, user_id: str, target=None, context=(), limit: int = 10,
+                       filters: Optional[Dict] = None) -> List[ScoredPoint]:
+        """One request of discover_batch; target=None is context search."""
+        res = await self.discover_batch(user_id, [{"target": target, "context": context}], limit=limit, filters=filters)
         return res[0] if res else []
 
     # ------------------------------------------------------------------------ distance matrix

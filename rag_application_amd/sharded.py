@@ -479,6 +479,7 @@ class ShardedHandler(QdrantHandler):
     _late_rerank = False             # create_token_index / hybrid_search_rerank raise ValueError: token columns likewise
     _boost_search = False            # hybrid_search_boost raises ValueError: nothing is sent to the ranks
     _recommend = False               # recommend / recommend_batch raise ValueError: nothing is sent to the ranks
+    _discover = False                # discover / discover_batch raise ValueError: nothing is sent to the ranks
     _scroll = False                  # scroll / retrieve raise ValueError: the rows of a collection lie in several indexes
     _matrix_search = False           # search_matrix_pairs / _offsets raise ValueError: a sample's rows lie in several indexes
 
