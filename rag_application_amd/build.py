@@ -25,7 +25,8 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("matrix.hip", "matrix.o", ()),
            ("scroll.hip", "scroll.o", ()),
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),
-           ("paystore.hip", "paystore.o", ()), ("bm25.cpp", "bm25.o", ())]
+           ("paystore.hip", "paystore.o", ()), ("poolstage.hip", "poolstage.o", ()), ("byexample.hip", "byexample.o", ()),
+           ("bm25.cpp", "bm25.o", ())]
 HEADERS = ["hx_common.hpp", "index.hpp", "kernels.hpp", "replace.hpp", "wsort.hpp",
            os.path.join("..", "..", "include", "hx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",

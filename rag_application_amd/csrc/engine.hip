@@ -4,7 +4,8 @@
 // (app/core/vector_store/qdrant/qdrant_handler.py:296-372) as launches on one HIP
 // stream.  See include/hx.h for the boundary and DESIGN.md for the algorithms.
 // The state of a collection (struct hx_index) is in index.hpp; what removes or rewrites stored rows is in
-// lifecycle.hip, the payload index in paystore.hip.
+// lifecycle.hip, the payload index in paystore.hip, the stages over the query's pool and the *_host query entries in
+// poolstage.hip, the searches by example (recommend, discover, distance matrix) in byexample.hip.
 #include "index.hpp"
 
 #include <algorithm>
@@ -307,14 +308,14 @@ static void ids_upload(hx_index* h) {
   b.dirty = false;
 }
 // keys a stage hands out: internal ids -> global ids, in place
-static void remap_out(hx_index* h, uint64_t* keys, int64_t n, hipStream_t st) {
+void remap_out(hx_index* h, uint64_t* keys, int64_t n, hipStream_t st) {
   if (n <= 0 || ids_identity(h)) return;
   ids_upload(h);
   launch_remap_ids(keys, keys, n, h->ids.dev, h->ids.dev + h->ids.dev_cap, (int)h->ids.row0.size(),
                    (uint32_t)h->id_base, (uint32_t)h->n, 1, st);
 }
 // candidate keys a stage takes in: global ids -> internal ids (rows of other shards become empty slots)
-static const uint64_t* remap_in(hx_index* h, const uint64_t* keys, int64_t n, hipStream_t st, int slot = WS_ID_IN) {
+const uint64_t* remap_in(hx_index* h, const uint64_t* keys, int64_t n, hipStream_t st, int slot) {
   if (n <= 0 || ids_identity(h)) return keys;
   ids_upload(h);
   uint64_t* tmp = (uint64_t*)h->ws.get(slot, (size_t)n * 8);
@@ -469,7 +470,7 @@ static MatrixRef pick_matrix(hx_index* h, int prefix) {
   throw Error("unknown prefix size " + std::to_string(prefix));
 }
 
-static void zero_outputs(uint64_t* keys, int* cnt, int B, int L, hipStream_t st) {
+void zero_outputs(uint64_t* keys, int* cnt, int B, int L, hipStream_t st) {
   HX_HIP(hipMemsetAsync(keys, 0, (size_t)B * L * 8, st));
   HX_HIP(hipMemsetAsync(cnt, 0, (size_t)B * 4, st));
 }
@@ -1306,8 +1307,8 @@ static void search_sparse(hx_index* h, const int64_t* q_indptr, const int32_t* q
   sparse_resolve(h, q_indptr, q_idx, q_val, B, L, out_keys, out_cnt, st);
 }
 
-static void rescore(hx_index* h, const float* q_dev, int B, int prefix, const uint64_t* cand, int cstride,
-                    const int* ccnt, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
+void rescore(hx_index* h, const float* q_dev, int B, int prefix, const uint64_t* cand, int cstride,
+             const int* ccnt, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
   HX_CHECK(B > 0, "B must be positive");
   HX_CHECK(L >= 1 && L <= MAX_LIMIT, "limit out of range [1, 2048]");
   HX_CHECK(cstride >= 1 && cstride <= CAND_CAP, "candidate stride out of range");
@@ -1365,9 +1366,9 @@ static void ensure_side_stream(hx_index* h) {
   HX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
 }
 
-static void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix,
-                             const float* qv, int B, const hx_params* p, uint64_t* out_keys, int* out_cnt,
-                             hipStream_t st, bool tree_sync = false) {
+void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix,
+                      const float* qv, int B, const hx_params* p, uint64_t* out_keys, int* out_cnt,
+                      hipStream_t st, bool tree_sync) {
   // A batch beyond 4096 queries goes through in equal slices: the scan's threshold table and the sparse launch
   // plan end there (measured on 10M x 768: B = 5000 in one piece 100 ms, in two slices 75 ms; slicing at 2048
   // instead changes nothing at 4096 and costs 3 % at 5000), and a slice reads the query CSR through the same offsets.
@@ -1640,12 +1641,53 @@ static bool with_mask_view(hx_index* h, const uint32_t* mask_dev, int64_t count_
 }
 
 // hybrid_query_dev restricted to the rows of mask_dev.  Keys leave with internal ids, as those of hybrid_query_dev.
-static void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
-                             const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
-                             int* out_cnt, hipStream_t st) {
+void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
+                      const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
+                      int* out_cnt, hipStream_t st) {
   if (!with_mask_view(h, mask_dev, count_known, true, st,
                       [&] { hybrid_query_dev(h, qd, qip, qix, qv, B, p, out_keys, out_cnt, st); }))
     zero_outputs(out_keys, out_cnt, B, p->final_limit, st);
+}
+
+// The dense stage over the rows of mask_dev (NULL = every row), with_mask_view's one use outside this file (the recommend
+// call's average route, byexample.hip); false, with nothing written, when the mask keeps no row.
+bool masked_dense_dev(hx_index* h, const float* q_dev, int B, int L, const uint32_t* mask_dev, int64_t count_known,
+                      uint64_t* out_keys, int* out_cnt, hipStream_t st) {
+  const auto run = [&] { search_dense(h, q_dev, B, 0, L, out_keys, out_cnt, st); };
+  return mask_dev ? with_mask_view(h, mask_dev, count_known, false, st, run) : (run(), true);
+}
+
+// ---- what every *_host entry does with a host mask and with its lists (poolstage.hip, byexample.hip) -------------------
+// the kept rows of a host mask: the caller's count, no read-back (bits past row n of the last word are not rows)
+int64_t host_mask_count(const hx_index* h, const uint32_t* mask_host) {
+  const int64_t nw = (h->n + 31) / 32;
+  int64_t kept = 0;
+  for (int64_t w = 0; w < nw; ++w) {
+    uint32_t m = mask_host[w];
+    if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
+    kept += __builtin_popcount(m);
+  }
+  return kept;
+}
+
+// a host mask into the workspace slot `slot`: its words on the device
+uint32_t* host_mask_upload(hx_index* h, const uint32_t* mask_host, int slot, hipStream_t st) {
+  const int64_t nw = (h->n + 31) / 32;
+  uint32_t* dm = (uint32_t*)h->ws.get(slot, (size_t)std::max<int64_t>(nw, 1) * 4);
+  if (nw) HX_HIP(hipMemcpyAsync(dm, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
+  return dm;
+}
+
+// keys [n] with internal ids, on the device -> the ids that cross the ABI, then scores and ids on the host.  Enqueues
+// only: the caller adds the copies of its own outputs and synchronises.
+void results_to_host(hx_index* h, uint64_t* keys, int64_t n, int sc_slot, int id_slot, float* scores, int64_t* ids,
+                     hipStream_t st) {
+  float* sc = (float*)h->ws.get(sc_slot, (size_t)n * 4);
+  int64_t* id = (int64_t*)h->ws.get(id_slot, (size_t)n * 8);
+  remap_out(h, keys, n, st);
+  launch_unpack(keys, n, sc, id, st);
+  HX_HIP(hipMemcpyAsync(scores, sc, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HX_HIP(hipMemcpyAsync(ids, id, (size_t)n * 8, hipMemcpyDeviceToHost, st));
 }
 
 // RRF settings: k finite and positive with 2 / k finite -- a document's two contributions
@@ -1658,7 +1700,7 @@ static void check_rrf(float k, int rank_base) {
   HX_CHECK(rank_base >= 0 && rank_base <= RRF_RANK_BASE_MAX, "rrf_rank_base must be in [0, 2^30]");
 }
 
-static void check_params(const hx_params* p) {
+void check_params(const hx_params* p) {
   HX_CHECK(p != nullptr, "params is NULL");
   HX_CHECK(p->mode == HX_MODE_TREE || p->mode == HX_MODE_H1, "unknown mode");
   check_rrf(p->rrf_k, p->rrf_rank_base);
@@ -1669,380 +1711,6 @@ static void check_params(const hx_params* p) {
                  ok(p->quantized_limit) && ok(p->rrf_limit),
              "limit out of range [1, 2048]");
   }
-}
-
-// ---------------------------------------------------------------------------------
-// recommend search (hx_recommend)
-// ---------------------------------------------------------------------------------
-// A call as the kernels take it: the examples request by request, positives first, each group in the order given.
-struct RecoCall {
-  std::vector<RecoReq> req;
-  std::vector<int64_t> src;       // per example: the stored row, or -1 - (index of the raw vector)
-  std::vector<uint32_t> excl;     // per request from excl0: its stored rows, ascending, unique
-  int n_raw = 0, max_excl = 0;
-};
-
-// every refusal of the call, before any device work
-static RecoCall reco_check(hx_index* h, int strategy, int R, const int64_t* indptr, const int64_t* rows, const int8_t* sign,
-                           const float* vecs, const void* mask, int64_t mask_rows, int limit) {
-  HX_CHECK(h && indptr && rows && sign, "NULL argument");
-  HX_CHECK(strategy == HX_RECO_AVERAGE || strategy == HX_RECO_BEST_SCORE || strategy == HX_RECO_SUM_SCORES,
-           "recommend: unknown strategy");
-  HX_CHECK(R >= 1 && R <= HX_RECO_MAX_REQUESTS, "recommend: requests out of range [1, 16]");
-  HX_CHECK(limit >= 1 && limit <= HX_RECO_MAX_LIMIT, "recommend: limit out of range [1, 1024]");
-  HX_CHECK(!mask || mask_rows == h->n, "recommend: mask_rows must equal the index's row count (hx_count)");
-  HX_CHECK(indptr[0] == 0, "recommend: bad example indptr");
-  RecoCall c;
-  for (int r = 0; r < R; ++r) {
-    const int64_t b = indptr[r], e = indptr[r + 1];
-    HX_CHECK(e - b >= 1 && e - b <= HX_RECO_MAX_EXAMPLES, "recommend: a request takes 1 to 32 examples");
-    HX_CHECK((e - b) * h->dim_pad <= RECO_LDS_FLOATS, "recommend: examples x padded width above 32768 floats");
-    RecoReq q{};
-    q.ex0 = (int)c.src.size();
-    q.excl0 = (int)c.excl.size();
-    q.slot = r;
-    std::vector<int64_t> raw_of((size_t)(e - b), -1);
-    for (int64_t i = b; i < e; ++i) {
-      HX_CHECK(sign[i] == 1 || sign[i] == -1, "recommend: a sign must be +1 or -1");
-      if (rows[i] == -1) {
-        HX_CHECK(vecs != nullptr, "NULL argument");
-        const float* v = vecs + (int64_t)c.n_raw * h->dim;
-        for (int k = 0; k < h->dim; ++k) HX_CHECK(std::isfinite(v[k]), "recommend: example vector values must be finite");
-        raw_of[(size_t)(i - b)] = c.n_raw++;
-      } else {
-        HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "recommend: example row out of range");
-        c.excl.push_back((uint32_t)rows[i]);
-      }
-    }
-    for (int s = 1; s >= -1; s -= 2)
-      for (int64_t i = b; i < e; ++i)
-        if (sign[i] == s) {
-          c.src.push_back(rows[i] == -1 ? -1 - raw_of[(size_t)(i - b)] : rows[i]);
-          if (s == 1) ++q.n_pos;
-        }
-    q.n_ex = (int)(e - b);
-    HX_CHECK(strategy != HX_RECO_AVERAGE || q.n_pos >= 1, "recommend: the average strategy needs a positive example");
-    std::sort(c.excl.begin() + q.excl0, c.excl.end());
-    c.excl.erase(std::unique(c.excl.begin() + q.excl0, c.excl.end()), c.excl.end());
-    q.n_excl = (int)c.excl.size() - q.excl0;
-    c.max_excl = std::max(c.max_excl, q.n_excl);
-    c.req.push_back(q);
-  }
-  return c;
-}
-
-// count_known: the kept rows of the mask when the caller counted them (the host entry), -1 otherwise.  Keys leave with
-// internal ids.  Synchronises `st`.
-static void recommend_dev(hx_index* h, int strategy, int R, const RecoCall& c_in, const float* vecs, const uint32_t* mask_dev,
-                          int64_t count_known, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
-  if (h->n == 0 || count_known == 0) {
-    zero_outputs(out_keys, out_cnt, R, L, st);
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  RecoCall c = c_in;
-  const int E = (int)c.src.size(), dp = h->dim_pad;
-  // The scan's launches: requests in order, as many as fit the LDS together -- the corpus is read once per launch.
-  std::vector<std::pair<int, int>> groups;   // [first request, end) and, in lds0, where each request's examples are staged
-  for (int r = 0, g0 = 0, used = 0; r < R; ++r) {
-    if ((int64_t)(used + c.req[r].n_ex) * dp > RECO_LDS_FLOATS) {
-      groups.push_back({g0, r});
-      g0 = r;
-      used = 0;
-    }
-    c.req[r].lds0 = used;
-    used += c.req[r].n_ex;
-    if (r == R - 1) groups.push_back({g0, R});
-  }
-  // one upload: the descriptors, the example sources, the excluded rows
-  const size_t o_src = round_up(R * sizeof(RecoReq), 16), o_excl = o_src + round_up((size_t)E * 8, 16);
-  const size_t meta_bytes = o_excl + c.excl.size() * 4 + 16;
-  std::vector<uint8_t> meta(meta_bytes, 0);
-  std::memcpy(meta.data(), c.req.data(), R * sizeof(RecoReq));
-  std::memcpy(meta.data() + o_src, c.src.data(), (size_t)E * 8);
-  if (!c.excl.empty()) std::memcpy(meta.data() + o_excl, c.excl.data(), c.excl.size() * 4);
-  uint8_t* meta_dev = (uint8_t*)h->ws.get(WS_RECO_META, meta_bytes);
-  HX_HIP(hipMemcpyAsync(meta_dev, meta.data(), meta_bytes, hipMemcpyHostToDevice, st));
-  const RecoReq* req_dev = (const RecoReq*)meta_dev;
-  const uint32_t* excl_dev = (const uint32_t*)(meta_dev + o_excl);
-  float* raw_n = nullptr;
-  if (c.n_raw) {   // raw vectors: the dense stage's query preparation (finite: checked on the host)
-    float* raw = (float*)h->ws.get(WS_RECO_RAW, (size_t)c.n_raw * h->dim * 4);
-    raw_n = (float*)h->ws.get(WS_RECO_RAWN, (size_t)c.n_raw * dp * 4);
-    HX_HIP(hipMemcpyAsync(raw, vecs, (size_t)c.n_raw * h->dim * 4, hipMemcpyHostToDevice, st));
-    launch_prep_queries_f(raw, h->dim, c.n_raw, c.n_raw, h->dim, dp, raw_n, nullptr, st);
-  }
-  float* X = (float*)h->ws.get(WS_RECO_X, (size_t)E * dp * 4);
-  launch_reco_examples(h->dense, raw_n, (const int64_t*)(meta_dev + o_src), E, dp, X, st);
-
-  if (strategy == HX_RECO_AVERAGE) {
-    // the dense stage, unchanged, for R queries and room for every stored example; then the examples are dropped
-    const int Lin = L + c.max_excl;
-    float* q = (float*)h->ws.get(WS_RECO_Q, (size_t)R * h->dim * 4);
-    uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_KEYS, (size_t)R * Lin * 8);
-    int* kcnt = (int*)h->ws.get(WS_RECO_KCNT, (size_t)R * 4);
-    launch_reco_average(X, req_dev, R, h->dim, dp, q, st);
-    const auto run = [&] { search_dense(h, q, R, 0, Lin, keys, kcnt, st); };
-    const bool any = mask_dev ? with_mask_view(h, mask_dev, count_known, false, st, run) : (run(), true);
-    if (any) launch_reco_drop(keys, Lin, kcnt, req_dev, excl_dev, (uint32_t)h->id_base, R, L, out_keys, out_cnt, st);
-    else zero_outputs(out_keys, out_cnt, R, L, st);
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-
-  // BEST_SCORE / SUM_SCORES: the exhaustive scan in geometric chunks with a non-predictive threshold, as chunked_scan:
-  // the first chunk passes every row (tau = -inf), every compaction keeps the best L and sets tau to the exact L-th score
-  // so far.  A doubling chunk of an exchangeable corpus appends about L ln 2 keys; the buffer takes C - L.
-  int C = std::clamp(next_pow2(8 * L), 2048, CAND_CAP);
-  if (h->reco_cap) C = std::max(h->reco_cap, 2 * L);
-  const int64_t chunk0 = h->reco_chunk0 ? std::min(h->reco_chunk0, C) : C;
-  uint64_t* cand = (uint64_t*)h->ws.get(WS_RECO_CAND, (size_t)R * C * 8);
-  int* cnt = (int*)h->ws.get(WS_RECO_CNT, (size_t)R * 4);
-  int* ovf = (int*)h->ws.get(WS_RECO_OVF, (size_t)R * 4);
-  float* tau = (float*)h->ws.get(WS_RECO_TAU, (size_t)R * 4);
-  float* tau0 = (float*)h->ws.get(WS_RECO_TAU0, (size_t)R * 4);   // stays -inf: the redo's threshold
-  HX_HIP(hipMemsetAsync(cnt, 0, (size_t)R * 4, st));
-  HX_HIP(hipMemsetAsync(ovf, 0, (size_t)R * 4, st));
-  launch_fill_f32(tau, R, -__builtin_inff(), st);
-  launch_fill_f32(tau0, R, -__builtin_inff(), st);
-  RecoScanArgs a{};
-  a.dense = h->dense;
-  a.dim_pad = dp;
-  a.X = X;
-  a.excl = excl_dev;
-  a.mask = mask_dev;
-  a.strategy = strategy;
-  a.cand = cand;
-  a.cnt = cnt;
-  a.ovf = ovf;
-  a.cap = C;
-  a.id_base = (uint32_t)h->id_base;
-  const auto scan = [&](int g0, int g1, int64_t r0, int64_t r1, const float* t) {
-    a.req = req_dev + g0;
-    a.n_req = g1 - g0;
-    a.row_begin = r0;
-    a.row_end = r1;
-    a.tau = t;
-    launch_reco_scan(a, c.req[g1 - 1].lds0 + c.req[g1 - 1].n_ex, st);
-  };
-  for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
-    for (const auto& g : groups) scan(g.first, g.second, r0, r1, tau);
-    launch_compact(cand, C, cnt, R, L, 0, cand, C, cnt, tau, C, st);
-    r0 = r1;
-    r1 = std::min<int64_t>(h->n, 2 * r1);
-  }
-  // the overflow word, read once behind the scan
-  std::vector<int> flagged((size_t)R);
-  HX_HIP(hipMemcpyAsync(flagged.data(), ovf, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
-  // A request whose buffer overflowed (a corpus ordered so that every chunk beats the threshold): again in fixed chunks of
-  // C - L rows, every row appended, a compaction after each -- as exact_range_fallback; the same list by construction.
-  for (int r = 0; r < R; ++r) {
-    if (!flagged[(size_t)r]) continue;
-    c.req[r].lds0 = 0;
-    HX_HIP(hipMemcpyAsync(meta_dev + r * sizeof(RecoReq), &c.req[r], sizeof(RecoReq), hipMemcpyHostToDevice, st));
-    HX_HIP(hipMemsetAsync(cnt + r, 0, 4, st));
-    for (int64_t r0 = 0; r0 < h->n; r0 += C - L) {
-      scan(r, r + 1, r0, std::min<int64_t>(h->n, r0 + (C - L)), tau0);
-      launch_compact(cand + (int64_t)r * C, C, cnt + r, 1, L, 0, cand + (int64_t)r * C, C, cnt + r, nullptr, C, st);
-    }
-  }
-  HX_HIP(hipMemcpy2DAsync(out_keys, (size_t)L * 8, cand, (size_t)C * 8, (size_t)L * 8, (size_t)R, hipMemcpyDeviceToDevice, st));
-  HX_HIP(hipMemcpyAsync(out_cnt, cnt, (size_t)R * 4, hipMemcpyDeviceToDevice, st));
-  HX_HIP(hipStreamSynchronize(st));
-}
-
-// ---------------------------------------------------------------------------------
-// discovery and context search (hx_discover)
-// ---------------------------------------------------------------------------------
-// every refusal of the call, before any device work.  The examples keep the order given (the target, then the pairs);
-// RecoReq.n_pos = 1 when the request has a target.
-static RecoCall discover_check(hx_index* h, int R, const int64_t* indptr, const int64_t* rows, const float* vecs,
-                               const int32_t* has_target, const void* mask, int64_t mask_rows, int limit) {
-  HX_CHECK(h && indptr && rows && has_target, "NULL argument");
-  HX_CHECK(R >= 1 && R <= HX_RECO_MAX_REQUESTS, "discover: requests out of range [1, 16]");
-  HX_CHECK(limit >= 1 && limit <= HX_RECO_MAX_LIMIT, "discover: limit out of range [1, 1024]");
-  HX_CHECK(!mask || mask_rows == h->n, "discover: mask_rows must equal the index's row count (hx_count)");
-  HX_CHECK(indptr[0] == 0, "discover: bad example indptr");
-  RecoCall c;
-  for (int r = 0; r < R; ++r) {
-    const int64_t b = indptr[r], e = indptr[r + 1];
-    HX_CHECK(has_target[r] == 0 || has_target[r] == 1, "discover: has_target must be 0 or 1");
-    HX_CHECK(e - b >= 1, "discover: a request needs a target or a context pair");
-    HX_CHECK(e - b <= HX_RECO_MAX_EXAMPLES, "discover: a request takes at most 32 examples (the target and two per pair)");
-    HX_CHECK((e - b - has_target[r]) % 2 == 0, "discover: context examples come in pairs (positive, negative)");
-    HX_CHECK((e - b) * h->dim_pad <= RECO_LDS_FLOATS, "discover: examples x padded width above 32768 floats");
-    RecoReq q{};
-    q.ex0 = (int)c.src.size();
-    q.excl0 = (int)c.excl.size();
-    q.slot = r;
-    q.n_pos = has_target[r];
-    q.n_ex = (int)(e - b);
-    for (int64_t i = b; i < e; ++i) {
-      if (rows[i] == -1) {
-        HX_CHECK(vecs != nullptr, "NULL argument");
-        const float* v = vecs + (int64_t)c.n_raw * h->dim;
-        for (int k = 0; k < h->dim; ++k) HX_CHECK(std::isfinite(v[k]), "discover: example vector values must be finite");
-        c.src.push_back(-1 - (int64_t)c.n_raw++);
-      } else {
-        HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "discover: example row out of range");
-        c.src.push_back(rows[i]);
-        c.excl.push_back((uint32_t)rows[i]);
-      }
-    }
-    std::sort(c.excl.begin() + q.excl0, c.excl.end());
-    c.excl.erase(std::unique(c.excl.begin() + q.excl0, c.excl.end()), c.excl.end());
-    q.n_excl = (int)c.excl.size() - q.excl0;
-    c.max_excl = std::max(c.max_excl, q.n_excl);
-    c.req.push_back(q);
-  }
-  return c;
-}
-
-// count_known: the kept rows of the mask when the caller counted them (the host entry), -1 otherwise.  Keys leave with
-// internal ids.  Synchronises `st`.
-static void discover_dev(hx_index* h, int R, const RecoCall& c_in, const float* vecs, const uint32_t* mask_dev,
-                         int64_t count_known, int L, uint64_t* out_keys, int* out_cnt, hipStream_t st) {
-  if (h->n == 0 || count_known == 0) {
-    zero_outputs(out_keys, out_cnt, R, L, st);
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  RecoCall c = c_in;
-  const int E = (int)c.src.size(), dp = h->dim_pad;
-  // the scan's launches, the upload and the example matrix: as recommend_dev makes them
-  std::vector<std::pair<int, int>> groups;
-  for (int r = 0, g0 = 0, used = 0; r < R; ++r) {
-    if ((int64_t)(used + c.req[r].n_ex) * dp > RECO_LDS_FLOATS) {
-      groups.push_back({g0, r});
-      g0 = r;
-      used = 0;
-    }
-    c.req[r].lds0 = used;
-    used += c.req[r].n_ex;
-    if (r == R - 1) groups.push_back({g0, R});
-  }
-  const size_t o_src = round_up(R * sizeof(RecoReq), 16), o_excl = o_src + round_up((size_t)E * 8, 16);
-  const size_t meta_bytes = o_excl + c.excl.size() * 4 + 16;
-  std::vector<uint8_t> meta(meta_bytes, 0);
-  std::memcpy(meta.data(), c.req.data(), R * sizeof(RecoReq));
-  std::memcpy(meta.data() + o_src, c.src.data(), (size_t)E * 8);
-  if (!c.excl.empty()) std::memcpy(meta.data() + o_excl, c.excl.data(), c.excl.size() * 4);
-  uint8_t* meta_dev = (uint8_t*)h->ws.get(WS_RECO_META, meta_bytes);
-  HX_HIP(hipMemcpyAsync(meta_dev, meta.data(), meta_bytes, hipMemcpyHostToDevice, st));
-  const RecoReq* req_dev = (const RecoReq*)meta_dev;
-  const uint32_t* excl_dev = (const uint32_t*)(meta_dev + o_excl);
-  float* raw_n = nullptr;
-  if (c.n_raw) {
-    float* raw = (float*)h->ws.get(WS_RECO_RAW, (size_t)c.n_raw * h->dim * 4);
-    raw_n = (float*)h->ws.get(WS_RECO_RAWN, (size_t)c.n_raw * dp * 4);
-    HX_HIP(hipMemcpyAsync(raw, vecs, (size_t)c.n_raw * h->dim * 4, hipMemcpyHostToDevice, st));
-    launch_prep_queries_f(raw, h->dim, c.n_raw, c.n_raw, h->dim, dp, raw_n, nullptr, st);
-  }
-  float* X = (float*)h->ws.get(WS_RECO_X, (size_t)E * dp * 4);
-  launch_reco_examples(h->dense, raw_n, (const int64_t*)(meta_dev + o_src), E, dp, X, st);
-
-  // The exhaustive scan in geometric chunks with a non-predictive threshold ON THE KEY: the first chunk, at most the
-  // buffer's capacity, passes every row (tau_key = 0); every compaction keeps the best L, sorted, and k_discover_tau sets
-  // tau_key to the L-th of them.  Chunks ascend in row order, so a later row that ties the L-th score has a larger id, a
-  // smaller key, and is not appended: a collection of tied scores appends what one of distinct scores appends.
-  int C = std::clamp(next_pow2(8 * L), 2048, CAND_CAP);
-  if (h->discover_cap) C = std::max(h->discover_cap, 2 * L);
-  const int64_t chunk0 = h->discover_chunk0 ? std::min(h->discover_chunk0, C) : C;
-  uint64_t* cand = (uint64_t*)h->ws.get(WS_RECO_CAND, (size_t)R * C * 8);
-  int* cnt = (int*)h->ws.get(WS_RECO_CNT, (size_t)R * 4);
-  int* ovf = (int*)h->ws.get(WS_RECO_OVF, (size_t)R * 4);
-  uint64_t* tau = (uint64_t*)h->ws.get(WS_DISC_TAU, (size_t)R * 8);
-  uint64_t* tau0 = (uint64_t*)h->ws.get(WS_DISC_TAU0, (size_t)R * 8);   // stays 0: the redo's threshold
-  HX_HIP(hipMemsetAsync(cnt, 0, (size_t)R * 4, st));
-  HX_HIP(hipMemsetAsync(ovf, 0, (size_t)R * 4, st));
-  HX_HIP(hipMemsetAsync(tau, 0, (size_t)R * 8, st));
-  HX_HIP(hipMemsetAsync(tau0, 0, (size_t)R * 8, st));
-  DiscoverScanArgs a{};
-  a.dense = h->dense;
-  a.dim_pad = dp;
-  a.X = X;
-  a.excl = excl_dev;
-  a.mask = mask_dev;
-  a.cand = cand;
-  a.cnt = cnt;
-  a.ovf = ovf;
-  a.cap = C;
-  a.id_base = (uint32_t)h->id_base;
-  const auto scan = [&](int g0, int g1, int64_t r0, int64_t r1, const uint64_t* t) {
-    a.req = req_dev + g0;
-    a.n_req = g1 - g0;
-    a.row_begin = r0;
-    a.row_end = r1;
-    a.tau_key = t;
-    launch_discover_scan(a, c.req[g1 - 1].lds0 + c.req[g1 - 1].n_ex, st);
-  };
-  for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
-    for (const auto& g : groups) scan(g.first, g.second, r0, r1, tau);
-    launch_compact(cand, C, cnt, R, L, 0, cand, C, cnt, nullptr, C, st);
-    launch_discover_tau(cand, C, cnt, R, L, tau, st);
-    r0 = r1;
-    r1 = std::min<int64_t>(h->n, 2 * r1);
-  }
-  // the overflow word, read once behind the scan
-  std::vector<int> flagged((size_t)R);
-  HX_HIP(hipMemcpyAsync(flagged.data(), ovf, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
-  // A request whose buffer overflowed (rows ordered so that every chunk beats the threshold): again in fixed chunks of
-  // C - L rows, every row appended, a compaction after each -- the same list by construction.
-  for (int r = 0; r < R; ++r) {
-    if (!flagged[(size_t)r]) continue;
-    ++h->discover_redone;
-    c.req[r].lds0 = 0;
-    HX_HIP(hipMemcpyAsync(meta_dev + r * sizeof(RecoReq), &c.req[r], sizeof(RecoReq), hipMemcpyHostToDevice, st));
-    HX_HIP(hipMemsetAsync(cnt + r, 0, 4, st));
-    for (int64_t r0 = 0; r0 < h->n; r0 += C - L) {
-      scan(r, r + 1, r0, std::min<int64_t>(h->n, r0 + (C - L)), tau0);
-      launch_compact(cand + (int64_t)r * C, C, cnt + r, 1, L, 0, cand + (int64_t)r * C, C, cnt + r, nullptr, C, st);
-    }
-  }
-  HX_HIP(hipMemcpy2DAsync(out_keys, (size_t)L * 8, cand, (size_t)C * 8, (size_t)L * 8, (size_t)R, hipMemcpyDeviceToDevice, st));
-  HX_HIP(hipMemcpyAsync(out_cnt, cnt, (size_t)R * 4, hipMemcpyDeviceToDevice, st));
-  HX_HIP(hipStreamSynchronize(st));
-}
-
-// ---------------------------------------------------------------------------------
-// distance matrix search (hx_search_matrix)
-// ---------------------------------------------------------------------------------
-// every refusal of the call, before any device work; the sample as the kernels take it
-static std::vector<uint32_t> matrix_check(hx_index* h, const int64_t* rows, int S, int limit, float threshold) {
-  HX_CHECK(h, "NULL argument");
-  HX_CHECK(S >= 1 && S <= HX_MATRIX_MAX_SAMPLE, "search_matrix: sample out of range [1, 4096]");
-  HX_CHECK(limit >= 1 && limit <= HX_MATRIX_MAX_LIMIT, "search_matrix: limit out of range [1, 1024]");
-  HX_CHECK(rows, "NULL argument");
-  HX_CHECK(!std::isnan(threshold), "search_matrix: the score threshold is NaN");
-  std::vector<uint32_t> r((size_t)S);
-  for (int i = 0; i < S; ++i) {
-    HX_CHECK(rows[i] >= 0 && rows[i] < h->n, "search_matrix: sample row out of range");
-    r[(size_t)i] = (uint32_t)rows[i];
-  }
-  std::vector<uint32_t> sorted = r;
-  std::sort(sorted.begin(), sorted.end());
-  HX_CHECK(std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end(), "search_matrix: a sample row is listed twice");
-  return r;
-}
-
-// Keys leave with internal ids.  Synchronises `st` (the row list is uploaded from this frame).
-static void search_matrix_dev(hx_index* h, const std::vector<uint32_t>& rows, int L, float threshold, uint64_t* out_keys,
-                              int* out_cnt, hipStream_t st) {
-  const int S = (int)rows.size();
-  MatrixArgs a{};
-  a.dense = h->dense;
-  a.S = S;
-  a.dim_pad = h->dim_pad;
-  uint32_t* rows_dev = (uint32_t*)h->ws.get(WS_MATRIX_ROWS, (size_t)S * 4);
-  HX_HIP(hipMemcpyAsync(rows_dev, rows.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-  a.rows = rows_dev;
-  a.plane = (float*)h->ws.get(WS_MATRIX_PLANE, (size_t)S * S * 4);   // 64 MB at the cap, sized by S, freed with the index
-  launch_matrix_scan(a, st);
-  if (h->matrix_scan_only) zero_outputs(out_keys, out_cnt, S, L, st);
-  else launch_matrix_select(a, threshold, (uint32_t)h->id_base, L, out_keys, out_cnt, st);
-  HX_HIP(hipStreamSynchronize(st));
 }
 
 }  // namespace hx
@@ -3052,726 +2720,6 @@ int hx_hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const 
   h->set_device();
   hybrid_query_dev(h, qd, qip, qix, qv, B, p, keys_dev, counts_dev, (hipStream_t)stream);
   remap_out(h, keys_dev, (int64_t)B * p->final_limit, (hipStream_t)stream);
-  HX_CATCH
-}
-
-// ---- grouped search ----------------------------------------------------------------------------
-// the checks of hx_group on its sizes and its column, before any device work; returns the column's cells
-static const uint32_t* group_plane(hx_index* h, int32_t col, int32_t n_groups, int32_t group_size) {
-  HX_CHECK(n_groups >= 1 && group_size >= 1 && (int64_t)n_groups * group_size <= MAX_LIMIT,
-           "group: n_groups and group_size must be at least 1 and n_groups * group_size at most 2048");
-  const hx_index::PayCol& c = pay_col(h, col);
-  HX_CHECK(c.kind == HX_PAY_U32, "group: the column kind must be HX_PAY_U32 (keyword codes or bools)");
-  HX_CHECK(c.filled == h->n, "group: the column is not filled to the index's row count (hx_count)");
-  return c.p0;
-}
-static void group_enqueue(hx_index* h, const uint32_t* p0, const uint64_t* keys, const uint64_t* ikeys, int stride,
-                          const int* counts, int B, int n_groups, int group_size, uint64_t* out, uint32_t* codes,
-                          int* group_counts, hipStream_t st) {
-  GroupArgs g{};
-  g.keys = keys;
-  g.ikeys = ikeys;
-  g.stride = stride;
-  g.counts = counts;
-  g.p0 = p0;
-  g.n_rows = h->n;
-  g.id_base = (uint32_t)h->id_base;
-  g.n_groups = n_groups;
-  g.group_size = group_size;
-  g.out = out;
-  g.group_codes = codes;
-  g.group_counts = group_counts;
-  launch_group_select(g, B, st);
-}
-// what hx_hybrid_query_groups_host adds to hx_hybrid_query_host
-struct GroupSpec {
-  int32_t col, pool, n_groups, group_size;
-  uint32_t* codes_host;
-  int32_t* counts_host;
-};
-
-// ---- MMR search -------------------------------------------------------------------------------
-// the checks of hx_mmr on its sizes, before any device work
-static void mmr_check(int32_t limit, float diversity) {
-  HX_CHECK(limit >= 1 && limit <= HX_MMR_MAX_LIMIT, "mmr: limit out of range [1, 256]");
-  HX_CHECK(diversity >= 0.0f && diversity <= 1.0f, "mmr: diversity must be in [0, 1]");   // (false for a NaN)
-}
-static void mmr_enqueue(hx_index* h, const uint64_t* keys, const uint64_t* ikeys, int stride, const int* counts, int B,
-                        int limit, float diversity, const uint32_t* eligible, uint64_t* out_keys, float* out_values,
-                        int* out_counts, hipStream_t st) {
-  HX_CHECK(h->dim_pad <= 4096, "mmr: rows wider than 4096 floats");
-  MmrArgs m{};
-  m.keys = keys;
-  m.ikeys = ikeys;
-  m.stride = stride;
-  m.counts = counts;
-  m.rows = h->dense;
-  m.dim_pad = (int)h->dim_pad;
-  m.n_rows = h->n;
-  m.id_base = (uint32_t)h->id_base;
-  m.eligible = eligible;
-  m.limit = limit;
-  m.diversity = diversity;
-  m.out_keys = out_keys;
-  m.out_values = out_values;
-  m.out_counts = out_counts;
-  launch_mmr_select(m, B, st);
-}
-// what hx_hybrid_query_mmr_host adds to hx_hybrid_query_host
-struct MmrSpec {
-  int32_t root_only, candidates, limit;
-  float diversity;
-  float* values_host;
-  int32_t* counts_host;
-};
-
-// ---- late-interaction rerank ---------------------------------------------------------------------
-// every refusal of hx_maxsim, before any device work; returns the token column
-static const hx_index::PayCol& maxsim_check(hx_index* h, int32_t col, int32_t stride, int32_t B, const int64_t* q_indptr_host,
-                                            int32_t limit) {
-  HX_CHECK(B >= 1, "maxsim: B < 1");
-  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "maxsim: stride out of range [1, 2048]");
-  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "maxsim: limit out of range [1, 2048]");
-  HX_CHECK(q_indptr_host[0] == 0, "maxsim: the query token offsets start at 0");
-  for (int b = 0; b < B; ++b) {
-    const int64_t tq = q_indptr_host[b + 1] - q_indptr_host[b];
-    HX_CHECK(tq >= 1 && tq <= HX_MAXSIM_MAX_QTOKENS, "maxsim: a query holds 1 to 64 tokens");
-  }
-  const hx_index::PayCol& c = pay_col(h, col);
-  HX_CHECK(c.kind == HX_PAY_TOKENS, "maxsim: the column kind must be HX_PAY_TOKENS");
-  HX_CHECK(c.filled == h->n, "maxsim: the column is not filled to the index's row count (hx_count)");
-  return c;
-}
-// out_keys [B x limit] and out_counts [B] as hx_maxsim hands them out; first (may be NULL) = the scores the pool carried
-static void maxsim_enqueue(hx_index* h, const hx_index::PayCol& c, const uint64_t* keys, const uint64_t* ikeys, int stride,
-                           const int* counts, int B, const int8_t* q8, const float* qscale, const int64_t* q_indptr,
-                           const uint32_t* eligible, int limit, uint64_t* out_keys, int* out_counts, float* first,
-                           hipStream_t st) {
-  MaxsimArgs m{};
-  m.keys = keys;
-  m.ikeys = ikeys;
-  m.stride = stride;
-  m.counts = counts;
-  m.head = c.p0;
-  m.off = c.off;
-  m.words = c.e0;
-  m.dim_t = c.dim_t;
-  m.n_rows = h->n;
-  m.id_base = (uint32_t)h->id_base;
-  m.eligible = eligible;
-  m.q8 = q8;
-  m.qscale = qscale;
-  m.q_indptr = q_indptr;
-  m.pos_keys = (uint64_t*)h->ws.get(WS_MS_POS, (size_t)B * stride * 8);
-  if (h->n == 0) {                       // (no row, no column arrays: nothing is eligible)
-    HX_HIP(hipMemsetAsync(out_keys, 0, (size_t)B * limit * 8, st));
-    HX_HIP(hipMemsetAsync(out_counts, 0, (size_t)B * 4, st));
-    if (first) launch_fill_f32(first, (int64_t)B * limit, -__builtin_inff(), st);
-    return;
-  }
-  launch_maxsim_score(m, B, st);
-  launch_compact(m.pos_keys, stride, nullptr, B, std::min(limit, stride), 0, out_keys, limit, out_counts, nullptr, stride, st);
-  launch_maxsim_finish(keys, stride, out_keys, first, B, limit, st);
-}
-// what hx_hybrid_query_rerank_host adds to hx_hybrid_query_host
-struct RerankSpec {
-  int32_t root_only, candidates, col, limit;
-  const int8_t* q8_host;
-  const float* qscale_host;
-  const int64_t* qtok_indptr_host;
-  float* first_host;
-  int32_t* counts_host;
-};
-
-// ---- score-boosting search ------------------------------------------------------------------------
-// the checks of hx_formula on its sizes, before any device work (formula_lower holds those on the program)
-static void formula_check(int32_t stride, int32_t B, int32_t limit) {
-  HX_CHECK(B >= 1, "formula: B < 1");
-  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "formula: stride out of range [1, 2048]");
-  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "formula: limit out of range [1, 2048]");
-}
-// f: lowered by formula_lower; planes: n_planes device planes; out_base may be NULL
-static void formula_enqueue(hx_index* h, FormulaArgs& f, const uint32_t* const* planes, int n_planes, const uint64_t* keys,
-                            const uint64_t* ikeys, int stride, const int* counts, int B, int limit, float threshold,
-                            const uint32_t* eligible, uint64_t* out_keys, int* out_pos, float* out_base, int* out_counts,
-                            int* out_dropped, hipStream_t st) {
-  for (int i = 0; i < n_planes; ++i) f.planes[i] = planes[i];
-  f.keys = keys;
-  f.ikeys = ikeys;
-  f.counts = counts;
-  f.eligible = eligible;
-  f.out_keys = out_keys;
-  f.out_pos = out_pos;
-  f.out_base = out_base;
-  f.out_counts = out_counts;
-  f.out_dropped = out_dropped;
-  f.n_rows = h->n;
-  f.id_base = (uint32_t)h->id_base;
-  f.stride = stride;
-  f.limit = limit;
-  f.threshold = threshold;
-  f.has_threshold = threshold == threshold;
-  launch_formula(f, B, st);
-}
-// what hx_hybrid_query_formula_host adds to hx_hybrid_query_host
-struct FormulaSpec {
-  int32_t root_only, candidates, limit;
-  const hx_formula_op* ops;
-  int32_t n_ops;
-  const uint32_t* const* planes_host;
-  int32_t n_planes;
-  float threshold;
-  float* base_host;
-  int32_t* counts_host;
-  int32_t* dropped_host;
-};
-
-// hx_hybrid_query_host, its masked form (mask_host NULL = every row), its grouped form (grp NULL = the plain lists;
-// otherwise the lists are the pool -- final_limit = the pool size -- and scores / ids receive the groups' slots), its
-// MMR form (mmr: the pool likewise, scores / ids receive the picks), its rerank form (rr: the pool likewise, scores /
-// ids receive the pool's rows in MaxSim order) and its boosted form (fm: the pool likewise, scores / ids receive the
-// pool's rows in the order of the formula's values)
-static void hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                              int32_t B, const hx_params* p_in, const uint32_t* mask_host, float* scores, int64_t* ids,
-                              int32_t* counts, const GroupSpec* grp = nullptr, const MmrSpec* mmr = nullptr,
-                              const RerankSpec* rr = nullptr, const FormulaSpec* fm = nullptr) {
-  HX_CHECK(h && qd && qip && scores && ids && (counts || grp || mmr || rr || fm) && B > 0, "bad argument");
-  HX_CHECK(p_in != nullptr, "params is NULL");
-  hx_params pool_params = *p_in;          // (the caller's params are never written)
-  const hx_params* p = p_in;
-  const uint32_t* group_p0 = nullptr;
-  if (grp) {
-    HX_CHECK(grp->codes_host && grp->counts_host, "bad argument");
-    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
-    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
-    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
-    HX_CHECK(grp->pool >= 0 && grp->pool <= pool_max && pool_max >= 1,
-             "group_pool must be 0 (the whole pool) or in [1, the mode's pool size]");
-    pool_params.final_limit = grp->pool ? grp->pool : (int32_t)pool_max;
-    p = &pool_params;
-    check_params(p);
-    group_p0 = group_plane(h, grp->col, grp->n_groups, grp->group_size);
-  }
-  const uint32_t* root_mask = nullptr;    // the MMR call's root-only mask: the query runs unmasked, the stage reads it
-  if (mmr) {
-    HX_CHECK(mmr->values_host && mmr->counts_host, "bad argument");
-    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
-    HX_CHECK(mmr->root_only == 0 || mmr->root_only == 1, "mmr: mask_root_only must be 0 or 1");
-    HX_CHECK(!(mask_host && mmr->root_only && p_in->mode == HX_MODE_H1),
-             "mmr: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
-    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
-    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
-    HX_CHECK(mmr->candidates >= 0 && mmr->candidates <= pool_max && pool_max >= 1,
-             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
-    mmr_check(mmr->limit, mmr->diversity);
-    pool_params.final_limit = mmr->candidates ? mmr->candidates : (int32_t)pool_max;
-    p = &pool_params;
-    if (mmr->root_only) {
-      root_mask = mask_host;
-      mask_host = nullptr;
-    }
-  }
-  const hx_index::PayCol* tok = nullptr;
-  if (rr) {
-    HX_CHECK(rr->q8_host && rr->qscale_host && rr->qtok_indptr_host && rr->first_host && rr->counts_host, "bad argument");
-    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
-    HX_CHECK(rr->root_only == 0 || rr->root_only == 1, "rerank: mask_root_only must be 0 or 1");
-    HX_CHECK(!(mask_host && rr->root_only && p_in->mode == HX_MODE_H1),
-             "rerank: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
-    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
-    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
-    HX_CHECK(rr->candidates >= 0 && rr->candidates <= pool_max && pool_max >= 1,
-             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
-    pool_params.final_limit = rr->candidates ? rr->candidates : (int32_t)pool_max;
-    p = &pool_params;
-    tok = &maxsim_check(h, rr->col, pool_params.final_limit, B, rr->qtok_indptr_host, rr->limit);
-    if (rr->root_only) {
-      root_mask = mask_host;
-      mask_host = nullptr;
-    }
-  }
-  FormulaArgs fargs{};
-  if (fm) {
-    HX_CHECK(fm->base_host && fm->counts_host && fm->dropped_host, "bad argument");
-    HX_CHECK(p_in->mode == HX_MODE_TREE || p_in->mode == HX_MODE_H1, "unknown mode");
-    HX_CHECK(fm->root_only == 0 || fm->root_only == 1, "formula: mask_root_only must be 0 or 1");
-    HX_CHECK(!(mask_host && fm->root_only && p_in->mode == HX_MODE_H1),
-             "formula: a root-only mask belongs to the tree query's root: use HX_MODE_TREE (or mask_root_only = 0)");
-    const int64_t other = p_in->mode == HX_MODE_TREE ? p_in->rrf_limit : p_in->sparse_limit;
-    const int64_t pool_max = std::min<int64_t>((int64_t)p_in->dense_limit + other, MAX_LIMIT);
-    HX_CHECK(fm->candidates >= 0 && fm->candidates <= pool_max && pool_max >= 1,
-             "candidates_limit must be 0 (the whole pool) or in [1, the mode's pool size]");
-    pool_params.final_limit = fm->candidates ? fm->candidates : (int32_t)pool_max;
-    p = &pool_params;
-    formula_check(pool_params.final_limit, B, fm->limit);
-    formula_lower(h, fm->ops, fm->n_ops, fm->n_planes, fargs);
-    HX_CHECK(fm->n_planes == 0 || fm->planes_host, "NULL argument");
-    for (int i = 0; i < fm->n_planes; ++i) HX_CHECK(fm->planes_host[i] != nullptr, "NULL argument");
-    if (fm->root_only) {
-      root_mask = mask_host;
-      mask_host = nullptr;
-    }
-  }
-  check_params(p);
-  h->set_device();
-  hipStream_t st = nullptr;
-  int64_t kept = -1;
-  if (mask_host) {                      // the count from the host mask: no read-back
-    const int64_t nw = (h->n + 31) / 32;
-    kept = 0;
-    for (int64_t w = 0; w < nw; ++w) {
-      uint32_t m = mask_host[w];
-      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
-      kept += __builtin_popcount(m);
-    }
-  }
-  const int64_t nnz = qip[B];
-  HX_CHECK(qip[0] == 0 && nnz >= 0, "bad query indptr");
-  // sort each query's terms by id (the spec's summation order), reject duplicates
-  std::vector<int32_t> six((size_t)nnz);
-  std::vector<float> sv((size_t)nnz);
-  std::vector<int> ord;
-  for (int b = 0; b < B; ++b) {
-    const int64_t s = qip[b], e = qip[b + 1];
-    HX_CHECK(e >= s && e <= nnz, "bad query indptr");
-    ord.resize((size_t)(e - s));
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return qix[s + x] < qix[s + y]; });
-    for (size_t i = 0; i < ord.size(); ++i) {
-      six[(size_t)s + i] = qix[s + ord[i]];
-      sv[(size_t)s + i] = qv[s + ord[i]];
-      HX_CHECK(six[(size_t)s + i] >= 0, "sparse index out of range");
-      HX_CHECK(i == 0 || six[(size_t)s + i] != six[(size_t)s + i - 1], "duplicate sparse index in query");
-    }
-  }
-  const int L = p->final_limit;
-  float* dq = (float*)h->ws.get(WS_H_QD, (size_t)B * h->dim * 4);
-  int64_t* dip = (int64_t*)h->ws.get(WS_H_QIP, (size_t)(B + 1) * 8);
-  int32_t* dix = (int32_t*)h->ws.get(WS_H_QIX, (size_t)std::max<int64_t>(nnz, 1) * 4);
-  float* dv = (float*)h->ws.get(WS_H_QV, (size_t)std::max<int64_t>(nnz, 1) * 4);
-  uint64_t* ok = (uint64_t*)h->ws.get(WS_H_OUT, (size_t)B * L * 8);
-  int* oc = (int*)h->ws.get(WS_H_OCNT, (size_t)B * 4);
-  const int OL = grp ? std::max(L, grp->n_groups * grp->group_size) : mmr ? std::max(L, mmr->limit)
-                                                                     : rr ? std::max(L, rr->limit)
-                                                                     : fm ? std::max(L, fm->limit) : L;   // slots of a result
-  float* osc = (float*)h->ws.get(WS_H_SC, (size_t)B * OL * 4);
-  int64_t* oid = (int64_t*)h->ws.get(WS_H_ID, (size_t)B * OL * 8);
-  HX_HIP(hipMemcpyAsync(dq, qd, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-  HX_HIP(hipMemcpyAsync(dip, qip, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-  if (nnz) {
-    HX_HIP(hipMemcpyAsync(dix, six.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-    HX_HIP(hipMemcpyAsync(dv, sv.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-  }
-  if (kept < 0 || kept == h->n) {
-    hybrid_query_dev(h, dq, dip, dix, dv, B, p, ok, oc, st);
-  } else {
-    const int64_t nw = (h->n + 31) / 32;
-    uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-    if (nw) HX_HIP(hipMemcpyAsync(dm, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-    masked_query_dev(h, dq, dip, dix, dv, B, p, dm, kept, ok, oc, st);
-  }
-  if (grp) {                             // the stage reads internal ids: before remap_out
-    const int G = grp->n_groups, GS = grp->n_groups * grp->group_size;
-    uint64_t* gk = (uint64_t*)h->ws.get(WS_G_KEYS, (size_t)B * GS * 8);
-    uint32_t* gc = (uint32_t*)h->ws.get(WS_G_CODES, (size_t)B * G * 4);
-    int* gn = (int*)h->ws.get(WS_G_CNT, (size_t)B * 4);
-    group_enqueue(h, group_p0, ok, ok, L, oc, B, G, grp->group_size, gk, gc, gn, st);
-    remap_out(h, gk, (int64_t)B * GS, st);
-    launch_unpack(gk, (int64_t)B * GS, osc, oid, st);
-    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * GS * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * GS * 8, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(grp->codes_host, gc, (size_t)B * G * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(grp->counts_host, gn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  if (mmr) {                             // the stage reads internal ids: before remap_out
-    const uint64_t* pool = ok;
-    const int* pcnt = oc;
-    if (p->mode == HX_MODE_H1) {         // relevance is the dense cosine: the fused list through the re-score stage
-      uint64_t* rk = (uint64_t*)h->ws.get(WS_MMR_POOL, (size_t)B * L * 8);
-      int* rc = (int*)h->ws.get(WS_MMR_PCNT, (size_t)B * 4);
-      rescore(h, dq, B, 0, ok, L, oc, L, rk, rc, st);
-      pool = rk;
-      pcnt = rc;
-    }
-    const uint32_t* elig = nullptr;
-    if (root_mask) {
-      const int64_t nw = (h->n + 31) / 32;
-      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-      elig = dm;
-    }
-    const int ML = mmr->limit;
-    uint64_t* mk = (uint64_t*)h->ws.get(WS_MMR_KEYS, (size_t)B * ML * 8);
-    float* mv = (float*)h->ws.get(WS_MMR_VAL, (size_t)B * ML * 4);
-    int* mn = (int*)h->ws.get(WS_MMR_CNT, (size_t)B * 4);
-    mmr_enqueue(h, pool, pool, L, pcnt, B, ML, mmr->diversity, elig, mk, mv, mn, st);
-    remap_out(h, mk, (int64_t)B * ML, st);
-    launch_unpack(mk, (int64_t)B * ML, osc, oid, st);
-    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * ML * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * ML * 8, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(mmr->values_host, mv, (size_t)B * ML * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(mmr->counts_host, mn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  if (rr) {                              // the stage reads internal ids: before remap_out
-    const uint32_t* elig = nullptr;
-    if (root_mask) {
-      const int64_t nw = (h->n + 31) / 32;
-      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-      elig = dm;
-    }
-    const int RL = rr->limit;
-    const int64_t nt = rr->qtok_indptr_host[B];
-    int8_t* q8 = (int8_t*)h->ws.get(WS_MS_Q8, (size_t)nt * tok->dim_t);
-    float* qs = (float*)h->ws.get(WS_MS_QS, (size_t)nt * 4);
-    int64_t* qtip = (int64_t*)h->ws.get(WS_MS_QIP, (size_t)(B + 1) * 8);
-    HX_HIP(hipMemcpyAsync(q8, rr->q8_host, (size_t)nt * tok->dim_t, hipMemcpyHostToDevice, st));
-    HX_HIP(hipMemcpyAsync(qs, rr->qscale_host, (size_t)nt * 4, hipMemcpyHostToDevice, st));
-    HX_HIP(hipMemcpyAsync(qtip, rr->qtok_indptr_host, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    uint64_t* mk = (uint64_t*)h->ws.get(WS_MS_KEYS, (size_t)B * RL * 8);
-    float* mf = (float*)h->ws.get(WS_MS_FIRST, (size_t)B * RL * 4);
-    int* mn = (int*)h->ws.get(WS_MS_CNT, (size_t)B * 4);
-    maxsim_enqueue(h, *tok, ok, ok, L, oc, B, q8, qs, qtip, elig, RL, mk, mn, mf, st);
-    remap_out(h, mk, (int64_t)B * RL, st);
-    launch_unpack(mk, (int64_t)B * RL, osc, oid, st);
-    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * RL * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * RL * 8, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(rr->first_host, mf, (size_t)B * RL * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(rr->counts_host, mn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  if (fm) {                              // the stage reads internal ids: before remap_out
-    const int64_t nw = (h->n + 31) / 32;
-    const uint32_t* elig = nullptr;
-    if (root_mask) {
-      uint32_t* dm = (uint32_t*)h->ws.get(WS_M_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-      if (nw) HX_HIP(hipMemcpyAsync(dm, root_mask, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-      elig = dm;
-    }
-    const uint32_t* planes[HX_FORMULA_MAX_PLANES] = {};
-    if (fm->n_planes) {
-      uint32_t* dp = (uint32_t*)h->ws.get(WS_FORMULA_PLANES, (size_t)fm->n_planes * std::max<int64_t>(nw, 1) * 4);
-      for (int i = 0; i < fm->n_planes; ++i) {
-        if (nw) HX_HIP(hipMemcpyAsync(dp + (int64_t)i * nw, fm->planes_host[i], (size_t)nw * 4, hipMemcpyHostToDevice, st));
-        planes[i] = dp + (int64_t)i * nw;
-      }
-    }
-    const int FL = fm->limit;
-    uint64_t* fk = (uint64_t*)h->ws.get(WS_FORMULA_KEYS, (size_t)B * FL * 8);
-    int* fp = (int*)h->ws.get(WS_FORMULA_POS, (size_t)B * FL * 4);
-    float* fb = (float*)h->ws.get(WS_FORMULA_BASE, (size_t)B * FL * 4);
-    int* fn = (int*)h->ws.get(WS_FORMULA_CNT, (size_t)B * 4);
-    int* fd = (int*)h->ws.get(WS_FORMULA_DROP, (size_t)B * 4);
-    formula_enqueue(h, fargs, planes, fm->n_planes, ok, ok, L, oc, B, FL, fm->threshold, elig, fk, fp, fb, fn, fd, st);
-    remap_out(h, fk, (int64_t)B * FL, st);
-    launch_unpack(fk, (int64_t)B * FL, osc, oid, st);
-    HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * FL * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * FL * 8, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(fm->base_host, fb, (size_t)B * FL * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(fm->counts_host, fn, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipMemcpyAsync(fm->dropped_host, fd, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HX_HIP(hipStreamSynchronize(st));
-    return;
-  }
-  remap_out(h, ok, (int64_t)B * L, st);
-  launch_unpack(ok, (int64_t)B * L, osc, oid, st);
-  HX_HIP(hipMemcpyAsync(scores, osc, (size_t)B * L * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(ids, oid, (size_t)B * L * 8, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(counts, oc, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
-}
-
-int hx_hybrid_query_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix,
-                         const float* qv, int32_t B, const hx_params* p, float* scores, int64_t* ids,
-                         int32_t* counts) {
-  HX_TRY
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, nullptr, scores, ids, counts);
-  HX_CATCH
-}
-
-int hx_hybrid_query_host_masked(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
-                                float* scores, int64_t* ids, int32_t* counts) {
-  HX_TRY
-  HX_CHECK(h && mask_host, "NULL argument");
-  HX_CHECK(mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, counts);
-  HX_CATCH
-}
-
-int hx_group(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
-             int32_t n_groups, int32_t group_size, uint64_t* out_keys_dev, uint32_t* group_codes_dev,
-             int32_t* group_counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(h && keys_dev && out_keys_dev && group_codes_dev && group_counts_dev, "NULL argument");
-  HX_CHECK(B >= 1, "group: B < 1");
-  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "group: stride out of range [1, 2048]");
-  const uint32_t* p0 = group_plane(h, col, n_groups, group_size);
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
-  group_enqueue(h, p0, keys_dev, ikeys, stride, counts_dev, B, n_groups, group_size, out_keys_dev, group_codes_dev,
-                group_counts_dev, st);
-  HX_CATCH
-}
-
-int hx_hybrid_query_groups_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows, int32_t col,
-                                int32_t group_pool, int32_t n_groups, int32_t group_size, float* scores, int64_t* ids,
-                                uint32_t* group_codes, int32_t* group_counts) {
-  HX_TRY
-  HX_CHECK(h, "NULL argument");
-  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  const GroupSpec g{col, group_pool, n_groups, group_size, group_codes, group_counts};
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, &g);
-  HX_CATCH
-}
-
-int hx_mmr(hx_index* h, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B, int32_t limit,
-           float diversity, const uint32_t* eligible_dev, int64_t eligible_rows, uint64_t* out_keys_dev,
-           float* out_values_dev, int32_t* out_counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(h && keys_dev && out_keys_dev && out_values_dev && out_counts_dev, "NULL argument");
-  HX_CHECK(B >= 1, "mmr: B < 1");
-  HX_CHECK(stride >= 1 && stride <= MAX_LIMIT, "mmr: stride out of range [1, 2048]");
-  mmr_check(limit, diversity);
-  HX_CHECK(!eligible_dev || eligible_rows == h->n, "mmr: eligible_rows must equal the index's row count (hx_count)");
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
-  mmr_enqueue(h, keys_dev, ikeys, stride, counts_dev, B, limit, diversity, eligible_dev, out_keys_dev, out_values_dev,
-              out_counts_dev, st);
-  HX_CATCH
-}
-
-int hx_hybrid_query_mmr_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                             int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
-                             int32_t mask_root_only, int32_t candidates_limit, int32_t limit, float diversity,
-                             float* scores, int64_t* ids, float* values, int32_t* counts) {
-  HX_TRY
-  HX_CHECK(h, "NULL argument");
-  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  const MmrSpec m{mask_root_only, candidates_limit, limit, diversity, values, counts};
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, &m);
-  HX_CATCH
-}
-
-int hx_formula(hx_index* h, const hx_formula_op* ops_host, int32_t n_ops, const uint32_t* const* planes_dev,
-               int32_t n_planes, int64_t plane_rows, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev,
-               int32_t B, int32_t limit, float score_threshold, const uint32_t* eligible_dev, int64_t eligible_rows,
-               uint64_t* out_keys_dev, int32_t* out_pos_dev, int32_t* out_counts_dev, int32_t* out_dropped_dev,
-               void* stream) {
-  HX_TRY
-  HX_CHECK(h && ops_host && keys_dev && out_keys_dev && out_pos_dev && out_counts_dev && out_dropped_dev, "NULL argument");
-  formula_check(stride, B, limit);
-  FormulaArgs f{};
-  formula_lower(h, ops_host, n_ops, n_planes, f);
-  HX_CHECK(n_planes == 0 || planes_dev, "NULL argument");
-  for (int i = 0; i < n_planes; ++i) HX_CHECK(planes_dev[i] != nullptr, "NULL argument");
-  HX_CHECK(n_planes == 0 || plane_rows == h->n, "formula: plane_rows must equal the index's row count (hx_count)");
-  HX_CHECK(!eligible_dev || eligible_rows == h->n, "formula: eligible_rows must equal the index's row count (hx_count)");
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
-  formula_enqueue(h, f, planes_dev, n_planes, keys_dev, ikeys, stride, counts_dev, B, limit, score_threshold, eligible_dev,
-                  out_keys_dev, out_pos_dev, nullptr, out_counts_dev, out_dropped_dev, st);
-  HX_CATCH
-}
-
-int hx_hybrid_query_formula_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                                 int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
-                                 int32_t mask_root_only, int32_t candidates_limit, const hx_formula_op* ops_host,
-                                 int32_t n_ops, const uint32_t* const* planes_host, int32_t n_planes, int32_t limit,
-                                 float score_threshold, float* scores, int64_t* ids, float* base_scores, int32_t* counts,
-                                 int32_t* dropped) {
-  HX_TRY
-  HX_CHECK(h, "NULL argument");
-  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  const FormulaSpec f{mask_root_only, candidates_limit, limit, ops_host, n_ops, planes_host, n_planes, score_threshold,
-                      base_scores, counts, dropped};
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, nullptr, nullptr, &f);
-  HX_CATCH
-}
-
-int hx_maxsim(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
-              const int8_t* q8_dev, const float* qscale_dev, const int64_t* q_indptr_dev, const int64_t* q_indptr_host,
-              const uint32_t* eligible_dev, int64_t eligible_rows, int32_t limit, uint64_t* out_keys_dev,
-              int32_t* out_counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(h && keys_dev && q8_dev && qscale_dev && q_indptr_dev && q_indptr_host && out_keys_dev && out_counts_dev,
-           "NULL argument");
-  const hx_index::PayCol& c = maxsim_check(h, col, stride, B, q_indptr_host, limit);
-  HX_CHECK(!eligible_dev || eligible_rows == h->n, "maxsim: eligible_rows must equal the index's row count (hx_count)");
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  const uint64_t* ikeys = remap_in(h, keys_dev, (int64_t)B * stride, st);
-  maxsim_enqueue(h, c, keys_dev, ikeys, stride, counts_dev, B, q8_dev, qscale_dev, q_indptr_dev, eligible_dev, limit,
-                 out_keys_dev, out_counts_dev, nullptr, st);
-  HX_CATCH
-}
-
-int hx_hybrid_query_rerank_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
-                                int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows,
-                                int32_t mask_root_only, int32_t candidates_limit, int32_t col, const int8_t* q8_host,
-                                const float* qscale_host, const int64_t* qtok_indptr_host, int32_t limit, float* scores,
-                                int64_t* ids, float* first_scores, int32_t* counts) {
-  HX_TRY
-  HX_CHECK(h, "NULL argument");
-  HX_CHECK(!mask_host || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
-  const RerankSpec r{mask_root_only, candidates_limit, col, limit, q8_host, qscale_host, qtok_indptr_host, first_scores,
-                     counts};
-  hybrid_query_host(h, qd, qip, qix, qv, B, p, mask_host, scores, ids, nullptr, nullptr, nullptr, &r);
-  HX_CATCH
-}
-
-int hx_recommend(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
-                 const int8_t* ex_sign_host, const float* ex_vecs_host, const uint32_t* mask_dev, int64_t mask_rows,
-                 int32_t limit, uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(keys_dev && counts_dev, "NULL argument");
-  const RecoCall c = reco_check(h, strategy, R, ex_indptr_host, ex_rows_host, ex_sign_host, ex_vecs_host, mask_dev, mask_rows,
-                                limit);
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  recommend_dev(h, strategy, R, c, ex_vecs_host, mask_dev, -1, limit, keys_dev, counts_dev, st);
-  remap_out(h, keys_dev, (int64_t)R * limit, st);
-  HX_HIP(hipStreamSynchronize(st));
-  HX_CATCH
-}
-
-int hx_recommend_host(hx_index* h, int32_t strategy, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
-                      const int8_t* ex_sign_host, const float* ex_vecs_host, const uint32_t* mask_host, int64_t mask_rows,
-                      int32_t limit, float* scores_host, int64_t* ids_host, int32_t* counts_host) {
-  HX_TRY
-  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
-  const RecoCall c = reco_check(h, strategy, R, ex_indptr_host, ex_rows_host, ex_sign_host, ex_vecs_host, mask_host, mask_rows,
-                                limit);
-  h->set_device();
-  hipStream_t st = nullptr;
-  const int64_t n_out = (int64_t)R * limit;
-  uint32_t* mask_dev = nullptr;
-  int64_t kept = -1;
-  if (mask_host) {                      // the count from the host mask: no read-back
-    const int64_t nw = (h->n + 31) / 32;
-    kept = 0;
-    for (int64_t w = 0; w < nw; ++w) {
-      uint32_t m = mask_host[w];
-      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
-      kept += __builtin_popcount(m);
-    }
-    mask_dev = (uint32_t*)h->ws.get(WS_RECO_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-    HX_HIP(hipMemcpyAsync(mask_dev, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-  }
-  uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_OUT, (size_t)n_out * 8);
-  int* cnt = (int*)h->ws.get(WS_RECO_OCNT, (size_t)R * 4);
-  float* sc = (float*)h->ws.get(WS_RECO_SC, (size_t)n_out * 4);
-  int64_t* id = (int64_t*)h->ws.get(WS_RECO_ID, (size_t)n_out * 8);
-  recommend_dev(h, strategy, R, c, ex_vecs_host, mask_dev, kept, limit, keys, cnt, st);
-  remap_out(h, keys, n_out, st);
-  launch_unpack(keys, n_out, sc, id, st);
-  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
-  HX_CATCH
-}
-
-int hx_discover(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host, const float* ex_vecs_host,
-                const int32_t* has_target_host, const uint32_t* mask_dev, int64_t mask_rows, int32_t limit,
-                uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(keys_dev && counts_dev, "NULL argument");
-  const RecoCall c = discover_check(h, R, ex_indptr_host, ex_rows_host, ex_vecs_host, has_target_host, mask_dev, mask_rows,
-                                    limit);
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  discover_dev(h, R, c, ex_vecs_host, mask_dev, -1, limit, keys_dev, counts_dev, st);
-  remap_out(h, keys_dev, (int64_t)R * limit, st);
-  HX_HIP(hipStreamSynchronize(st));
-  HX_CATCH
-}
-
-int hx_discover_host(hx_index* h, int32_t R, const int64_t* ex_indptr_host, const int64_t* ex_rows_host,
-                     const float* ex_vecs_host, const int32_t* has_target_host, const uint32_t* mask_host, int64_t mask_rows,
-                     int32_t limit, float* scores_host, int64_t* ids_host, int32_t* counts_host) {
-  HX_TRY
-  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
-  const RecoCall c = discover_check(h, R, ex_indptr_host, ex_rows_host, ex_vecs_host, has_target_host, mask_host, mask_rows,
-                                    limit);
-  h->set_device();
-  hipStream_t st = nullptr;
-  const int64_t n_out = (int64_t)R * limit;
-  uint32_t* mask_dev = nullptr;
-  int64_t kept = -1;
-  if (mask_host) {                      // the count from the host mask: no read-back
-    const int64_t nw = (h->n + 31) / 32;
-    kept = 0;
-    for (int64_t w = 0; w < nw; ++w) {
-      uint32_t m = mask_host[w];
-      if (w == nw - 1 && (h->n & 31)) m &= (1u << (h->n & 31)) - 1u;
-      kept += __builtin_popcount(m);
-    }
-    mask_dev = (uint32_t*)h->ws.get(WS_RECO_MASK, (size_t)std::max<int64_t>(nw, 1) * 4);
-    HX_HIP(hipMemcpyAsync(mask_dev, mask_host, (size_t)nw * 4, hipMemcpyHostToDevice, st));
-  }
-  uint64_t* keys = (uint64_t*)h->ws.get(WS_RECO_OUT, (size_t)n_out * 8);
-  int* cnt = (int*)h->ws.get(WS_RECO_OCNT, (size_t)R * 4);
-  float* sc = (float*)h->ws.get(WS_RECO_SC, (size_t)n_out * 4);
-  int64_t* id = (int64_t*)h->ws.get(WS_RECO_ID, (size_t)n_out * 8);
-  discover_dev(h, R, c, ex_vecs_host, mask_dev, kept, limit, keys, cnt, st);
-  remap_out(h, keys, n_out, st);
-  launch_unpack(keys, n_out, sc, id, st);
-  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
-  HX_CATCH
-}
-
-int hx_discover_redone(hx_index* h, int64_t* requests) {
-  HX_TRY
-  HX_CHECK(h && requests, "NULL argument");
-  *requests = h->discover_redone;
-  HX_CATCH
-}
-
-int hx_search_matrix(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
-                     uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
-  HX_TRY
-  HX_CHECK(keys_dev && counts_dev, "NULL argument");
-  const std::vector<uint32_t> rows = matrix_check(h, rows_host, S, limit, score_threshold);
-  h->set_device();
-  hipStream_t st = (hipStream_t)stream;
-  search_matrix_dev(h, rows, limit, score_threshold, keys_dev, counts_dev, st);
-  remap_out(h, keys_dev, (int64_t)S * limit, st);
-  HX_HIP(hipStreamSynchronize(st));
-  HX_CATCH
-}
-
-int hx_search_matrix_host(hx_index* h, const int64_t* rows_host, int32_t S, int32_t limit, float score_threshold,
-                          float* scores_host, int64_t* ids_host, int32_t* counts_host) {
-  HX_TRY
-  HX_CHECK(scores_host && ids_host && counts_host, "NULL argument");
-  const std::vector<uint32_t> rows = matrix_check(h, rows_host, S, limit, score_threshold);
-  h->set_device();
-  hipStream_t st = nullptr;
-  const int64_t n_out = (int64_t)S * limit;
-  uint64_t* keys = (uint64_t*)h->ws.get(WS_MATRIX_OUT, (size_t)n_out * 8);
-  int* cnt = (int*)h->ws.get(WS_MATRIX_OCNT, (size_t)S * 4);
-  float* sc = (float*)h->ws.get(WS_MATRIX_SC, (size_t)n_out * 4);
-  int64_t* id = (int64_t*)h->ws.get(WS_MATRIX_ID, (size_t)n_out * 8);
-  search_matrix_dev(h, rows, limit, score_threshold, keys, cnt, st);
-  remap_out(h, keys, n_out, st);
-  launch_unpack(keys, n_out, sc, id, st);
-  HX_HIP(hipMemcpyAsync(scores_host, sc, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(ids_host, id, (size_t)n_out * 8, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipMemcpyAsync(counts_host, cnt, (size_t)S * 4, hipMemcpyDeviceToHost, st));
-  HX_HIP(hipStreamSynchronize(st));
   HX_CATCH
 }
 

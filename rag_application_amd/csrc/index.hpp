@@ -1,5 +1,6 @@
-// Internal to the host files of libhx -- engine.hip, lifecycle.hip, paystore.hip (DESIGN.md section 3 says what
-// each owns): the state of one collection (struct hx_index) and what one file calls in another.
+// Internal to the host files of libhx -- engine.hip, lifecycle.hip, paystore.hip, poolstage.hip, byexample.hip
+// (DESIGN.md section 3 says what each owns): the state of one collection (struct hx_index) and what one file calls
+// in another.
 #pragma once
 #include "../../include/hx.h"
 #include "hx_common.hpp"
@@ -289,6 +290,24 @@ void track_weights_dev(hx_index* h, const float* val, int64_t n, hipStream_t st)
 bool ids_identity(const hx_index* h);
 int* host_pin(hx_index* h);
 void mask_rows_dev(hx_index* h, const uint32_t* mask_dev, uint32_t*& rows, uint32_t*& count_dev, hipStream_t st);
+// the query as the *_host entries of poolstage.hip and byexample.hip run it (the comments are at the definitions)
+void check_params(const hx_params* p);
+void hybrid_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
+                      const hx_params* p, uint64_t* out_keys, int* out_cnt, hipStream_t st, bool tree_sync = false);
+void masked_query_dev(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv, int B,
+                      const hx_params* p, const uint32_t* mask_dev, int64_t count_known, uint64_t* out_keys,
+                      int* out_cnt, hipStream_t st);
+bool masked_dense_dev(hx_index* h, const float* q_dev, int B, int L, const uint32_t* mask_dev, int64_t count_known,
+                      uint64_t* out_keys, int* out_cnt, hipStream_t st);
+void rescore(hx_index* h, const float* q_dev, int B, int prefix, const uint64_t* cand, int cstride, const int* ccnt, int L,
+             uint64_t* out_keys, int* out_cnt, hipStream_t st);
+void remap_out(hx_index* h, uint64_t* keys, int64_t n, hipStream_t st);
+const uint64_t* remap_in(hx_index* h, const uint64_t* keys, int64_t n, hipStream_t st, int slot = WS_ID_IN);
+void zero_outputs(uint64_t* keys, int* cnt, int B, int L, hipStream_t st);
+int64_t host_mask_count(const hx_index* h, const uint32_t* mask_host);
+uint32_t* host_mask_upload(hx_index* h, const uint32_t* mask_host, int slot, hipStream_t st);
+void results_to_host(hx_index* h, uint64_t* keys, int64_t n, int sc_slot, int id_slot, float* scores, int64_t* ids,
+                     hipStream_t st);
 int* rows_check_begin(hx_index* h, hipStream_t st);
 void rows_check_fetch(hx_index* h, int* w, hipStream_t st);
 void rows_check_end(hx_index* h, int* w, hipStream_t st);

@@ -65,7 +65,7 @@ def requests(rng, R, E):
 
 
 def groups(reqs):
-    """launch groups of a batch: requests in order while their examples fit 32768 floats (engine.hip deals them so)"""
+    """launch groups of a batch: requests in order while their examples fit 32768 floats (byexample.hip: example_plan deals them so)"""
     g, used = 1, 0
     for rq in reqs:
         if (used + len(rq)) * DIM > 32768:

@@ -1,6 +1,7 @@
 """CPU: the source and header lists of rag_application_amd/build.py against the files of csrc/.
 
-The three host files (engine.hip, lifecycle.hip, paystore.hip) share struct hx_index through index.hpp.  A source
+The five host files (engine.hip, lifecycle.hip, paystore.hip, poolstage.hip, byexample.hip) share struct hx_index
+through index.hpp.  A source
 outside SOURCES is not linked; a header outside HEADERS leaves stale objects behind an edit to that struct, and the
 translation units then disagree about its layout.  Needs no GPU and no compiler."""
 from __future__ import annotations
