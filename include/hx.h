@@ -239,6 +239,46 @@ int hx_rrf(int32_t device, const uint64_t* a_keys_dev, int32_t a_stride, const i
 int hx_merge(int32_t device, const uint64_t* in_keys_dev, int32_t stride, const int32_t* in_counts_dev,
              int32_t B, int32_t limit, int32_t dedupe,
              uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+
+/* ---- general fusion: FusionQuery(Fusion.RRF | Fusion.DBSF) over N ranked lists ----------------
+ * The fusion node of a caller-defined Prefetch tree (client.query_points(prefetch=[...], query=FusionQuery(...))):
+ * n_lists ranked lists per query -> one.  hx_rrf is the two-list, unweighted special case and keeps its own kernels.
+ * Additive to the ABI: HX_ABI_VERSION stays 3.  No index is involved (device ordinal, as hx_rrf).
+ *
+ * keys_dev and counts_dev are HOST arrays of n_lists DEVICE pointers: list l of query b is keys_dev[l][b * strides[l] +
+ * r], r < n_l = min(max(counts_dev[l][b], 0), strides[l]), best first; every slot below n_l is an entry (id and fp32
+ * score as the key carries them).  weights_host: n_lists weights w_l, or NULL = all 1.0f.  The output must not overlap
+ * an input.  out_keys_dev [B x limit] holds min(limit, distinct ids) keys (fused score, id) in key order -- fused score
+ * descending, id ascending -- and 0 after them; out_counts_dev [B] that number.
+ *
+ * Refused before any device work: n_lists outside [1, HX_FUSE_MAX_LISTS]; a stride outside [1, 2048] or strides that
+ * sum above HX_FUSE_MAX_SLOTS; limit outside [1, 2048]; a weight that is not finite or is negative; an unknown method;
+ * for HX_FUSE_RRF the rrf_k / rank_base hx_rrf refuses (HX_FUSE_DBSF ignores both).
+ *
+ * Arithmetic (exact: rag_application_amd/fusion.py restates it in numpy, bit for bit).  s_r = the fp32 score in the key
+ * at rank r of list l; c_l(r) = the contribution of that entry:
+ *   HX_FUSE_RRF   c_l(r) = w_l * (1 / (f32(r + rank_base) + rrf_k)): the conversion, the addition, the reciprocal (the
+ *                 correctly rounded fp32 quotient 1 / x) and the product are one fp32 round-to-nearest operation each.
+ *   HX_FUSE_DBSF  each list is normalised to its mean +- 3 standard deviations (Qdrant's documented rule; its own
+ *                 arithmetic is not pinned here).  Statistics in fp64, every step one IEEE double operation (no FMA,
+ *                 correctly rounded divide and square root).  T(v) = the sum over a fixed tree: v padded with +0.0 to the
+ *                 next power of two P >= n_l, then v[i] += v[i + h] for h = P/2, P/4, ..., 1; T(v) = v[0].
+ *                   mean = T(s) / n_l;  var = T((s_r - mean) * (s_r - mean)) / (n_l - 1);  sd = sqrt(var);
+ *                 n_l == 1, or sd not > 0 (a NaN included): norm_r = 0.5f for the whole list; otherwise
+ *                   norm_r = f32((s_r - (mean - 3 * sd)) / (6 * sd));
+ *                 c_l(r) = w_l * norm_r in fp32.
+ *   both          fused(id) = 0.0f + c_l1 + c_l2 + ... over the lists that hold the id, added in ascending list order in
+ *                 fp32 round-to-nearest (the order of hx_rrf).  A list's FIRST entry of an id counts; a later entry of
+ *                 the same id in the same list is ignored -- it still occupies its rank and, for DBSF, still counts in
+ *                 the list's statistics. */
+#define HX_FUSE_RRF   0
+#define HX_FUSE_DBSF  1
+#define HX_FUSE_MAX_LISTS 8
+#define HX_FUSE_MAX_SLOTS 4096      /* sum of the strides */
+int hx_fuse(int32_t device, int32_t method, int32_t n_lists,
+            const uint64_t* const* keys_dev, const int32_t* strides_host, const int32_t* const* counts_dev,
+            const float* weights_host, int32_t B, float rrf_k, int32_t rank_base, int32_t limit,
+            uint64_t* out_keys_dev, int32_t* out_counts_dev, void* stream);
 /* Row-sharded H1 query, one process per GPU (the reference has no
  * multi-device path -- these two calls bracket the one all-gather of the step):
  *  hx_h1_local  the shard's dense top-`dense_limit` and sparse top-`sparse_limit` of every

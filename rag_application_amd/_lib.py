@@ -90,6 +90,7 @@ _SIGS = {
     "hx_rescore": [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P],
     "hx_rrf": [C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_float, C.c_int32,
                C.c_int32, _P, _P, _P],
+    "hx_fuse": [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P],
     "hx_merge": [C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P],
     "hx_h1_local": [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P],
     "hx_h1_local_async": [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P],

@@ -2263,6 +2263,45 @@ int hx_rrf(int32_t device, const uint64_t* a, int32_t as, const int32_t* ac, con
   HX_CATCH
 }
 
+// N-way fusion (fuse.hip): the kernel keeps a query's lists in LDS, so the entry needs no scratch of its own.
+int hx_fuse(int32_t device, int32_t method, int32_t n_lists, const uint64_t* const* keys_dev, const int32_t* strides,
+            const int32_t* const* counts_dev, const float* weights, int32_t B, float rrf_k, int32_t rank_base,
+            int32_t limit, uint64_t* out_keys, int32_t* out_counts, void* stream) {
+  HX_TRY
+  HX_CHECK(keys_dev && strides && counts_dev && out_keys && out_counts && B > 0, "bad argument");
+  HX_CHECK(method == HX_FUSE_RRF || method == HX_FUSE_DBSF, "fuse: unknown method");
+  HX_CHECK(n_lists >= 1 && n_lists <= HX_FUSE_MAX_LISTS, "fuse: n_lists out of range [1, 8]");
+  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "fuse: limit out of range [1, 2048]");
+  FuseArgs a{};
+  int total = 0;
+  for (int l = 0; l < n_lists; ++l) {
+    HX_CHECK(keys_dev[l] && counts_dev[l], "fuse: NULL list");
+    HX_CHECK(strides[l] >= 1 && strides[l] <= MAX_LIMIT, "fuse: stride out of range [1, 2048]");
+    const float w = weights ? weights[l] : 1.0f;
+    HX_CHECK(std::isfinite(w) && w >= 0.0f, "fuse: a weight must be finite and not negative");
+    const uint64_t* lo = keys_dev[l];
+    HX_CHECK(!(lo < out_keys + (size_t)B * limit && out_keys < lo + (size_t)B * strides[l]),
+             "fuse: the output overlaps an input list");
+    a.keys[l] = lo;
+    a.cnt[l] = counts_dev[l];
+    a.stride[l] = strides[l];
+    a.w[l] = w;
+    total += strides[l];
+  }
+  HX_CHECK(total <= HX_FUSE_MAX_SLOTS, "fuse: the strides sum above 4096");
+  if (method == HX_FUSE_RRF) check_rrf(rrf_k, rank_base);
+  a.n_lists = n_lists;
+  a.method = method;
+  a.k = rrf_k;
+  a.rank_base = rank_base;
+  a.limit = limit;
+  a.out = out_keys;
+  a.out_cnt = out_counts;
+  HX_HIP(hipSetDevice(device));
+  launch_fuse(a, B, (hipStream_t)stream);
+  HX_CATCH
+}
+
 int hx_merge(int32_t device, const uint64_t* in_keys, int32_t stride, const int32_t* in_counts, int32_t B,
              int32_t limit, int32_t dedupe, uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
   HX_TRY

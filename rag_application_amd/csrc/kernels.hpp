@@ -197,6 +197,24 @@ void launch_rrf(const uint64_t* a, int a_stride, const int* a_cnt, const uint64_
 // launch_rrf + launch_compact); out [B x out_stride], out_cnt [B]
 bool launch_rrf_top(const uint64_t* a, int a_stride, const int* a_cnt, const uint64_t* b, int b_stride, const int* b_cnt,
                     int B, float k, int rank_base, int limit, uint64_t* out, int out_stride, int* out_cnt, hipStream_t st);
+// ---- fuse.hip: N-way fusion (hx_fuse) ------------------------------------------------------------
+constexpr int FUSE_MAX_LISTS = 8;        // HX_FUSE_MAX_LISTS
+constexpr int FUSE_MAX_SLOTS = 4096;     // HX_FUSE_MAX_SLOTS
+constexpr int FUSE_SMALL_SLOTS = 256;    // strides summing to at most this: the one-wave form
+struct FuseArgs {
+  const uint64_t* keys[FUSE_MAX_LISTS];  // list l of query b: keys[l] + b * stride[l]
+  const int* cnt[FUSE_MAX_LISTS];        // [B] each
+  int stride[FUSE_MAX_LISTS];
+  float w[FUSE_MAX_LISTS];
+  int n_lists, method;                   // HX_FUSE_RRF / HX_FUSE_DBSF
+  float k;
+  int rank_base, limit;
+  uint64_t* out;                         // [B x limit]
+  int* out_cnt;                          // [B]
+};
+// 0 = the one-wave form (k_fuse<64, 4>), 1 = the general one (k_fuse<512, 8>): host arithmetic only
+int fuse_form(int total_slots);
+void launch_fuse(const FuseArgs& a, int B, hipStream_t st);
 void launch_unpack(const uint64_t* keys, int64_t n, float* scores, int64_t* ids, hipStream_t st);
 // out[b*(sa+sb) ...] = a-list then b-list (empty slots 0)
 void launch_concat(const uint64_t* a, int a_stride, const int* a_cnt, const uint64_t* b, int b_stride,

@@ -1217,6 +1217,44 @@ def rrf(a_keys: torch.Tensor, a_cnt: torch.Tensor, b_keys: torch.Tensor, b_cnt: 
     return keys, cnt
 
 
+FUSE_RRF, FUSE_DBSF = 0, 1
+FUSE_METHODS = {"rrf": FUSE_RRF, "dbsf": FUSE_DBSF}
+
+
+def fuse(lists: Sequence[torch.Tensor], counts: Sequence[torch.Tensor], method="rrf", weights=None, limit: int = 10,
+         k: float = 2.0, rank_base: int = 0):
+    """N ranked lists -> one (hx_fuse; include/hx.h states the arithmetic): lists[l] [B, stride_l] int64 keys, counts[l]
+    [B] int32, method "rrf" | "dbsf" (or the HX_FUSE_* code), weights = one number per list or None (all 1).  Returns
+    (keys [B, limit], counts [B]).  What the entry refuses raises HxError."""
+    if len(lists) == 0 or len(lists) != len(counts):
+        raise HxError("fuse: one count tensor per list, at least one list")
+    lists = [_need_cuda(t, torch.int64, "lists") for t in lists]
+    counts = [_need_cuda(c, torch.int32, "counts") for c in counts]
+    dev = lists[0].device
+    B = lists[0].shape[0]
+    if any(t.dim() != 2 or t.shape[0] != B or t.device != dev for t in lists) or \
+            any(c.numel() != B or c.device != dev for c in counts):
+        raise HxError("fuse: every list is [B, stride] and every count [B], on one device")
+    n = len(lists)
+    code = FUSE_METHODS.get(method, method) if isinstance(method, str) else method
+    if isinstance(code, str):
+        raise HxError(f"fuse: unknown method {method!r}")
+    kp = (C.c_void_p * n)(*[t.data_ptr() for t in lists])
+    cp = (C.c_void_p * n)(*[c.data_ptr() for c in counts])
+    st = (C.c_int32 * n)(*[t.shape[1] for t in lists])
+    wp = None
+    if weights is not None:
+        weights = [float(w) for w in weights]
+        if len(weights) != n:
+            raise HxError(f"fuse: {n} lists need {n} weights")
+        wp = (C.c_float * n)(*weights)
+    keys = torch.empty((B, limit), dtype=torch.int64, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int32, device=dev)
+    check(_lib.lib().hx_fuse(dev.index or 0, int(code), n, kp, st, cp, wp, B, float(k), int(rank_base), int(limit),
+                             _ptr(keys), _ptr(cnt), _stream()))
+    return keys, cnt
+
+
 def h1_fuse(gathered: torch.Tensor, world: int, dense_limit: int, sparse_limit: int, limit: int = 10,
             k: float = 2.0, rank_base: int = 0):
     """gathered: [world * B, dense_limit + sparse_limit], rank-major (all_gather_into_tensor of h1_local):

@@ -27,10 +27,12 @@ from . import boosting as _boosting
 from . import engine as _engine
 from . import faceting as _faceting
 from . import filters as _filters
+from . import fusion as _fusion
 from . import grouping as _grouping
 from . import late_interaction as _late
 from . import matrix as _matrix
 from . import payload_index as _pindex
+from . import query_tree as _query_tree
 from . import scrolling as _scrolling
 from .matrix import MatrixOffsets, MatrixPair
 from ._lib import HX_MODE_H1, HX_MODE_TREE
@@ -597,6 +599,8 @@ class QdrantHandler:
     _scroll = True
     # search_matrix_pairs / _offsets compare rows of ONE engine index with each other
     _matrix_search = True
+    # query_points runs a caller's tree over the stage entries of ONE engine index
+    _query_tree = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -1396,6 +1400,83 @@ class QdrantHandler:
         except Exception as e:
             logging.error("reranker raised, order kept: %s", e)
             return results
+
+    # ------------------------------------------------------------------------ query trees
+    def _query_points_sync(self, user_id, requests):
+        if not self._query_tree:
+            raise ValueError("query_points is not supported on a sharded collection")
+        requests = list(requests)
+        col = self._collections[str(user_id)]
+        parsed, roots = [], []
+        for req in requests:
+            shape, vecs = _query_tree.parse(req, col.dim, col.msizes)
+            get = req.get if isinstance(req, dict) else (lambda k, d=None, r=req: getattr(r, k, d))
+            flt = get("filters") if get("filters") is not None else get("filter")
+            thr = get("score_threshold")
+            if thr is not None and (isinstance(thr, bool) or not isinstance(thr, (int, float)) or thr != thr):
+                raise ValueError(f"score_threshold must be a number, got {thr!r}")
+            if flt:
+                if not shape[-1]:
+                    raise ValueError("filters on a root without prefetch are not supported: the stage entries take no row "
+                                     "mask (filter the root of a tree with prefetches, or use hybrid_search_batch with "
+                                     "filter_stages='all')")
+                _filters.matches({}, flt)                  # validates the clause names before any GPU work
+            with_payload = get("with_payload", True)
+            parsed.append((shape, bool(flt)))
+            roots.append((vecs, flt or None, thr, True if with_payload is None else bool(with_payload)))
+        out: List[Optional[List[ScoredPoint]]] = [None] * len(requests)
+        stages = _query_tree.DeviceStages(col.index, _engine)
+        cids, cpay = col.ids, col.payloads
+        for (shape, filtered), members in _query_tree.group_by_shape(parsed).items():
+            limit = _query_tree.shape_limit(shape)
+            # a filter is the ROOT's (:297, :371): its candidates are filtered before its cut, so the root stage runs at
+            # the width of its input and the rows are tested against the packed row mask here
+            width = min(_query_tree.input_width(shape), 2048) if filtered else None
+            vectors = _query_tree.batch_vectors([roots[i][0] for i in members])
+            keys, counts = stages.to_host(*_query_tree.run(shape, vectors, stages, root_limit=width))
+            for b, i in enumerate(members):
+                _, flt, thr, with_payload = roots[i]
+                k = keys[b, :int(counts[b])]
+                rows, scores = _fusion.key_ids(k), _fusion.key_scores(k)
+                if flt:
+                    words = col.row_mask(flt)
+                    keep = (words[rows >> 5] >> (rows & 31).astype(words.dtype)) & 1 != 0
+                    rows, scores = rows[keep], scores[keep]
+                if thr is not None:
+                    keep = ~(scores < np.float32(thr))
+                    rows, scores = rows[keep], scores[keep]
+                out[i] = [ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r] if with_payload else None)
+                          for s, r in zip(scores[:limit].tolist(), rows[:limit].tolist())]
+        return out
+
+    async def query_points_batch(self, user_id: str, requests) -> List[List[ScoredPoint]]:
+        """The reference's general call, client.query_points(prefetch=[...], query=..., using=..., limit=...), for many
+        requests at once (additive).  A request is a dict (or an object with the same attributes):
+        "prefetch", "query", "using", "limit" as query_tree.py states them, and for the root "filters" (or "filter"),
+        "score_threshold", "with_payload".  The requests are grouped by shape -- the tree without its vectors -- and every
+        group runs as one batch over the engine's stage entries, fusion nodes through hx_fuse; results come back in
+        request order.  Raises ValueError for a tree no stage can serve (query_tree.parse names the reason) and on a
+        sharded collection; any other failure is logged and gives [], as in every search."""
+        try:
+            return await self._run(self._query_points_sync, user_id, requests)
+        except ValueError as ve:
+            logging.error("query_points for %s refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error("query_points for %s failed: %s", user_id, e)
+            return []
+
+    async def query_points(self, user_id: str, prefetch=None, query=None, using: str = "dense", limit: int = 10,
+                           filters: Optional[Dict] = None, score_threshold: Optional[float] = None,
+                           with_payload: bool = True) -> List[ScoredPoint]:
+        """One request of query_points_batch.  `filters` is the root's filter, as in the reference (:297, :371): the
+        root's candidates are filtered before its cut; a root without prefetch takes none.  `score_threshold` drops
+        root hits that score below it."""
+        res = await self.query_points_batch(user_id, [{"prefetch": prefetch, "query": query, "using": using,
+                                                       "limit": limit, "filters": filters,
+                                                       "score_threshold": score_threshold,
+                                                       "with_payload": with_payload}])
+        return res[0] if res else []
 
     # ------------------------------------------------------------------------ recommend
     def _recommend_sync(self, user_id, requests, limit, filters):

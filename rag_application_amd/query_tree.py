@@ -1,0 +1,289 @@
+"""Caller-defined query trees: the general form of the reference's call,
+client.query_points(prefetch=[...], query=..., using=..., limit=...), parsed into a *shape* (the tree without its
+vectors) and run for B queries of one shape at once over the engine's stage entries.
+
+A request is a dict, or an object with attributes of the same names (qdrant_client's Prefetch / QueryRequest fit):
+  nearest node  query = a dense vector, or a sparse one ({"indices", "values"} or .indices / .values); using = "dense",
+                "matryoshka_<d>", "quantized" or "sparse".  Without prefetch: a whole-collection search.  With prefetch:
+                the union of the children's lists re-scored by the named vector ("dense" and "matryoshka_<d>" only).
+  fusion node   query = {"fusion": "rrf" | "dbsf"} with optional "weights", "rrf_k", "rank_base"; 1 to 8 prefetches.
+A missing limit is 10, at the root too.  Everything else raises ValueError with the reason: nothing is answered with
+something else."""
+from __future__ import annotations
+
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import fusion as _fusion
+
+PREFETCH_DEFAULT_LIMIT = 10
+MAX_DEPTH = 8
+MAX_LIMIT = 2048                 # the largest list a stage keeps (hx.h)
+RESCORE_MAX = 8192               # the widest candidate list hx_rescore takes
+USINGS = ("dense", "quantized", "sparse")
+NODE_KEYS = ("prefetch", "query", "using", "limit", "filter", "score_threshold", "params", "lookup_from")
+# what Qdrant's query interface also offers and a tree here does not
+FOREIGN_QUERIES = ("order_by", "recommend", "discover", "context", "formula", "mmr", "sample")
+_MISSING = object()
+
+
+def _get(node, name, default=None):
+    if isinstance(node, dict):
+        return node.get(name, default)
+    return getattr(node, name, default)
+
+
+def _is_sparse(q) -> bool:
+    if isinstance(q, dict):
+        return "indices" in q and "values" in q
+    return hasattr(q, "indices") and hasattr(q, "values")
+
+
+def _fusion_of(q):
+    """(method name, the query object) when q is a fusion query, else None"""
+    f = _get(q, "fusion", _MISSING) if (isinstance(q, dict) or hasattr(q, "fusion")) else _MISSING
+    if f is _MISSING or f is None:
+        return None
+    return str(getattr(f, "value", f)).lower()
+
+
+def _limit(node, where: str) -> int:
+    limit = _get(node, "limit")
+    if limit is None:
+        return PREFETCH_DEFAULT_LIMIT
+    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= int(limit) <= MAX_LIMIT:
+        raise ValueError(f"{where}: limit must be an integer in [1, {MAX_LIMIT}], got {limit!r}")
+    return int(limit)
+
+
+def _dense(q, using: str, prefix: int, dim: int, where: str) -> np.ndarray:
+    try:
+        v = np.asarray(q, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: the query of a nearest node is a vector of numbers or a sparse vector") from None
+    if not np.isfinite(v).all():
+        raise ValueError(f"{where}: query vector values must be finite")
+    if prefix and v.shape[0] == prefix:                      # the prefix stage reads the first d values only
+        v = np.concatenate([v, np.zeros(dim - prefix, dtype=np.float32)])
+    if v.shape[0] != dim:
+        want = f"{prefix} or {dim}" if prefix else f"{dim}"
+        raise ValueError(f"{where}: a query of {v.shape[0]} values under using={using!r}, want {want}")
+    return v
+
+
+def _sparse(q, where: str):
+    idx, val = (q["indices"], q["values"]) if isinstance(q, dict) else (q.indices, q.values)
+    try:
+        idx = np.asarray(list(idx), dtype=np.int64).reshape(-1)
+        val = np.asarray(list(val), dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: a sparse query holds integer indices and numeric values") from None
+    if idx.shape[0] != val.shape[0]:
+        raise ValueError(f"{where}: a sparse query needs as many values as indices")
+    if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+        raise ValueError(f"{where}: sparse index out of range")
+    if not np.isfinite(val).all():
+        raise ValueError(f"{where}: sparse query values must be finite")
+    return idx.astype(np.int32), val.astype(np.float32)
+
+
+def parse(node, dim: int, msizes: Sequence[int], _depth: int = 1, _root: bool = True, _vecs: Optional[list] = None):
+    """A request -> (shape, vectors).  shape: ("nearest", using, prefix, limit, children) or ("fusion", method, weights,
+    rrf_k, rank_base, limit, children), hashable; vectors: the nearest nodes' queries in pre-order, a float32 [dim] array
+    or an (indices int32, values float32) pair each.  The root's filter and score_threshold are the caller's business
+    (handler.query_points); below the root both are refused."""
+    where = "query_points" if _root else f"prefetch (depth {_depth})"
+    vecs = [] if _vecs is None else _vecs
+    if _depth > MAX_DEPTH:
+        raise ValueError(f"a query tree is at most {MAX_DEPTH} levels deep")
+    if node is None or isinstance(node, (str, bytes, int, float, list, tuple, np.ndarray)):
+        raise ValueError(f"{where}: a node is a dict or an object with prefetch / query / using / limit")
+    if isinstance(node, dict):
+        allowed = NODE_KEYS + (("filters", "with_payload", "with_vector") if _root else ())
+        unknown = [k for k in node if k not in allowed]
+        if unknown:
+            raise ValueError(f"{where}: unknown field(s) {unknown}")
+    if not _root:
+        if _get(node, "filter") is not None or _get(node, "filters") is not None:
+            raise ValueError(f"{where}: a filter inside a prefetch is not supported (the stage entries take no mask); "
+                             "filter at the root")
+        if _get(node, "score_threshold") is not None:
+            raise ValueError(f"{where}: score_threshold belongs to the root")
+    if _get(node, "lookup_from") is not None:
+        raise ValueError(f"{where}: lookup_from is not supported")
+    q = _get(node, "query")
+    if q is None:
+        raise ValueError(f"{where}: a node needs a query (a vector or a fusion)")
+    if isinstance(q, (dict,)) and "nearest" in q:            # NearestQuery(nearest=vector)
+        if q.get("mmr") is not None:
+            raise ValueError(f"{where}: an MMR query cannot be part of a tree (hybrid_search_mmr reranks a pool)")
+        q = q["nearest"]
+    elif not isinstance(q, dict) and hasattr(q, "nearest"):
+        if getattr(q, "mmr", None) is not None:
+            raise ValueError(f"{where}: an MMR query cannot be part of a tree (hybrid_search_mmr reranks a pool)")
+        q = q.nearest
+    for name in FOREIGN_QUERIES:
+        if (isinstance(q, dict) and name in q) or (not isinstance(q, (dict, list, tuple, np.ndarray)) and hasattr(q, name)):
+            raise ValueError(f"{where}: a {name} query cannot be part of a tree")
+    if isinstance(q, (str, bytes, int, np.integer)) and not isinstance(q, bool):
+        raise ValueError(f"{where}: a query by point id cannot be part of a tree")
+    pre = _get(node, "prefetch")
+    if pre is None:
+        pre = []
+    elif isinstance(pre, dict) or not isinstance(pre, (list, tuple)):
+        pre = [pre]
+    limit = _limit(node, where)
+    method = _fusion_of(q)
+    if method is not None:
+        if isinstance(q, dict):
+            unknown = [k for k in q if k not in ("fusion", "weights", "rrf_k", "rank_base")]
+            if unknown:
+                raise ValueError(f"{where}: unknown field(s) {unknown} in a fusion query")
+        if method not in _fusion.METHODS:
+            raise ValueError(f"{where}: fusion must be one of {tuple(_fusion.METHODS)}, got {method!r}")
+        if not 1 <= len(pre) <= _fusion.MAX_LISTS:
+            raise ValueError(f"{where}: a fusion takes 1 to {_fusion.MAX_LISTS} prefetches, got {len(pre)}")
+        rrf_k = _get(q, "rrf_k")
+        rank_base = _get(q, "rank_base")
+        rrf_k = _fusion.RRF_K if rrf_k is None else rrf_k
+        rank_base = _fusion.RRF_RANK_BASE if rank_base is None else rank_base
+        if isinstance(rrf_k, bool) or not isinstance(rrf_k, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{where}: rrf_k must be a number")
+        if isinstance(rank_base, bool) or not isinstance(rank_base, (int, np.integer)):
+            raise ValueError(f"{where}: rank_base must be an integer")
+        children = tuple(parse(c, dim, msizes, _depth + 1, False, vecs)[0] for c in pre)
+        try:
+            code, w = _fusion.check(method, [c[-2] for c in children], _get(q, "weights"), limit, rrf_k, rank_base)
+        except ValueError as e:
+            raise ValueError(f"{where}: {e}") from None
+        weights = None if _get(q, "weights") is None else tuple(float(x) for x in w)
+        if code != _fusion.RRF:                              # DBSF ignores both: one shape whatever they are
+            rrf_k, rank_base = _fusion.RRF_K, _fusion.RRF_RANK_BASE
+        return ("fusion", code, weights, float(np.float32(rrf_k)), int(rank_base), limit, children), vecs
+    # a nearest node
+    using = _get(node, "using")
+    using = "dense" if using is None else using
+    prefix = 0
+    if isinstance(using, str) and using.startswith("matryoshka_"):
+        try:
+            prefix = int(using[len("matryoshka_"):])
+        except ValueError:
+            prefix = -1
+        if prefix not in tuple(msizes):
+            raise ValueError(f"{where}: using={using!r}, but the collection's matryoshka sizes are {tuple(msizes)}")
+    elif using not in USINGS:
+        raise ValueError(f"{where}: using must be 'dense', 'matryoshka_<d>', 'quantized' or 'sparse', got {using!r}")
+    if _is_sparse(q):
+        if using != "sparse":
+            raise ValueError(f"{where}: a sparse query needs using='sparse', got {using!r}")
+        vec = _sparse(q, where)
+    else:
+        if isinstance(q, dict) or not isinstance(q, (list, tuple, np.ndarray)) and not hasattr(q, "__iter__"):
+            raise ValueError(f"{where}: unknown query {type(q).__name__}: a vector, a sparse vector or a fusion")
+        if using == "sparse":
+            raise ValueError(f"{where}: using='sparse' needs a sparse query ({{'indices', 'values'}})")
+        vec = _dense(q, using, prefix, dim, where)
+    if pre and using in ("quantized", "sparse"):
+        raise ValueError(f"{where}: using={using!r} cannot re-score a prefetch (only 'dense' and 'matryoshka_<d>' can)")
+    vecs.append(vec)
+    children = tuple(parse(c, dim, msizes, _depth + 1, False, vecs)[0] for c in pre)
+    if sum(c[-2] for c in children) > RESCORE_MAX:
+        raise ValueError(f"{where}: the prefetches hold {sum(c[-2] for c in children)} candidates together, the "
+                         f"re-scoring stage takes at most {RESCORE_MAX}")
+    return ("nearest", using, prefix, limit, children), vecs
+
+
+def shape_limit(shape) -> int:
+    return shape[-2]
+
+
+def input_width(shape) -> int:
+    """The candidates a node with prefetches sees: the sum of its children's limits (0 for a leaf)."""
+    return sum(shape_limit(c) for c in shape[-1])
+
+
+def group_by_shape(shapes: Sequence[Any]) -> Dict[Any, List[int]]:
+    """shape -> the positions of the requests that have it, in request order (dicts keep insertion order)."""
+    groups: Dict[Any, List[int]] = {}
+    for i, s in enumerate(shapes):
+        groups.setdefault(s, []).append(i)
+    return groups
+
+
+def batch_vectors(vector_lists: Sequence[Sequence[Any]]) -> List[Any]:
+    """The vectors of B requests of one shape -> per nearest node (pre-order) a float32 [B, dim] array or a list of B
+    (indices, values) pairs."""
+    out = []
+    for slot in zip(*vector_lists):
+        out.append(list(slot) if isinstance(slot[0], tuple) else np.stack(slot).astype(np.float32, copy=False))
+    return out
+
+
+def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None):
+    """Run one shape for the B queries whose vectors are `vectors` (batch_vectors).  `stages` offers the stage entries:
+    dense(Q, limit, prefix), i8(Q, limit), sparse(pairs, limit), rescore(Q, [(keys, counts)], limit, prefix) and
+    fuse([(keys, counts)], method, weights, limit, rrf_k, rank_base), each returning (keys [B, limit], counts [B]) in
+    whatever array type it keeps lists in -- they stay where the stages put them between nodes.  root_limit overrides
+    the root's limit (a filtered root runs at the width of its input)."""
+    cursor = [0]
+
+    def walk(s, limit=None):
+        limit = shape_limit(s) if limit is None else limit
+        if s[0] == "fusion":
+            _, method, weights, rrf_k, rank_base, _, children = s
+            lists = [walk(c) for c in children]
+            return stages.fuse(lists, method, weights, limit, rrf_k, rank_base)
+        _, using, prefix, _, children = s
+        q = vectors[cursor[0]]
+        cursor[0] += 1
+        if children:
+            lists = [walk(c) for c in children]
+            return stages.rescore(q, lists, limit, prefix)
+        if using == "sparse":
+            return stages.sparse(q, limit)
+        if using == "quantized":
+            return stages.i8(q, limit)
+        return stages.dense(q, limit, prefix)
+
+    return walk(shape, root_limit)
+
+
+class DeviceStages:
+    """The stage entries of one engine index (engine.HxIndex), lists as int64 device tensors."""
+
+    def __init__(self, index, engine):
+        import torch
+        self.ix, self.eng, self.torch = index, engine, torch
+        self.dev = index._tdev
+
+    def _q(self, Q):
+        return self.torch.from_numpy(np.ascontiguousarray(Q, dtype=np.float32)).to(self.dev)
+
+    def dense(self, Q, limit, prefix):
+        return self.ix.search_dense(self._q(Q), limit, prefix)
+
+    def i8(self, Q, limit):
+        return self.ix.search_i8(self._q(Q), limit)
+
+    def sparse(self, pairs, limit):
+        t = self.torch
+        indptr = np.zeros(len(pairs) + 1, dtype=np.int64)
+        np.cumsum([len(i) for i, _ in pairs], out=indptr[1:])
+        idx = np.concatenate([i for i, _ in pairs]).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
+        val = np.concatenate([v for _, v in pairs]).astype(np.float32) if indptr[-1] else np.zeros(0, np.float32)
+        return self.ix.search_sparse(t.from_numpy(indptr).to(self.dev), t.from_numpy(idx).to(self.dev),
+                                     t.from_numpy(val).to(self.dev), limit)
+
+    def rescore(self, Q, lists, limit, prefix):
+        # a stage's slots past its count are 0, and hx_rescore skips a 0: the union is the lists side by side
+        if len(lists) == 1:
+            return self.ix.rescore(self._q(Q), lists[0][0], lists[0][1], limit, prefix)
+        return self.ix.rescore(self._q(Q), self.torch.cat([k for k, _ in lists], dim=1), None, limit, prefix)
+
+    def fuse(self, lists, method, weights, limit, rrf_k, rank_base):
+        return self.eng.fuse([k for k, _ in lists], [c for _, c in lists], method, weights, limit, rrf_k, rank_base)
+
+    @staticmethod
+    def to_host(keys, counts) -> Tuple[np.ndarray, np.ndarray]:
+        return keys.cpu().numpy().view(np.uint64), counts.cpu().numpy()

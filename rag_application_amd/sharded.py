@@ -482,6 +482,7 @@ class ShardedHandler(QdrantHandler):
     _discover = False                # discover / discover_batch raise ValueError: nothing is sent to the ranks
     _scroll = False                  # scroll / retrieve raise ValueError: the rows of a collection lie in several indexes
     _matrix_search = False           # search_matrix_pairs / _offsets raise ValueError: a sample's rows lie in several indexes
+    _query_tree = False              # query_points / query_points_batch raise ValueError: nothing is sent to the ranks
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
