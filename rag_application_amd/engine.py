@@ -401,6 +401,54 @@ class HxIndex:
             raise ValueError(f"mask: {m.shape[0]} words for {n} rows (want {(n + 31) // 32})")
         return np.ascontiguousarray(m), n
 
+    # -- what every entry does with its queries, its masks, its pools and its outputs ---------------------------------
+    def _host_mask(self, mask):
+        """(words, mask_rows) of a *_host call: None = every row, else as `_mask` takes it"""
+        return (None, 0) if mask is None else self._mask(mask)
+
+    def _dev_mask(self, mask):
+        """(words, mask_rows) of a device call: None = every row; the packed words on the device (an int32 / uint32
+        tensor, as payload_mask returns them) go as they are, ceil(count / 32) of them; a bool mask (host or device) or
+        host words are packed on the host (`_mask`) and uploaded."""
+        if mask is None:
+            return None, 0
+        if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
+            if mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not mask.is_contiguous():
+                raise TypeError("device mask: a contiguous int32 / uint32 tensor holding the packed words, or a bool tensor")
+            rows = self.count()
+            if mask.shape[0] != (rows + 31) // 32:
+                raise ValueError(f"mask: {mask.shape[0]} words for {rows} rows")
+            return mask, rows
+        packed, rows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
+        return torch.from_numpy(packed.view(np.int32)).to(self._tdev), rows
+
+    def _host_queries(self, q, q_indptr, q_idx, q_val):
+        """the batch of a *_host call as the engine reads it: (q [B, dim] float32, the sparse CSR int64 / int32 /
+        float32, B)"""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
+        return (q, np.ascontiguousarray(q_indptr, dtype=np.int64), np.ascontiguousarray(q_idx, dtype=np.int32),
+                np.ascontiguousarray(q_val, dtype=np.float32), q.shape[0])
+
+    @staticmethod
+    def _pool_args(keys, counts):
+        """the ranked pools of a stage: (keys [B, stride] int64, counts [B] int32 or None, B, stride)"""
+        keys = _need_cuda(keys, torch.int64, "keys")
+        if keys.dim() != 2:
+            raise HxError("keys must be a [B, stride] tensor")
+        if counts is not None:
+            counts = _need_cuda(counts, torch.int32, "counts")
+        return keys, counts, int(keys.shape[0]), int(keys.shape[1])
+
+    @staticmethod
+    def _host_out(B: int, L: int, bound: Optional[int] = None, extra: int = 0):
+        """(scores [B, L] float32, ids [B, L] int64, counts [B] int32, then `extra` more float32 planes [B, L]) for a
+        *_host entry to fill.  bound: an L outside [1, bound] gets one slot (the engine refuses; nothing huge is
+        allocated)."""
+        if bound is not None and not 1 <= L <= bound:
+            L = 1
+        return (np.empty((B, L), dtype=np.float32), np.empty((B, L), dtype=np.int64), np.empty((B,), dtype=np.int32),
+                *(np.empty((B, L), dtype=np.float32) for _ in range(extra)))
+
     def hybrid_query(self, q: torch.Tensor, q_indptr: torch.Tensor, q_idx: torch.Tensor,
                      q_val: torch.Tensor, params: HxParams, mask=None):
         """mask: None = every row; else a packed uint32 tensor / array or a bool array (hx_hybrid_query_dev_masked)."""
@@ -414,15 +462,7 @@ class HxIndex:
             check(_lib.lib().hx_hybrid_query_dev(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                  C.byref(params), _ptr(keys), _ptr(cnt), _stream()))
             return keys, cnt
-        if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
-            if mask.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not mask.is_contiguous():
-                raise TypeError("device mask: a contiguous int32 / uint32 tensor holding the packed words, or a bool tensor")
-            words, rows = mask, self.count()
-            if words.shape[0] != (rows + 31) // 32:
-                raise ValueError(f"mask: {words.shape[0]} words for {rows} rows")
-        else:   # a bool mask (host or device) or host words: packed on the host
-            packed, rows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
-            words = torch.from_numpy(packed.view(np.int32)).to(q.device)
+        words, rows = self._dev_mask(mask)
         check(_lib.lib().hx_hybrid_query_dev_masked(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                     C.byref(params), _ptr(words), rows, _ptr(keys), _ptr(cnt),
                                                     _stream()))
@@ -581,14 +621,8 @@ class HxIndex:
                           params: HxParams, mask=None):
         """mask: None = every row; else a bool array (one entry per row) or packed np.uint32 words
         (hx_hybrid_query_host_masked: the lists of the same query on an index of the kept rows only)."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
-        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
-        B, L = q.shape[0], params.final_limit
-        scores = np.empty((B, L), dtype=np.float32)
-        ids = np.empty((B, L), dtype=np.int64)
-        counts = np.empty((B,), dtype=np.int32)
+        q, q_indptr, q_idx, q_val, B = self._host_queries(q, q_indptr, q_idx, q_val)
+        scores, ids, counts = self._host_out(B, params.final_limit)
         if mask is None:
             check(_lib.lib().hx_hybrid_query_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                   C.byref(params), _ptr(scores), _ptr(ids), _ptr(counts)))
@@ -602,18 +636,13 @@ class HxIndex:
     # -- payload facets (hx.h: hx_payload_facet / hx_facet_top / hx_payload_facet_host) --------
     def payload_facet(self, col: int, n_codes: int, mask: Optional[torch.Tensor] = None, counts=None, stray=None):
         """How many kept rows hold each code below n_codes of the U32 or LIST_U32 column `col` (hx_payload_facet).  mask:
-        None = every row, or the packed words as payload_mask returns them (an int32 device tensor).  Returns (counts
+        None = every row, or a row mask as hybrid_query takes it (payload_mask's device words go as they are).  Returns (counts
         [n_codes] int32 holding the uint32 counts, stray [1] int64: the kept cells / elements with a code at or above
         n_codes).  counts / stray: the tensors to write (tests hand in sentinels).  Only enqueues work."""
         n_codes = int(n_codes)
         if not 0 <= n_codes <= 0xFFFFFFFF:
             raise HxError("facet: n_codes out of range [1, 0xFFFFFFFE]")
-        rows = 0
-        if mask is not None:
-            mask = _need_cuda(mask, torch.int32, "mask")
-            rows = self.count()
-            if mask.shape[0] != (rows + 31) // 32:
-                raise ValueError(f"mask: {mask.shape[0]} words for {rows} rows")
+        mask, rows = self._dev_mask(mask)
         if counts is None:
             counts = torch.empty((n_codes if 1 <= n_codes <= 0xFFFFFFFE else 1,), dtype=torch.int32, device=self._tdev)
         if stray is None:
@@ -655,7 +684,7 @@ class HxIndex:
             rank = np.ascontiguousarray(rank, dtype=np.uint32)
             if rank.shape[0] != n_codes:
                 raise ValueError(f"rank: {rank.shape[0]} entries for {n_codes} codes")
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        words, rows = self._host_mask(mask)
         first = np.empty((L,), dtype=np.uint32)
         counts = np.empty((L,), dtype=np.uint32)
         n_out, stray = C.c_int32(), C.c_uint64()
@@ -664,16 +693,6 @@ class HxIndex:
         return first[:n_out.value], counts[:n_out.value], int(stray.value)
 
     # -- scroll (hx.h: hx_scroll_rows / hx_payload_order and their _host forms) ----------------
-    def _dev_mask(self, mask):
-        """(mask, mask_rows) of a device call: None = every row, else the packed words as payload_mask returns them."""
-        if mask is None:
-            return None, 0
-        mask = _need_cuda(mask, torch.int32, "mask")
-        rows = self.count()
-        if mask.shape[0] != (rows + 31) // 32:
-            raise ValueError(f"mask: {mask.shape[0]} words for {rows} rows")
-        return mask, rows
-
     def scroll_rows(self, limit: int, start_row: int = 0, mask: Optional[torch.Tensor] = None, out=None, out_count=None):
         """The first `limit` rows r >= start_row whose mask bit is set, ascending (hx_scroll_rows).  Returns (rows [limit]
         int32 holding the uint32 rows, 0 past the hits; count [1] int32).  out / out_count: the tensors to write (tests
@@ -724,7 +743,7 @@ class HxIndex:
         L = int(limit)
         if not 1 <= L <= 2048:
             raise HxError("scroll: limit out of range [1, 2048]")
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        words, rows = self._host_mask(mask)
         out = np.empty((L,), dtype=np.uint32)
         n_out = C.c_int32()
         check(_lib.lib().hx_scroll_rows_host(self._h, _ptr(words), rows, int(start_row), L, _ptr(out), C.byref(n_out)))
@@ -737,7 +756,7 @@ class HxIndex:
         L = int(limit)
         if not 1 <= L <= 2048:
             raise HxError("scroll: limit out of range [1, 2048]")
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        words, rows = self._host_mask(mask)
         fl, sf, av, ar = self._order_bounds(start_from, after)
         out = np.empty((L,), dtype=np.uint32)
         bits = np.empty((L,), dtype=np.uint64)
@@ -752,12 +771,7 @@ class HxIndex:
         group_size hits each, grouped by the cells of the U32 column `col` (hx_group).  Returns (out_keys
         [B, n_groups, group_size] int64, 0 = an empty slot; group_codes [B, n_groups] int32 holding the uint32 codes,
         -1 = HX_PAY_U32_MISSING = no such group; group_counts [B] int32).  Only enqueues work."""
-        keys = _need_cuda(keys, torch.int64, "keys")
-        if keys.dim() != 2:
-            raise HxError("keys must be a [B, stride] tensor")
-        if counts is not None:
-            counts = _need_cuda(counts, torch.int32, "counts")
-        B, stride = int(keys.shape[0]), int(keys.shape[1])
+        keys, counts, B, stride = self._pool_args(keys, counts)
         G, S = int(n_groups), int(group_size)
         slots = G * S if 1 <= G <= 2048 and 1 <= S <= 2048 else 0      # (the engine refuses; nothing huge is allocated)
         out = torch.empty((B, max(slots, 1)), dtype=torch.int64, device=keys.device)
@@ -774,18 +788,14 @@ class HxIndex:
         final_limit = the pool (group_pool = 0: the mode's whole pool; params.final_limit is not used), the pool is
         grouped on the device.  Returns (scores [B, n_groups, group_size] float32, ids [B, n_groups, group_size] int64 --
         empty slots (-inf, -1) --, group_codes [B, n_groups] uint32, group_counts [B] int32).  mask as hybrid_query_host."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
-        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
-        B, G, S = q.shape[0], int(n_groups), int(group_size)
+        q, q_indptr, q_idx, q_val, B = self._host_queries(q, q_indptr, q_idx, q_val)
+        G, S = int(n_groups), int(group_size)
         if not (1 <= G <= 2048 and 1 <= S <= 2048 and G * S <= 2048):
             raise HxError("group: n_groups and group_size must be at least 1 and n_groups * group_size at most 2048")
-        scores = np.empty((B, G, S), dtype=np.float32)
-        ids = np.empty((B, G, S), dtype=np.int64)
+        scores, ids, counts = self._host_out(B, G * S)
+        scores, ids = scores.reshape(B, G, S), ids.reshape(B, G, S)
         codes = np.empty((B, G), dtype=np.uint32)
-        counts = np.empty((B,), dtype=np.int32)
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        words, rows = self._host_mask(mask)
         check(_lib.lib().hx_hybrid_query_groups_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                      C.byref(params), _ptr(words), rows, int(col), int(group_pool), G, S,
                                                      _ptr(scores), _ptr(ids), _ptr(codes), _ptr(counts)))
@@ -794,20 +804,13 @@ class HxIndex:
     # -- MMR search (hx.h: hx_mmr / hx_hybrid_query_mmr_host) ----------------------------------
     def mmr(self, keys: torch.Tensor, counts: Optional[torch.Tensor], limit: int, diversity: float, eligible=None):
         """Maximal marginal relevance over the ranked pools keys [B, stride] (+ counts [B], None = every slot): `limit`
-        picks per query (hx_mmr).  eligible: None, or a row mask as hybrid_query_host takes it (a bool array of one entry
+        picks per query (hx_mmr).  eligible: None, or a row mask as hybrid_query takes it (a bool array of one entry
         per row, or packed uint32 words); rows whose bit is clear are never picked.  Returns (out_keys [B, limit] int64, 0
         past the picks; values [B, limit] float32, the picks' MMR values; counts [B] int32).  Only enqueues work."""
-        keys = _need_cuda(keys, torch.int64, "keys")
-        if keys.dim() != 2:
-            raise HxError("keys must be a [B, stride] tensor")
-        if counts is not None:
-            counts = _need_cuda(counts, torch.int32, "counts")
-        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        keys, counts, B, stride = self._pool_args(keys, counts)
+        L = int(limit)
         slots = L if 1 <= L <= 256 else 1                   # (the engine refuses; nothing huge is allocated)
-        words, rows = None, 0
-        if eligible is not None:
-            w, rows = self._mask(eligible)
-            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
+        words, rows = self._dev_mask(eligible)
         out = torch.empty((B, slots), dtype=torch.int64, device=keys.device)
         val = torch.empty((B, slots), dtype=torch.float32, device=keys.device)
         cnt = torch.empty((B,), dtype=torch.int32, device=keys.device)
@@ -823,18 +826,12 @@ class HxIndex:
         the device.  mask as hybrid_query_host; mask_root_only: the query runs unmasked and only the picks honour the mask
         (tree mode).  Returns (scores [B, limit] float32 -- the dense cosines, in both modes --, ids [B, limit] int64,
         values [B, limit] float32, counts [B] int32) in pick order, the slots past the picks (-inf, -1, 0)."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
-        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
-        B, L = q.shape[0], int(limit)
+        q, q_indptr, q_idx, q_val, B = self._host_queries(q, q_indptr, q_idx, q_val)
+        L = int(limit)
         if not 1 <= L <= 256:
             raise HxError("mmr: limit out of range [1, 256]")
-        scores = np.empty((B, L), dtype=np.float32)
-        ids = np.empty((B, L), dtype=np.int64)
-        values = np.empty((B, L), dtype=np.float32)
-        counts = np.empty((B,), dtype=np.int32)
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        scores, ids, counts, values = self._host_out(B, L, extra=1)
+        words, rows = self._host_mask(mask)
         check(_lib.lib().hx_hybrid_query_mmr_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                   C.byref(params), _ptr(words), rows, int(bool(mask_root_only)),
                                                   int(candidates_limit), L, float(diversity), _ptr(scores), _ptr(ids),
@@ -853,26 +850,19 @@ class HxIndex:
                 score_threshold: Optional[float] = None, eligible=None, out=None):
         """The pools keys [B, stride] (+ counts [B], None = every slot) ranked again by the value the postfix program
         `ops` -- (op, arg, imm) triples, imm an int holding the bits of a double -- gives every position (hx_formula).
-        planes: the condition planes, row masks as hybrid_query_host takes them; eligible: None or one more such mask;
+        planes: the condition planes, row masks as hybrid_query takes them; eligible: None or one more such mask;
         score_threshold None = no cut.  out: None, or the four output tensors to write into.  Returns (out_keys [B, limit]
         int64, 0 past the hits; positions [B, limit] int32, -1 past them; counts [B] int32; dropped [B] int32).  Only
         enqueues work."""
-        keys = _need_cuda(keys, torch.int64, "keys")
-        if keys.dim() != 2:
-            raise HxError("keys must be a [B, stride] tensor")
-        if counts is not None:
-            counts = _need_cuda(counts, torch.int32, "counts")
-        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        keys, counts, B, stride = self._pool_args(keys, counts)
+        L = int(limit)
         slots = L if 1 <= L <= 2048 else 1                  # (the engine refuses; nothing huge is allocated)
         dev_planes, rows = [], 0
         for m in planes:
-            w, rows = self._mask(m)
-            dev_planes.append(torch.from_numpy(w.view(np.int32)).to(keys.device))
+            w, rows = self._dev_mask(m)
+            dev_planes.append(w)
         parr = (C.c_void_p * max(len(dev_planes), 1))(*[t.data_ptr() for t in dev_planes])
-        words, erows = None, 0
-        if eligible is not None:
-            w, erows = self._mask(eligible)
-            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
+        words, erows = self._dev_mask(eligible)
         if out is None:
             out = (torch.empty((B, slots), dtype=torch.int64, device=keys.device),
                    torch.empty((B, slots), dtype=torch.int32, device=keys.device),
@@ -894,11 +884,8 @@ class HxIndex:
         score_threshold as `formula` takes them, mask / mask_root_only as hybrid_query_mmr_host.  Returns (scores
         [B, limit] float32 -- the values --, ids [B, limit] int64, base_scores [B, limit] float32 -- the scores the pool
         carried --, counts [B] int32, dropped [B] int32); the slots past the hits (-inf, -1, -inf)."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
-        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
-        B, L = q.shape[0], int(limit)
+        q, q_indptr, q_idx, q_val, B = self._host_queries(q, q_indptr, q_idx, q_val)
+        L = int(limit)
         if not 1 <= L <= 2048:
             raise HxError("formula: limit out of range [1, 2048]")
         host_planes = []
@@ -908,12 +895,9 @@ class HxIndex:
                 raise HxError("formula: a condition plane must hold one bit per row of the index (hx_count)")
             host_planes.append(w)
         parr = (C.c_void_p * max(len(host_planes), 1))(*[w.ctypes.data for w in host_planes])
-        scores = np.empty((B, L), dtype=np.float32)
-        ids = np.empty((B, L), dtype=np.int64)
-        base = np.empty((B, L), dtype=np.float32)
-        counts = np.empty((B,), dtype=np.int32)
+        scores, ids, counts, base = self._host_out(B, L, extra=1)
         dropped = np.empty((B,), dtype=np.int32)
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        words, rows = self._host_mask(mask)
         thr = float("nan") if score_threshold is None else float(score_threshold)
         check(_lib.lib().hx_hybrid_query_formula_host(
             self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B, C.byref(params), _ptr(words), rows,
@@ -923,6 +907,24 @@ class HxIndex:
         return scores, ids, base, counts, dropped
 
     # -- recommend search (hx.h: hx_recommend / hx_recommend_host) --------------------------------
+    def _example(self, ex, rows: list, vecs: list, what: str) -> None:
+        """one example onto the flat lists: a local row (an int) -> that row; anything else -> a vector of `dim`
+        float32 numbers and the row -1.  what: "recommend" | "discover", for the refusal."""
+        if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
+            rows.append(int(ex))
+        else:
+            v = np.asarray(ex, dtype=np.float32).reshape(-1)
+            if v.shape[0] != self.dim:
+                raise HxError(f"{what}: an example vector of {v.shape[0]} values, the index holds {self.dim}")
+            rows.append(-1)
+            vecs.append(v)
+
+    @staticmethod
+    def _examples_csr(indptr, rows, vecs):
+        """(indptr int64 [R + 1], rows int64 [E], vecs float32 [n_raw, dim] or None) of the flat lists"""
+        return (np.asarray(indptr, np.int64), np.asarray(rows, np.int64).reshape(-1),
+                np.ascontiguousarray(np.stack(vecs)) if vecs else None)
+
     def _reco_examples(self, requests):
         """requests: per request a sequence of (example, sign) -- example = a local row (an int) or a vector of `dim`
         numbers, sign = +1 | -1 -> (indptr int64 [R + 1], rows int64 [E] with -1 for a raw vector, signs int8 [E], vecs
@@ -930,19 +932,11 @@ class HxIndex:
         indptr, rows, signs, vecs = [0], [], [], []
         for req in requests:
             for ex, sign in req:
-                if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
-                    rows.append(int(ex))
-                else:
-                    v = np.asarray(ex, dtype=np.float32).reshape(-1)
-                    if v.shape[0] != self.dim:
-                        raise HxError(f"recommend: an example vector of {v.shape[0]} values, the index holds {self.dim}")
-                    rows.append(-1)
-                    vecs.append(v)
+                self._example(ex, rows, vecs, "recommend")
                 signs.append(int(sign))
             indptr.append(len(rows))
-        return (np.asarray(indptr, np.int64), np.asarray(rows, np.int64).reshape(-1),
-                np.asarray(signs, np.int64).clip(-128, 127).astype(np.int8).reshape(-1),
-                np.ascontiguousarray(np.stack(vecs)) if vecs else None)
+        indptr, rows, vecs = self._examples_csr(indptr, rows, vecs)
+        return indptr, rows, np.asarray(signs, np.int64).clip(-128, 127).astype(np.int8).reshape(-1), vecs
 
     def recommend(self, requests, strategy: int, limit: int, mask=None, keys=None, counts=None):
         """Points like given examples (hx_recommend): requests as _reco_examples takes them, strategy = RECO_AVERAGE |
@@ -952,13 +946,7 @@ class HxIndex:
         R, L = len(indptr) - 1, int(limit)
         if keys is None or counts is None:
             keys, counts = self._out(max(R, 1), L if 1 <= L <= 1024 else 1)   # (the engine refuses; nothing huge is allocated)
-        words, mrows = None, 0
-        if mask is not None:
-            if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
-                words, mrows = mask, self.count()
-            else:
-                packed, mrows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
-                words = torch.from_numpy(packed.view(np.int32)).to(keys.device)
+        words, mrows = self._dev_mask(mask)
         check(_lib.lib().hx_recommend(self._h, int(strategy), R, _ptr(indptr), _ptr(rows), _ptr(signs), _ptr(vecs),
                                       _ptr(words), mrows, L, _ptr(keys), _ptr(counts), _stream()))
         return keys, counts
@@ -968,11 +956,8 @@ class HxIndex:
         int32), the slots past a request's count (-inf, -1)."""
         indptr, rows, signs, vecs = self._reco_examples(requests)
         R, L = len(indptr) - 1, int(limit)
-        slots = L if 1 <= L <= 1024 else 1
-        scores = np.empty((max(R, 1), slots), dtype=np.float32)
-        ids = np.empty((max(R, 1), slots), dtype=np.int64)
-        counts = np.empty((max(R, 1),), dtype=np.int32)
-        words, mrows = (None, 0) if mask is None else self._mask(mask)
+        scores, ids, counts = self._host_out(max(R, 1), L, 1024)
+        words, mrows = self._host_mask(mask)
         check(_lib.lib().hx_recommend_host(self._h, int(strategy), R, _ptr(indptr), _ptr(rows), _ptr(signs), _ptr(vecs),
                                            _ptr(words), mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores[:R], ids[:R], counts[:R]
@@ -989,18 +974,10 @@ class HxIndex:
                 pos, neg = pair
                 flat += [pos, neg]
             for ex in flat:
-                if isinstance(ex, (int, np.integer)) and not isinstance(ex, bool):
-                    rows.append(int(ex))
-                else:
-                    v = np.asarray(ex, dtype=np.float32).reshape(-1)
-                    if v.shape[0] != self.dim:
-                        raise HxError(f"discover: an example vector of {v.shape[0]} values, the index holds {self.dim}")
-                    rows.append(-1)
-                    vecs.append(v)
+                self._example(ex, rows, vecs, "discover")
             has_target.append(0 if target is None else 1)
             indptr.append(len(rows))
-        return (np.asarray(indptr, np.int64), np.asarray(rows, np.int64).reshape(-1),
-                np.ascontiguousarray(np.stack(vecs)) if vecs else None, np.asarray(has_target, np.int32).reshape(-1))
+        return (*self._examples_csr(indptr, rows, vecs), np.asarray(has_target, np.int32).reshape(-1))
 
     def discover(self, requests, limit: int, mask=None, keys=None, counts=None):
         """Discovery (a target and context pairs) and context search (pairs only) in one exact scan (hx_discover):
@@ -1010,13 +987,7 @@ class HxIndex:
         R, L = len(indptr) - 1, int(limit)
         if keys is None or counts is None:
             keys, counts = self._out(max(R, 1), L if 1 <= L <= 1024 else 1)   # (the engine refuses; nothing huge is allocated)
-        words, mrows = None, 0
-        if mask is not None:
-            if isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype != torch.bool:
-                words, mrows = mask, self.count()
-            else:
-                packed, mrows = self._mask(mask.cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
-                words = torch.from_numpy(packed.view(np.int32)).to(keys.device)
+        words, mrows = self._dev_mask(mask)
         check(_lib.lib().hx_discover(self._h, R, _ptr(indptr), _ptr(rows), _ptr(vecs), _ptr(has_target), _ptr(words), mrows,
                                      L, _ptr(keys), _ptr(counts), _stream()))
         return keys, counts
@@ -1026,11 +997,8 @@ class HxIndex:
         int32), the slots past a request's count (-inf, -1)."""
         indptr, rows, vecs, has_target = self._discover_examples(requests)
         R, L = len(indptr) - 1, int(limit)
-        slots = L if 1 <= L <= 1024 else 1
-        scores = np.empty((max(R, 1), slots), dtype=np.float32)
-        ids = np.empty((max(R, 1), slots), dtype=np.int64)
-        counts = np.empty((max(R, 1),), dtype=np.int32)
-        words, mrows = (None, 0) if mask is None else self._mask(mask)
+        scores, ids, counts = self._host_out(max(R, 1), L, 1024)
+        words, mrows = self._host_mask(mask)
         check(_lib.lib().hx_discover_host(self._h, R, _ptr(indptr), _ptr(rows), _ptr(vecs), _ptr(has_target), _ptr(words),
                                           mrows, L, _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores[:R], ids[:R], counts[:R]
@@ -1064,9 +1032,7 @@ class HxIndex:
         """search_matrix, host out (hx_search_matrix_host): (scores [S, limit] float32, ids [S, limit] int64, counts [S]
         int32), the slots past a row's count (-inf, -1)."""
         rows, S, L, thr, out_rows, out_cols = self._matrix_args(rows, limit, score_threshold)
-        scores = np.empty((out_rows, out_cols), dtype=np.float32)
-        ids = np.empty((out_rows, out_cols), dtype=np.int64)
-        counts = np.empty((out_rows,), dtype=np.int32)
+        scores, ids, counts = self._host_out(out_rows, out_cols)
         check(_lib.lib().hx_search_matrix_host(self._h, _ptr(rows), S, L, thr, _ptr(scores), _ptr(ids), _ptr(counts)))
         return scores[:S], ids[:S], counts[:S]
 
@@ -1141,24 +1107,17 @@ class HxIndex:
         np.float32: the queries' tokens one after another, q_indptr [B + 1] the first token of every query.  eligible as
         mmr takes it.  Returns (out_keys [B, limit] int64 carrying the MaxSim scores, 0 past the eligible positions;
         counts [B] int32).  out / out_counts: the tensors to write (tests hand in sentinels).  Only enqueues work."""
-        keys = _need_cuda(keys, torch.int64, "keys")
-        if keys.dim() != 2:
-            raise HxError("keys must be a [B, stride] tensor")
-        if counts is not None:
-            counts = _need_cuda(counts, torch.int32, "counts")
+        keys, counts, B, stride = self._pool_args(keys, counts)
         q8, qscale, q_indptr = self._query_tokens(q8, qscale, q_indptr)
-        B, stride, L = int(keys.shape[0]), int(keys.shape[1]), int(limit)
+        L = int(limit)
         if q_indptr.shape[0] != B + 1:
             raise ValueError(f"{q_indptr.shape[0] - 1} queries' tokens for {B} pools")
         dim_t = self._token_dim(col)
         if dim_t and q8.shape[1] != dim_t:
             raise ValueError(f"query tokens of {q8.shape[1]} values for a column of {dim_t}")
         slots = L if 1 <= L <= 2048 else 1                  # (the engine refuses; nothing huge is allocated)
-        words, rows = None, 0
-        if eligible is not None:
-            w, rows = self._mask(eligible)
-            words = torch.from_numpy(w.view(np.int32)).to(keys.device)
-        dq8 = torch.from_numpy(q8.reshape(-1) if q8.size else np.zeros(16, np.int8)).to(keys.device)
+        words, rows = self._dev_mask(eligible)
+        dq8 =torch.from_numpy(q8.reshape(-1) if q8.size else np.zeros(16, np.int8)).to(keys.device)
         dqs = torch.from_numpy(qscale if qscale.size else np.zeros(1, np.float32)).to(keys.device)
         dip = torch.from_numpy(q_indptr).to(keys.device)
         if out is None:
@@ -1178,12 +1137,9 @@ class HxIndex:
         mask_root_only as hybrid_query_mmr_host.  Returns (scores [B, limit] float32 -- MaxSim --, ids [B, limit] int64,
         first_scores [B, limit] float32 -- what the pool carried --, counts [B] int32), the slots past the counts
         (-inf, -1, -inf)."""
-        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self.dim)
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
-        q_val = np.ascontiguousarray(q_val, dtype=np.float32)
+        q, q_indptr, q_idx, q_val, B = self._host_queries(q, q_indptr, q_idx, q_val)
         q8, qscale, qtok_indptr = self._query_tokens(q8, qscale, qtok_indptr)
-        B, L = q.shape[0], int(limit)
+        L = int(limit)
         if qtok_indptr.shape[0] != B + 1:
             raise ValueError(f"{qtok_indptr.shape[0] - 1} queries' tokens for {B} queries")
         if not 1 <= L <= 2048:
@@ -1191,11 +1147,8 @@ class HxIndex:
         dim_t = self._token_dim(col)
         if dim_t and q8.shape[1] != dim_t:
             raise ValueError(f"query tokens of {q8.shape[1]} values for a column of {dim_t}")
-        scores = np.empty((B, L), dtype=np.float32)
-        ids = np.empty((B, L), dtype=np.int64)
-        first = np.empty((B, L), dtype=np.float32)
-        counts = np.empty((B,), dtype=np.int32)
-        words, rows = (None, 0) if mask is None else self._mask(mask)
+        scores, ids, counts, first = self._host_out(B, L, extra=1)
+        words, rows = self._host_mask(mask)
         check(_lib.lib().hx_hybrid_query_rerank_host(self._h, _ptr(q), _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B,
                                                      C.byref(params), _ptr(words), rows, int(bool(mask_root_only)),
                                                      int(candidates_limit), int(col), _ptr(q8), _ptr(qscale),

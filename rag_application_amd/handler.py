@@ -171,6 +171,15 @@ class _Collection:
         self._idrows_n = len(self.ids)
         return m if len(m) == len(self.ids) else None
 
+    def first_rows(self) -> Dict[str, int]:
+        """id -> row for the searches that take point ids; an id held twice: the first row that holds it"""
+        rows = self._id_rows()
+        if rows is None:
+            rows = {}
+            for r, pid in enumerate(self.ids):
+                rows.setdefault(pid, r)
+        return rows
+
     def _device_mask(self, flt, n: int) -> Optional[np.ndarray]:
         """The packed row mask of `flt` from hx_payload_mask, or None: no payload index, or the filter is declined."""
         pi = getattr(self, "pindex", None)
@@ -622,6 +631,121 @@ class QdrantHandler:
                 return fn(*a)
         return await loop.run_in_executor(None, locked)
 
+    # ------------------------------------------------- what the search entries share
+    async def _guarded(self, what, user_id, empty, fn, *a, failed=None):
+        """The async face of a search entry: fn(*a) under the lock; a ValueError is logged and raised, any other failure
+        is logged and answered with `empty`.  what / failed: how the two log lines name the call ("... for %s")."""
+        try:
+            return await self._run(fn, *a)
+        except ValueError as ve:
+            logging.error(what + " refused: %s", user_id, ve)
+            raise
+        except Exception as e:
+            logging.error((failed or what) + " failed: %s", user_id, e)
+            return empty
+
+    @staticmethod
+    def _check_int(name, v, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+
+    @staticmethod
+    def _check_candidates(candidates_limit):
+        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
+                                             or candidates_limit < 1):
+            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
+
+    @staticmethod
+    def _is_number(v) -> bool:
+        """an int or a float that is no bool and no NaN"""
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v
+
+    @staticmethod
+    def _check_stages(filter_stages):
+        if filter_stages not in FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+
+    @staticmethod
+    def _check_mode(mode):
+        if mode not in ("tree", "h1"):
+            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+
+    @staticmethod
+    def _root_filter(filters, mode, filter_stages) -> bool:
+        """whether `filters` is the root's filter (:297, :371), which only the reference query has"""
+        root_filter = bool(filters) and filter_stages == "root"
+        if root_filter and mode != "tree":
+            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
+                             "(or filter_stages='all')")
+        return root_filter
+
+    def _routing(self, filters, mode, filter_stages) -> bool:
+        """The routing arguments of a pool entry, checked in this order: filter_stages, mode, a root filter outside the
+        reference query.  Returns whether `filters` is a root filter.  (_search_sync runs the three checks between
+        steps of its own, in the order it always had.)"""
+        self._check_stages(filter_stages)
+        self._check_mode(mode)
+        return self._root_filter(filters, mode, filter_stages)
+
+    @staticmethod
+    def _pool_max(hp, mode) -> int:
+        """the longest pool the mode hands out: tree = the root's re-scored union, h1 = the fused list"""
+        return min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
+
+    def _pool_size(self, hp, mode, want) -> int:
+        """the pool of a pool entry: `want` (candidates_limit / group_pool) clipped to the mode's maximum, None = the
+        maximum; an empty pool is refused"""
+        pool_max = self._pool_max(hp, mode)
+        if pool_max < 1:
+            raise ValueError("the search_params leave an empty pool")
+        return pool_max if want is None else min(want, pool_max)
+
+    @staticmethod
+    def _check_filter(filters) -> None:
+        if filters:
+            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+
+    def _filter_mask(self, col, filters):
+        """the packed row mask of `filters` (None = no filter), its clause names validated first"""
+        self._check_filter(filters)
+        return col.row_mask(filters) if filters else None
+
+    @staticmethod
+    def _points(col, scores, rows, counts, cls=ScoredPoint, extra=None):
+        """Per query the first counts[b] (score, row) pairs as points of `cls`.  extra: one more float column [B, L] for
+        the one field a subclass adds behind ScoredPoint's seven (mmr_score / first_score / base_score)."""
+        cids, cpay = col.ids, col.payloads
+        if extra is None:                                  # (python floats / ints in one go)
+            return [[cls(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+                    for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist())]
+        return [[cls(cids[r], 0, s, cpay[r], None, None, None, x) for s, r, x in zip(sc[:n], rw[:n], ex[:n])]
+                for sc, rw, ex, n in zip(scores.tolist(), rows.tolist(), extra.tolist(), counts.tolist())]
+
+    @staticmethod
+    def _example_resolver(col, what):
+        """example -> its stored row (a point id: a str or an int) or a float32 vector of `dim` finite numbers (anything
+        else); what: "recommend" | "discover", for the refusals"""
+        id_rows = None
+
+        def example(ex):
+            nonlocal id_rows
+            if isinstance(ex, (str, int)) and not isinstance(ex, bool):
+                if id_rows is None:
+                    id_rows = col.first_rows()
+                if str(ex) not in id_rows:
+                    raise ValueError(f"{what}: unknown point id {ex!r}")
+                return id_rows[str(ex)]
+            try:
+                v = np.asarray(ex, dtype=np.float32).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: an example is a point id or a vector of numbers") from None
+            if v.shape[0] != col.dim:
+                raise ValueError(f"example dimension {v.shape[0]} != collection dimension {col.dim}")
+            if not np.isfinite(v).all():
+                raise ValueError(f"{what}: example vector values must be finite")
+            return v
+        return example
+
     # ---------------------------------------------------------------- create_collection
     async def create_collection(self, user_id: str, dense_vector_size: int = 768,
                                 matryoshka_sizes: list = [64, 128, 256], quantized_size: int = 768,
@@ -923,42 +1047,29 @@ class QdrantHandler:
 
     def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree",
                      filter_stages="root"):
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
+        self._check_stages(filter_stages)
         if filter_stages == "all" and not self._masked_search:
             raise ValueError("filter_stages='all' is not supported on a sharded collection: use filter_stages='root'")
         col = self._collections[str(user_id)]
         q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
-        if mode not in ("tree", "h1"):
-            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
+        self._check_mode(mode)
         # KeyError/TypeError like the reference when search_params lacks a key / is None
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
         final_limit = int(hp.final_limit)
         if filters and filter_stages == "all":
             # the filter applies to every stage: the engine searches the kept rows only, the root included
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            scores, ids, counts = col.index.hybrid_query_host(q, indptr, idx.astype(np.int32), val.astype(np.float32),
-                                                              hp, mask=col.row_mask(filters))
-            cids, cpay = col.ids, col.payloads
-            return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
-                    for sc, rw, n in zip(scores.tolist(), ids.tolist(), counts.tolist())]
-        if filters and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
-                             "(or filter_stages='all')")
-        if filters:
+            mask = self._filter_mask(col, filters)
+            return self._points(col, *col.index.hybrid_query_host(q, indptr, idx.astype(np.int32),
+                                                                  val.astype(np.float32), hp, mask=mask))
+        if self._root_filter(filters, mode, filter_stages):
             # query_filter belongs to the ROOT query only (:297, :371): the union of the branches'
             # candidates (<= dense_limit + the fusion's 10) is re-scored, filtered, cut to final_limit.
             # So: ask the engine for the whole re-scored union and filter it here.
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            hp.final_limit = min(int(hp.dense_limit) + int(hp.rrf_limit), 2048)
-        scores, ids, counts = col.index.hybrid_query_host(q, indptr, idx.astype(np.int32), val.astype(np.float32), hp)
-        out = []
-        cids, cpay = col.ids, col.payloads
-        for sc, rw, n in zip(scores.tolist(), ids.tolist(), counts.tolist()):     # (python floats / ints in one go)
-            pts = [ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
-            if filters:
-                pts = [p for p in pts if _filters.matches(p.payload, filters, p.id)][:final_limit]
-            out.append(pts)
+            self._check_filter(filters)
+            hp.final_limit = self._pool_max(hp, mode)
+        out = self._points(col, *col.index.hybrid_query_host(q, indptr, idx.astype(np.int32), val.astype(np.float32), hp))
+        if filters:
+            out = [[p for p in pts if _filters.matches(p.payload, filters, p.id)][:final_limit] for pts in out]
         return out
 
     async def hybrid_search(self, user_id: str, query_text: str, dense_vector: List[float],
@@ -1004,31 +1115,18 @@ class QdrantHandler:
         _grouping.check_sizes(limit, group_size)
         if not isinstance(group_by, str) or not group_by:
             raise ValueError("group_by must be a non-empty string (a payload key, dotted paths allowed)")
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
-        if mode not in ("tree", "h1"):
-            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
-        root_filter = bool(filters) and filter_stages == "root"
-        if root_filter and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
-                             "(or filter_stages='all')")
+        root_filter = self._routing(filters, mode, filter_stages)
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
-        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit),
-                       _grouping.MAX_SLOTS)
-        if group_pool is None:
-            pool = pool_max
-        elif isinstance(group_pool, bool) or not isinstance(group_pool, int) or not 1 <= group_pool <= pool_max:
+        pool_max = self._pool_max(hp, mode)                 # (_grouping.MAX_SLOTS is the pools' 2048)
+        if group_pool is not None and (isinstance(group_pool, bool) or not isinstance(group_pool, int)
+                                       or not 1 <= group_pool <= pool_max):
             raise ValueError(f"group_pool must be an integer in [1, {pool_max}] (this mode's pool) or None, "
                              f"got {group_pool!r}")
-        else:
-            pool = group_pool
-        if pool < 1:
-            raise ValueError("the search_params leave an empty pool")
+        pool = self._pool_size(hp, mode, group_pool)
         col = self._collections[str(user_id)]
         q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
         idx, val = idx.astype(np.int32), val.astype(np.float32)
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        self._check_filter(filters)
         cids, cpay = col.ids, col.payloads
         pi = getattr(col, "pindex", None)
         k = pi.keys.get(group_by) if pi is not None else None
@@ -1069,8 +1167,7 @@ class QdrantHandler:
         else:
             scores, rows, counts = col.index.hybrid_query_host(q, indptr, idx, val, hp)
         out = []
-        for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist()):
-            pts = [ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
+        for pts in self._points(col, scores, rows, counts):
             if root_filter:                                 # the root's filter comes before the grouping, as in Qdrant
                 pts = [p for p in pts if _filters.matches(p.payload, filters, p.id)]
             values = [_grouping.group_value(p.payload, group_by) for p in pts]
@@ -1099,54 +1196,29 @@ class QdrantHandler:
         Raises ValueError for arguments no search can serve (limit or group_size below 1, limit * group_size above 2048,
         a group_pool out of range, mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages
         or filter clause); any other failure is logged and gives [], as in every search."""
-        try:
-            return await self._run(self._groups_sync, user_id, dense_vectors, sparse_vectors, group_by, limit, group_size,
-                                   search_params, filters, mode, filter_stages, group_pool)
-        except ValueError as ve:
-            logging.error("grouped hybrid search for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("grouped hybrid search for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("grouped hybrid search for %s", user_id, [], self._groups_sync, user_id, dense_vectors,
+                                   sparse_vectors, group_by, limit, group_size, search_params, filters, mode,
+                                   filter_stages, group_pool)
 
     # ------------------------------------------------------------------------ MMR search
     def _mmr_sync(self, user_id, dense_vectors, sparse_vectors, limit, diversity, candidates_limit, search_params, filters,
                   mode, filter_stages):
         if not self._mmr_search:
             raise ValueError("hybrid_search_mmr is not supported on a sharded collection")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= MMR_MAX_LIMIT:
-            raise ValueError(f"limit must be an integer in [1, {MMR_MAX_LIMIT}], got {limit!r}")
-        if isinstance(diversity, bool) or not isinstance(diversity, (int, float)) or not 0.0 <= diversity <= 1.0:
+        self._check_int("limit", limit, 1, MMR_MAX_LIMIT)
+        if not self._is_number(diversity) or not 0.0 <= diversity <= 1.0:
             raise ValueError(f"diversity must be a number in [0, 1], got {diversity!r}")
-        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
-                                             or candidates_limit < 1):
-            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
-        if mode not in ("tree", "h1"):
-            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
-        root_filter = bool(filters) and filter_stages == "root"
-        if root_filter and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
-                             "(or filter_stages='all')")
+        self._check_candidates(candidates_limit)
+        root_filter = self._routing(filters, mode, filter_stages)
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
-        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
-        if pool_max < 1:
-            raise ValueError("the search_params leave an empty pool")
-        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        pool = self._pool_size(hp, mode, candidates_limit)
         col = self._collections[str(user_id)]
         q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
-        mask = None
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            mask = col.row_mask(filters)
+        mask = self._filter_mask(col, filters)
         scores, rows, values, counts = col.index.hybrid_query_mmr_host(
             q, indptr, idx.astype(np.int32), val.astype(np.float32), hp, limit, float(diversity), candidates_limit=pool,
             mask=mask, mask_root_only=root_filter)
-        cids, cpay = col.ids, col.payloads
-        return [[MmrPoint(id=cids[r], version=0, score=s, payload=cpay[r], mmr_score=v)
-                 for s, r, v in zip(sc[:n], rw[:n], vl[:n])]
-                for sc, rw, vl, n in zip(scores.tolist(), rows.tolist(), values.tolist(), counts.tolist())]
+        return self._points(col, scores, rows, counts, MmrPoint, values)
 
     async def hybrid_search_mmr(self, user_id: str, dense_vectors, sparse_vectors, limit: int = 10, diversity: float = 0.5,
                                 candidates_limit: Optional[int] = 100, search_params: Optional[Dict[str, Any]] = None,
@@ -1168,15 +1240,9 @@ class QdrantHandler:
         Raises ValueError for arguments no search can serve (a limit outside [1, 256], a diversity outside [0, 1], a
         candidates_limit below 1, mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or
         filter clause); any other failure is logged and gives [], as in every search."""
-        try:
-            return await self._run(self._mmr_sync, user_id, dense_vectors, sparse_vectors, limit, diversity,
-                                   candidates_limit, search_params, filters, mode, filter_stages)
-        except ValueError as ve:
-            logging.error("MMR hybrid search for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("MMR hybrid search for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("MMR hybrid search for %s", user_id, [], self._mmr_sync, user_id, dense_vectors,
+                                   sparse_vectors, limit, diversity, candidates_limit, search_params, filters, mode,
+                                   filter_stages)
 
     # ------------------------------------------------------------- late-interaction rerank
     async def create_token_index(self, user_id: str, dim: int) -> None:
@@ -1200,24 +1266,11 @@ class QdrantHandler:
                      filters, mode, filter_stages):
         if not self._late_rerank:
             raise ValueError("hybrid_search_rerank is not supported on a sharded collection")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= 2048:
-            raise ValueError(f"limit must be an integer in [1, 2048], got {limit!r}")
-        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
-                                             or candidates_limit < 1):
-            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
-        if mode not in ("tree", "h1"):
-            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
-        root_filter = bool(filters) and filter_stages == "root"
-        if root_filter and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
-                             "(or filter_stages='all')")
+        self._check_int("limit", limit, 1, 2048)
+        self._check_candidates(candidates_limit)
+        root_filter = self._routing(filters, mode, filter_stages)
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
-        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
-        if pool_max < 1:
-            raise ValueError("the search_params leave an empty pool")
-        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        pool = self._pool_size(hp, mode, candidates_limit)
         col = self._collections[str(user_id)]
         tk = getattr(col, "tokens", None)
         if tk is None:
@@ -1226,17 +1279,11 @@ class QdrantHandler:
             raise ValueError(f"{len(sparse_vectors)} queries but {len(query_tokens)} token lists")
         q8, qs, qtip = _late.pack_queries(query_tokens, tk["dim"])      # ValueError: 0 or > 64 tokens, too wide, non-finite
         q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
-        mask = None
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            mask = col.row_mask(filters)
+        mask = self._filter_mask(col, filters)
         scores, rows, first, counts = col.index.hybrid_query_rerank_host(
             q, indptr, idx.astype(np.int32), val.astype(np.float32), hp, col._token_column(), q8, qs, qtip, limit,
             candidates_limit=pool, mask=mask, mask_root_only=root_filter)
-        cids, cpay = col.ids, col.payloads
-        return [[RerankedPoint(id=cids[r], version=0, score=s, payload=cpay[r], first_score=f)
-                 for s, r, f in zip(sc[:n], rw[:n], fs[:n])]
-                for sc, rw, fs, n in zip(scores.tolist(), rows.tolist(), first.tolist(), counts.tolist())]
+        return self._points(col, scores, rows, counts, RerankedPoint, first)
 
     async def hybrid_search_rerank(self, user_id: str, dense_vectors, sparse_vectors, query_tokens, limit: int = 10,
                                    candidates_limit: Optional[int] = 100,
@@ -1256,52 +1303,30 @@ class QdrantHandler:
         query with no or more than 64 tokens or tokens wider than the index, a collection without a token index, mode
         "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or filter clause); any other
         failure is logged and gives [], as in every search."""
-        try:
-            return await self._run(self._rerank_sync, user_id, dense_vectors, sparse_vectors, query_tokens, limit,
-                                   candidates_limit, search_params, filters, mode, filter_stages)
-        except ValueError as ve:
-            logging.error("rerank hybrid search for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("rerank hybrid search for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("rerank hybrid search for %s", user_id, [], self._rerank_sync, user_id, dense_vectors,
+                                   sparse_vectors, query_tokens, limit, candidates_limit, search_params, filters, mode,
+                                   filter_stages)
 
     # ---------------------------------------------------------------------- score boosting
     def _boost_sync(self, user_id, dense_vectors, sparse_vectors, formula, defaults, limit, candidates_limit,
                     score_threshold, search_params, filters, mode, filter_stages):
         if not self._boost_search:
             raise ValueError("hybrid_search_boost is not supported on a sharded collection")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= BOOST_MAX_LIMIT:
-            raise ValueError(f"limit must be an integer in [1, {BOOST_MAX_LIMIT}], got {limit!r}")
-        if candidates_limit is not None and (isinstance(candidates_limit, bool) or not isinstance(candidates_limit, int)
-                                             or candidates_limit < 1):
-            raise ValueError(f"candidates_limit must be a positive integer or None, got {candidates_limit!r}")
-        if score_threshold is not None and (isinstance(score_threshold, bool)
-                                            or not isinstance(score_threshold, (int, float))
-                                            or score_threshold != score_threshold):
+        self._check_int("limit", limit, 1, BOOST_MAX_LIMIT)
+        self._check_candidates(candidates_limit)
+        if score_threshold is not None and not self._is_number(score_threshold):
             raise ValueError(f"score_threshold must be a number that is not a NaN or None, got {score_threshold!r}")
         if defaults is not None and not isinstance(defaults, dict):
             raise ValueError("defaults must be a dict (variable -> value) or None")
-        if filter_stages not in FILTER_STAGES:
-            raise ValueError(f"filter_stages must be one of {FILTER_STAGES}, got {filter_stages!r}")
-        if mode not in ("tree", "h1"):
-            raise ValueError("mode must be 'tree' (the reference query) or 'h1'")
-        root_filter = bool(filters) and filter_stages == "root"
-        if root_filter and mode != "tree":
-            raise ValueError("filters belong to the reference query's root (:297, :371): use mode='tree' "
-                             "(or filter_stages='all')")
+        root_filter = self._routing(filters, mode, filter_stages)
         defaults = defaults or {}
         _boosting.check(formula, defaults)                 # ValueError: a formula no evaluation can serve
         hp = _engine.make_params(search_params, mode=HX_MODE_TREE if mode == "tree" else HX_MODE_H1)
-        pool_max = min(int(hp.dense_limit) + int(hp.rrf_limit if mode == "tree" else hp.sparse_limit), 2048)
-        if pool_max < 1:
-            raise ValueError("the search_params leave an empty pool")
-        pool = pool_max if candidates_limit is None else min(candidates_limit, pool_max)
+        pool = self._pool_size(hp, mode, candidates_limit)
         col = self._collections[str(user_id)]
         q, indptr, idx, val = self._pack_queries(col, dense_vectors, sparse_vectors)
         idx, val = idx.astype(np.int32), val.astype(np.float32)
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        self._check_filter(filters)
         cids, cpay = col.ids, col.payloads
         pi = getattr(col, "pindex", None)
         prog = _boosting.compile(formula, defaults, pi, col._id_rows)
@@ -1325,9 +1350,7 @@ class QdrantHandler:
                         logging.warning("boosted search: query %d dropped %d points whose value was not finite", b, d)
                 if pi is not None:
                     pi.boost_device_calls += 1
-                return [[BoostedPoint(id=cids[r], version=0, score=s, payload=cpay[r], base_score=f)
-                         for s, r, f in zip(sc[:n], rw[:n], bs[:n])]
-                        for sc, rw, bs, n in zip(scores.tolist(), rows.tolist(), base.tolist(), counts.tolist())]
+                return self._points(col, scores, rows, counts, BoostedPoint, base)
             except Exception as e:                          # never a wrong rank: the walk over the payloads is always right
                 logging.warning("boosted search: the device path failed, Python path taken: %s", e)
                 reason = "engine refused"
@@ -1378,15 +1401,9 @@ class QdrantHandler:
         score_threshold that is no number, a malformed formula, a variable without a default, a scale <= 0, a midpoint
         outside (0, 1), mode "h1" with a root filter, a sharded collection, an unknown mode, filter_stages or filter
         clause); any other failure is logged and gives [], as in every search."""
-        try:
-            return await self._run(self._boost_sync, user_id, dense_vectors, sparse_vectors, formula, defaults, limit,
-                                   candidates_limit, score_threshold, search_params, filters, mode, filter_stages)
-        except ValueError as ve:
-            logging.error("boosted hybrid search for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("boosted hybrid search for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("boosted hybrid search for %s", user_id, [], self._boost_sync, user_id, dense_vectors,
+                                   sparse_vectors, formula, defaults, limit, candidates_limit, score_threshold,
+                                   search_params, filters, mode, filter_stages)
 
     async def rerank_with_colbert(self, query: str, documents: List[str], results: List[Dict],
                                   max_tokens: int) -> List[Dict]:
@@ -1413,14 +1430,14 @@ class QdrantHandler:
             get = req.get if isinstance(req, dict) else (lambda k, d=None, r=req: getattr(r, k, d))
             flt = get("filters") if get("filters") is not None else get("filter")
             thr = get("score_threshold")
-            if thr is not None and (isinstance(thr, bool) or not isinstance(thr, (int, float)) or thr != thr):
+            if thr is not None and not self._is_number(thr):
                 raise ValueError(f"score_threshold must be a number, got {thr!r}")
             if flt:
                 if not shape[-1]:
                     raise ValueError("filters on a root without prefetch are not supported: the stage entries take no row "
                                      "mask (filter the root of a tree with prefetches, or use hybrid_search_batch with "
                                      "filter_stages='all')")
-                _filters.matches({}, flt)                  # validates the clause names before any GPU work
+                self._check_filter(flt)
             with_payload = get("with_payload", True)
             parsed.append((shape, bool(flt)))
             roots.append((vecs, flt or None, thr, True if with_payload is None else bool(with_payload)))
@@ -1457,14 +1474,7 @@ class QdrantHandler:
         group runs as one batch over the engine's stage entries, fusion nodes through hx_fuse; results come back in
         request order.  Raises ValueError for a tree no stage can serve (query_tree.parse names the reason) and on a
         sharded collection; any other failure is logged and gives [], as in every search."""
-        try:
-            return await self._run(self._query_points_sync, user_id, requests)
-        except ValueError as ve:
-            logging.error("query_points for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("query_points for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("query_points for %s", user_id, [], self._query_points_sync, user_id, requests)
 
     async def query_points(self, user_id: str, prefetch=None, query=None, using: str = "dense", limit: int = 10,
                            filters: Optional[Dict] = None, score_threshold: Optional[float] = None,
@@ -1482,14 +1492,13 @@ class QdrantHandler:
     def _recommend_sync(self, user_id, requests, limit, filters):
         if not self._recommend:
             raise ValueError("recommend is not supported on a sharded collection")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= RECO_MAX_LIMIT:
-            raise ValueError(f"limit must be an integer in [1, {RECO_MAX_LIMIT}], got {limit!r}")
+        self._check_int("limit", limit, 1, RECO_MAX_LIMIT)
         requests = list(requests)
         if not 1 <= len(requests) <= RECO_MAX_REQUESTS:
             raise ValueError(f"a recommend batch takes 1 to {RECO_MAX_REQUESTS} requests, got {len(requests)}")
         col = self._collections[str(user_id)]
         dim_pad = (col.dim + 63) // 64 * 64
-        id_rows = None
+        example = self._example_resolver(col, "recommend")
         strategies, packed = set(), []
         for req in requests:
             positive, negative, strategy = req.get("positive"), req.get("negative"), req.get("strategy", "average_vector")
@@ -1500,27 +1509,7 @@ class QdrantHandler:
             strategies.add(strategy)
             examples = []
             for group, sign in ((positive, 1), (negative, -1)):
-                for ex in group:
-                    if isinstance(ex, (str, int)) and not isinstance(ex, bool):   # a point id -> its stored row
-                        if id_rows is None:
-                            id_rows = col._id_rows()
-                            if id_rows is None:                      # an id held twice: the first row that holds it
-                                id_rows = {}
-                                for r, pid in enumerate(col.ids):
-                                    id_rows.setdefault(pid, r)
-                        if str(ex) not in id_rows:
-                            raise ValueError(f"recommend: unknown point id {ex!r}")
-                        examples.append((id_rows[str(ex)], sign))
-                    else:
-                        try:
-                            v = np.asarray(ex, dtype=np.float32).reshape(-1)
-                        except (TypeError, ValueError):
-                            raise ValueError("recommend: an example is a point id or a vector of numbers") from None
-                        if v.shape[0] != col.dim:
-                            raise ValueError(f"example dimension {v.shape[0]} != collection dimension {col.dim}")
-                        if not np.isfinite(v).all():
-                            raise ValueError("recommend: example vector values must be finite")
-                        examples.append((v, sign))
+                examples.extend((example(ex), sign) for ex in group)
             if not examples:
                 raise ValueError("recommend: a request needs at least one example")
             if len(examples) > RECO_MAX_EXAMPLES or len(examples) * dim_pad > 32768:
@@ -1531,14 +1520,8 @@ class QdrantHandler:
             packed.append(examples)
         if len(strategies) != 1:
             raise ValueError("recommend_batch: one strategy per batch")
-        mask = None
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            mask = col.row_mask(filters)
-        scores, rows, counts = col.index.recommend_host(packed, RECO_STRATEGIES[strategies.pop()], limit, mask=mask)
-        cids, cpay = col.ids, col.payloads
-        return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
-                for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist())]
+        mask = self._filter_mask(col, filters)
+        return self._points(col, *col.index.recommend_host(packed, RECO_STRATEGIES[strategies.pop()], limit, mask=mask))
 
     async def recommend_batch(self, user_id: str, requests, limit: int = 10,
                               filters: Optional[Dict] = None) -> List[List[ScoredPoint]]:
@@ -1552,14 +1535,8 @@ class QdrantHandler:
         point id or strategy, no example, average_vector without a positive, too many examples, a limit outside [1,
         1024], a vector of the wrong length or with a non-finite element, a sharded collection); any other failure is
         logged and gives [], as in every search."""
-        try:
-            return await self._run(self._recommend_sync, user_id, requests, limit, filters)
-        except ValueError as ve:
-            logging.error("recommend for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("recommend for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("recommend for %s", user_id, [], self._recommend_sync, user_id, requests, limit,
+                                   filters)
 
     async def recommend(self, user_id: str, positive, negative=None, strategy: str = "average_vector", limit: int = 10,
                         filters: Optional[Dict] = None) -> List[ScoredPoint]:
@@ -1573,37 +1550,13 @@ class QdrantHandler:
     def _discover_sync(self, user_id, requests, limit, filters):
         if not self._discover:
             raise ValueError("discover is not supported on a sharded collection")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= RECO_MAX_LIMIT:
-            raise ValueError(f"limit must be an integer in [1, {RECO_MAX_LIMIT}], got {limit!r}")
+        self._check_int("limit", limit, 1, RECO_MAX_LIMIT)
         requests = list(requests)
         if not 1 <= len(requests) <= RECO_MAX_REQUESTS:
             raise ValueError(f"a discover batch takes 1 to {RECO_MAX_REQUESTS} requests, got {len(requests)}")
         col = self._collections[str(user_id)]
         dim_pad = (col.dim + 63) // 64 * 64
-        id_rows = None
-
-        def example(ex):
-            nonlocal id_rows
-            if isinstance(ex, (str, int)) and not isinstance(ex, bool):   # a point id -> its stored row
-                if id_rows is None:
-                    id_rows = col._id_rows()
-                    if id_rows is None:                      # an id held twice: the first row that holds it
-                        id_rows = {}
-                        for r, pid in enumerate(col.ids):
-                            id_rows.setdefault(pid, r)
-                if str(ex) not in id_rows:
-                    raise ValueError(f"discover: unknown point id {ex!r}")
-                return id_rows[str(ex)]
-            try:
-                v = np.asarray(ex, dtype=np.float32).reshape(-1)
-            except (TypeError, ValueError):
-                raise ValueError("discover: an example is a point id or a vector of numbers") from None
-            if v.shape[0] != col.dim:
-                raise ValueError(f"example dimension {v.shape[0]} != collection dimension {col.dim}")
-            if not np.isfinite(v).all():
-                raise ValueError("discover: example vector values must be finite")
-            return v
-
+        example = self._example_resolver(col, "discover")
         packed = []
         for req in requests:
             target, context = req.get("target"), req.get("context")
@@ -1623,14 +1576,8 @@ class QdrantHandler:
                 raise ValueError(f"discover: too many examples ({n_ex}, the target and two per pair): at most "
                                  f"{RECO_MAX_EXAMPLES}, and examples x padded width at most 32768 (width {dim_pad})")
             packed.append((None if target is None else example(target), pairs))
-        mask = None
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            mask = col.row_mask(filters)
-        scores, rows, counts = col.index.discover_host(packed, limit, mask=mask)
-        cids, cpay = col.ids, col.payloads
-        return [[ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r]) for s, r in zip(sc[:n], rw[:n])]
-                for sc, rw, n in zip(scores.tolist(), rows.tolist(), counts.tolist())]
+        mask = self._filter_mask(col, filters)
+        return self._points(col, *col.index.discover_host(packed, limit, mask=mask))
 
     async def discover_batch(self, user_id: str, requests, limit: int = 10,
                              filters: Optional[Dict] = None) -> List[List[ScoredPoint]]:
@@ -1645,14 +1592,7 @@ class QdrantHandler:
         unknown point id, neither target nor pair, a malformed pair, too many examples, a limit outside [1, 1024], a
         vector of the wrong length or with a non-finite element, a sharded collection); any other failure is logged and
         gives [], as in every search."""
-        try:
-            return await self._run(self._discover_sync, user_id, requests, limit, filters)
-        except ValueError as ve:
-            logging.error("discover for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("discover for %s failed: %s", user_id, e)
-            return []
+        return await self._guarded("discover for %s", user_id, [], self._discover_sync, user_id, requests, limit, filters)
 
     async def discover(self, user_id: str, target=None, context=(), limit: int = 10,
                        filters: Optional[Dict] = None) -> List[ScoredPoint]:
@@ -1666,11 +1606,9 @@ class QdrantHandler:
         engine call, or None when fewer than two points are sampled"""
         if not self._matrix_search:
             raise ValueError("search_matrix is not supported on a sharded collection")
-        if isinstance(sample, bool) or not isinstance(sample, int) or not 1 <= sample <= _matrix.MAX_SAMPLE:
-            raise ValueError(f"sample must be an integer in [1, {_matrix.MAX_SAMPLE}], got {sample!r}")
-        if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= _matrix.MAX_LIMIT:
-            raise ValueError(f"limit must be an integer in [1, {_matrix.MAX_LIMIT}], got {limit!r}")
-        if score_threshold is not None:
+        self._check_int("sample", sample, 1, _matrix.MAX_SAMPLE)
+        self._check_int("limit", limit, 1, _matrix.MAX_LIMIT)
+        if score_threshold is not None:                    # (anything float() takes, unlike the boost and tree entries)
             try:
                 score_threshold = float(score_threshold)
             except (TypeError, ValueError):
@@ -1679,19 +1617,12 @@ class QdrantHandler:
                 raise ValueError("score_threshold must not be NaN")
         col = self._collections[str(user_id)]
         n = len(col.ids)
-        mask = None
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
-            mask = col.row_mask(filters)
+        mask = self._filter_mask(col, filters)
         if point_ids is not None:                          # exactly these points, in the order given
             point_ids = list(point_ids)
             if len(point_ids) > _matrix.MAX_SAMPLE:
                 raise ValueError(f"search_matrix: at most {_matrix.MAX_SAMPLE} point ids, got {len(point_ids)}")
-            id_rows = col._id_rows()
-            if id_rows is None:                            # an id held twice: the first row that holds it
-                id_rows = {}
-                for r, pid in enumerate(col.ids):
-                    id_rows.setdefault(pid, r)
+            id_rows = col.first_rows()
             rows, seen = [], set()
             for pid in point_ids:
                 if isinstance(pid, bool) or not isinstance(pid, (str, int)) or str(pid) not in id_rows:
@@ -1712,15 +1643,8 @@ class QdrantHandler:
         return ids, scores, _matrix.neighbour_positions(rows.tolist(), nbr_rows, counts), counts
 
     async def _search_matrix(self, user_id, sample, limit, filters, point_ids, seed, score_threshold):
-        try:
-            return await self._run(self._search_matrix_sync, user_id, sample, limit, filters, point_ids, seed,
-                                   score_threshold)
-        except ValueError as ve:
-            logging.error("search_matrix for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:                             # logged, an empty response: as in every search
-            logging.error("search_matrix for %s failed: %s", user_id, e)
-            return None
+        return await self._guarded("search_matrix for %s", user_id, None, self._search_matrix_sync, user_id, sample,
+                                   limit, filters, point_ids, seed, score_threshold)
 
     async def search_matrix_pairs(self, user_id: str, sample: int = 10, limit: int = 3, filters: Optional[Dict] = None,
                                   point_ids=None, seed=None, score_threshold=None) -> List[MatrixPair]:
@@ -1767,10 +1691,8 @@ class QdrantHandler:
         col = self._collections[str(user_id)]              # KeyError if absent: re-raised
         n = len(col.ids)
         gone = np.zeros(n, dtype=bool)
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before anything moves
-            hit = np.unpackbits(col.row_mask(filters).view(np.uint8), bitorder="little")[:n].astype(bool)
-            gone |= hit
+        if filters:                                        # (the clause names are validated before anything moves)
+            gone |= np.unpackbits(self._filter_mask(col, filters).view(np.uint8), bitorder="little")[:n].astype(bool)
         if point_ids:
             listed = {str(p) for p in point_ids}
             gone |= np.fromiter((i in listed for i in col.ids), dtype=bool, count=n)
@@ -1813,8 +1735,7 @@ class QdrantHandler:
             raise
 
     def _facet_sync(self, user_id, key, filters, limit):
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        self._check_filter(filters)
         return [FacetHit(value=v, count=c) for v, c in self._collections[str(user_id)].facet(key, filters, limit)]
 
     async def facet(self, user_id: str, key: str, filters: Optional[Dict] = None, limit: int = 10,
@@ -1843,8 +1764,7 @@ class QdrantHandler:
             return []
 
     def _scroll_sync(self, user_id, filters, limit, offset, order_by, with_payload):
-        if filters:
-            _filters.matches({}, filters)                  # validates the clause names before any GPU work
+        self._check_filter(filters)
         col = self._collections[str(user_id)]
         page, nxt = col.scroll(filters, limit, offset, order_by)
         return [Record(id=col.ids[r], payload=col.payloads[r] if with_payload else None, order_value=v)
@@ -1875,17 +1795,11 @@ class QdrantHandler:
         _scrolling.check_limit(limit, _scrolling.MAX_LIMIT - 1)
         if order_by is not None:
             _scrolling.check_order_by(order_by)
-        try:
-            if str(user_id) not in self._collections:
-                logging.warning("scroll: no collection for %s", user_id)
-                return [], None
-            return await self._run(self._scroll_sync, user_id, filters, limit, offset, order_by, with_payload)
-        except ValueError as ve:
-            logging.error("scroll for %s refused: %s", user_id, ve)
-            raise
-        except Exception as e:
-            logging.error("scroll(%s) failed: %s", user_id, e)
+        if str(user_id) not in self._collections:
+            logging.warning("scroll: no collection for %s", user_id)
             return [], None
+        return await self._guarded("scroll for %s", user_id, ([], None), self._scroll_sync, user_id, filters, limit,
+                                   offset, order_by, with_payload, failed="scroll(%s)")
 
     async def retrieve(self, user_id: str, point_ids, with_payload: bool = True) -> List[Record]:
         """Qdrant's retrieve(collection, ids) (additive): the points with the given ids, in the order asked, unknown ids
