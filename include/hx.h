@@ -1092,6 +1092,39 @@ int hx_hybrid_query_formula_host(hx_index* h, const float* q_dense_host, const i
                                  float score_threshold, float* scores_host, int64_t* ids_host, float* base_scores_host,
                                  int32_t* counts_host, int32_t* dropped_host);
 
+/* ---- collection term statistics and the sparse IDF modifier --------------------------------------
+ * Qdrant's SparseVectorParams(modifier=Modifier.IDF): the server keeps per-term document frequencies and multiplies
+ * every query weight by ln(1 + (N - df + 0.5) / (df + 0.5)) at query time.  The statistics are read off the inverted
+ * index, so they follow every add, delete, upsert, truncate and load with no bookkeeping of their own.  Parity unpinned
+ * (DESIGN.md section 0): Qdrant's own arithmetic is recalled, not run; the arithmetic below is this project's, bit for bit.
+ *   df_t  = postings of term t in the base view plus postings in the tail view of the up-to-date inverted index (the
+ *           entries bring it up to date as hx_search_sparse does).  A term in neither view, or a negative id: 0.  Row
+ *           masks do not enter: a filtered query uses the whole collection's statistics, as in Qdrant.
+ *   N     = rows r < hx_count whose document-major CSR row is not empty (indptr[r + 1] > indptr[r]): a point stored
+ *           without a sparse vector is not in the sparse index.
+ *   x     = 1.0 + ((double)(N - df) + 0.5) / ((double)df + 0.5), N - df in int64 after N = max(N, 0) and df clamped to
+ *           [0, N], so x > 1 whatever a caller passes; the add, the divide and the final add are one IEEE double
+ *           operation each.
+ *   idf   = (float)hx_ln(x), rounded to nearest;  out = q_val * idf, one fp32 multiply.  A non-finite q_val stays
+ *           non-finite (the search flags the query as before); idf > 0, so positive weights stay positive unless the
+ *           product underflows to 0 -- such a query takes the document-at-a-time path, which is exact.
+ *   hx_ln(x), x a positive normal double: (m, e) = frexp(x), m in [0.5, 1); if m < 0.7071067811865476 then m = m * 2,
+ *           e = e - 1; s = (m - 1) / (m + 1); z = s * s; p = c_11, then for i = 10 .. 0: p = p * z, p = p + c_i with
+ *           c_i = (double)(1.0 / (2 i + 1)) (two roundings a step); t = 2.0 * s, t = t * p; the result is
+ *           (double)e * 0.6931471805599453 + t, one multiply and one add.  Within 4 ulp of the correctly rounded
+ *           logarithm over the arguments x(N, df) above (DESIGN.md section 31 has the measurement).
+ * hx_sparse_df: df_dev [nnz] and *n_docs_dev (one int64 on the device) for the flat array of term ids q_idx_dev [nnz];
+ * nnz = 0 writes N only (q_idx_dev and df_dev may then be NULL).  hx_sparse_idf_apply needs no index (as hx_rrf):
+ * out_val_dev [nnz] from q_val_dev, df_dev and *n_docs_dev; out_val_dev may be q_val_dev; nnz = 0 does nothing.  Both
+ * are enqueued on `stream`; nothing is read back.  hx_sparse_idf_host: host in, host out -- out_val_host [nnz], and when
+ * not NULL df_host [nnz] and *n_docs_host.  Refused before any device work, every output untouched: a NULL handle, a
+ * NULL pointer (the two optional outputs and the nnz = 0 cases aside), nnz < 0. */
+int hx_sparse_df(hx_index* h, const int32_t* q_idx_dev, int64_t nnz, int64_t* df_dev, int64_t* n_docs_dev, void* stream);
+int hx_sparse_idf_apply(int32_t device, const float* q_val_dev, const int64_t* df_dev, const int64_t* n_docs_dev,
+                        int64_t nnz, float* out_val_dev, void* stream);
+int hx_sparse_idf_host(hx_index* h, const int32_t* q_idx_host, const float* q_val_host, int64_t nnz,
+                       float* out_val_host, int64_t* df_host, int64_t* n_docs_host);
+
 /* ---- persistence ------------------------------------------------------------
  * The reference asks Qdrant for on-disk vectors (qdrant_handler.py:47-55, 62: on_disk=True,
  * memmap_threshold).  hx_save writes the collection to one file (stored vectors as they stand plus

@@ -105,6 +105,9 @@ _SIGS = {
                         C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
     "hx_sparse_wmax": [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
     "hx_set_sparse_wmax": [_P, C.c_float],
+    "hx_sparse_df": [_P, _P, C.c_int64, _P, _P, _P],
+    "hx_sparse_idf_apply": [C.c_int32, _P, _P, _P, C.c_int64, _P, _P],
+    "hx_sparse_idf_host": [_P, _P, _P, C.c_int64, _P, _P, _P],
     "hx_h1_nominate_async": [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P],
     "hx_h1_rescore_async": [_P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                             C.c_int32, C.c_int32, C.c_int32, _P, _P],

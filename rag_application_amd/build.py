@@ -15,7 +15,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("prep.hip", "prep.o", ()), ("shardx.hip", "shardx.o", ()),
            ("sparse2.hip", "sparse2_v32k.o", ("HX_SP_VARIANT=v32k", "HX_SEG_DOCS=32768", "HX_SP_THREADS=512")),
            ("sparse2.hip", "sparse2_v64k.o", ("HX_SP_VARIANT=v64k", "HX_SEG_DOCS=65536", "HX_SP_THREADS=1024")),
-           ("sprescore.hip", "sprescore.o", ()), ("mask.hip", "mask.o", ()), ("compact.hip", "compact.o", ()),
+           ("sprescore.hip", "sprescore.o", ()), ("spstats.hip", "spstats.o", ()), ("mask.hip", "mask.o", ()), ("compact.hip", "compact.o", ()),
            ("replace.hip", "replace.o", ()),
            ("payload.hip", "payload.o", ()), ("paytext.hip", "paytext.o", ()),
            ("paynested.hip", "paynested.o", ()),
@@ -27,7 +27,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),
            ("paystore.hip", "paystore.o", ()), ("poolstage.hip", "poolstage.o", ()), ("byexample.hip", "byexample.o", ()),
            ("bm25.cpp", "bm25.o", ())]
-HEADERS = ["hx_common.hpp", "index.hpp", "kernels.hpp", "replace.hpp", "wsort.hpp",
+HEADERS = ["hx_common.hpp", "index.hpp", "kernels.hpp", "replace.hpp", "spfind.hpp", "wsort.hpp",
            os.path.join("..", "..", "include", "hx.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
          "-Wall", "-Wno-unused-function"]

@@ -260,6 +260,7 @@ static void finalize(hx_index* h, hipStream_t st) {
   }
   h->sparse_stale = false;
 }
+void sparse_up_to_date(hx_index* h, hipStream_t st) { finalize(h, st); }
 
 // ---------------------------------------------------------------------------------
 // global (insertion-order) ids: hx_index::IdBlocks

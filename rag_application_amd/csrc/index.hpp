@@ -1,4 +1,4 @@
-// Internal to the host files of libhx -- engine.hip, lifecycle.hip, paystore.hip, poolstage.hip, byexample.hip
+// Internal to the host files of libhx -- engine.hip, lifecycle.hip, paystore.hip, poolstage.hip, byexample.hip, spstats.hip
 // (DESIGN.md section 3 says what each owns): the state of one collection (struct hx_index) and what one file calls
 // in another.
 #pragma once
@@ -55,7 +55,8 @@ enum WsSlot {
   WS_SCROLL_WORK, WS_SCROLL_MASK, WS_SCROLL_OUT,
   WS_FORMULA_PLANES, WS_FORMULA_KEYS, WS_FORMULA_POS, WS_FORMULA_BASE, WS_FORMULA_CNT, WS_FORMULA_DROP,
   WS_MATRIX_ROWS, WS_MATRIX_PLANE, WS_MATRIX_OUT, WS_MATRIX_OCNT, WS_MATRIX_SC, WS_MATRIX_ID,
-  WS_DISC_TAU, WS_DISC_TAU0
+  WS_DISC_TAU, WS_DISC_TAU0,
+  WS_IDF_IDX, WS_IDF_VAL, WS_IDF_DF
 };
 
 template <typename T>
@@ -286,6 +287,8 @@ void reserve_rows(hx_index* h, int64_t want);
 void reserve_sparse(hx_index* h, int64_t rows, int64_t nnz);
 void free_sparse_ix(hx_index::SparseIx& x);
 void free_sparse_index(hx_index* h);
+// the inverted index brought up to date with the stored sparse rows, as every sparse search does first (spstats.hip)
+void sparse_up_to_date(hx_index* h, hipStream_t st);
 void track_weights_dev(hx_index* h, const float* val, int64_t n, hipStream_t st);
 bool ids_identity(const hx_index* h);
 int* host_pin(hx_index* h);

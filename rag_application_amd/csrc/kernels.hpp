@@ -796,4 +796,15 @@ void launch_formula(const FormulaArgs& a, int B, hipStream_t st);
 void launch_csr_compact_u32(const int64_t* indptr, const uint32_t* rows, const int64_t* off, int64_t m, const uint32_t* src,
                             uint32_t* dst, hipStream_t st);
 
+// ---- spstats.hip: collection term statistics and the IDF modifier (hx_sparse_df / hx_sparse_idf_apply; DESIGN.md
+// section 31) --------------------------------------------------------------------------------------------------------
+// df[i] = postings of term q_idx[i] in ix[0] plus those in ix[1] (a view with n_live = 0 holds none; a negative id: 0),
+// one wave per position
+void launch_sparse_df(const SparseIndexView* ix, const int32_t* q_idx, int64_t nnz, int64_t* df, hipStream_t st);
+// *n_docs = rows r < rows with indptr[r + 1] > indptr[r] (the launch zeroes *n_docs first; indptr may be NULL when rows = 0)
+void launch_sparse_rows_nonempty(const int64_t* indptr, int64_t rows, int64_t* n_docs, hipStream_t st);
+// out[i] = q_val[i] * idf(*n_docs, df[i]) in the arithmetic hx.h states; out may be q_val
+void launch_sparse_idf(const float* q_val, const int64_t* df, const int64_t* n_docs, int64_t nnz, float* out,
+                       hipStream_t st);
+
 }  // namespace hx

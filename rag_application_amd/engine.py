@@ -303,6 +303,35 @@ class HxIndex:
                                               _ptr(keys), _ptr(cnt), _stream()))
         return keys, cnt
 
+    # -- collection term statistics and the IDF modifier (hx.h: hx_sparse_df / hx_sparse_idf_*) ----
+    def sparse_df(self, q_idx: torch.Tensor):
+        """(df [nnz] int64, n_docs [1] int64) on the device for a flat tensor of term ids; nothing is read back."""
+        q_idx = _need_cuda(q_idx, torch.int32, "q_idx").reshape(-1)
+        nnz = q_idx.shape[0]
+        df = torch.empty((nnz,), dtype=torch.int64, device=self._tdev)
+        n_docs = torch.empty((1,), dtype=torch.int64, device=self._tdev)
+        check(_lib.lib().hx_sparse_df(self._h, _ptr(q_idx), nnz, _ptr(df), _ptr(n_docs), _stream()))
+        return df, n_docs
+
+    def sparse_idf(self, q_idx: torch.Tensor, q_val: torch.Tensor) -> torch.Tensor:
+        """q_val scaled by the collection's IDF of its term, on the device (a new tensor)."""
+        df, n_docs = self.sparse_df(q_idx)
+        return sparse_idf_apply(q_val, df, n_docs)
+
+    def sparse_idf_host(self, idx: np.ndarray, val: np.ndarray, want_stats: bool = False):
+        """numpy in, numpy out (hx_sparse_idf_host): the scaled float32 weights; with want_stats also df [nnz] int64
+        and N."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1)
+        if idx.shape != val.shape:
+            raise HxError("sparse_idf_host: as many values as indices")
+        out = np.empty(idx.shape[0], np.float32)
+        df = np.empty(idx.shape[0], np.int64) if want_stats else None
+        n_docs = C.c_int64(0)
+        check(_lib.lib().hx_sparse_idf_host(self._h, _ptr(idx), _ptr(val), idx.shape[0], _ptr(out), _ptr(df),
+                                            C.byref(n_docs) if want_stats else None))
+        return (out, df, int(n_docs.value)) if want_stats else out
+
     def h1_local(self, q: torch.Tensor, q_indptr: torch.Tensor, q_idx: torch.Tensor, q_val: torch.Tensor,
                  dense_limit: int, sparse_limit: int) -> torch.Tensor:
         """This shard's dense and sparse lists side by side, [B, dense_limit + sparse_limit] (hx_h1_local)."""
@@ -1168,6 +1197,24 @@ def rrf(a_keys: torch.Tensor, a_cnt: torch.Tensor, b_keys: torch.Tensor, b_cnt: 
                             _ptr(b_keys.contiguous()), b_keys.shape[1], _ptr(b_cnt), B, k, rank_base, limit,
                             _ptr(keys), _ptr(cnt), _stream()))
     return keys, cnt
+
+
+def sparse_idf_apply(q_val: torch.Tensor, df: torch.Tensor, n_docs: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """q_val * idf(n_docs, df) per position (hx_sparse_idf_apply; include/hx.h states the arithmetic): q_val float32
+    [nnz], df int64 [nnz], n_docs int64 [1], all on one device.  `out` may be q_val; a new tensor when None."""
+    q_val = _need_cuda(q_val, torch.float32, "q_val").reshape(-1)
+    df = _need_cuda(df, torch.int64, "df").reshape(-1)
+    n_docs = _need_cuda(n_docs, torch.int64, "n_docs").reshape(-1)
+    if df.shape != q_val.shape or n_docs.shape[0] != 1:
+        raise HxError("sparse_idf_apply: one df per value and one n_docs")
+    if out is None:
+        out = torch.empty_like(q_val)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and out.numel() == q_val.numel()):
+        raise HxError("sparse_idf_apply: out must be a contiguous cuda float32 tensor of q_val's size")
+    check(_lib.lib().hx_sparse_idf_apply(q_val.device.index or 0, _ptr(q_val), _ptr(df), _ptr(n_docs), q_val.shape[0],
+                                         _ptr(out), _stream()))
+    return out
 
 
 FUSE_RRF, FUSE_DBSF = 0, 1

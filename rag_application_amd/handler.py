@@ -126,6 +126,14 @@ def _sparse_parts(sv):
     return sv.indices, sv.values
 
 
+def _check_modifier(m):
+    """the sparse modifier of a collection: None, or "idf" (Qdrant's Modifier.IDF)"""
+    m = getattr(m, "value", m)
+    if m is not None and not (isinstance(m, str) and m.lower() == "idf"):
+        raise ValueError(f"sparse_modifier must be None or 'idf', got {m!r}")
+    return None if m is None else "idf"
+
+
 class _Collection:
     """One user collection: the engine index (anything with HxIndex's add / hybrid_query_host / count / save /
     close: sharded.ShardedHandler plugs in a row-sharded one) plus the point ids and payloads, which never cross
@@ -138,6 +146,7 @@ class _Collection:
         self.ids: List[str] = []
         self.payloads: List[Dict[str, Any]] = []
         self.sparse_enabled = True
+        self.sparse_modifier: Optional[str] = None     # None | "idf" 
         self._masks: Dict[str, Any] = {}
         self.pindex: Optional[_pindex.PayloadIndex] = None
         self.tokens: Optional[Dict[str, Any]] = None
@@ -535,6 +544,7 @@ class _Collection:
             os.remove(base + ".tokens.npz")
         with open(base + ".json", "w") as f:
             json.dump({"dim": self.dim, "msizes": list(self.msizes), "sparse_enabled": self.sparse_enabled,
+                       "sparse_modifier": getattr(self, "sparse_modifier", None),
                        "ids": self.ids, "payloads": self.payloads,
                        "payload_indexes": self.pindex.definitions() if getattr(self, "pindex", None) else {},
                        "token_index": {"dim": tk["dim"]} if tk is not None else None}, f)
@@ -551,6 +561,7 @@ class _Collection:
         self.ids = list(meta["ids"])
         self.payloads = list(meta["payloads"])
         self.sparse_enabled = bool(meta["sparse_enabled"])
+        self.sparse_modifier = _check_modifier(meta.get("sparse_modifier"))   # (an old file has no such key)
         self._masks = {}
         self.pindex = None
         # the payload indexes are derived data: the sidecar names them (old files have none), the payloads rebuild them
@@ -610,6 +621,8 @@ class QdrantHandler:
     _matrix_search = True
     # query_points runs a caller's tree over the stage entries of ONE engine index
     _query_tree = True
+    # sparse_modifier="idf" reads the term statistics of ONE engine index
+    _sparse_modifiers = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -749,12 +762,24 @@ class QdrantHandler:
     # ---------------------------------------------------------------- create_collection
     async def create_collection(self, user_id: str, dense_vector_size: int = 768,
                                 matryoshka_sizes: list = [64, 128, 256], quantized_size: int = 768,
-                                sparse_enabled: bool = True, force_recreate: bool = False):
+                                sparse_enabled: bool = True, force_recreate: bool = False,
+                                sparse_modifier: Optional[str] = None):
+        """sparse_modifier (additive): None = the reference's collection (no IDF, :24-32), "idf" = Qdrant's
+        SparseVectorParams(modifier=Modifier.IDF): every sparse query weight is multiplied by the collection's IDF of
+        its term at query time.  It is fixed at creation."""
         try:
             if not user_id:
                 raise ValueError("user_id cannot be empty")
             user_id = str(user_id)
+            sparse_modifier = _check_modifier(sparse_modifier)
+            if sparse_modifier and not self._sparse_modifiers:
+                raise ValueError("sparse_modifier='idf' is not supported on a sharded collection: the shard command "
+                                 "protocol carries no collection statistics (sharded.ShardedCollection does)")
             if user_id in self._collections and not force_recreate:
+                have = getattr(self._collections[user_id], "sparse_modifier", None)
+                if have != sparse_modifier:
+                    raise ValueError(f"collection {user_id} exists with sparse_modifier={have!r}: the modifier of a "
+                                     "live collection cannot change (force_recreate=True makes a new one)")
                 logging.info("create_collection: %s is already there", user_id)
                 return
             if quantized_size != dense_vector_size:
@@ -764,9 +789,16 @@ class QdrantHandler:
                 old = self._collections.pop(user_id, None)
                 if old is not None:
                     self._drop(user_id, old)
-                self._collections[user_id] = self._open_collection(
+                col = self._open_collection(
                     user_id, int(dense_vector_size), [int(m) for m in matryoshka_sizes], bool(sparse_enabled),
                     bool(force_recreate))
+                have = getattr(col, "sparse_modifier", None)
+                if have != sparse_modifier:
+                    if have is not None or getattr(col, "ids", None):   # a stored collection keeps what it was created with
+                        self._drop(user_id, col)
+                        raise ValueError(f"stored collection has sparse_modifier={have!r}")
+                    col.sparse_modifier = sparse_modifier
+                self._collections[user_id] = col
             await self._run(make)
             logging.info("create_collection: new collection for %s", user_id)
         except ValueError as ve:
@@ -1043,6 +1075,10 @@ class QdrantHandler:
         val = np.fromiter(itertools.chain.from_iterable(vv for _, vv in parts), dtype=np.float64, count=nnz)
         if nnz and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
             raise ValueError("sparse index out of range")
+        if getattr(col, "sparse_modifier", None) == "idf":
+            # Modifier.IDF: the weights the engine sees are q_t * idf_t, made on the device from the collection's own
+            # statistics.  This is the one place the hybrid_search* entries pack their queries.
+            val = col.index.sparse_idf_host(idx, val)
         return q, indptr, idx, val
 
     def _search_sync(self, user_id, dense_vectors, sparse_vectors, search_params, filters, mode="tree",
@@ -1442,7 +1478,7 @@ class QdrantHandler:
             parsed.append((shape, bool(flt)))
             roots.append((vecs, flt or None, thr, True if with_payload is None else bool(with_payload)))
         out: List[Optional[List[ScoredPoint]]] = [None] * len(requests)
-        stages = _query_tree.DeviceStages(col.index, _engine)
+        stages = _query_tree.DeviceStages(col.index, _engine, sparse_modifier=getattr(col, "sparse_modifier", None))
         cids, cpay = col.ids, col.payloads
         for (shape, filtered), members in _query_tree.group_by_shape(parsed).items():
             limit = _query_tree.shape_limit(shape)
@@ -1487,6 +1523,28 @@ class QdrantHandler:
                                                        "score_threshold": score_threshold,
                                                        "with_payload": with_payload}])
         return res[0] if res else []
+
+    # ------------------------------------------------------------------------ term statistics
+    def _term_stats_sync(self, user_id, indices):
+        if not self._sparse_modifiers:
+            raise ValueError("term_stats is not supported on a sharded collection")
+        col = self._collections[str(user_id)]
+        try:
+            idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("term_stats: indices must be integers") from None
+        if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise ValueError("sparse index out of range")
+        _, df, n_docs = col.index.sparse_idf_host(idx.astype(np.int32), np.ones(idx.shape[0], np.float32),
+                                                  want_stats=True)
+        return {"n_docs": int(n_docs), "df": [int(d) for d in df]}
+
+    async def term_stats(self, user_id: str, indices) -> Dict[str, Any]:
+        """The collection's sparse statistics (additive): {"n_docs": points that hold a sparse
+        vector, "df": per given term id the points whose sparse vector holds it}.  These are what sparse_modifier="idf"
+        weighs queries with; they are there whatever the collection's modifier.  Raises ValueError for indices that
+        are no int32 and on a sharded collection; KeyError for an unknown collection."""
+        return await self._run(self._term_stats_sync, user_id, indices)
 
     # ------------------------------------------------------------------------ recommend
     def _recommend_sync(self, user_id, requests, limit, filters):

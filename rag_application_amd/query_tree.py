@@ -252,9 +252,10 @@ def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None)
 class DeviceStages:
     """The stage entries of one engine index (engine.HxIndex), lists as int64 device tensors."""
 
-    def __init__(self, index, engine):
+    def __init__(self, index, engine, sparse_modifier=None):
         import torch
         self.ix, self.eng, self.torch = index, engine, torch
+        self.sparse_modifier = sparse_modifier          # the collection's (handler.create_collection): None | "idf"
         self.dev = index._tdev
 
     def _q(self, Q):
@@ -272,8 +273,10 @@ class DeviceStages:
         np.cumsum([len(i) for i, _ in pairs], out=indptr[1:])
         idx = np.concatenate([i for i, _ in pairs]).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
         val = np.concatenate([v for _, v in pairs]).astype(np.float32) if indptr[-1] else np.zeros(0, np.float32)
-        return self.ix.search_sparse(t.from_numpy(indptr).to(self.dev), t.from_numpy(idx).to(self.dev),
-                                     t.from_numpy(val).to(self.dev), limit)
+        d_idx, d_val = t.from_numpy(idx).to(self.dev), t.from_numpy(val).to(self.dev)
+        if self.sparse_modifier == "idf":               # Modifier.IDF: scaled on the device, no host round trip
+            d_val = self.ix.sparse_idf(d_idx, d_val)
+        return self.ix.search_sparse(t.from_numpy(indptr).to(self.dev), d_idx, d_val, limit)
 
     def rescore(self, Q, lists, limit, prefix):
         # a stage's slots past its count are 0, and hx_rescore skips a 0: the union is the lists side by side

@@ -162,8 +162,12 @@ class ShardedCollection:
     host-side control group (made here when not given)."""
 
     def __init__(self, dim: int = 768, msizes: Sequence[int] = (64, 128, 256), group=None, index_factory=None,
-                 ops=None, src: int = 0, ctl=None, local=None, counts=None, device: Optional[torch.device] = None):
+                 ops=None, src: int = 0, ctl=None, local=None, counts=None, device: Optional[torch.device] = None,
+                 sparse_modifier: Optional[str] = None):
         self.dim, self.msizes, self.group, self.src = int(dim), tuple(msizes), group, src
+        if sparse_modifier not in (None, "idf"):
+            raise ValueError(f"sparse_modifier must be None or 'idf', got {sparse_modifier!r}")
+        self.sparse_modifier = sparse_modifier               # "idf": search weighs by the GLOBAL statistics (_idf_weights)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         # `dev`: where this rank's shard lives and the stages run; `cdev`: where the collectives run (the device for
@@ -356,6 +360,8 @@ class ShardedCollection:
         params, mode, rrf_k, rank_base, rrf_limit = head
         q, ip, ix, v = bcast_queries(q, q_indptr, q_idx, q_val, self.src, self.bgroup, self.dev,
                                      header_group=self.ctl if self.world > 1 else None)
+        if self.sparse_modifier == "idf":
+            v = self._idf_weights(ix, v)
         if mode == "h1":
             out = self.sh.hybrid_h1(q, ip, ix, v, params["dense_limit"], params["sparse_limit"], params["final_limit"],
                                     rrf_k, rank_base)
@@ -367,6 +373,27 @@ class ShardedCollection:
         if bad:
             raise ShardError("search failed: " + "; ".join(f"rank {j}: {outs[j]}" for j in bad))
         return out
+
+    def _idf_weights(self, ix: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """Collective: the batch's sparse weights times the IDF of the WHOLE collection.  Each
+        rank's (df, N) over its own rows travel as one int64 tensor of nnz + 1 entries through one all_reduce; every
+        rank then scales alike, so the sharded lists equal the single index's.  A rank whose statistics failed keeps
+        the error for the status exchange at the end of the search and adds zeros."""
+        nnz = int(ix.shape[0])
+        stats = torch.zeros(nnz + 1, dtype=torch.int64, device=ix.device)
+        if self.sh.err is None:
+            try:
+                df, n_docs = self.local.sparse_df(ix)
+                stats[:nnz] = df
+                stats[nnz:] = n_docs.reshape(-1)
+            except Exception as e:
+                self.sh.err = e
+        self.sh.reduce_sum(stats)
+        if v.is_cuda:
+            from . import engine as _engine
+            return _engine.sparse_idf_apply(v.contiguous(), stats[:nnz].contiguous(), stats[nnz:].contiguous())
+        from . import sparse_stats as _stats                 # CPU tensors (a gloo group of host shards): the same bits
+        return torch.from_numpy(_stats.idf_weights(v.numpy(), stats[:nnz].numpy(), int(stats[nnz])))
 
     @staticmethod
     def unpack(keys: torch.Tensor, counts: Optional[torch.Tensor]):
@@ -483,6 +510,8 @@ class ShardedHandler(QdrantHandler):
     _scroll = False                  # scroll / retrieve raise ValueError: the rows of a collection lie in several indexes
     _matrix_search = False           # search_matrix_pairs / _offsets raise ValueError: a sample's rows lie in several indexes
     _query_tree = False              # query_points / query_points_batch raise ValueError: nothing is sent to the ranks
+    _sparse_modifiers = False        # create_collection(sparse_modifier="idf") and term_stats raise ValueError: the command
+                                     # protocol carries no collection statistics (ShardedCollection itself does)
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
@@ -622,12 +651,14 @@ class ShardedHandler(QdrantHandler):
 
     async def create_collection(self, user_id: str, dense_vector_size: Optional[int] = None,
                                 matryoshka_sizes: Optional[list] = None, quantized_size: Optional[int] = None,
-                                sparse_enabled: bool = True, force_recreate: bool = False):
-        """qdrant_handler.py:24-32, with the handler's own vector sizes as the defaults"""
+                                sparse_enabled: bool = True, force_recreate: bool = False,
+                                sparse_modifier: Optional[str] = None):
+        """qdrant_handler.py:24-32, with the handler's own vector sizes as the defaults.  sparse_modifier="idf" is
+        refused (ValueError): the command protocol and the shard sidecars carry no collection statistics."""
         d = self.dim if dense_vector_size is None else int(dense_vector_size)
         return await super().create_collection(
             user_id, d, list(self.msizes) if matryoshka_sizes is None else matryoshka_sizes,
-            d if quantized_size is None else quantized_size, sparse_enabled, force_recreate)
+            d if quantized_size is None else quantized_size, sparse_enabled, force_recreate, sparse_modifier)
 
     # ---- QdrantHandler's two hooks -------------------------------------------------------------------------------
     def _open_collection(self, user_id, dim, msizes, sparse_enabled, force_recreate) -> _Collection:
