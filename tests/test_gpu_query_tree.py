@@ -2,7 +2,10 @@
 DESIGN.md section 30) on the corpus of tests/golden/corpus_a_2048x768.npz.  The reference's tree and the H1 tree written
 as requests equal hybrid_search_batch's two modes in ids and scores; a three-list DBSF tree equals tests/fusion_helpers.py
 over the lists the stage entries return; a root filter equals filtering the unfiltered root's full list; a batch of mixed
-shapes equals its requests issued one by one."""
+shapes equals its requests issued one by one.  Then the same surface against the oracle interpreter
+(tests/query_tree_helpers.py: query_tree.run over OracleIndex, fusion by tests/fusion_helpers.py): a dozen seeded requests
+in one batch, root filters on a fusion root and on a re-scoring root, a root input wider than 2048, and score_threshold on
+a fusion root."""
 from __future__ import annotations
 
 import asyncio
@@ -12,7 +15,9 @@ import pytest
 
 from oracle import oracle as O
 from rag_application_amd import filters as FL
+from rag_application_amd import query_tree as QT
 from tests import fusion_helpers as H
+from tests import query_tree_helpers as T
 
 pytestmark = pytest.mark.gpu
 
@@ -229,3 +234,122 @@ def test_a_batch_of_three_interleaved_shapes_equals_its_requests_one_by_one(hand
         one = asyncio.run(handler.query_points_batch("u", [r]))
         assert flat(one) == flat([batch[i]]), i
     assert [len(x) for x in batch] == [30, 25, 7] * 4
+
+
+# ---- the same surface against the oracle interpreter (tests/query_tree_helpers.py) -----------------------------------------
+# Everything above except the two fixed trees takes its expected values from the engine's own stage entries.  Below, the
+# expected lists come from query_tree.run over OracleIndex with fusion by tests/fusion_helpers.py: nothing of the product.
+MS = (64, 128, 256)
+DOC5 = {"must": [{"key": "document_id", "match": {"value": "doc5"}}]}     # rows 320..383: 1 row in 32
+
+
+@pytest.fixture(scope="module")
+def oracle_ix(corpus):
+    return T.oracle_index(corpus[:4], DIM, MS)
+
+
+def oracle_lists(ora, reqs, root_limit=None):
+    """the oracle interpreter over requests of ONE shape: per request [(row, score bits)], best first"""
+    parsed = [QT.parse(r, DIM, MS) for r in reqs]
+    assert len({s for s, _ in parsed}) == 1
+    keys, cnt = QT.run(parsed[0][0], QT.batch_vectors([v for _, v in parsed]), T.OracleStages(ora, fuse=H), root_limit)
+    return [[(H.key_id(int(x)), bits(H.key_score(int(x)))) for x in keys[b, :int(cnt[b])]] for b in range(len(reqs))]
+
+
+def as_rows(handler, res):
+    """the handler's answer as [(row, score bits)]: its point ids mapped back to rows"""
+    row_of = {pid: r for r, pid in enumerate(handler._collections["u"].ids)}
+    return [[(row_of[p.id], bits(p.score)) for p in pts] for pts in res]
+
+
+def keeps(flt, row):
+    return row % 2 == 0 if flt is HALF else row // 64 == 5
+
+
+def test_a_dozen_seeded_requests_in_one_batch_equal_the_oracle_interpreter(handler, corpus, oracle_ix):
+    assert not np.isin(T.ABSENT_TERMS, corpus[2]).any()
+    pools = [T.sparse_pool(*corpus[1:4], *corpus[6], b) for b in range(2)]
+    trees = T.seeded_requests(DIM, MS, 2, pools)
+    chosen, covered = [], set()
+    for name, reqs in trees:                                 # the first six shapes that each add a class
+        shape, vecs = QT.parse(reqs[0], DIM, MS)
+        new = T.shape_classes(shape, vecs) - covered
+        if new and len(chosen) < 6:
+            chosen.append((name, reqs))
+            covered |= new
+    assert len(chosen) == 6 and len(covered) >= 8, sorted(covered)
+    batch = [chosen[i % 6][1][i // 6] for i in range(12)]    # interleaved: no two neighbours share a shape
+    got = as_rows(handler, asyncio.run(handler.query_points_batch("u", batch)))
+    assert len(got) == 12
+    for s, (name, reqs) in enumerate(chosen):
+        want = oracle_lists(oracle_ix, reqs)
+        for b in range(2):
+            assert got[s + 6 * b] == want[b], f"{name}, query {b}"
+
+
+def wide_fusion(q, sp, **root):
+    return dict({"prefetch": [{"query": q, "using": "dense", "limit": 1024}, {"query": sp, "using": "sparse", "limit": 512},
+                              {"query": q, "using": "quantized", "limit": 512}],
+                 "query": {"fusion": "rrf", "weights": [1, 2, 0.5], "rrf_k": 7.25, "rank_base": 1}, "limit": 12}, **root)
+
+
+def wide_rescore(q, sp, **root):
+    return dict({"prefetch": [{"query": q[:64], "using": "matryoshka_64", "limit": 1024},
+                              {"query": q, "using": "quantized", "limit": 1000}],
+                 "query": q, "using": "dense", "limit": 12}, **root)
+
+
+@pytest.mark.parametrize("tree", [wide_fusion, wide_rescore])
+@pytest.mark.parametrize("flt", [HALF, DOC5], ids=["half", "one-in-32"])
+def test_a_root_filter_equals_the_filtered_oracle_root_at_the_width_of_its_input(handler, corpus, oracle_ix, tree, flt):
+    """the filter is the caller's on the oracle side: the oracle root runs at the width of its input (2048 and 2024
+    here), its list is filtered with filters.matches and cut to the limit"""
+    qs, sps = queries(corpus, 4)
+    col = handler._collections["u"]
+    assert all(FL.matches(col.payloads[r], flt, col.ids[r]) == keeps(flt, r) for r in range(N))
+    reqs = [tree(q, sp) for q, sp in zip(qs, sps)]
+    width = QT.input_width(QT.parse(reqs[0], DIM, MS)[0])
+    assert 2000 < width <= 2048
+    full = oracle_lists(oracle_ix, reqs, root_limit=width)
+    got = as_rows(handler, asyncio.run(handler.query_points_batch("u", [tree(q, sp, filters=flt) for q, sp in zip(qs, sps)])))
+    for b in range(4):
+        kept = [x for x in full[b] if keeps(flt, x[0])]
+        assert len(kept) > 12 and any(not keeps(flt, x[0]) for x in full[b][:12])   # both the filter and the cut bite
+        assert got[b] == kept[:12], b
+
+
+def test_a_root_input_wider_than_2048_is_ranked_at_2048_before_the_filter(handler, corpus, oracle_ix):
+    """This pins the documented cap ("the root stage runs at the width of its input (at most
+    2048)"): with a root filter the root keeps the best 2048 of a wider input, THEN the filter and the cut apply, so a
+    caller can lose hits that pass the filter but rank beyond 2048 at the root."""
+    qs, sps = queries(corpus, 3)
+    trees = (lambda q, sp, **kw: dict({"prefetch": [{"query": q, "limit": 2048}, {"query": q[:64], "using": "matryoshka_64",
+                                                                                  "limit": 2048},
+                                                    {"query": sp, "using": "sparse", "limit": 300}],
+                                       "query": q[:128], "using": "matryoshka_128", "limit": 10}, **kw),
+             lambda q, sp, **kw: dict({"prefetch": [{"query": q, "limit": 2048}, {"query": q, "using": "quantized",
+                                                                                  "limit": 2048}],
+                                       "query": {"fusion": "dbsf", "weights": [1, 0.5]}, "limit": 10}, **kw))
+    for tree in trees:
+        reqs = [tree(q, sp) for q, sp in zip(qs, sps)]
+        assert QT.input_width(QT.parse(reqs[0], DIM, MS)[0]) > 2048
+        full = oracle_lists(oracle_ix, reqs, root_limit=2048)
+        got = as_rows(handler, asyncio.run(handler.query_points_batch("u", [tree(q, sp, filters=DOC5)
+                                                                            for q, sp in zip(qs, sps)])))
+        for b in range(3):
+            kept = [x for x in full[b] if keeps(DOC5, x[0])]
+            assert len(kept) > 10
+            assert got[b] == kept[:10], b
+
+
+def test_score_threshold_on_a_fusion_root_cuts_by_the_fused_score(handler, corpus, oracle_ix):
+    qs, sps = queries(corpus, 3)
+    reqs = [dbsf_tree(q, sp, 25) for q, sp in zip(qs, sps)]
+    full = oracle_lists(oracle_ix, reqs)
+    thr = [float(np.array([x[1] for x in l], dtype=np.uint32).view(np.float32)[9]) for l in full]
+    got = as_rows(handler, asyncio.run(handler.query_points_batch(
+        "u", [dict(r, score_threshold=t) for r, t in zip(reqs, thr)])))
+    for b in range(3):
+        sc = np.array([x[1] for x in full[b]], dtype=np.uint32).view(np.float32)
+        want = [x for x, s in zip(full[b], sc) if not s < np.float32(thr[b])]
+        assert 10 <= len(want) < 25 and got[b] == want, b
