@@ -434,6 +434,25 @@ int hx_hybrid_query_dev_masked(hx_index* h, const float* q_dense_dev, const int6
                                uint64_t* keys_dev, int32_t* counts_dev, void* stream);
 /* free the copies of kept rows the pre-filtered queries keep allocated between calls (synchronises the device) */
 int hx_release_mask_view(hx_index* h);
+/* ONE whole-collection stage restricted to the rows of a mask (a `filter` inside a Prefetch):
+ * hx_search_dense / hx_search_i8 / hx_search_sparse with the contract above stated for one stage.  The list is exactly
+ * what the unmasked entry returns on an index holding only the kept rows, added in the same order: ids mapped back
+ * through the ascending list of kept rows, same order, same fp32 score bits.  Mask layout, mask_rows == hx_count, "every
+ * row kept = the unmasked call, same keys", "no row kept = counts 0, empty slots", the synchronisation (one read-back of
+ * the kept-row count per call, on top of the stage's own round trip) and the lifetime of the view's buffers are those of
+ * hx_hybrid_query_dev_masked.  mask_dev == NULL is the unmasked entry (mask_rows is not read).  A prefix other than the
+ * first has no scanned fp16 copy: its masked stage gathers the kept rows of the prefix's fp32 copy and scores them
+ * exactly, as the unmasked one scores all of them.  The sparse query weights are used as given: a caller applying an IDF
+ * modifier scales them by the WHOLE collection's statistics first (hx_sparse_df), as Qdrant does under a filter.
+ * There are no masked _async forms.  Additive to the ABI: HX_ABI_VERSION stays 3. */
+int hx_search_dense_masked(hx_index* h, const float* q_dev, int32_t B, int32_t prefix, int32_t limit,
+                           const uint32_t* mask_dev, int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev,
+                           void* stream);
+int hx_search_i8_masked(hx_index* h, const float* q_dev, int32_t B, int32_t limit, const uint32_t* mask_dev,
+                        int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+int hx_search_sparse_masked(hx_index* h, const int64_t* q_indptr_dev, const int32_t* q_idx_dev, const float* q_val_dev,
+                            int32_t B, int32_t limit, const uint32_t* mask_dev, int64_t mask_rows, uint64_t* keys_dev,
+                            int32_t* counts_dev, void* stream);
 
 /* ---- payload index -------------------------------------
  * Qdrant's create_payload_index, the engine's way: indexed payload fields live as columns beside the vectors, a filter
@@ -633,6 +652,29 @@ int hx_payload_debug_list(hx_index* h, int32_t col, int64_t row, uint32_t* head,
 int hx_group(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
              int32_t n_groups, int32_t group_size, uint64_t* out_keys_dev, uint32_t* group_codes_dev,
              int32_t* group_counts_dev, void* stream);
+/* ---- a ranked list filtered on the device ------------------
+ * The filter and the score_threshold of a node of a caller-defined Prefetch tree, applied to the list the node's stage
+ * handed out (or, for a re-scoring node's filter, to its candidates before hx_rescore).  Additive to the ABI:
+ * HX_ABI_VERSION stays 3.  keys_dev [B x stride] + counts_dev [B] is a ranked list (global ids, best first).  Per query b
+ * the list is walked in rank order and slot r is kept when ALL of these hold:
+ *   - r < n, n = counts_dev[b] clamped to [0, stride], or stride when counts_dev is NULL;
+ *   - the key is not 0 (a 0 slot inside a list is skipped, as hx_rescore and hx_group skip it);
+ *   - mask_dev given: the key's id is a row of this index (ids are global: they go through the id map as hx_rescore's
+ *     candidates do; an id of another shard, or past hx_count, is dropped) and that row's bit is set.  The mask is that of
+ *     hx_hybrid_query_dev_masked: bit r & 31 of word r >> 5 = local row r, bits at or past mask_rows are ignored,
+ *     mask_rows must equal hx_count;
+ *   - thr_dev given (B floats): !(score < thr_dev[b]) in fp32, score decoded from the key.  A score equal to the threshold
+ *     stays; -inf keeps every score, +inf keeps only +inf scores, and a NaN threshold keeps EVERYTHING (the comparison is
+ *     false for a NaN).
+ * out_keys_dev [B x limit]: the first `limit` kept keys as they came (same id, same score bits), in order, 0 after them;
+ * out_counts_dev [B]: the keys written.  A repeated id stays repeated.  Everything is enqueued on `stream`; nothing is
+ * read back; the mask and the thresholds must stay valid until the work on `stream` is done.
+ * Refused before any device work (the outputs are not touched): a NULL argument other than counts_dev / mask_dev /
+ * thr_dev; mask_dev and thr_dev both NULL; B < 1; stride or limit outside [1, 8192] (a re-scoring union is up to 8192
+ * wide and is filtered before hx_rescore); mask_rows != hx_count when a mask is given; an output that overlaps the input. */
+int hx_list_keep(hx_index* h, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+                 const uint32_t* mask_dev, int64_t mask_rows, const float* thr_dev, int32_t limit,
+                 uint64_t* out_keys_dev, int32_t* out_counts_dev, void* stream);
 /* The whole grouped query, host in, host out: hx_hybrid_query_host (mask_host NULL) or hx_hybrid_query_host_masked run
  * with final_limit = the POOL size, then hx_group over the pool on the device, then the ids' map, the unpacking and the
  * copy out.  The pool is the ranked list the root hands out: HX_MODE_TREE the re-scored union, at most

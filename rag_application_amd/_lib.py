@@ -119,6 +119,10 @@ _SIGS = {
     "hx_hybrid_query_host_masked": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, _P, _P, _P],
     "hx_hybrid_query_dev_masked": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, _P, _P, _P],
     "hx_release_mask_view": [_P],
+    "hx_search_dense_masked": [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_search_i8_masked": [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_search_sparse_masked": [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_list_keep": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P],
     "hx_group": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],
     "hx_hybrid_query_groups_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],

@@ -19,7 +19,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("replace.hip", "replace.o", ()),
            ("payload.hip", "payload.o", ()), ("paytext.hip", "paytext.o", ()),
            ("paynested.hip", "paynested.o", ()),
-           ("group.hip", "group.o", ()), ("mmr.hip", "mmr.o", ()), ("maxsim.hip", "maxsim.o", ()),
+           ("group.hip", "group.o", ()), ("listkeep.hip", "listkeep.o", ()), ("mmr.hip", "mmr.o", ()), ("maxsim.hip", "maxsim.o", ()),
            ("formula.hip", "formula.o", ()), ("fuse.hip", "fuse.o", ()),
            ("facet.hip", "facet.o", ()), ("reco.hip", "reco.o", ()), ("discover.hip", "discover.o", ()),
            ("matrix.hip", "matrix.o", ()),

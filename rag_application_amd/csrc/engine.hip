@@ -1658,6 +1658,20 @@ bool masked_dense_dev(hx_index* h, const float* q_dev, int B, int L, const uint3
   return mask_dev ? with_mask_view(h, mask_dev, count_known, false, st, run) : (run(), true);
 }
 
+// One stage inside with_mask_view, as masked_dense_dev runs the dense one: run() under the view of the kept rows, zeros
+// when the mask keeps none, then the ids that cross the ABI.  mask_dev == NULL: the unmasked entry.
+template <typename F>
+static void masked_stage(hx_index* h, const uint32_t* mask_dev, int64_t mask_rows, bool sparse, int B, int limit,
+                         uint64_t* keys_dev, int* counts_dev, hipStream_t st, F&& run) {
+  HX_CHECK(!mask_dev || mask_rows == h->n, "mask_rows must equal the index's row count (hx_count)");
+  HX_CHECK(B > 0, "B must be positive");                                   // (run() checks both; a mask that keeps no
+  HX_CHECK(limit >= 1 && limit <= MAX_LIMIT, "limit out of range [1, 2048]");   // row never calls it)
+  h->set_device();
+  if (!mask_dev) run();
+  else if (!with_mask_view(h, mask_dev, -1, sparse, st, run)) zero_outputs(keys_dev, counts_dev, B, limit, st);
+  remap_out(h, keys_dev, (int64_t)B * limit, st);
+}
+
 // ---- what every *_host entry does with a host mask and with its lists (poolstage.hip, byexample.hip) -------------------
 // the kept rows of a host mask: the caller's count, no read-back (bits past row n of the last word are not rows)
 int64_t host_mask_count(const hx_index* h, const uint32_t* mask_host) {
@@ -2188,6 +2202,43 @@ int hx_search_sparse(hx_index* h, const int64_t* q_indptr_dev, const int32_t* q_
   h->set_device();
   search_sparse(h, q_indptr_dev, q_idx_dev, q_val_dev, B, limit, keys_dev, counts_dev, (hipStream_t)stream);
   remap_out(h, keys_dev, (int64_t)B * limit, (hipStream_t)stream);
+  HX_CATCH
+}
+
+// ---- the whole-collection stages over the rows of a mask (hx.h: hx_search_*_masked) -------------
+int hx_search_dense_masked(hx_index* h, const float* q_dev, int32_t B, int32_t prefix, int32_t limit,
+                           const uint32_t* mask_dev, int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev,
+                           void* stream) {
+  HX_TRY
+  HX_CHECK(h && q_dev && keys_dev && counts_dev, "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  masked_stage(h, mask_dev, mask_rows, false, B, limit, keys_dev, counts_dev, st,
+               [&] { search_dense(h, q_dev, B, prefix, limit, keys_dev, counts_dev, st); });
+  HX_CATCH
+}
+
+int hx_search_i8_masked(hx_index* h, const float* q_dev, int32_t B, int32_t limit, const uint32_t* mask_dev,
+                        int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && q_dev && keys_dev && counts_dev, "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  masked_stage(h, mask_dev, mask_rows, false, B, limit, keys_dev, counts_dev, st,
+               [&] { search_i8(h, q_dev, B, limit, keys_dev, counts_dev, st); });
+  HX_CATCH
+}
+
+int hx_search_sparse_masked(hx_index* h, const int64_t* q_indptr_dev, const int32_t* q_idx_dev, const float* q_val_dev,
+                            int32_t B, int32_t limit, const uint32_t* mask_dev, int64_t mask_rows, uint64_t* keys_dev,
+                            int32_t* counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && q_indptr_dev && keys_dev && counts_dev, "NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  struct Reset {                                       // the stage's summary belongs to this call, however it ends
+    hx_index* h;
+    ~Reset() { h->sp_sum_pending = h->sp_sum_fetched = false; }
+  } reset{h};
+  masked_stage(h, mask_dev, mask_rows, true, B, limit, keys_dev, counts_dev, st,
+               [&] { search_sparse(h, q_indptr_dev, q_idx_dev, q_val_dev, B, limit, keys_dev, counts_dev, st); });
   HX_CATCH
 }
 

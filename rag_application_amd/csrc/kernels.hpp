@@ -562,6 +562,27 @@ struct GroupArgs {
   int* group_counts;
 };
 void launch_group_select(const GroupArgs& a, int B, hipStream_t st);
+// ---- listkeep.hip: a ranked list filtered by a row mask and / or a score threshold (hx_list_keep)
+// Per query b < B: the walk of keys[b * stride + r], r < counts[b] clamped to [0, stride] (NULL: stride), in rank order.
+// Slot r is kept when its key is not 0, (mask != NULL) the id of ikeys[b * stride + r] -- the same slot with internal ids,
+// id_base + row; the same pointer where the two id spaces are one; 0 = an id of another index -- names a row of [0, n_rows)
+// whose bit row & 31 of mask[row >> 5] is set, and (thr != NULL) !(score < thr[b]) in fp32.  out[b * limit + t] = the t-th
+// kept key of `keys` as it came, t < limit, 0 after them; out_counts[b] = the keys written.
+struct ListKeepArgs {
+  const uint64_t* keys;
+  const uint64_t* ikeys;
+  int stride;              // 1 .. 8192
+  const int* counts;
+  int B;
+  const uint32_t* mask;    // ceil(n_rows / 32) words, or NULL
+  int64_t n_rows;
+  uint32_t id_base;
+  const float* thr;        // B thresholds, or NULL
+  int limit;               // 1 .. 8192
+  uint64_t* out;
+  int* out_counts;
+};
+void launch_list_keep(const ListKeepArgs& a, hipStream_t st);
 // ---- mmr.hip: MMR search (hx_mmr) --------------------------------------------------------------
 // Per query b: the ranked pool keys[b * stride + i], i < counts[b] (NULL: stride), 0 = an empty slot; ikeys = the same
 // slots with internal ids (id_base + row), which name the fp32 row rows[row * dim_pad ..].  A position is eligible when

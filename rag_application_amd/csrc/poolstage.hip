@@ -311,6 +311,39 @@ int hx_group(hx_index* h, int32_t col, const uint64_t* keys_dev, int32_t stride,
   HX_CATCH
 }
 
+// ---- a ranked list filtered by a row mask and / or a score threshold ---------------------------
+int hx_list_keep(hx_index* h, const uint64_t* keys_dev, int32_t stride, const int32_t* counts_dev, int32_t B,
+                 const uint32_t* mask_dev, int64_t mask_rows, const float* thr_dev, int32_t limit,
+                 uint64_t* out_keys_dev, int32_t* out_counts_dev, void* stream) {
+  HX_TRY
+  HX_CHECK(h && keys_dev && out_keys_dev && out_counts_dev, "NULL argument");
+  HX_CHECK(mask_dev || thr_dev, "list_keep: a mask or thresholds (or both) are needed");
+  HX_CHECK(B >= 1, "list_keep: B < 1");
+  HX_CHECK(stride >= 1 && stride <= CAND_CAP, "list_keep: stride out of range [1, 8192]");
+  HX_CHECK(limit >= 1 && limit <= CAND_CAP, "list_keep: limit out of range [1, 8192]");
+  HX_CHECK(!mask_dev || mask_rows == h->n, "list_keep: mask_rows must equal the index's row count (hx_count)");
+  const uintptr_t in0 = (uintptr_t)keys_dev, in1 = in0 + (size_t)B * stride * 8;
+  const uintptr_t out0 = (uintptr_t)out_keys_dev, out1 = out0 + (size_t)B * limit * 8;
+  HX_CHECK(out1 <= in0 || in1 <= out0, "list_keep: the output must not overlap the input");
+  h->set_device();
+  hipStream_t st = (hipStream_t)stream;
+  ListKeepArgs a{};
+  a.keys = keys_dev;
+  a.ikeys = mask_dev ? remap_in(h, keys_dev, (int64_t)B * stride, st) : keys_dev;   // (ids matter under a mask only)
+  a.stride = stride;
+  a.counts = counts_dev;
+  a.B = B;
+  a.mask = mask_dev;
+  a.n_rows = h->n;
+  a.id_base = (uint32_t)h->id_base;
+  a.thr = thr_dev;
+  a.limit = limit;
+  a.out = out_keys_dev;
+  a.out_counts = out_counts_dev;
+  launch_list_keep(a, st);
+  HX_CATCH
+}
+
 int hx_hybrid_query_groups_host(hx_index* h, const float* qd, const int64_t* qip, const int32_t* qix, const float* qv,
                                 int32_t B, const hx_params* p, const uint32_t* mask_host, int64_t mask_rows, int32_t col,
                                 int32_t group_pool, int32_t n_groups, int32_t group_size, float* scores, int64_t* ids,

@@ -266,10 +266,22 @@ class HxIndex:
     # behind all the stages of its query and redoes the batch without `flag` when it is not zero.
     deferred_stages = True
 
-    def search_dense(self, q: torch.Tensor, limit: int, prefix: int = 0, flag: Optional[torch.Tensor] = None):
+    # `mask` (None = every row; else as `_dev_mask` takes it): the stage over the rows the mask keeps (hx_search_*_masked) --
+    # the list of an index holding only those rows, ids mapped back.  The deferred forms have no masked twin.
+    @staticmethod
+    def _no_masked_flag(mask, flag):
+        if mask is not None and flag is not None:
+            raise ValueError("mask and flag together: the deferred (flag=) stage forms have no masked twin")
+
+    def search_dense(self, q: torch.Tensor, limit: int, prefix: int = 0, flag: Optional[torch.Tensor] = None, mask=None):
+        HxIndex._no_masked_flag(mask, flag)
         q = _need_cuda(q, torch.float32, "q")
         keys, cnt = self._out(q.shape[0], limit)
-        if flag is not None:
+        if mask is not None:
+            words, rows = self._dev_mask(mask)
+            check(_lib.lib().hx_search_dense_masked(self._h, _ptr(q), q.shape[0], prefix, limit, _ptr(words), rows,
+                                                    _ptr(keys), _ptr(cnt), _stream()))
+        elif flag is not None:
             check(_lib.lib().hx_search_dense_async(self._h, _ptr(q), q.shape[0], prefix, limit, _ptr(keys), _ptr(cnt),
                                                    _ptr(_need_cuda(flag, torch.int32, "flag")), _stream()))
         else:
@@ -277,10 +289,15 @@ class HxIndex:
                                              _stream()))
         return keys, cnt
 
-    def search_i8(self, q: torch.Tensor, limit: int, flag: Optional[torch.Tensor] = None):
+    def search_i8(self, q: torch.Tensor, limit: int, flag: Optional[torch.Tensor] = None, mask=None):
+        HxIndex._no_masked_flag(mask, flag)
         q = _need_cuda(q, torch.float32, "q")
         keys, cnt = self._out(q.shape[0], limit)
-        if flag is not None:
+        if mask is not None:
+            words, rows = self._dev_mask(mask)
+            check(_lib.lib().hx_search_i8_masked(self._h, _ptr(q), q.shape[0], limit, _ptr(words), rows, _ptr(keys),
+                                                 _ptr(cnt), _stream()))
+        elif flag is not None:
             check(_lib.lib().hx_search_i8_async(self._h, _ptr(q), q.shape[0], limit, _ptr(keys), _ptr(cnt),
                                                 _ptr(_need_cuda(flag, torch.int32, "flag")), _stream()))
         else:
@@ -288,13 +305,18 @@ class HxIndex:
         return keys, cnt
 
     def search_sparse(self, q_indptr: torch.Tensor, q_idx: torch.Tensor, q_val: torch.Tensor, limit: int,
-                      flag: Optional[torch.Tensor] = None):
+                      flag: Optional[torch.Tensor] = None, mask=None):
+        HxIndex._no_masked_flag(mask, flag)
         q_indptr = _need_cuda(q_indptr, torch.int64, "q_indptr")
         q_idx = _need_cuda(q_idx, torch.int32, "q_idx")
         q_val = _need_cuda(q_val, torch.float32, "q_val")
         B = q_indptr.shape[0] - 1
         keys, cnt = self._out(B, limit)
-        if flag is not None:
+        if mask is not None:
+            words, rows = self._dev_mask(mask)
+            check(_lib.lib().hx_search_sparse_masked(self._h, _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B, limit,
+                                                     _ptr(words), rows, _ptr(keys), _ptr(cnt), _stream()))
+        elif flag is not None:
             check(_lib.lib().hx_search_sparse_async(self._h, _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B, limit,
                                                     _ptr(keys), _ptr(cnt), _ptr(_need_cuda(flag, torch.int32, "flag")),
                                                     _stream()))
@@ -302,6 +324,28 @@ class HxIndex:
             check(_lib.lib().hx_search_sparse(self._h, _ptr(q_indptr), _ptr(q_idx), _ptr(q_val), B, limit,
                                               _ptr(keys), _ptr(cnt), _stream()))
         return keys, cnt
+
+    def list_keep(self, keys: torch.Tensor, counts: Optional[torch.Tensor], limit: int, mask=None, thresholds=None):
+        """The ranked lists keys [B, stride] (+ counts [B], None = every slot) filtered in rank order (hx_list_keep): a
+        slot stays when its key is not 0, (mask: a row mask as `_dev_mask` takes it) its id is a row of this index whose
+        bit is set and (thresholds: B float32 values, a tensor or anything numpy reads) its score is not below its
+        query's threshold.  Returns (out_keys [B, limit] int64 -- the first `limit` kept keys unchanged, 0 after them --,
+        counts [B] int32).  Only enqueues work."""
+        keys, counts, B, stride = self._pool_args(keys, counts)
+        L = int(limit)
+        words, rows = self._dev_mask(mask)
+        thr = None
+        if thresholds is not None:
+            if not isinstance(thresholds, torch.Tensor):
+                thresholds = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1))
+            thr = _need_cuda(thresholds.to(keys.device), torch.float32, "thresholds")
+            if thr.dim() != 1 or thr.shape[0] != B:
+                raise HxError(f"thresholds: want {B} values, one per query")
+        out = torch.empty((B, L if 1 <= L <= 8192 else 1), dtype=torch.int64, device=keys.device)   # (the engine refuses)
+        cnt = torch.empty((B,), dtype=torch.int32, device=keys.device)
+        check(_lib.lib().hx_list_keep(self._h, _ptr(keys), stride, _ptr(counts), B, _ptr(words), rows, _ptr(thr), L,
+                                      _ptr(out), _ptr(cnt), _stream()))
+        return out, cnt
 
     # -- collection term statistics and the IDF modifier (hx.h: hx_sparse_df / hx_sparse_idf_*; DESIGN.md section 31) ----
     def sparse_df(self, q_idx: torch.Tensor):

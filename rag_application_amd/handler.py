@@ -584,6 +584,7 @@ class _Collection:
 
 
 FILTER_STAGES = ("root", "all")
+QUERY_FILTER_STAGES = ("root", "node", "all")   # of query_points: "node" = every node's own filter
 RECO_MAX_LIMIT, RECO_MAX_REQUESTS, RECO_MAX_EXAMPLES = 1024, 16, 32   # HX_RECO_MAX_* of hx.h
 RECO_STRATEGIES = {"average_vector": 0, "best_score": 1, "sum_scores": 2}   # HX_RECO_AVERAGE / _BEST_SCORE / _SUM_SCORES
 MMR_MAX_LIMIT = 256                   # HX_MMR_MAX_LIMIT of hx.h: most hits hybrid_search_mmr picks per query
@@ -1459,7 +1460,57 @@ class QdrantHandler:
         if not self._query_tree:
             raise ValueError("query_points is not supported on a sharded collection")
         requests = list(requests)
+        out: List[Optional[List[ScoredPoint]]] = [None] * len(requests)
+        # every request's own "filter_stages": "root" (the default) takes the path it always took, untouched
+        root, node = [], []
+        for i, req in enumerate(requests):
+            how = req.get("filter_stages") if isinstance(req, dict) else getattr(req, "filter_stages", None)
+            how = "root" if how is None else how
+            if how not in QUERY_FILTER_STAGES:
+                raise ValueError(f"filter_stages must be one of {QUERY_FILTER_STAGES}, got {how!r}")
+            if isinstance(req, dict) and "filter_stages" in req:
+                req = {k: v for k, v in req.items() if k != "filter_stages"}
+            (root if how == "root" else node).append((i, req, how))
         col = self._collections[str(user_id)]
+        if root:
+            for (i, _, _), res in zip(root, self._query_points_root(col, [r for _, r, _ in root])):
+                out[i] = res
+        if node:
+            for (i, _, _), res in zip(node, self._query_points_nodes(col, [r for _, r, _ in node], [h for _, _, h in node])):
+                out[i] = res
+        return out
+
+    def _query_points_nodes(self, col, requests, hows):
+        """filter_stages "node" | "all" (DESIGN.md section 32): every node's own filter and score_threshold, served on the
+        device by the masked stage entries and hx_list_keep; "all" pushes the root's filter into every leaf first."""
+        parsed, roots = [], []
+        filters: Dict[str, Any] = {}
+        for req, how in zip(requests, hows):
+            shape, vecs, thrs, flts = _query_tree.parse_nodes(req, col.dim, col.msizes, self._check_filter,
+                                                              prefetch_filters=how == "node")
+            if how == "all":
+                shape = _query_tree.push_to_leaves(shape)
+            filters.update(flts)
+            get = req.get if isinstance(req, dict) else (lambda k, d=None, r=req: getattr(r, k, d))
+            with_payload = get("with_payload", True)
+            parsed.append(shape)
+            roots.append((vecs, thrs, True if with_payload is None else bool(with_payload)))
+        out: List[Optional[List[ScoredPoint]]] = [None] * len(requests)
+        stages = _query_tree.DeviceStages(col.index, _engine, sparse_modifier=getattr(col, "sparse_modifier", None),
+                                          masks=lambda key: col.row_mask(filters[key]))
+        cids, cpay = col.ids, col.payloads
+        for shape, members in _query_tree.group_by_shape(parsed).items():
+            vectors = _query_tree.batch_vectors([roots[i][0] for i in members])
+            thresholds = _query_tree.batch_thresholds([roots[i][1] for i in members])
+            keys, counts = stages.to_host(*_query_tree.run(shape, vectors, stages, thresholds=thresholds))
+            for b, i in enumerate(members):
+                k = keys[b, :int(counts[b])]
+                with_payload = roots[i][2]
+                out[i] = [ScoredPoint(id=cids[r], version=0, score=s, payload=cpay[r] if with_payload else None)
+                          for s, r in zip(_fusion.key_scores(k).tolist(), _fusion.key_ids(k).tolist())]
+        return out
+
+    def _query_points_root(self, col, requests):
         parsed, roots = [], []
         for req in requests:
             shape, vecs = _query_tree.parse(req, col.dim, col.msizes)
@@ -1506,7 +1557,8 @@ class QdrantHandler:
         """The reference's general call, client.query_points(prefetch=[...], query=..., using=..., limit=...), for many
         requests at once (additive).  A request is a dict (or an object with the same attributes):
         "prefetch", "query", "using", "limit" as query_tree.py states them, and for the root "filters" (or "filter"),
-        "score_threshold", "with_payload".  The requests are grouped by shape -- the tree without its vectors -- and every
+        "score_threshold", "with_payload", "filter_stages" (query_points states it; "root" when absent: a batch may mix
+        them).  The requests are grouped by shape -- the tree without its vectors -- and every
         group runs as one batch over the engine's stage entries, fusion nodes through hx_fuse; results come back in
         request order.  Raises ValueError for a tree no stage can serve (query_tree.parse names the reason) and on a
         sharded collection; any other failure is logged and gives [], as in every search."""
@@ -1514,14 +1566,22 @@ class QdrantHandler:
 
     async def query_points(self, user_id: str, prefetch=None, query=None, using: str = "dense", limit: int = 10,
                            filters: Optional[Dict] = None, score_threshold: Optional[float] = None,
-                           with_payload: bool = True) -> List[ScoredPoint]:
+                           with_payload: bool = True, filter_stages: str = "root") -> List[ScoredPoint]:
         """One request of query_points_batch.  `filters` is the root's filter, as in the reference (:297, :371): the
         root's candidates are filtered before its cut; a root without prefetch takes none.  `score_threshold` drops
-        root hits that score below it."""
+        root hits that score below it.  filter_stages (DESIGN.md section 32), as hybrid_search's: "root" = the above;
+        "node" = every node of the tree may carry its own "filter" and "score_threshold" (Qdrant's Prefetch(filter=...)),
+        the root's being `filters` / `score_threshold`, each served on the device -- a root without prefetch and with
+        `filters` is a filtered nearest-neighbour search; "all" = `filters` pushed into every leaf (a filter inside a
+        prefetch is refused)."""
+        if filter_stages not in QUERY_FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {QUERY_FILTER_STAGES}, got {filter_stages!r}")
         res = await self.query_points_batch(user_id, [{"prefetch": prefetch, "query": query, "using": using,
                                                        "limit": limit, "filters": filters,
                                                        "score_threshold": score_threshold,
-                                                       "with_payload": with_payload}])
+                                                       "with_payload": with_payload,
+                                                       **({} if filter_stages == "root" else
+                                                          {"filter_stages": filter_stages})}])
         return res[0] if res else []
 
     # ------------------------------------------------------------------------ term statistics
