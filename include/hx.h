@@ -454,6 +454,45 @@ int hx_search_sparse_masked(hx_index* h, const int64_t* q_indptr_dev, const int3
                             int32_t B, int32_t limit, const uint32_t* mask_dev, int64_t mask_rows, uint64_t* keys_dev,
                             int32_t* counts_dev, void* stream);
 
+/* ---- binary quantization ----------------------------------
+ * Qdrant's BinaryQuantization, the engine's way: an optional 1-bit copy of the stored rows and a whole-collection stage
+ * that ranks by Hamming distance.  A caller puts the stage under a dense re-scoring node (hx_rescore) with a limit a few
+ * times the final one -- Qdrant's `oversampling` and `rescore`.  Additive to the ABI: HX_ABI_VERSION stays 3.
+ *
+ * The copy.  hx_binary_enable (idempotent) allocates it at the index's row capacity and derives rows [0, hx_count) from
+ * the stored normalised fp32 rows; from then on every entry that adds, replaces, removes or truncates rows carries it.  Bit
+ * j & 31 of word j >> 5 of a row is 1 when the STORED normalised value dense[row][j] > 0: +0.0, -0.0, a value that
+ * underflowed to zero in normalisation and the padding columns give 0.  It is derived data: hx_save does not write it and
+ * hx_load gives an index without it (enable it again; the rows are derived again).  An index on which hx_binary_enable was
+ * never called allocates nothing and runs no kernel for it.  hx_binary_debug_row copies the dim_pad / 32 words
+ * (dim_pad = dim rounded up to 64) of one row to the host: the tests' hook.
+ *
+ * The stage.  hx_search_bin / hx_search_bin_masked, B queries q_dev [B x dim] fp32 on the device:
+ *   query bits   bit j is 1 when the RAW element q[b][j] > 0 -- no normalisation (the sign does not need it).  Every one of
+ *                the dim elements must be finite: a batch holding a NaN or +-Inf fails ("query values must be finite"),
+ *                as hx_search_dense's does;
+ *   score        of row r for query b = dim - 2 * popcount(query bits XOR row bits) over the padded width: the dot product
+ *                of the two +-1 vectors, an integer in [-dim, dim], carried in the key as that fp32 value:
+ *                key = (orderable(score) << 32) | (0xFFFFFFFF - id), the engine's key;
+ *   order, ids   the best `limit` rows in the engine's total order (score descending, id ascending); counts[b] =
+ *                min(limit, rows considered), the slots behind it 0; 1 <= limit <= 2048; ids are global, as every stage's;
+ *   mask         the masked form considers exactly the rows whose bit is set: layout and the mask_rows == hx_count rule of
+ *                hx_search_dense_masked; mask_dev == NULL is the unmasked entry; no row kept = counts 0, empty slots.  The
+ *                mask is read inside the scan: no gathered view of the kept rows is built;
+ *   refusals     before any device work: the copy is not enabled ("binary" in the message), B < 1, a limit out of range, a
+ *                mask_rows that is not hx_count.  An empty index gives zero counts;
+ *   synchronisation  ONE host round trip per call: behind the scan the host reads, together, the count of non-finite
+ *                queries and the per-query flags of a candidate buffer that overflowed (such a query -- a corpus ordered
+ *                so that every chunk beats the threshold of the rows before it -- is scanned again in fixed chunks, all
+ *                enqueued).  The outputs are written by work enqueued on `stream` behind that. */
+int hx_binary_enable(hx_index* h);
+int hx_binary_enabled(hx_index* h, int32_t* on);
+int hx_binary_debug_row(hx_index* h, int64_t row, uint32_t* words_out, int32_t cap_words);
+int hx_search_bin(hx_index* h, const float* q_dev, int32_t B, int32_t limit, uint64_t* keys_dev, int32_t* counts_dev,
+                  void* stream);
+int hx_search_bin_masked(hx_index* h, const float* q_dev, int32_t B, int32_t limit, const uint32_t* mask_dev,
+                         int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+
 /* ---- payload index -------------------------------------
  * Qdrant's create_payload_index, the engine's way: indexed payload fields live as columns beside the vectors, a filter
  * arrives as a small postfix program, and one kernel evaluates it over every row and writes the packed row mask of

@@ -122,6 +122,11 @@ _SIGS = {
     "hx_search_dense_masked": [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
     "hx_search_i8_masked": [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
     "hx_search_sparse_masked": [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_binary_enable": [_P],
+    "hx_binary_enabled": [_P, C.POINTER(C.c_int32)],
+    "hx_binary_debug_row": [_P, C.c_int64, _P, C.c_int32],
+    "hx_search_bin": [_P, _P, C.c_int32, C.c_int32, _P, _P, _P],
+    "hx_search_bin_masked": [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
     "hx_list_keep": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P],
     "hx_group": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],
     "hx_hybrid_query_groups_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32,

@@ -86,6 +86,7 @@ std::vector<RowArray> row_arrays(hx_index* h) {
   for (int p = 0; p < h->n_pre; ++p)
     add(h->pre[p], (int64_t)h->psize[p] * 4, true, offsetof(PrepRowsArgs, pre) + (size_t)p * sizeof(float*));
   if (h->n_pre > 0) add(h->pre_h0, (int64_t)h->psize[0] * 2, true, offsetof(PrepRowsArgs, pre_h0));
+  if (h->bin_on) add(h->bits, (int64_t)h->bin_words() * 4, false, offsetof(PrepRowsArgs, bits));
   return r;
 }
 
@@ -98,6 +99,7 @@ PrepRowsArgs prep_rows_args(hx_index* h, const std::vector<RowArray>& ra, void* 
   a.n_prefix = h->n_pre;
   for (int p = 0; p < h->n_pre; ++p) a.psize[p] = h->psize[p];
   a.err_max = h->cand8 ? h->s8_err : nullptr;
+  a.bits_words = h->bin_words();
   for (size_t i = 0; i < ra.size(); ++i) {
     void* row = (uint8_t*)base[i] + r * ra[i].rb;
     std::memcpy((uint8_t*)&a + ra[i].arg, &row, sizeof row);
@@ -1787,6 +1789,8 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_RECO_CAP")) h->reco_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
   if (const char* e = getenv("HX_DEBUG_DISCOVER_CHUNK0")) h->discover_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the discover scan's chunks
   if (const char* e = getenv("HX_DEBUG_DISCOVER_CAP")) h->discover_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
+  if (const char* e = getenv("HX_DEBUG_BIN_CHUNK0")) h->bin_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the binary scan's chunks
+  if (const char* e = getenv("HX_DEBUG_BIN_CAP")) h->bin_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
   if (const char* e = getenv("HX_DEBUG_MATRIX_SCAN_ONLY")) h->matrix_scan_only = atoi(e) != 0;             // diagnostics: the matrix scan's own time
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);

@@ -56,7 +56,8 @@ enum WsSlot {
   WS_FORMULA_PLANES, WS_FORMULA_KEYS, WS_FORMULA_POS, WS_FORMULA_BASE, WS_FORMULA_CNT, WS_FORMULA_DROP,
   WS_MATRIX_ROWS, WS_MATRIX_PLANE, WS_MATRIX_OUT, WS_MATRIX_OCNT, WS_MATRIX_SC, WS_MATRIX_ID,
   WS_DISC_TAU, WS_DISC_TAU0,
-  WS_IDF_IDX, WS_IDF_VAL, WS_IDF_DF
+  WS_IDF_IDX, WS_IDF_VAL, WS_IDF_DF,
+  WS_BIN_Q, WS_BIN_CAND, WS_BIN_CNT, WS_BIN_FLAGS, WS_BIN_TAU, WS_BIN_TAU0
 };
 
 template <typename T>
@@ -101,6 +102,13 @@ struct hx_index {
   int8_t* q8s = nullptr;
   float* q8s_scale = nullptr;
   uint32_t* s8_err = nullptr;
+  // 1-bit copy of the normalised rows (hx_binary_enable): bit j & 31 of word j >> 5 of a row =
+  // dense[row][j] > 0; bin_words() words per row -- dim_pad8 / 32, at least eight: the kernels that move stored rows take
+  // them as two or more 16-byte pieces -- the words past dim_pad / 32 zero.  Derived, never saved; a member of
+  // row_arrays() once enabled.
+  uint32_t* bits = nullptr;
+  bool bin_on = false;
+  int bin_words() const { return std::max(dim_pad8 / 32, 8); }
   int cand8 = 1;                      // 0: fp16 candidates only, no int8 copy is kept (HX_DENSE_CAND=f16)
   bool cand8_off = false;             // hx_set_dense_candidates(h, 0): the copy is kept but the fp16 scan nominates
   int64_t cand8_queries = 0, cand8_failed = 0;   // queries the int8 candidate pass took / could not certify
@@ -239,6 +247,8 @@ struct hx_index {
   int reco_cap = 0;                   // HX_DEBUG_RECO_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
   int discover_chunk0 = 0;            // HX_DEBUG_DISCOVER_CHUNK0 (tests): rows of the first chunk of the discover scan, 0 = the buffer's capacity
   int discover_cap = 0;               // HX_DEBUG_DISCOVER_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
+  int bin_chunk0 = 0;                 // HX_DEBUG_BIN_CHUNK0 (tests): rows of the first chunk of the binary scan, 0 = the buffer's capacity
+  int bin_cap = 0;                    // HX_DEBUG_BIN_CAP (tests): keys of a query's candidate buffer there, 0 = by the limit
   int64_t discover_redone = 0;        // hx_discover_redone: requests that went through the overflow redo
   bool matrix_scan_only = false;      // HX_DEBUG_MATRIX_SCAN_ONLY (scripts/matrix_bench.py): hx_search_matrix stops behind k_matrix_scan, the outputs zeroed
   int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap

@@ -264,8 +264,14 @@ struct PrepRowsArgs {
   float* q8s_scale;        // [n]
   uint32_t* err_max;       // one device word
   int* nonfinite;          // one device word (may be NULL): set to 1 when a row holds a NaN or +-Inf element
+  // 1-bit copy of the NORMALISED row (may be NULL): k_prep_rows does not read the field --
+  // launch_prep_rows runs k_binarize_rows behind it on the same stream, over the `dense` rows that launch just wrote
+  uint32_t* bits;          // [n x bits_words]
+  int bits_words;          // words of a row of `bits`: at least dim_pad / 32, a multiple of four
 };
 void launch_prep_rows(const PrepRowsArgs& a, hipStream_t st);
+// bits[r * words + (j >> 5)] bit (j & 31) = dense[r * dim_pad + j] > 0 for j < dim_pad, 0 up to 32 * words
+void launch_binarize_rows(const float* dense, int dim_pad, int words, int64_t n, uint32_t* bits, hipStream_t st);
 void launch_requant_rows(const float* dense, int dim_pad, int dim_pad8, int64_t n, int8_t* q8s, float* scale,
                          uint32_t* err_max, hipStream_t st);
 // candidate-pass form of normalised queries qn [B x dpad]: int8 rows [Bpad x dpad8], scales [Bpad], certificate
@@ -827,5 +833,31 @@ void launch_sparse_rows_nonempty(const int64_t* indptr, int64_t rows, int64_t* n
 // out[i] = q_val[i] * idf(*n_docs, df[i]) in the arithmetic hx.h states; out may be q_val
 void launch_sparse_idf(const float* q_val, const int64_t* df, const int64_t* n_docs, int64_t nnz, float* out,
                        hipStream_t st);
+
+// ---- binscan.hip: binary quantization, the Hamming scan stage (hx_search_bin) -------------------
+// qbits[b * words + (j >> 5)] bit (j & 31) = q[b * dim + j] > 0 for j < dim, 0 up to 32 * words; *bad += the queries with a
+// NaN or +-Inf among their dim elements
+void launch_bin_queries(const float* q, int dim, int B, int words, uint32_t* qbits, int* bad, hipStream_t st);
+// The exhaustive scan of rows [row_begin, row_end) for B queries: score = dim - 2 popcount(qbits XOR row bits); a row whose
+// mask bit is set (mask NULL: every row) and whose KEY make_key(score, id_base + row) is > tau_key[b] is appended to
+// cand[b * cap + atomicAdd(cnt[b])]; ovf[b] = 1 when the buffer is full.
+struct BinScanArgs {
+  const uint32_t* bits;    // the stored rows, `words` words each (a multiple of 4)
+  int words;
+  int dim;
+  int64_t row_begin, row_end;
+  const uint32_t* qbits;   // [B x words]
+  int B;
+  const uint32_t* mask;    // packed row mask, NULL = every row
+  const uint64_t* tau_key; // per query: the limit-th best key so far, 0 = none yet (every key passes)
+  uint64_t* cand;
+  int* cnt;
+  int* ovf;
+  int cap;
+  uint32_t id_base;
+};
+void launch_bin_scan(const BinScanArgs& a, hipStream_t st);
+// tau_key[b] = cand[b * cap + limit - 1] when cnt[b] >= limit (lists sorted by launch_compact), else 0
+void launch_bin_tau(const uint64_t* cand, int cap, const int* cnt, int B, int limit, uint64_t* tau_key, hipStream_t st);
 
 }  // namespace hx

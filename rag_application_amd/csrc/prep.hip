@@ -204,6 +204,41 @@ void launch_prep_rows(const PrepRowsArgs& a, hipStream_t st) {
   const size_t lds = (size_t)4 * a.dim_pad8 * sizeof(float);
   hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)((a.n + 3) / 4)), dim3(256), lds, st, a);
   HX_HIP(hipGetLastError());
+  // the 1-bit copy is derived from the normalised rows this launch wrote, behind it on the stream
+  if (a.bits) launch_binarize_rows(a.dense, a.dim_pad, a.bits_words, a.n, a.bits, st);
+}
+
+// The 1-bit copy of stored rows (hx_binary_enable, and behind every k_prep_rows of an index that keeps the copy): one wave
+// per row, four rows per workgroup.  A trip takes four 64-column chunks -- four loads in flight, one ballot each -- and
+// lanes 0..3 store the two words of "their" chunk.  The padding columns of `dense` are zero, so their bits are; the words
+// from dim_pad / 32 up to the row's `words` are written as zero.
+__global__ __launch_bounds__(256) void k_binarize_rows(const float* __restrict__ dense, int dim_pad, int words, int64_t n,
+                                                       uint32_t* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  const float* x = dense + row * dim_pad;
+  uint32_t* o = bits + row * words;
+  const int nch = dim_pad >> 6;
+  for (int j0 = 0; j0 < nch; j0 += 4) {
+    float t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = j0 + u < nch ? x[((j0 + u) << 6) + lane] : 0.0f;
+    uint64_t mine = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const uint64_t m = __ballot(t[u] > 0.0f);
+      mine = lane == u ? m : mine;
+    }
+    if (lane < 4 && j0 + lane < nch) *(uint2*)(o + 2 * (j0 + lane)) = make_uint2((uint32_t)mine, (uint32_t)(mine >> 32));
+  }
+  for (int w = 2 * nch + lane; w < words; w += 64) o[w] = 0u;
+}
+void launch_binarize_rows(const float* dense, int dim_pad, int words, int64_t n, uint32_t* bits, hipStream_t st) {
+  if (n <= 0) return;
+  HX_CHECK(dim_pad % 64 == 0 && words % 4 == 0 && words * 32 >= dim_pad, "binarize: row width");
+  hipLaunchKernelGGL(k_binarize_rows, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, dense, dim_pad, words, n, bits);
+  HX_HIP(hipGetLastError());
 }
 
 // The candidate copy of rows that are already stored (hx_load: the copy is derived data and is not in the file).

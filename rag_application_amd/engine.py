@@ -304,6 +304,34 @@ class HxIndex:
             check(_lib.lib().hx_search_i8(self._h, _ptr(q), q.shape[0], limit, _ptr(keys), _ptr(cnt), _stream()))
         return keys, cnt
 
+    # -- binary quantization (hx.h: hx_binary_*, hx_search_bin) -----------------
+    def binary_enable(self):
+        """Keep a 1-bit copy of the rows from now on (hx_binary_enable; idempotent): search_bin needs it."""
+        check(_lib.lib().hx_binary_enable(self._h))
+
+    def binary_enabled(self) -> bool:
+        on = C.c_int32()
+        check(_lib.lib().hx_binary_enabled(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def binary_row(self, row: int) -> np.ndarray:
+        """The stored sign bits of one row (hx_binary_debug_row): dim rounded up to 64, / 32, uint32 words."""
+        out = np.zeros((self.dim + 63) // 64 * 2, dtype=np.uint32)
+        check(_lib.lib().hx_binary_debug_row(self._h, int(row), _ptr(out), out.shape[0]))
+        return out
+
+    def search_bin(self, q: torch.Tensor, limit: int, mask=None):
+        """The Hamming scan stage (hx_search_bin): keys [B, limit] with the integer scores dim - 2 popcount(xor), counts."""
+        q = _need_cuda(q, torch.float32, "q")
+        keys, cnt = self._out(q.shape[0], limit)
+        if mask is not None:
+            words, rows = self._dev_mask(mask)
+            check(_lib.lib().hx_search_bin_masked(self._h, _ptr(q), q.shape[0], limit, _ptr(words), rows, _ptr(keys),
+                                                  _ptr(cnt), _stream()))
+        else:
+            check(_lib.lib().hx_search_bin(self._h, _ptr(q), q.shape[0], limit, _ptr(keys), _ptr(cnt), _stream()))
+        return keys, cnt
+
     def search_sparse(self, q_indptr: torch.Tensor, q_idx: torch.Tensor, q_val: torch.Tensor, limit: int,
                       flag: Optional[torch.Tensor] = None, mask=None):
         HxIndex._no_masked_flag(mask, flag)

@@ -147,6 +147,7 @@ class _Collection:
         self.payloads: List[Dict[str, Any]] = []
         self.sparse_enabled = True
         self.sparse_modifier: Optional[str] = None     # None | "idf" 
+        self.binary_quantization = False               # the index keeps a 1-bit copy of the rows
         self._masks: Dict[str, Any] = {}
         self.pindex: Optional[_pindex.PayloadIndex] = None
         self.tokens: Optional[Dict[str, Any]] = None
@@ -545,6 +546,7 @@ class _Collection:
         with open(base + ".json", "w") as f:
             json.dump({"dim": self.dim, "msizes": list(self.msizes), "sparse_enabled": self.sparse_enabled,
                        "sparse_modifier": getattr(self, "sparse_modifier", None),
+                       "binary_quantization": bool(getattr(self, "binary_quantization", False)),
                        "ids": self.ids, "payloads": self.payloads,
                        "payload_indexes": self.pindex.definitions() if getattr(self, "pindex", None) else {},
                        "token_index": {"dim": tk["dim"]} if tk is not None else None}, f)
@@ -562,6 +564,10 @@ class _Collection:
         self.payloads = list(meta["payloads"])
         self.sparse_enabled = bool(meta["sparse_enabled"])
         self.sparse_modifier = _check_modifier(meta.get("sparse_modifier"))   # (an old file has no such key)
+        # the 1-bit copy is derived data (the engine's file does not hold it): made again here, before the first search
+        self.binary_quantization = bool(meta.get("binary_quantization", False))
+        if self.binary_quantization:
+            self.index.binary_enable()
         self._masks = {}
         self.pindex = None
         # the payload indexes are derived data: the sidecar names them (old files have none), the payloads rebuild them
@@ -624,6 +630,8 @@ class QdrantHandler:
     _query_tree = True
     # sparse_modifier="idf" reads the term statistics of ONE engine index
     _sparse_modifiers = True
+    # binary_quantization=True keeps a 1-bit copy of the rows of ONE engine index
+    _binary_quantization = True
 
     def __init__(self, reranker=None, device: int = 0, persist_dir: Optional[str] = None):
         # The reference loads jinaai/jina-colbert-v2 here (:17-22) and falls back to the
@@ -764,15 +772,24 @@ class QdrantHandler:
     async def create_collection(self, user_id: str, dense_vector_size: int = 768,
                                 matryoshka_sizes: list = [64, 128, 256], quantized_size: int = 768,
                                 sparse_enabled: bool = True, force_recreate: bool = False,
-                                sparse_modifier: Optional[str] = None):
+                                sparse_modifier: Optional[str] = None, binary_quantization: bool = False):
         """sparse_modifier (additive): None = the reference's collection (no IDF, :24-32), "idf" = Qdrant's
         SparseVectorParams(modifier=Modifier.IDF): every sparse query weight is multiplied by the collection's IDF of
-        its term at query time.  It is fixed at creation."""
+        its term at query time.  It is fixed at creation.
+        binary_quantization (additive): True = Qdrant's quantization_config=BinaryQuantization: the engine keeps one sign
+        bit per dimension beside the rows, a using="binary" node of query_points and search_binary rank by it (DESIGN.md
+        section 33).  It is fixed at creation and stored with the collection."""
         try:
             if not user_id:
                 raise ValueError("user_id cannot be empty")
             user_id = str(user_id)
             sparse_modifier = _check_modifier(sparse_modifier)
+            if not isinstance(binary_quantization, (bool, np.bool_)):
+                raise ValueError(f"binary_quantization must be True or False, got {binary_quantization!r}")
+            binary_quantization = bool(binary_quantization)
+            if binary_quantization and not self._binary_quantization:
+                raise ValueError("binary_quantization=True is not supported on a sharded collection: the shard command "
+                                 "protocol has no binary stage")
             if sparse_modifier and not self._sparse_modifiers:
                 raise ValueError("sparse_modifier='idf' is not supported on a sharded collection: the shard command "
                                  "protocol carries no collection statistics (sharded.ShardedCollection does)")
@@ -781,6 +798,10 @@ class QdrantHandler:
                 if have != sparse_modifier:
                     raise ValueError(f"collection {user_id} exists with sparse_modifier={have!r}: the modifier of a "
                                      "live collection cannot change (force_recreate=True makes a new one)")
+                have = bool(getattr(self._collections[user_id], "binary_quantization", False))
+                if have != binary_quantization:
+                    raise ValueError(f"collection {user_id} exists with binary_quantization={have!r}: the quantization of "
+                                     "a live collection cannot change (force_recreate=True makes a new one)")
                 logging.info("create_collection: %s is already there", user_id)
                 return
             if quantized_size != dense_vector_size:
@@ -799,6 +820,13 @@ class QdrantHandler:
                         self._drop(user_id, col)
                         raise ValueError(f"stored collection has sparse_modifier={have!r}")
                     col.sparse_modifier = sparse_modifier
+                have = bool(getattr(col, "binary_quantization", False))
+                if have != binary_quantization:
+                    if have or getattr(col, "ids", None):               # ... and so does its quantization
+                        self._drop(user_id, col)
+                        raise ValueError(f"stored collection has binary_quantization={have!r}")
+                    col.index.binary_enable()
+                    col.binary_quantization = True
                 self._collections[user_id] = col
             await self._run(make)
             logging.info("create_collection: new collection for %s", user_id)
@@ -1488,6 +1516,7 @@ class QdrantHandler:
         for req, how in zip(requests, hows):
             shape, vecs, thrs, flts = _query_tree.parse_nodes(req, col.dim, col.msizes, self._check_filter,
                                                               prefetch_filters=how == "node")
+            self._check_binary(col, shape)
             if how == "all":
                 shape = _query_tree.push_to_leaves(shape)
             filters.update(flts)
@@ -1514,6 +1543,7 @@ class QdrantHandler:
         parsed, roots = [], []
         for req in requests:
             shape, vecs = _query_tree.parse(req, col.dim, col.msizes)
+            self._check_binary(col, shape)
             get = req.get if isinstance(req, dict) else (lambda k, d=None, r=req: getattr(r, k, d))
             flt = get("filters") if get("filters") is not None else get("filter")
             thr = get("score_threshold")
@@ -1553,6 +1583,11 @@ class QdrantHandler:
                           for s, r in zip(scores[:limit].tolist(), rows[:limit].tolist())]
         return out
 
+    @staticmethod
+    def _check_binary(col, shape):
+        if _query_tree.uses_binary(shape) and not getattr(col, "binary_quantization", False):
+            raise ValueError("using='binary' needs a collection created with binary_quantization=True")
+
     async def query_points_batch(self, user_id: str, requests) -> List[List[ScoredPoint]]:
         """The reference's general call, client.query_points(prefetch=[...], query=..., using=..., limit=...), for many
         requests at once (additive).  A request is a dict (or an object with the same attributes):
@@ -1582,6 +1617,37 @@ class QdrantHandler:
                                                        "with_payload": with_payload,
                                                        **({} if filter_stages == "root" else
                                                           {"filter_stages": filter_stages})}])
+        return res[0] if res else []
+
+    # ------------------------------------------------------------------------ binary quantization
+    async def search_binary_batch(self, user_id: str, dense_vectors, limit: int = 10, oversampling: float = 4.0,
+                                  rescore: bool = True, filters: Optional[Dict] = None,
+                                  filter_stages: str = "root") -> List[List[ScoredPoint]]:
+        """Qdrant's search under quantization_config=BinaryQuantization with QuantizationSearchParams(oversampling,
+        rescore), for B query vectors (additive): the sign bits nominate min(ceil(limit *
+        oversampling), 2048) candidates per query with XOR and popcount, the exact vectors re-score them and the best
+        `limit` come back -- the tree query_tree.binary_request builds, run by query_points_batch.  rescore=False returns
+        the binary stage's own list at `limit`.  ScoredPoint.score is the cosine after a re-score and the integer score
+        dim - 2 * (differing sign bits) without one.  filters / filter_stages as query_points takes them ("root": the
+        re-scoring root's candidates are filtered before its cut, so rescore=False takes no filter there; "node" / "all":
+        on the device).  Raises ValueError for a collection created without binary_quantization, a limit outside
+        [1, 2048], an oversampling that is no finite number >= 1, and on a sharded collection; any other failure is
+        logged and gives [], as in every search."""
+        if filter_stages not in QUERY_FILTER_STAGES:
+            raise ValueError(f"filter_stages must be one of {QUERY_FILTER_STAGES}, got {filter_stages!r}")
+        try:
+            vectors = [v for v in dense_vectors]
+        except TypeError:
+            raise ValueError("dense_vectors: a list of query vectors") from None
+        reqs = [dict(_query_tree.binary_request(v, limit, oversampling, rescore, filters),
+                     **({} if filter_stages == "root" else {"filter_stages": filter_stages})) for v in vectors]
+        return await self.query_points_batch(user_id, reqs)
+
+    async def search_binary(self, user_id: str, dense_vector, limit: int = 10, oversampling: float = 4.0,
+                            rescore: bool = True, filters: Optional[Dict] = None,
+                            filter_stages: str = "root") -> List[ScoredPoint]:
+        """One query of search_binary_batch."""
+        res = await self.search_binary_batch(user_id, [dense_vector], limit, oversampling, rescore, filters, filter_stages)
         return res[0] if res else []
 
     # ------------------------------------------------------------------------ term statistics

@@ -4,8 +4,11 @@ vectors) and run for B queries of one shape at once over the engine's stage entr
 
 A request is a dict, or an object with attributes of the same names (qdrant_client's Prefetch / QueryRequest fit):
   nearest node  query = a dense vector, or a sparse one ({"indices", "values"} or .indices / .values); using = "dense",
-                "matryoshka_<d>", "quantized" or "sparse".  Without prefetch: a whole-collection search.  With prefetch:
-                the union of the children's lists re-scored by the named vector ("dense" and "matryoshka_<d>" only).
+                "matryoshka_<d>", "quantized", "sparse" or "binary".  Without prefetch: a whole-collection search.  With
+                prefetch: the union of the children's lists re-scored by the named vector ("dense" and "matryoshka_<d>"
+                only).  "binary"  takes a dense vector and ranks by the sign bits of a collection
+                created with binary_quantization=True: the leaf under a dense re-scoring node is Qdrant's
+                BinaryQuantization with oversampling and rescore (handler.search_binary builds exactly that).
   fusion node   query = {"fusion": "rrf" | "dbsf"} with optional "weights", "rrf_k", "rank_base"; 1 to 8 prefetches.
 A missing limit is 10, at the root too.  Everything else raises ValueError with the reason: nothing is answered with
 something else.
@@ -27,7 +30,7 @@ PREFETCH_DEFAULT_LIMIT = 10
 MAX_DEPTH = 8
 MAX_LIMIT = 2048                 # the largest list a stage keeps (hx.h)
 RESCORE_MAX = 8192               # the widest candidate list hx_rescore takes
-USINGS = ("dense", "quantized", "sparse")
+USINGS = ("dense", "quantized", "sparse", "binary")
 NODE_KEYS = ("prefetch", "query", "using", "limit", "filter", "score_threshold", "params", "lookup_from")
 # what Qdrant's query interface also offers and a tree here does not
 FOREIGN_QUERIES = ("order_by", "recommend", "discover", "context", "formula", "mmr", "sample")
@@ -182,7 +185,7 @@ def parse(node, dim: int, msizes: Sequence[int], _depth: int = 1, _root: bool = 
         if prefix not in tuple(msizes):
             raise ValueError(f"{where}: using={using!r}, but the collection's matryoshka sizes are {tuple(msizes)}")
     elif using not in USINGS:
-        raise ValueError(f"{where}: using must be 'dense', 'matryoshka_<d>', 'quantized' or 'sparse', got {using!r}")
+        raise ValueError(f"{where}: using must be 'dense', 'matryoshka_<d>', 'quantized', 'sparse' or 'binary', got {using!r}")
     if _is_sparse(q):
         if using != "sparse":
             raise ValueError(f"{where}: a sparse query needs using='sparse', got {using!r}")
@@ -193,7 +196,7 @@ def parse(node, dim: int, msizes: Sequence[int], _depth: int = 1, _root: bool = 
         if using == "sparse":
             raise ValueError(f"{where}: using='sparse' needs a sparse query ({{'indices', 'values'}})")
         vec = _dense(q, using, prefix, dim, where)
-    if pre and using in ("quantized", "sparse"):
+    if pre and using in ("quantized", "sparse", "binary"):
         raise ValueError(f"{where}: using={using!r} cannot re-score a prefetch (only 'dense' and 'matryoshka_<d>' can)")
     vecs.append(vec)
     children = tuple(parse(c, dim, msizes, _depth + 1, False, vecs, _notes)[0] for c in pre)
@@ -283,6 +286,36 @@ def push_to_leaves(shape):
     return ("keep", None, True, limit, (pushed,))
 
 
+def uses_binary(shape) -> bool:
+    """whether some leaf of the shape is a using="binary" one (the collection must keep the 1-bit copy)"""
+    if shape[0] == "nearest" and shape[1] == "binary":
+        return True
+    return any(uses_binary(c) for c in shape[-1])
+
+
+def binary_request(vector, limit=10, oversampling=4.0, rescore=True, filters=None):
+    """The request of handler.search_binary -- Qdrant's QuantizationSearchParams(oversampling, rescore) -- for one query
+    vector: a using="binary" leaf of min(ceil(limit * oversampling), 2048) hits under a dense re-scoring node of `limit`,
+    or with rescore=False the leaf alone at `limit`.  `filters` becomes the root's.  ValueError for a limit outside
+    [1, 2048] and for an oversampling that is no finite number >= 1."""
+    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= int(limit) <= MAX_LIMIT:
+        raise ValueError(f"search_binary: limit must be an integer in [1, {MAX_LIMIT}], got {limit!r}")
+    if isinstance(oversampling, bool) or not isinstance(oversampling, (int, float, np.integer, np.floating)):
+        raise ValueError(f"search_binary: oversampling must be a number, got {oversampling!r}")
+    if not np.isfinite(oversampling) or oversampling < 1:
+        raise ValueError(f"search_binary: oversampling must be finite and at least 1, got {oversampling!r}")
+    limit = int(limit)
+    leaf = {"using": "binary", "query": vector}
+    if rescore:
+        wide = min(int(np.ceil(limit * float(oversampling))), MAX_LIMIT)
+        req = {"using": "dense", "query": vector, "limit": limit, "prefetch": [dict(leaf, limit=max(wide, limit))]}
+    else:
+        req = dict(leaf, limit=limit)
+    if filters:
+        req["filters"] = filters
+    return req
+
+
 def shape_limit(shape) -> int:
     return shape[-2]
 
@@ -316,7 +349,8 @@ def batch_thresholds(threshold_lists: Sequence[Sequence[Any]]) -> List[np.ndarra
 
 def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None, thresholds: Sequence[Any] = ()):
     """Run one shape for the B queries whose vectors are `vectors` (batch_vectors).  `stages` offers the stage entries:
-    dense(Q, limit, prefix), i8(Q, limit), sparse(pairs, limit), rescore(Q, [(keys, counts)], limit, prefix) and
+    dense(Q, limit, prefix), i8(Q, limit), sparse(pairs, limit), bin(Q, limit) (only a shape with a using="binary" leaf
+    calls it), rescore(Q, [(keys, counts)], limit, prefix) and
     fuse([(keys, counts)], method, weights, limit, rrf_k, rank_base), each returning (keys [B, limit], counts [B]) in
     whatever array type it keeps lists in -- they stay where the stages put them between nodes.  root_limit overrides
     the root's limit (a filtered root runs at the width of its input).
@@ -342,6 +376,8 @@ def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None,
             return stages.sparse(q, limit, **mask)
         if using == "quantized":
             return stages.i8(q, limit, **mask)
+        if using == "binary":
+            return stages.bin(q, limit, **mask)
         return stages.dense(q, limit, prefix, **mask)
 
     def walk(s, limit=None, key=None, thr=None):
@@ -412,6 +448,9 @@ class DeviceStages:
 
     def i8(self, Q, limit, mask=None):
         return self.ix.search_i8(self._q(Q), limit, **self._kw(mask))
+
+    def bin(self, Q, limit, mask=None):
+        return self.ix.search_bin(self._q(Q), limit, **self._kw(mask))
 
     def keep(self, lists, mask, thresholds, limit):
         # several lists: side by side, every slot walked (a stage's slots past its count are 0, and hx_list_keep skips a 0)

@@ -512,6 +512,7 @@ class ShardedHandler(QdrantHandler):
     _query_tree = False              # query_points / query_points_batch raise ValueError: nothing is sent to the ranks
     _sparse_modifiers = False        # create_collection(sparse_modifier="idf") and term_stats raise ValueError: the command
                                      # protocol carries no collection statistics (ShardedCollection itself does)
+    _binary_quantization = False     # create_collection(binary_quantization=True) raises ValueError: no binary stage is sent
 
     def __init__(self, group=None, index_factory=None, ops=None, src: int = 0, dense_vector_size: int = 768,
                  matryoshka_sizes: Sequence[int] = (64, 128, 256), reranker=None, persist_dir: Optional[str] = None,
@@ -652,13 +653,15 @@ class ShardedHandler(QdrantHandler):
     async def create_collection(self, user_id: str, dense_vector_size: Optional[int] = None,
                                 matryoshka_sizes: Optional[list] = None, quantized_size: Optional[int] = None,
                                 sparse_enabled: bool = True, force_recreate: bool = False,
-                                sparse_modifier: Optional[str] = None):
+                                sparse_modifier: Optional[str] = None, binary_quantization: bool = False):
         """qdrant_handler.py:24-32, with the handler's own vector sizes as the defaults.  sparse_modifier="idf" is
-        refused (ValueError): the command protocol and the shard sidecars carry no collection statistics."""
+        refused (ValueError): the command protocol and the shard sidecars carry no collection statistics; so is
+        binary_quantization=True: the protocol has no binary stage."""
         d = self.dim if dense_vector_size is None else int(dense_vector_size)
         return await super().create_collection(
             user_id, d, list(self.msizes) if matryoshka_sizes is None else matryoshka_sizes,
-            d if quantized_size is None else quantized_size, sparse_enabled, force_recreate, sparse_modifier)
+            d if quantized_size is None else quantized_size, sparse_enabled, force_recreate, sparse_modifier,
+            binary_quantization)
 
     # ---- QdrantHandler's two hooks -------------------------------------------------------------------------------
     def _open_collection(self, user_id, dim, msizes, sparse_enabled, force_recreate) -> _Collection:
