@@ -162,7 +162,8 @@ void launch_bin_scan(const BinScanArgs& a, hipStream_t st) {
   const int64_t n_tiles = (a.row_end - a.row_begin + BIN_NT - 1) / BIN_NT;
   // what the rows give, at most the CUs times the workgroups one CU's 160 KB of LDS hold
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / (lds + 1024)));
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, 256 * per_cu));
+  int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, 256 * per_cu));
+  if (a.max_grid > 0) grid = std::min(grid, a.max_grid);     // tests: a workgroup walks several tiles at a few thousand rows
 #define HX_BIN(QG)                                                                                              \
   hipLaunchKernelGGL(k_bin_scan<QG>, dim3(grid), dim3(BIN_NT), lds, st, a, nslots, lstride, bin_magic(pass), \
                      bin_magic(last), n_tiles)
@@ -230,6 +231,7 @@ static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint
   a.ovf = flags;
   a.cap = C;
   a.id_base = (uint32_t)h->id_base;
+  a.max_grid = h->bin_grid;
   for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
     a.row_begin = r0;
     a.row_end = r1;

@@ -1791,6 +1791,7 @@ int hx_create(int32_t dim, const int32_t* msizes, int32_t n_msizes, int32_t devi
   if (const char* e = getenv("HX_DEBUG_DISCOVER_CAP")) h->discover_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
   if (const char* e = getenv("HX_DEBUG_BIN_CHUNK0")) h->bin_chunk0 = std::clamp(atoi(e), 0, CAND_CAP);   // tests: the binary scan's chunks
   if (const char* e = getenv("HX_DEBUG_BIN_CAP")) h->bin_cap = std::clamp(atoi(e), 0, CAND_CAP);         // ... and its overflow path
+  if (const char* e = getenv("HX_DEBUG_BIN_GRID")) h->bin_grid = std::clamp(atoi(e), 0, 1 << 20);         // ... and its grid-stride loop
   if (const char* e = getenv("HX_DEBUG_MATRIX_SCAN_ONLY")) h->matrix_scan_only = atoi(e) != 0;             // diagnostics: the matrix scan's own time
   if (const char* e = getenv("HX_DEBUG_SCAN8_LOGCAP")) {   // tests: force the log-overflow path
     const int v = atoi(e);

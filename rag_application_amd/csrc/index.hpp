@@ -249,6 +249,7 @@ struct hx_index {
   int discover_cap = 0;               // HX_DEBUG_DISCOVER_CAP (tests): keys of a request's candidate buffer there, 0 = by the limit
   int bin_chunk0 = 0;                 // HX_DEBUG_BIN_CHUNK0 (tests): rows of the first chunk of the binary scan, 0 = the buffer's capacity
   int bin_cap = 0;                    // HX_DEBUG_BIN_CAP (tests): keys of a query's candidate buffer there, 0 = by the limit
+  int bin_grid = 0;                   // HX_DEBUG_BIN_GRID (tests): the most workgroups of a binary scan launch, 0 = no cap
   int64_t discover_redone = 0;        // hx_discover_redone: requests that went through the overflow redo
   bool matrix_scan_only = false;      // HX_DEBUG_MATRIX_SCAN_ONLY (scripts/matrix_bench.py): hx_search_matrix stops behind k_matrix_scan, the outputs zeroed
   int pay_grid = 0;                   // HX_DEBUG_PAY_GRID (tests): caps the grid of the mask kernel, 0 = no cap

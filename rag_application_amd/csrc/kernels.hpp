@@ -855,6 +855,7 @@ struct BinScanArgs {
   int* ovf;
   int cap;
   uint32_t id_base;
+  int max_grid;            // HX_DEBUG_BIN_GRID (tests): at most this many workgroups, 0 = what the rows and the CUs give
 };
 void launch_bin_scan(const BinScanArgs& a, hipStream_t st);
 // tau_key[b] = cand[b * cap + limit - 1] when cnt[b] >= limit (lists sorted by launch_compact), else 0

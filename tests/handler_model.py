@@ -18,7 +18,11 @@ sequence(seed, n, profile) is reproducible and a prefix of every longer one.  Ev
 is set, and after the last op, the lived-in handler is compared bit for bit with a FRESH handler of the model's points.
 The fresh handler is filled by store_document_vectors / store_chat_vectors, one call per run of points of one kind, and
 then given the model's ids: upsert_points stores document payloads only (handler._document_payload), a chat message
-upserted would lose its timestamp."""
+upserted would lose its timestamp.
+
+The reads added behind the first version (`later_searches`: query trees, boost, discover, the distance matrix, the binary
+search, term statistics) run under capabilities of their own; the profiles `binary` and `idf` create their collection
+with binary_quantization / sparse_modifier (PROFILES[...]["collection"]), which the loaded and the fresh handler get too."""
 from __future__ import annotations
 
 import asyncio
@@ -30,10 +34,20 @@ import numpy as np
 
 from oracle import oracle as O
 from rag_application_amd import filters as F
+from rag_application_amd import boosting as BO
 from rag_application_amd import grouping as GR
+from rag_application_amd import payload_index as PI
+from rag_application_amd import query_tree as QTR
+from tests import binary_helpers as BH
+from tests import discover_helpers as DH
+from tests import formula_helpers as FH
+from tests import fusion_helpers as FU
 from tests import lifecycle_model as L
+from tests import matrix_helpers as XH
 from tests import maxsim_helpers as MH
+from tests import query_tree_helpers as QT
 from tests import reco_helpers as RH
+from tests import sparse_idf_helpers as SH
 from tests.mmr_helpers import mmr_select
 
 U = "u"
@@ -56,7 +70,21 @@ WORDS = ("vector", "Search", "engine", "KERNEL", "wavefront", "payload", "shard"
 PAGES = (0, 1, 1.0, 2, 2.5, 3)
 STORE_SIZES = (1, 3, 64, 257)
 STRATEGIES = ("average_vector", "best_score", "sum_scores")
-ALL_CAPS = frozenset({"facet", "scroll", "groups", "mmr", "rerank", "recommend", "oracle"})
+ALL_CAPS = frozenset({"facet", "scroll", "groups", "mmr", "rerank", "recommend", "oracle",
+                      "tree", "boost", "discover", "matrix", "binary", "idf"})
+# the reads added behind the first drivers: their tags in what `searches` returns
+LATER_TAGS = ("qtree", "boost", "discover", "matrix", "binary", "term_stats")
+KNOBS_BIN = {"HX_DEBUG_BIN_CHUNK0": "96", "HX_DEBUG_BIN_CAP": "64"}
+# one formula per searched step: a number column, a keyword-match condition, a datetime decay -- over SCHEMAS keys, so the
+# cells an upsert replaced are read (on the device where the keys are live, by boosting.evaluate elsewhere)
+FORMULAS = (
+    ("number", {"sum": ["$score", {"mult": [0.1, "page_number"]}]}, {"page_number": 0.5}),
+    ("condition", {"mult": ["$score", {"sum": [1, {"mult": [0.5, {"key": "document_id", "match": {
+        "any": ["doc000", "doc002", "doc005", "moved1"]}}]}]}]}, None),
+    ("decay", {"sum": ["$score", {"mult": [0.2, {"exp_decay": {"x": {"datetime_key": "timestamp"},
+                                                               "target": {"datetime": "2024-03-01T12:00:04Z"},
+                                                               "scale": 5}}]}]}, {"timestamp": "2024-03-01T12:00:00Z"}),
+)
 
 UPSERT_FORMS = ("known", "unknown_named", "none", "mixed", "moving")
 REFUSED_FORMS = ("duplicate_id", "dimension", "tokens_without_index", "nan_rollback")
@@ -66,7 +94,7 @@ INDEX_FORMS = ("create", "recreate", "drop", "poison", "cure")
 TOKEN_FORMS = ("create_empty", "create_filled", "again", "other_width")
 WEIGHTS = dict(store=0.15, upsert=0.19, upsert_refused=0.09, delete=0.20, index=0.22, token_index=0.07, save_load=0.08)
 
-_common = dict(dim=128, start=(300, 700), max_rows=1200, n_ops=24, env={}, weight={}, index=True, setup=())
+_common = dict(dim=128, start=(300, 700), max_rows=1200, n_ops=24, env={}, weight={}, index=True, setup=(), collection={})
 PROFILES = {
     "small": dict(_common, seeds=(1, 2, 30, 36)),
     "padded": dict(_common, dim=100, seeds=(24,)),
@@ -75,7 +103,13 @@ PROFILES = {
     # the token, list and text columns exist from the start and deletes come often: cells cross the 64-row seams
     "chunked": dict(_common, seeds=(4, 7), env={"HX_DEBUG_COMPACT_CHUNK": "64"}, weight=dict(delete=2.0),
                     setup=("languages", "content")),
+    # the 1-bit copy: every load must enable it again; the Hamming scan in several chunks with the overflow redo
+    "binary": dict(_common, seeds=(22, 26), env=KNOBS_BIN, weight=dict(save_load=4.0), collection=dict(binary_quantization=True)),
+    # the IDF modifier: every sparse query is weighed by the statistics of the rows as they are now
+    "idf": dict(_common, seeds=(3, 19), weight=dict(delete=2.0), collection=dict(sparse_modifier="idf")),
 }
+# a profile's number in the generator's seed: fixed, so that a new profile leaves the others' sequences alone
+PROFILE_IDS = dict(bare=0, chunked=1, padded=2, persist=3, small=4, binary=5, idf=6)
 CASES = [(seed, name) for name, p in PROFILES.items() for seed in p["seeds"]]
 
 
@@ -566,7 +600,7 @@ def sequence(seed, n_ops, profile, pool, with_states=False):
     """the first n_ops ops of the (seed, profile) sequence -- a prefix of every longer one.  with_states: also what the
     coverage table needs about the model in front of every op"""
     p = PROFILES[profile]
-    rng = np.random.default_rng([seed, sorted(PROFILES).index(profile), 77])
+    rng = np.random.default_rng([seed, PROFILE_IDS[profile], 77])
     m = Model(profile, pool)
     ops, states = [], []
     n0 = int(rng.integers(*p["start"]))
@@ -610,8 +644,9 @@ def col_of(h):
     return h._collections[U]
 
 
-def open_collection(h, dim):
-    run(h.create_collection(U, dense_vector_size=dim, matryoshka_sizes=[64], quantized_size=dim))
+def open_collection(h, dim, **collection):
+    """collection: the profile's create_collection arguments (binary_quantization, sparse_modifier)"""
+    run(h.create_collection(U, dense_vector_size=dim, matryoshka_sizes=[64], quantized_size=dim, **collection))
 
 
 def close(h):
@@ -701,7 +736,7 @@ def apply(h, model, op):
         close(h)
         h = model.make_handler(model.tmp)
         model.opened.append(h)
-        open_collection(h, pool.dim)
+        open_collection(h, pool.dim, **model.p["collection"])
     model.apply(op, new_ids)
     if k == "index" and op["form"] in ("create", "recreate"):
         assert got is model.live(key), ("create_payload_index returned", got, model.live(key))
@@ -755,6 +790,15 @@ def check(h, model, caps, seed=0):
     assert (pi.definitions() if pi is not None else {}) == {k: ("number" if s == "integer" else s) for k, s in model.defs.items()}
     for key in SCHEMAS:
         assert (pi is not None and pi.live(key)) == model.live(key), ("live", key, model.live(key))
+    # ---- what the collection was created with: a load must bring the 1-bit copy back ----
+    binq = bool(model.p["collection"].get("binary_quantization", False))
+    assert bool(getattr(col, "binary_quantization", False)) == binq, "the collection's binary_quantization flag"
+    assert col.index.binary_enabled() == binq, ("the index keeps a binary copy", col.index.binary_enabled(), binq)
+    assert getattr(col, "sparse_modifier", None) == model.p["collection"].get("sparse_modifier"), "the collection's modifier"
+    if model.p["collection"].get("sparse_modifier"):
+        got = run(h.term_stats(U, [0]))["n_docs"]
+        want = sum(1 for p in pts if model.pool.lens[p["spec"][0]] > 0)
+        assert got == want, ("term_stats n_docs", got, want)
     keeps = {}
     # ---- counts: every filter of the set, the mask cache in front of it ----
     for f in FILTERS:
@@ -867,7 +911,7 @@ def fresh_handler(model):
     not upsert_points): whatever per-id state _Collection keeps -- today _idrows and _masks -- is reset here by hand."""
     h = model.make_handler(None)
     model.opened.append(h)
-    open_collection(h, model.pool.dim)
+    open_collection(h, model.pool.dim, **model.p["collection"])
     for key in model.defs:
         run(h.create_payload_index(U, key, SCHEMAS[key]))
     if model.tdim:
@@ -964,7 +1008,138 @@ def searches(h, model, step, caps, Q, sparse, qtok):
             res = run(h.recommend_batch(U, reqs, limit=10, filters=flt))
             assert len(res) == len(reqs), ("recommend", strategy, name, "the search failed")
             out[("recommend", strategy, name)] = flat(res)
+    later_searches(h, model, step, caps, Q, sparse, out, (fa, ra), (fb, rb))
     return out
+
+
+def tree_sources(Q, sparse, b):
+    """random_tree's vector sources for query b: the batch's dense vectors in turn, and the four sparse kinds"""
+    count = [0]
+
+    def dense(width):
+        count[0] += 1
+        return Q[(b + count[0]) % B][:width].tolist()
+
+    order = np.argsort(sparse[b]["indices"], kind="stable")       # (a tree's sparse leaf wants its ids ascending)
+    own = {"indices": [sparse[b]["indices"][i] for i in order], "values": [sparse[b]["values"][i] for i in order]}
+    idx = own["indices"]
+    kinds = [own, {"indices": idx[:1], "values": [1.5]}, {"indices": list(QT.ABSENT_TERMS), "values": [1.0, 2.0]},
+             {"indices": idx[:3], "values": [1.0, -0.5, 0.75][:len(idx[:3])]}]
+    return dense, (lambda kind: kinds[(kind + b) % len(kinds)])
+
+
+def tree_requests(model, seed, step, Q, sparse):
+    """[(name, [the request of query b])]: the hand trees and two random trees drawn for (seed, step)"""
+    dim = model.pool.dim
+    out = [(name, [QT.hand_trees(dim, L.MS, *tree_sources(Q, sparse, b))[name] for b in range(B)])
+           for name in QT.hand_trees(dim, L.MS, *tree_sources(Q, sparse, 0))]
+    for k in (0, 1):
+        out.append((f"random {k}", [QT.random_tree(np.random.default_rng([seed, step, k]), dim, L.MS,
+                                                   *tree_sources(Q, sparse, b)) for b in range(B)]))
+    return out
+
+
+def tree_cases(model, step, Q, sparse, binq, a, b):
+    """[(tag, the B requests of one shape, filter_stages)]: the hand trees and two random ones (with a using="binary" leaf
+    among them where the collection has the copy) unfiltered; then one tree with a filter on a prefetch node and a score
+    threshold at the root under "node", and with the root's filter pushed into every leaf under "all" (the last two)"""
+    (fa, ra), (fb, rb) = a, b
+    q = Q.tolist()
+    named = tree_requests(model, model.seed, step, Q, sparse)
+    if binq:
+        named.append(("a binary leaf", [{"using": "dense", "query": q[i], "limit": 10, "prefetch": [
+            {"using": "binary", "query": q[i], "limit": 64},
+            {"using": "sparse", "query": tree_sources(Q, sparse, i)[1](-i), "limit": 20}]} for i in range(B)]))
+    out = [(("qtree", name), [dict(r, with_payload=False) for r in reqs], "root") for name, reqs in named]
+    deep3 = dict(named)["a re-score under a fusion under a re-score"]
+    node = [dict(r, prefetch=[dict(r["prefetch"][0]), dict(r["prefetch"][1]), dict(r["prefetch"][2], filter=ra)],
+                 filters=rb, score_threshold=0.0, filter_stages="node", with_payload=False) for r in deep3]
+    out.append((("qtree", "node", fa["name"], fb["name"]), node, "node"))
+    out.append((("qtree", "all", fa["name"]), [dict(r, filters=ra, filter_stages="all", with_payload=False) for r in deep3],
+                "all"))
+    return out
+
+
+def matrix_ids(model, Q):
+    """the points search_matrix_pairs is asked for by id: the discover target and rows at the seams, each once"""
+    ids, n = model.ids(), model.n
+    return list(dict.fromkeys([disco_requests(model, Q)[0]["target"], ids[0], ids[-1], ids[n // 2], ids[n // 3]]))
+
+
+def disco_requests(model, Q):
+    """as reco_requests: target and context pairs by stored ids (one an upsert replaced, one it appended, a middle one)
+    and by vector; the last is a context search"""
+    have, ids = set(model.ids()), model.ids()
+    a = model.replaced_id if model.replaced_id in have else ids[0]
+    b = model.appended_id if model.appended_id in have else ids[-1]
+    c = ids[len(ids) // 2]
+    v = (Q[0] * 3).tolist()
+    return [{"target": a, "context": [{"positive": b, "negative": c}]},
+            {"target": v, "context": [{"positive": a, "negative": Q[1].tolist()}, {"positive": Q[2].tolist(), "negative": b}]},
+            {"target": None, "context": [{"positive": b, "negative": c}, {"positive": v, "negative": a}]}]
+
+
+def later_searches(h, model, step, caps, Q, sparse, out, a, b):
+    """the reads added behind the first drivers (query trees with node filters, boost, discover, the distance matrix,
+    the binary search, term statistics), each under its capability; a, b: the step's two filters, (entry, resolved)"""
+    n, q = model.n, Q.tolist()
+    (fa, ra), (fb, rb) = a, b
+    binq = "binary" in caps and model.p["collection"].get("binary_quantization")
+    if "tree" in caps and n:
+        cases = tree_cases(model, step, Q, sparse, binq, a, b)
+        root = [c for c in cases if c[2] == "root"]          # every unfiltered tree in ONE call, grouped by shape inside
+        res = run(h.query_points_batch(U, [r for _, reqs, _ in root for r in reqs]))
+        assert len(res) == B * len(root), ("query_points_batch", "the search failed")
+        for k, (tag, _, _) in enumerate(root):
+            out[tag] = flat(res[k * B:(k + 1) * B])
+        for tag, reqs, how in cases[len(root):]:
+            res = run(h.query_points_batch(U, reqs))
+            assert len(res) == B, ("query_points_batch", tag, "the search failed")
+            out[tag] = flat(res)
+    if "boost" in caps and n:
+        name, formula, defaults = FORMULAS[step % len(FORMULAS)]
+        for mode in ("tree", "h1"):
+            for flt, fname in ((None, None), (rb, fb["name"])):
+                res = run(h.hybrid_search_boost(U, q, sparse, formula, defaults=defaults, limit=10, candidates_limit=None,
+                                                search_params=P, filters=flt, mode=mode,
+                                                filter_stages="all" if flt else "root"))
+                assert len(res) == B, ("boost", mode, name, fname, "the search failed")
+                out[("boost", mode, name, fname)] = [[(p.id, bits(p.score), bits(p.base_score)) for p in r] for r in res]
+    if "discover" in caps and n >= 3:
+        for flt, fname in ((None, None), (rb, fb["name"])):
+            reqs = disco_requests(model, Q)
+            res = run(h.discover_batch(U, reqs, limit=10, filters=flt))
+            assert len(res) == len(reqs), ("discover", fname, "the search failed")
+            out[("discover", fname)] = flat(res)
+    if "matrix" in caps and n >= 3:
+        ids = model.ids()
+        for flt, fname in ((None, None), (ra, fa["name"])):
+            pairs = run(h.search_matrix_pairs(U, sample=12, limit=3, filters=flt, seed=5))
+            off = run(h.search_matrix_offsets(U, sample=12, limit=3, filters=flt, seed=5))
+            assert flt is not None or (len(pairs) == 36 and len(off.ids) == 12) or n < 12, ("matrix", len(pairs), len(off.ids))
+            out[("matrix", "pairs", fname)] = [[(p.a, p.b, bits(p.score)) for p in pairs]]
+            out[("matrix", "offsets", fname)] = [[(list(off.offsets_row), list(off.offsets_col),
+                                                   [bits(x) for x in off.scores], list(off.ids))]]
+        named_ids = matrix_ids(model, Q)
+        pairs = run(h.search_matrix_pairs(U, limit=2, point_ids=named_ids))
+        assert len(pairs) == 2 * len(named_ids) or len(named_ids) < 3, ("matrix by point ids", len(pairs), len(named_ids))
+        out[("matrix", "point_ids")] = [[(p.a, p.b, bits(p.score)) for p in pairs]]
+    if binq and n:
+        for rescore in (True, False):
+            for flt, fname, stages in ((None, None, "root"), (ra, fa["name"], "all")):
+                res = run(h.search_binary_batch(U, q, limit=10, oversampling=4.0, rescore=rescore, filters=flt,
+                                                filter_stages=stages))
+                assert len(res) == B, ("search_binary_batch", rescore, fname, "the search failed")
+                out[("binary", rescore, fname)] = flat(res)
+    if "idf" in caps:
+        terms = stat_terms(sparse)
+        ts = run(h.term_stats(U, terms))
+        out[("term_stats",)] = [[(ts["n_docs"], tuple(ts["df"]))]]
+
+
+def stat_terms(sparse):
+    """the first query's terms, those of a stored row's own vector, and ids nobody holds"""
+    return [int(t) for t in sparse[0]["indices"][:12] + sparse[2]["indices"][:12]] + [1, 3, 2 ** 31 - 1]
 
 
 def reco_requests(model, Q, strategy):
@@ -986,6 +1161,8 @@ def expected_lengths(model, step, got):
     that cannot answer (no document_id, no tokens, not kept by a root filter) out of those 40."""
     n, floor = model.n, P["dense_limit"]
     for tag, lists in got.items():
+        if tag[0] in LATER_TAGS:
+            continue
         flt = tag[-1] if tag[0] in ("groups", "mmr", "rerank", "recommend") else (tag[2] if len(tag) == 3 else None)
         keep = model.keeps(BY[flt]["flt"]) if flt else [True] * n
         kept = sum(keep)
@@ -1031,7 +1208,7 @@ def expected_lengths(model, step, got):
                 assert lo <= len(lst) <= hi, what + (lo, hi)
 
 
-def deep(h, model, got, Q, sparse, qtok, caps):
+def deep(h, model, got, Q, sparse, qtok, caps, step=0):
     """the first and the last step: query 0 against the numpy oracle, the four pool stages against their host models
     over what hybrid_search_batch returns at final_limit = the pool"""
     pool, n = model.pool, model.n
@@ -1041,6 +1218,16 @@ def deep(h, model, got, Q, sparse, qtok, caps):
     row = {p["id"]: r for r, p in enumerate(model.pts)}
     ora = pool.oracle(src)
     qa, qb = np.asarray(sparse[0]["indices"], np.int64), np.asarray(sparse[0]["values"], F32)
+    csr = pool.csr(src)
+    if model.p["collection"].get("sparse_modifier") == "idf":   # the oracle is fed the weights the helper scales
+        qb = SH.weights(qb, *SH.stats(csr[0], csr[1], qa))
+    if ("term_stats",) in got:
+        terms = stat_terms(sparse)
+        df, n_docs = SH.stats(csr[0], csr[1], terms)
+        assert got[("term_stats",)] == [[(n_docs, tuple(df))]], "term_stats vs the rows of the model's points"
+    if ("binary", False, None) in got:
+        deep_binary(model, got, Q, src)
+    deep_later(h, model, got, step, Q, sparse, caps, src, ora, csr)
     for mode in ("tree", "h1"):
         if mode == "tree":
             os_, oi = O.hybrid_tree(ora, Q[0], qa, qb, P)
@@ -1094,6 +1281,163 @@ def deep(h, model, got, Q, sparse, qtok, caps):
                     (tag, "recommend vs the host model")
 
 
+def deep_binary(model, got, Q, src):
+    """search_binary_batch against tests/binary_helpers.py over the model's points: rescore=False is the stage's own list
+    (integer scores), unfiltered and under the filter; rescore=True the best 10 by the exact cosine of the 40 the stage
+    nominates (limit x oversampling), under filter_stages="all" of the 40 kept rows it nominates"""
+    pool = model.pool
+    xb = BH.row_bits(pool.X[src])
+    row_of = lambda keys: [int(0xFFFFFFFF - (int(k) & 0xFFFFFFFF)) for k in keys]
+    for tag, lists in got.items():
+        if tag[0] != "binary":
+            continue
+        keep = None if tag[2] is None else np.asarray(model.keeps(BY[tag[2]]["flt"]), bool)
+        if tag[1] is False:
+            keys, cnt = BH.search(xb, Q, 10, keep)
+            for b, lst in enumerate(lists):
+                want = [(model.pts[r]["id"], int(k) >> 32) for r, k in zip(row_of(keys[b, :cnt[b]]), keys[b, :cnt[b]])]
+                assert [(i, (~u & 0xFFFFFFFF) if u & 0x80000000 else u | 0x80000000) for i, u in lst] == want, \
+                    (tag, b, "search_binary vs the Hamming model")
+        else:
+            keys, cnt = BH.search(xb, Q, 40, keep)
+            for b, lst in enumerate(lists):
+                rows = np.array(row_of(keys[b, :cnt[b]]), np.int64)
+                rel = O.spec_dot(pool.Xn[src[rows]], O.cosine_preprocess(Q[b]))
+                order = np.lexsort((rows, -rel.astype(np.float64)))[:10]
+                assert lst == [(model.pts[int(rows[i])]["id"], bits(rel[i])) for i in order], \
+                    (tag, b, "search_binary, re-scored, vs the model")
+
+
+def un_key(u):
+    """a list's float32 score bits -> the upper half of the engine's 64-bit key"""
+    return (~u & 0xFFFFFFFF) if u & 0x80000000 else u | 0x80000000
+
+
+class ModelStages(BH.BinaryOracleStages):
+    """the oracle's stage set over the model's points (masks, keep and bin included); on a collection with the IDF
+    modifier a sparse leaf's weights are scaled by sparse_idf_helpers.weights over the model's rows first"""
+
+    def __init__(self, rows, dim, masks, ix, idf):
+        super().__init__(rows, dim, L.MS, masks, fuse=FU, ix=ix)
+        self.csr, self.idf = (rows[1], rows[2]), idf
+
+    def sparse(self, pairs, limit, mask=None):
+        if self.idf:
+            pairs = [(i, SH.weights(v, *L.counted_stats(*self.csr, i))) for i, v in pairs]
+        return super().sparse(pairs, limit, mask) if mask is not None else super().sparse(pairs, limit)
+
+
+def deep_trees(h, model, got, step, Q, sparse, caps, src, ora, csr):
+    """query_points_batch against query_tree.run over the oracle's stages (tests/query_tree_helpers.py and its filtered and
+    binary extensions, fusion by tests/fusion_helpers.py) over the model's points: every node's list of the device stages
+    against the oracle's, the Recorder naming the first node that differs, then the handler's lists against the root's"""
+    from rag_application_amd import engine
+    pool, col, dim = model.pool, col_of(h), model.pool.dim
+    fa, fb = FILTERS[step % len(FILTERS)], FILTERS[(step + 5) % len(FILTERS)]
+    binq = "binary" in caps and model.p["collection"].get("binary_quantization")
+    cases = tree_cases(model, step, Q, sparse, binq, (fa, model.resolve(fa["flt"])), (fb, model.resolve(fb["flt"])))
+    parsed, flts = {}, {}
+    for tag, reqs, how in cases:
+        parsed[tag] = [QTR.parse_nodes({k: v for k, v in r.items() if k != "filter_stages"}, dim, L.MS,
+                                       prefetch_filters=how == "node") for r in reqs]
+        for p in parsed[tag]:
+            flts.update(p[3])
+    ids = model.ids()
+    masks = {key: np.array([F.matches(p["payload"], flt, p["id"]) for p in model.pts], bool) for key, flt in flts.items()}
+    modifier = model.p["collection"].get("sparse_modifier")
+    stages = ModelStages((pool.X[src], csr[0], csr[1].astype(np.int64), csr[2]), dim, masks, ora, modifier == "idf")
+    for tag, reqs, how in cases:
+        shapes = {QTR.push_to_leaves(p[0]) if how == "all" else p[0] for p in parsed[tag]}
+        assert len(shapes) == 1, (tag, "the requests of one tree differ in shape")
+        shape = shapes.pop()
+        vectors = QTR.batch_vectors([p[1] for p in parsed[tag]])
+        thresholds = QTR.batch_thresholds([p[2] for p in parsed[tag]])
+        dev = BH.BinaryRecorder(QTR.DeviceStages(col.index, engine, sparse_modifier=modifier,
+                                                 masks=lambda key: col.row_mask(flts[key])), to_host=QTR.DeviceStages.to_host)
+        host = BH.BinaryRecorder(stages)
+        QTR.run(shape, vectors, dev, thresholds=thresholds)
+        keys, cnt = QTR.run(shape, vectors, host, thresholds=thresholds)
+        QT.assert_same_nodes(dev.nodes, host.nodes, str(tag))
+        want = [[(ids[FU.key_id(int(x))], bits(FU.key_score(int(x)))) for x in keys[b, :int(cnt[b])]] for b in range(B)]
+        assert got[tag] == want, (tag, "query_points_batch vs the oracle's root list")
+
+
+def boost_model(model, formula, defaults, pools, limit):
+    """hybrid_search_boost over `pools` (per query the ScoredPoints of hybrid_search_batch at final_limit = the pool):
+    formula_helpers.formula_stage with the columns a payload index of the MODEL's payloads encodes and the planes of
+    filters.matches; where a stored value breaks a schema (a poisoned page_number) no column exists and the values come
+    from boosting.evaluate, ranked as hx.h states (value descending, pool order on a tie)"""
+    pays, ids = [p["payload"] for p in model.pts], model.ids()
+    row = {i: r for r, i in enumerate(ids)}
+    defaults = defaults or {}
+    pidx, cols = PI.PayloadIndex(), {}
+    for c, key in enumerate(("page_number", "timestamp", "document_id")):
+        pidx.keys[key] = PI._Key(PI.schema_of(SCHEMAS[key]))
+        cols[key] = pidx.encode(key, pays)
+        pidx.keys[key].col = c if cols[key] is not None else None
+    prog = BO.compile(formula, defaults, pidx, lambda: row)
+    out = []
+    for pts in pools:
+        if prog is not None:
+            ops, conds = prog
+            planes = [np.array([F.matches(p, c, i) for p, i in zip(pays, ids)], bool) for c in conds]
+            columns = {pidx.keys[k].col: cols[k] for k in ("page_number", "timestamp") if cols[k] is not None}
+            keys = FH.make_keys(np.array([p.score for p in pts], F32), [row[p.id] for p in pts])[None, :]
+            ok, pos, cnt, _ = FH.formula_stage(ops, planes, keys, None, None, None, limit, columns, len(ids))
+            out.append([(ids[int(FH.key_ids(ok[0, t:t + 1])[0])], bits(FH.key_scores(ok[0, t:t + 1])[0]),
+                         bits(pts[pos[0, t]].score)) for t in range(cnt[0])])
+        else:
+            values = [BO.value_f32(BO.evaluate(formula, defaults, p.score, pays[row[p.id]], p.id)) for p in pts]
+            hits, _ = BO.rank(values, limit)
+            out.append([(pts[i].id, bits(values[i]), bits(pts[i].score)) for i in hits])
+    return out
+
+
+def deep_later(h, model, got, step, Q, sparse, caps, src, ora, csr):
+    """the reads of `later_searches` against their host models over the model's points"""
+    pool = model.pool
+    Xn, ids = pool.Xn[src], model.ids()
+    row = {i: r for r, i in enumerate(ids)}
+    kept = lambda name: None if name is None else np.asarray(model.keeps(BY[name]["flt"]), bool)
+    if "tree" in caps:
+        deep_trees(h, model, got, step, Q, sparse, caps, src, ora, csr)
+    for tag, lists in got.items():
+        if tag[0] == "boost":
+            _, mode, name, fname = tag
+            _, formula, defaults = next(f for f in FORMULAS if f[0] == name)
+            flt = model.resolve(BY[fname]["flt"]) if fname else None
+            pools = run(h.hybrid_search_batch(U, Q.tolist(), sparse, top_k=POOL[mode], mode=mode, filters=flt,
+                                              search_params=dict(P, final_limit=POOL[mode]),
+                                              filter_stages="all" if flt else "root"))
+            assert len(pools) == B
+            assert lists == boost_model(model, formula, defaults, pools, 10), (tag, "boost vs formula_stage over the pool")
+        elif tag[0] == "discover":
+            keep = kept(tag[1])
+            ex = lambda e: row[e] if isinstance(e, str) else np.asarray(e, F32)
+            for req, lst in zip(disco_requests(model, Q), lists):
+                request = (None if req["target"] is None else ex(req["target"]),
+                           [(ex(p["positive"]), ex(p["negative"])) for p in req["context"]])
+                keys, cnt = DH.request_model(Xn, request, 10, keep)
+                want = [(ids[int(0xFFFFFFFF - (int(k) & 0xFFFFFFFF))], int(k) >> 32) for k in keys[:cnt]]
+                assert [(i, un_key(u)) for i, u in lst] == want, (tag, "discover vs the host model")
+        elif tag[0] == "matrix" and tag[1] != "offsets":
+            if tag[1] == "pairs":
+                keep, limit = kept(tag[2]), 3
+                sample = got[("matrix", "offsets", tag[2])][0][0][3]        # the sample the call returned
+                n_kept = model.n if keep is None else int(keep.sum())
+                assert len(sample) == (min(12, n_kept) if n_kept >= 2 else 0), (tag, "sample size", len(sample), n_kept)
+            else:
+                keep, limit, sample = None, 2, matrix_ids(model, Q)
+            assert len(set(sample)) == len(sample) and all(i in row and (keep is None or keep[row[i]]) for i in sample), \
+                (tag, "a sampled id is not stored, or not kept by the filter")
+            keys, counts = XH.model(Xn, [row[i] for i in sample], limit)
+            id_of = dict(enumerate(ids))
+            assert lists == [XH.shape_pairs(sample, keys, counts, id_of)], (tag, "matrix pairs vs the host model")
+            if tag[1] == "pairs":
+                r_, c_, s_, i_ = XH.shape_offsets(sample, keys, counts, id_of)
+                assert got[("matrix", "offsets", tag[2])] == [[(r_, c_, s_, i_)]], (tag, "matrix offsets vs the host model")
+
+
 def compare(h, model, step, caps, with_deep):
     """the lived-in handler against a fresh one, bit for bit: ids, float32 score bits, list lengths"""
     Q, sparse = own_queries(model)
@@ -1117,7 +1461,7 @@ def compare(h, model, step, caps, with_deep):
     for tag in got:
         assert got[tag] == want[tag], (tag, "differs from the fresh handler's")
     if with_deep:
-        deep(h, model, got, Q, sparse, qtok, caps)
+        deep(h, model, got, Q, sparse, qtok, caps, step)
 
 
 def run_case(make_handler, seed, profile, tables, tmp, caps=ALL_CAPS | {"counters"}, n_ops=None):
@@ -1129,14 +1473,14 @@ def run_case(make_handler, seed, profile, tables, tmp, caps=ALL_CAPS | {"counter
     ops = sequence(seed, p["n_ops"] if n_ops is None else n_ops, profile, pool)
     model = Model(profile, pool)
     model.make_handler, model.tmp, model.opened = make_handler, str(tmp), []
-    model.qs = L.queries(p["dim"], tables)
+    model.qs, model.seed = L.queries(p["dim"], tables), seed
     g = np.random.default_rng(77)
     model.qtok = [g.standard_normal((t, 40 if t == 16 else TDIM)).astype(F32) for t in TQ]
     h = make_handler(str(tmp))
     model.opened.append(h)
     log = []
     try:
-        open_collection(h, p["dim"])
+        open_collection(h, p["dim"], **p["collection"])
         for step, op in enumerate(ops):
             log.append(brief(op))
             try:

@@ -207,6 +207,37 @@ def test_a_row_wider_than_one_staging_pass(eng):
         ix.close()
 
 
+@pytest.mark.parametrize("knobs", [None, KNOBS], ids=["default", "small-chunks"])
+@pytest.mark.parametrize("dim", [64, 768, 2048])
+def test_a_workgroup_walks_several_tiles(eng, dim, knobs):
+    """HX_DEBUG_BIN_GRID=3 over 2561 rows = 11 tiles, the last of one row: k_bin_scan's grid-stride loop, which the launch's
+    own grid (one workgroup per tile up to 256 per CU share) never takes below 65 000 rows.  At limit 2048 the first chunk
+    holds every row: workgroup w walks tiles w, w + 3, ...; at the small limits the chunks are shorter launches (8 + 3 tiles
+    by default, unaligned ones under the small-chunk knobs).  dim 64: one slot, one pass; 768: six slots; 2048: two passes,
+    the tile staged again per group (B 9 = two groups).  The masks keep rows of tiles 1, 4 and 10 (workgroups 0 and 2 skip
+    every tile, workgroup 1 skips its third between kept ones), of tiles 3, 5 and 9 (workgroups 0 and 2 skip their FIRST
+    tile and take later ones behind it) and one single row: a skipped tile leaves the LDS tile and s_q of the tile before."""
+    n = 2561
+    X, Q = rows_of(n, dim, 90 + dim), rows_of(9, dim, 91)
+    xb = BH.row_bits(X)
+    rng = np.random.default_rng(92)
+    tile = np.arange(n) // 256
+    masks = {"unmasked": None,
+             "tiles 1, 4, 10": np.isin(tile, (1, 4, 10)) & ((rng.random(n) < 0.5) | (tile == 10)),
+             "tiles 3, 5, 9": np.isin(tile, (3, 5, 9)) & (rng.random(n) < 0.5),
+             "one row": np.arange(n) == 1300}
+    assert masks["tiles 1, 4, 10"][n - 1] and n - 1 == 10 * 256
+    ix = make_index(eng, X, env=dict(knobs or {}, HX_DEBUG_BIN_GRID="3"))
+    try:
+        for what, mask in masks.items():
+            want = BH.search(xb, Q, 2048, mask)
+            for B in (1, 9):
+                for limit in (10, 300, 2048):
+                    BH.assert_same_lists(run(ix, Q[:B], limit, mask), BH.cut(want, B, limit), f"{what}: B {B} limit {limit}")
+    finally:
+        ix.close()
+
+
 def test_a_corpus_ordered_worst_first_goes_through_the_redo(eng):
     """Row i agrees with the query in i * 65 // n columns: every chunk beats the threshold of the rows before it, the small
     buffer overflows, and the query is scanned again in fixed chunks -- the same list."""

@@ -9,13 +9,24 @@ cached masks are), chained scrolls in row and payload order, facets, retrieve, t
 live flag of every key -- and WHICH PATH ran: the device counters advance by exactly one per read on a live key, the
 Python counters on a dead one, "engine refused" never.  Where the op's `search` flag is set the lists of every searching
 call are compared bit for bit with a fresh handler of the model's points; on the first and last such step also with the
-numpy oracle and the host models of the four pool stages.  tests/test_handler_model_host.py asserts what the committed
+numpy oracle and the host models of the four pool stages.  The searching calls include the later entries: query_points_batch
+(the hand trees and two random trees per step, node filters with a score threshold, the filter in every leaf),
+hybrid_search_boost (a number column, a keyword condition, a datetime decay in turn), discover_batch, search_matrix_pairs /
+_offsets (sampled, filtered, by point ids), term_stats, and on the `binary` profile search_binary_batch and a
+using="binary" leaf; on the deep steps each also against its host model over the model's points: the trees node by node
+against query_tree.run over the oracle's stages (masks, keep and bin included), boost against formula_helpers.formula_stage
+over the pool, discover against discover_helpers.request_model, the matrix calls against matrix_helpers.model over the
+sample they returned, search_binary_batch against tests/binary_helpers.py, term_stats against tests/sparse_idf_helpers.py,
+and on the `idf` profile the oracle is fed the helper's scaled weights.  After every op the
+index's binary_enabled() equals the collection's flag (a load must enable the copy again) and on the `idf` profile
+term_stats' n_docs the model's count.  tests/test_handler_model_host.py asserts what the committed
 sequences cover.  A failure names the seed, the step and the ops so far; handler_model.sequence(seed, step + 1, profile,
 pool) replays it.
 
-Wall time per case on an MI355X (24 ops each), measured: 32-bare 4.6 s, 30-small 3.8 s, 32-persist 3.1 s, 24-padded
-3.1 s, 36-small 2.8 s, 7-chunked 2.7 s, 4-chunked 2.5 s, 1-small 2.3 s, 7-persist 2.2 s, 2-small 2.0 s; the ten
-together 29 s."""
+Wall time per case on an MI355X (24 ops each), measured with the later reads and their deep models: 3-idf 9.2 s,
+30-small 7.7 s, 22-binary 7.3 s, 19-idf 7.2 s, 32-bare 7.2 s, 36-small 6.7 s, 26-binary 6.6 s, 24-padded 6.0 s, 1-small
+6.0 s, 7-chunked 5.7 s, 32-persist 5.5 s, 4-chunked 5.5 s, 7-persist 4.9 s, 2-small 4.1 s; the fourteen together 91 s
+(before the later reads the first ten took 2.0-4.6 s, 29 s together)."""
 import pytest
 
 from tests import handler_model as H

@@ -6,8 +6,13 @@ random order on one HxIndex; after EVERY op `check` compares count, nnz and n_se
 every stored copy and the cells of every payload column of sampled rows with a fresh index of the model's rows and with
 the model, a random compiled filter's mask word for word with the host interpreter and -- where the op's `search` flag
 is set -- the lists of 8 queries in both modes bit for bit with the fresh index (unmasked and under the filter's mask)
-and the first query with the numpy oracle.  tests/test_lifecycle_model_host.py asserts what the committed sequences
-cover.  A failure names the seed, the step and the ops so far; lifecycle_model.sequence(seed, step + 1, profile)
+and the first query with the numpy oracle.  The binary copy is checked after every op too:
+binary_enabled() against the model, the refusals without the copy, the sign bits of the sampled rows and the Hamming scan
+of the 8 queries and of the first alone (unmasked and under the filter's mask) word for word against the fresh index and
+tests/binary_helpers.py; the profiles `binary`, `binary_padded` and `binary_chunks` enable it at a random step and lose it
+at every load.  Behind the `search` flag df, N and the IDF weights of probe terms (hx_sparse_idf_host) are compared bit for
+bit with the fresh index and with counts over the model's rows weighed by tests/sparse_idf_helpers.py, in every profile.
+tests/test_lifecycle_model_host.py asserts what the committed sequences cover.  A failure names the seed, the step and the ops so far; lifecycle_model.sequence(seed, step + 1, profile)
 replays it."""
 import pytest
 

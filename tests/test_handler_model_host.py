@@ -7,9 +7,11 @@
     and no MMR, rerank or recommend, which have no Python path: the driver's capability set leaves those out.  A broken
     model or driver is found here;
   * the coverage table of the committed (seed, profile) list, computed from the generator alone and asserted;
-  * five mutants of the handler's cached state, each of which the driver must catch, naming seed and step;
+  * seven mutants of the handler's cached state, each of which the driver must catch, naming seed and step;
   * the brute-force restatement: after every op the model equals the state re-derived from the op log in plain Python."""
+import hashlib
 import os
+import re
 
 import numpy as np
 import pytest
@@ -37,6 +39,7 @@ class HFakeIndex(FakeIndex):
         self.inv = L.Model(type(self).profile, np.zeros(1, np.int64))
         self.cand = L.PROFILES[type(self).profile]["cand"]
         self.tok = {}                                         # token column -> one cell per row: (head, x8, scales)
+        self.bits = self.terms = None                         # (FakeIndex: the 1-bit copy, the term table)
 
     def _bools(self, mask):
         mask = np.asarray(mask)
@@ -142,7 +145,7 @@ def test_sequences_are_prefixes_of_longer_ones(synth_tables):
 def coverage(cases, tables):
     """what the sequences of `cases` cover, from the generator alone"""
     t = dict(kinds={}, store={}, upsert={}, refused={}, sel={}, target={}, index={}, token={}, refills=0, rollbacks=0,
-             poisoned_reads=0, cures=0, indexed_removals=0, seam_deletes=0, wide_seam_deletes=0, old_poison_scrolls=0, empty_steps=0, regrown=0, full_saves=0, filled_token_index=0, appending_upserts=0)
+             binary_loads_searched=0, binary_rollbacks=0, idf_deletes_searched=0, poisoned_reads=0, cures=0, indexed_removals=0, seam_deletes=0, wide_seam_deletes=0, old_poison_scrolls=0, empty_steps=0, regrown=0, full_saves=0, filled_token_index=0, appending_upserts=0)
 
     def count(table, what):
         t[table][what] = t[table].get(what, 0) + 1
@@ -190,6 +193,13 @@ def coverage(cases, tables):
                 t["filled_token_index"] += op["form"] == "create_filled"
             elif k == "save_load" and st["tdim"] and len(st["live"]) >= 2:
                 t["full_saves"] += 1
+            # the two later profiles: what their flag or statistics must survive, read at once or one op on
+            soon = op["search"] or step == len(ops) - 1 or ops[step + 1]["search"]
+            if p["collection"].get("binary_quantization"):
+                t["binary_loads_searched"] += k == "save_load" and soon
+                t["binary_rollbacks"] += k == "upsert_refused" and op["form"] == "nan_rollback"
+            if p["collection"].get("sparse_modifier") and k == "delete":
+                t["idf_deletes_searched"] += soon and 0 < len(m.gone(op)) < st["n"]
             m.apply(op)
             t["poisoned_reads"] += any(key in H.POISON for key in m.dead)     # (check reads every key after the op)
             # an ordered scroll by page_number (check runs four after every op) on a key poisoned two ops ago or more
@@ -224,6 +234,25 @@ def test_coverage_table(synth_tables):
     assert t["full_saves"] >= 2, "no save_load with a token index and two live payload indexes"
     assert t["filled_token_index"] >= 1
     assert t["appending_upserts"] >= 2
+    assert t["binary_loads_searched"] >= 2, "no searched step behind a save_load of the binary collection"
+    assert t["binary_rollbacks"] >= 2, "no rolled-back upsert under the binary copy"
+    assert t["idf_deletes_searched"] >= 2, "no searched step behind a delete of the IDF collection"
+
+
+# the op logs of the ten cases committed before the binary and idf profiles, taken at the commit before them
+LEGACY = ("small", "padded", "persist", "bare", "chunked")
+LEGACY_DIGEST = "3ceb4e77cea16ae79a506006933e144844ae68640aa322529be0812d270c19cc"
+
+
+def test_the_earlier_cases_keep_their_op_logs(synth_tables):
+    h = hashlib.sha256()
+    cases = [c for c in H.CASES if c[1] in LEGACY]
+    assert list(H.PROFILES)[:len(LEGACY)] == list(LEGACY) and len(cases) == 10
+    for seed, profile in cases:
+        p = H.PROFILES[profile]
+        ops = H.sequence(seed, p["n_ops"], profile, H.pool_of(p["dim"], synth_tables))
+        h.update((f"{seed} {profile}: " + " ".join(H.brief(op) for op in ops) + "\n").encode())
+    assert h.hexdigest() == LEGACY_DIGEST
 
 
 # ---- mutants: each stands for one piece of cached state --------------------------------------------------------------------
@@ -236,6 +265,11 @@ def caught(make, synth_tables, tmp_path, cases=H.CASES):
             assert str(e).startswith(f"seed {seed} profile {profile} step ") and "ops so far: " in str(e), str(e)[:300]
             return str(e)
     raise AssertionError("the driver passed the mutant in every case")
+
+
+def last_op(msg):
+    """the last entry of a failure's op log (an entry may hold blanks: "delete(ids last)*")"""
+    return re.findall(r"\w+\([^)]*\)\*?", msg.split("ops so far:")[1])[-1]
 
 
 def test_mutant_delete_keeps_the_cached_masks(synth_tables, tmp_path):
@@ -300,6 +334,54 @@ def test_mutant_retain_leaves_a_payload_column_uncompacted(synth_tables, tmp_pat
     class Mutant(FakeHandler):
         index_type = Lazy
     caught(maker(Mutant), synth_tables, tmp_path)
+
+
+def test_mutant_load_forgets_the_binary_copy(synth_tables, tmp_path, monkeypatch):
+    """_Collection.load without its binary_enable(): while a load runs, the index ignores that call"""
+    real = HD._Collection.load.__func__
+
+    class Deaf(HFakeIndex):
+        loading = False
+
+        def binary_enable(self):
+            if not Deaf.loading:
+                super().binary_enable()
+
+    def load(cls, base, device, index_loader=None):
+        Deaf.loading = True
+        try:
+            return real(cls, base, device, index_loader)
+        finally:
+            Deaf.loading = False
+
+    class Mutant(FakeHandler):
+        index_type = Deaf
+    monkeypatch.setattr(HD._Collection, "load", classmethod(load))
+    msg = caught(maker(Mutant), synth_tables, tmp_path, [c for c in H.CASES if c[1] == "binary"])
+    assert "the index keeps a binary copy" in msg and last_op(msg).startswith("save_load(")
+
+
+def test_mutant_term_statistics_keep_the_count_from_before_a_delete(synth_tables, tmp_path):
+    """a fake whose sparse_idf_host answers with the N of the rows before the last retain"""
+    class Stale(HFakeIndex):
+        old_n = None
+
+        def retain(self, keep):
+            self.finalize()
+            self.old_n = self._term_table()[1]
+            return super().retain(keep)
+
+        def sparse_idf_host(self, idx, val, want_stats=False):
+            out = super().sparse_idf_host(idx, val, want_stats=True)
+            if self.old_n is not None:
+                out = (out[0], out[1], self.old_n)
+            return out if want_stats else out[0]
+
+    class Mutant(FakeHandler):
+        index_type = Stale
+    cases = [c for c in H.CASES if c[1] == "idf"]
+    msg = caught(maker(Mutant), synth_tables, tmp_path, cases)
+    assert "term_stats n_docs" in msg and last_op(msg).startswith("delete(")
 
 
 # ---- the brute-force restatement -------------------------------------------------------------------------------------------
