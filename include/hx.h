@@ -493,6 +493,42 @@ int hx_search_bin(hx_index* h, const float* q_dev, int32_t B, int32_t limit, uin
 int hx_search_bin_masked(hx_index* h, const float* q_dev, int32_t B, int32_t limit, const uint32_t* mask_dev,
                          int64_t mask_rows, uint64_t* keys_dev, int32_t* counts_dev, void* stream);
 
+/* ---- binary quantization, asymmetric query -----------------
+ * Qdrant's BinaryQuantization(query_encoding = scalar4bits | scalar8bits): the stored rows stay at one sign bit per
+ * dimension -- the copy of hx_binary_enable, unchanged -- and the QUERY keeps query_bits = 4 or 8 bits per dimension.
+ * The stage nominates far better candidates than hx_search_bin at the same list length; like it, it belongs under a
+ * dense re-scoring node.  Additive to the ABI: HX_ABI_VERSION stays 3.
+ *
+ * hx_search_bin_asym / hx_search_bin_asym_masked, B queries q_dev [B x dim] fp32 on the device:
+ *   query codes  per query b, QMAX = 127 (8 bits) or 7 (4 bits), over the dim RAW fp32 elements (no normalisation):
+ *                m = max_j |q[b][j]|; d_j = q[b][j] / m, ONE correctly rounded fp32 division; t_j = d_j * QMAX, ONE fp32
+ *                multiplication; c_j = (int) rintf(t_j), round half to even.  |d_j| <= 1, so |c_j| <= QMAX: no clamp.
+ *                m == 0 gives every c_j = 0; the columns from dim up to the padded width have code 0.  Every one of the
+ *                dim elements must be finite: a batch holding a NaN or +-Inf fails ("query values must be finite").  A
+ *                query whose largest magnitude is subnormal (below 2^-126) is answered without error, but its codes are
+ *                outside the bit-exact contract;
+ *   score        of row r for query b = sum_{j < dim} c_j * (bit_j(r) ? +1 : -1) over the stored sign bits: an integer of
+ *                magnitude at most QMAX * dim <= 127 * 4096 < 2^24, carried in the key as that fp32 value (exact).  It is
+ *                computed as 2 S - T: T = sum_j c_j, one integer per query, and S = the sum of c_j over the row's set
+ *                bits, from the P = query_bits bit planes of the two's-complement codes:
+ *                S = -2^(P-1) popcount(plane_{P-1} & row) + sum_{k < P-1} 2^k popcount(plane_k & row);
+ *   order, ids, mask, limits, refusals, synchronisation
+ *                exactly hx_search_bin's: the engine's key and total order (score descending, id ascending), counts and
+ *                zero slots behind them, global ids, 1 <= limit <= 2048, the mask read inside the scan, the refusals before
+ *                any device work (the copy is not enabled, B < 1, a limit out of range, a wrong mask_rows) and, first of
+ *                all, a query_bits that is neither 4 nor 8 ("query_bits" in the message); ONE host round trip per call.
+ * hx_bin_asym_debug_query (the tests' hook, as hx_binary_debug_row) runs the query kernel alone on the null stream and
+ * copies to the host the planes, [B][query_bits][dim_pad / 32] words -- plane k of query b is one run of dim_pad / 32
+ * words, bit j & 31 of word j >> 5 is bit k of c_j's two's complement -- and the totals T, [B]; cap_words is the room at
+ * planes_out.  It needs no binary copy. */
+int hx_search_bin_asym(hx_index* h, const float* q_dev, int32_t B, int32_t limit, int32_t query_bits,
+                       uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+int hx_search_bin_asym_masked(hx_index* h, const float* q_dev, int32_t B, int32_t limit, int32_t query_bits,
+                              const uint32_t* mask_dev, int64_t mask_rows,
+                              uint64_t* keys_dev, int32_t* counts_dev, void* stream);
+int hx_bin_asym_debug_query(hx_index* h, const float* q_dev, int32_t B, int32_t query_bits,
+                            uint32_t* planes_out, int32_t* totals_out, int64_t cap_words);
+
 /* ---- payload index -------------------------------------
  * Qdrant's create_payload_index, the engine's way: indexed payload fields live as columns beside the vectors, a filter
  * arrives as a small postfix program, and one kernel evaluates it over every row and writes the packed row mask of

@@ -127,6 +127,9 @@ _SIGS = {
     "hx_binary_debug_row": [_P, C.c_int64, _P, C.c_int32],
     "hx_search_bin": [_P, _P, C.c_int32, C.c_int32, _P, _P, _P],
     "hx_search_bin_masked": [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_search_bin_asym": [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P],
+    "hx_search_bin_asym_masked": [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P],
+    "hx_bin_asym_debug_query": [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64],
     "hx_list_keep": [_P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, _P, _P],
     "hx_group": [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P],
     "hx_hybrid_query_groups_host": [_P, _P, _P, _P, _P, C.c_int32, C.POINTER(HxParams), _P, C.c_int64, C.c_int32,

@@ -23,6 +23,7 @@ SOURCES = [("scan.hip", "scan.o", ()), ("scan8.hip", "scan8.o", ()), ("select.hi
            ("formula.hip", "formula.o", ()), ("fuse.hip", "fuse.o", ()),
            ("facet.hip", "facet.o", ()), ("reco.hip", "reco.o", ()), ("discover.hip", "discover.o", ()),
            ("matrix.hip", "matrix.o", ()), ("binscan.hip", "binscan.o", ()),
+           ("binasym.hip", "binasym.o", ()),
            ("scroll.hip", "scroll.o", ()),
            ("spbuild.hip", "spbuild.o", ()), ("engine.hip", "engine.o", ()), ("lifecycle.hip", "lifecycle.o", ()),
            ("paystore.hip", "paystore.o", ()), ("poolstage.hip", "poolstage.o", ()), ("byexample.hip", "byexample.o", ()),

@@ -8,10 +8,7 @@
 
 namespace hx {
 
-constexpr int BIN_NT = 256;              // four waves; a tile is 256 rows, one per lane
-constexpr int BIN_PASS_SLOTS = 13;       // 16-byte slots of a row staged at a time: 256 x 13 x 16 B = 52 KB of LDS
-constexpr int BIN_MAX_SLOTS = 32;        // of a whole row (dim 4096): the staged query words, 8 x 32 x 16 B = 4 KB
-constexpr int BIN_QG = 8;                // queries scored per walk over a staged tile
+constexpr int BIN_QG = 8;                // queries scored per walk over a staged tile: 8 x BIN_MAX_SLOTS x 16 B = 4 KB of LDS
 
 // One wave per query, four per workgroup: the sign bits of the RAW query (no normalisation: the sign does not need it),
 // a ballot per 64 columns; the columns from dim up to 32 * words give 0.
@@ -146,10 +143,6 @@ __global__ __launch_bounds__(BIN_NT) void k_bin_scan(BinScanArgs a, int nslots, 
   }
 }
 
-static uint32_t bin_magic(int slots) {   // ceil(2^32 / slots), slots >= 2
-  return slots < 2 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)slots - 1) / (uint64_t)slots);
-}
-
 void launch_bin_scan(const BinScanArgs& a, hipStream_t st) {
   if (a.row_end <= a.row_begin || a.B <= 0) return;
   HX_CHECK(a.words % 4 == 0 && a.words >= 4 && a.words <= 128, "bin scan: row width");
@@ -179,7 +172,7 @@ void launch_bin_scan(const BinScanArgs& a, hipStream_t st) {
 // the stage (hx_search_bin; hx.h states the contract)
 // ---------------------------------------------------------------------------------
 // every refusal that needs no device work
-static void bin_check(hx_index* h, const void* q_dev, int B, int limit, const void* mask_dev, int64_t mask_rows,
+void bin_check(hx_index* h, const void* q_dev, int B, int limit, const void* mask_dev, int64_t mask_rows,
                       const void* keys_dev, const void* counts_dev) {
   HX_CHECK(h, "NULL argument");
   HX_CHECK(h->bin_on, "search_bin: the index keeps no binary copy of its rows (hx_binary_enable)");
@@ -196,18 +189,19 @@ static void bin_check(hx_index* h, const void* q_dev, int B, int limit, const vo
 // is at most half of the C - L keys the buffer takes.  A query whose buffer overflowed all the same (a corpus ordered so that
 // every chunk beats the threshold) is scanned again in fixed chunks of C - L rows, every row appended, a compaction after
 // each: the same list by construction.  ONE host round trip: the overflow flags and the count of non-finite queries, read
-// together behind the scan.  Keys leave with internal ids.
-static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint32_t* mask_dev, uint64_t* out_keys,
-                       int* out_cnt, hipStream_t st) {
+// together behind the scan.  Keys leave with internal ids.  The loop is the stage's whatever scores the rows: `s` (BinStage,
+// index.hpp) gives the kernel that stages the queries and the scan launch -- hx_search_bin's below, the asymmetric stage's
+// in binasym.hip.
+void bin_stage_search(hx_index* h, const BinStage& s, int B, int L, const uint32_t* mask_dev, uint64_t* out_keys,
+                      int* out_cnt, hipStream_t st) {
   if (h->n == 0) {
     zero_outputs(out_keys, out_cnt, B, L, st);
     return;
   }
-  const int words = h->bin_words();
   const int C = h->bin_cap ? std::max(h->bin_cap, 2 * L) : std::clamp(next_pow2(8 * L), 2048, CAND_CAP);
   const int64_t chunk0 = h->bin_chunk0 ? std::min(h->bin_chunk0, C) : C;
   const int64_t grow = std::clamp((C + L) / (2 * L), 2, 16);
-  uint32_t* qbits = (uint32_t*)h->ws.get(WS_BIN_Q, (size_t)B * words * 4);
+  uint32_t* qbits = (uint32_t*)h->ws.get(s.q_slot, (size_t)B * s.qwords * 4);
   uint64_t* cand = (uint64_t*)h->ws.get(WS_BIN_CAND, (size_t)B * C * 8);
   int* cnt = (int*)h->ws.get(WS_BIN_CNT, (size_t)B * 4);
   int* flags = (int*)h->ws.get(WS_BIN_FLAGS, (size_t)(B + 1) * 4);     // [0, B) overflow, [B] non-finite queries
@@ -217,10 +211,10 @@ static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint
   HX_HIP(hipMemsetAsync(flags, 0, (size_t)(B + 1) * 4, st));
   HX_HIP(hipMemsetAsync(tau, 0, (size_t)B * 8, st));
   HX_HIP(hipMemsetAsync(tau0, 0, (size_t)B * 8, st));
-  launch_bin_queries(q_dev, h->dim, B, words, qbits, flags + B, st);
+  s.queries(qbits, flags + B, st);
   BinScanArgs a{};
   a.bits = h->bits;
-  a.words = words;
+  a.words = h->bin_words();
   a.dim = h->dim;
   a.qbits = qbits;
   a.B = B;
@@ -235,7 +229,7 @@ static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint
   for (int64_t r0 = 0, r1 = std::min<int64_t>(h->n, chunk0); r0 < h->n;) {
     a.row_begin = r0;
     a.row_end = r1;
-    launch_bin_scan(a, st);
+    s.scan(a, 0, st);
     launch_compact(cand, C, cnt, B, L, 0, cand, C, cnt, nullptr, C, st);
     r0 = r1;
     r1 = std::min<int64_t>(h->n, grow * r1);
@@ -244,11 +238,11 @@ static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint
   std::vector<int> flagged((size_t)B + 1);
   HX_HIP(hipMemcpyAsync(flagged.data(), flags, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, st));
   HX_HIP(hipStreamSynchronize(st));
-  HX_CHECK(flagged[(size_t)B] == 0, "search_bin: query values must be finite");
+  HX_CHECK(flagged[(size_t)B] == 0, std::string(s.who) + ": query values must be finite");
   for (int b = 0; b < B; ++b) {
     if (!flagged[(size_t)b]) continue;
     BinScanArgs r = a;
-    r.qbits = qbits + (int64_t)b * words;
+    r.qbits = qbits + (int64_t)b * s.qwords;
     r.B = 1;
     r.tau_key = tau0;
     r.cand = cand + (int64_t)b * C;
@@ -258,12 +252,25 @@ static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint
     for (int64_t r0 = 0; r0 < h->n; r0 += C - L) {
       r.row_begin = r0;
       r.row_end = std::min<int64_t>(h->n, r0 + (C - L));
-      launch_bin_scan(r, st);
+      s.scan(r, b, st);
       launch_compact(r.cand, C, r.cnt, 1, L, 0, r.cand, C, r.cnt, nullptr, C, st);
     }
   }
   HX_HIP(hipMemcpy2DAsync(out_keys, (size_t)L * 8, cand, (size_t)C * 8, (size_t)L * 8, (size_t)B, hipMemcpyDeviceToDevice, st));
   HX_HIP(hipMemcpyAsync(out_cnt, cnt, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+}
+
+// hx_search_bin: the sign bits of the queries (k_bin_queries) and k_bin_scan in the loop above
+static void search_bin(hx_index* h, const float* q_dev, int B, int L, const uint32_t* mask_dev, uint64_t* out_keys,
+                       int* out_cnt, hipStream_t st) {
+  const int words = h->bin_words();
+  BinStage s;
+  s.who = "search_bin";
+  s.qwords = words;
+  s.q_slot = WS_BIN_Q;
+  s.queries = [=](uint32_t* qbits, int* bad, hipStream_t t) { launch_bin_queries(q_dev, h->dim, B, words, qbits, bad, t); };
+  s.scan = [](const BinScanArgs& a, int, hipStream_t t) { launch_bin_scan(a, t); };
+  bin_stage_search(h, s, B, L, mask_dev, out_keys, out_cnt, st);
 }
 
 }  // namespace hx

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <vector>
 
@@ -57,7 +58,8 @@ enum WsSlot {
   WS_MATRIX_ROWS, WS_MATRIX_PLANE, WS_MATRIX_OUT, WS_MATRIX_OCNT, WS_MATRIX_SC, WS_MATRIX_ID,
   WS_DISC_TAU, WS_DISC_TAU0,
   WS_IDF_IDX, WS_IDF_VAL, WS_IDF_DF,
-  WS_BIN_Q, WS_BIN_CAND, WS_BIN_CNT, WS_BIN_FLAGS, WS_BIN_TAU, WS_BIN_TAU0
+  WS_BIN_Q, WS_BIN_CAND, WS_BIN_CNT, WS_BIN_FLAGS, WS_BIN_TAU, WS_BIN_TAU0,
+  WS_ASYM_PLANES, WS_ASYM_TOT
 };
 
 template <typename T>
@@ -327,6 +329,23 @@ void rows_check_fetch(hx_index* h, int* w, hipStream_t st);
 void rows_check_end(hx_index* h, int* w, hipStream_t st);
 void check_sparse_batch_dev(hx_index* h, const int64_t* rows_ip, const int32_t* idx_dev, const float* val_dev, int64_t n,
                             int64_t first, int64_t last, const int64_t* indptr, const int32_t* idx, float* lo, float* hi);
+
+// ---- binscan.hip: what the asymmetric stage (binasym.hip) shares with hx_search_bin --------------------------------------
+// every refusal of a stage over the 1-bit copy that needs no device work
+void bin_check(hx_index* h, const void* q_dev, int B, int limit, const void* mask_dev, int64_t mask_rows,
+               const void* keys_dev, const void* counts_dev);
+// What a stage gives the chunked scan loop: `queries` stages the batch as qwords words per query in the workspace slot
+// q_slot and counts the non-finite queries in *bad; `scan` launches the scan of a.B queries over [a.row_begin, a.row_end),
+// a.qbits being the staged form of the batch's query b0 (0 in the main loop, the flagged query's in the overflow redo).
+struct BinStage {
+  const char* who = "";              // names the stage in its messages
+  int qwords = 0;
+  int q_slot = 0;
+  std::function<void(uint32_t* qdata, int* bad, hipStream_t st)> queries;
+  std::function<void(const BinScanArgs& a, int b0, hipStream_t st)> scan;
+};
+void bin_stage_search(hx_index* h, const BinStage& s, int B, int L, const uint32_t* mask_dev, uint64_t* out_keys,
+                      int* out_cnt, hipStream_t st);
 
 // ---- lifecycle.hip: what a payload column's replace shares with hx_replace_rows -----------------------------------------
 // the rows of a replace call -- in [0, limit), unique -- as the uint32 list the kernels read

@@ -860,5 +860,22 @@ struct BinScanArgs {
 void launch_bin_scan(const BinScanArgs& a, hipStream_t st);
 // tau_key[b] = cand[b * cap + limit - 1] when cnt[b] >= limit (lists sorted by launch_compact), else 0
 void launch_bin_tau(const uint64_t* cand, int cap, const int* cnt, int B, int limit, uint64_t* tau_key, hipStream_t st);
+// the schedule both scans over the 1-bit copy share (k_bin_scan; k_asym_scan in binasym.hip)
+constexpr int BIN_NT = 256;              // four waves; a tile is 256 rows, one per lane
+constexpr int BIN_PASS_SLOTS = 13;       // 16-byte slots of a row staged at a time: 256 x 13 x 16 B = 52 KB of LDS
+constexpr int BIN_MAX_SLOTS = 32;        // of a whole row (dim 4096)
+inline uint32_t bin_magic(int slots) {   // ceil(2^32 / slots), slots >= 2
+  return slots < 2 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)slots - 1) / (uint64_t)slots);
+}
+
+// ---- binasym.hip: the asymmetric stage over the 1-bit copy (hx_search_bin_asym) -----------------
+// The queries' codes c = rint(q / max|q| * QMAX), QMAX = 2^(P-1) - 1, as P bit planes of their two's complement:
+// planes[(b * P + k) * words + (j >> 5)] bit (j & 31) = bit k of c[b][j] for j < dim, 0 up to 32 * words;
+// totals[b] = sum_j c[b][j]; *bad += the queries with a NaN or +-Inf among their dim elements.  P = 4 or 8.
+void launch_asym_queries(const float* q, int dim, int B, int words, int P, uint32_t* planes, int* totals, int* bad,
+                         hipStream_t st);
+// launch_bin_scan's scan with score = 2 S - totals[b], S = the sum of c[b][j] over the row's set bits, taken plane by
+// plane: a.qbits = the planes of the launch's first query, totals = its total.
+void launch_asym_scan(const BinScanArgs& a, const int* totals, int P, hipStream_t st);
 
 }  // namespace hx

@@ -332,6 +332,31 @@ class HxIndex:
             check(_lib.lib().hx_search_bin(self._h, _ptr(q), q.shape[0], limit, _ptr(keys), _ptr(cnt), _stream()))
         return keys, cnt
 
+    def search_bin_asym(self, q: torch.Tensor, limit: int, query_bits: int, mask=None):
+        """The asymmetric stage over the 1-bit copy (hx_search_bin_asym): the query keeps query_bits
+        = 4 or 8 bits per dimension; keys [B, limit] with the integer scores sum_j code_j * (+-1 of the row), counts."""
+        q = _need_cuda(q, torch.float32, "q")
+        keys, cnt = self._out(q.shape[0], limit)
+        if mask is not None:
+            words, rows = self._dev_mask(mask)
+            check(_lib.lib().hx_search_bin_asym_masked(self._h, _ptr(q), q.shape[0], limit, int(query_bits), _ptr(words),
+                                                       rows, _ptr(keys), _ptr(cnt), _stream()))
+        else:
+            check(_lib.lib().hx_search_bin_asym(self._h, _ptr(q), q.shape[0], limit, int(query_bits), _ptr(keys),
+                                                _ptr(cnt), _stream()))
+        return keys, cnt
+
+    def binary_query_planes(self, q: torch.Tensor, query_bits: int):
+        """What the asymmetric stage makes of a batch of queries (hx_bin_asym_debug_query): (planes uint32 [B, query_bits,
+        dim rounded up to 64, / 32], totals int32 [B]) on the host -- bit j & 31 of word j >> 5 of plane k is bit k of
+        the two's complement of column j's code."""
+        q = _need_cuda(q, torch.float32, "q")
+        B, P = q.shape[0], int(query_bits)
+        planes = np.zeros((B, max(P, 0), (self.dim + 63) // 64 * 2), dtype=np.uint32)
+        totals = np.zeros(B, dtype=np.int32)
+        check(_lib.lib().hx_bin_asym_debug_query(self._h, _ptr(q), B, P, _ptr(planes), _ptr(totals), planes.size))
+        return planes, totals
+
     def search_sparse(self, q_indptr: torch.Tensor, q_idx: torch.Tensor, q_val: torch.Tensor, limit: int,
                       flag: Optional[torch.Tensor] = None, mask=None):
         HxIndex._no_masked_flag(mask, flag)

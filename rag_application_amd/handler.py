@@ -1622,7 +1622,7 @@ class QdrantHandler:
     # ------------------------------------------------------------------------ binary quantization
     async def search_binary_batch(self, user_id: str, dense_vectors, limit: int = 10, oversampling: float = 4.0,
                                   rescore: bool = True, filters: Optional[Dict] = None,
-                                  filter_stages: str = "root") -> List[List[ScoredPoint]]:
+                                  filter_stages: str = "root", query_encoding: str = "binary") -> List[List[ScoredPoint]]:
         """Qdrant's search under quantization_config=BinaryQuantization with QuantizationSearchParams(oversampling,
         rescore), for B query vectors (additive): the sign bits nominate min(ceil(limit *
         oversampling), 2048) candidates per query with XOR and popcount, the exact vectors re-score them and the best
@@ -1630,24 +1630,31 @@ class QdrantHandler:
         the binary stage's own list at `limit`.  ScoredPoint.score is the cosine after a re-score and the integer score
         dim - 2 * (differing sign bits) without one.  filters / filter_stages as query_points takes them ("root": the
         re-scoring root's candidates are filtered before its cut, so rescore=False takes no filter there; "node" / "all":
-        on the device).  Raises ValueError for a collection created without binary_quantization, a limit outside
-        [1, 2048], an oversampling that is no finite number >= 1, and on a sharded collection; any other failure is
-        logged and gives [], as in every search."""
+        on the device).  query_encoding (additive) is Qdrant's BinaryQuantization.query_encoding:
+        "binary" = the above; "scalar4bits" / "scalar8bits" = the rows stay at one bit and the query keeps 4 or 8 bits per
+        dimension, which nominates far better candidates at the same oversampling (the score without a re-score is then
+        the integer sum of the query's codes signed by the row's bits).  Raises ValueError for a collection created
+        without binary_quantization, a limit outside [1, 2048], an oversampling that is no finite number >= 1, an
+        unknown query_encoding, and on a sharded collection; any other failure is logged and gives [], as in every
+        search."""
         if filter_stages not in QUERY_FILTER_STAGES:
             raise ValueError(f"filter_stages must be one of {QUERY_FILTER_STAGES}, got {filter_stages!r}")
+        if not isinstance(query_encoding, str) or query_encoding not in _query_tree.QUERY_ENCODINGS:
+            raise ValueError(f"query_encoding must be one of {tuple(_query_tree.QUERY_ENCODINGS)}, got {query_encoding!r}")
         try:
             vectors = [v for v in dense_vectors]
         except TypeError:
             raise ValueError("dense_vectors: a list of query vectors") from None
-        reqs = [dict(_query_tree.binary_request(v, limit, oversampling, rescore, filters),
+        reqs = [dict(_query_tree.binary_request(v, limit, oversampling, rescore, filters, query_encoding),
                      **({} if filter_stages == "root" else {"filter_stages": filter_stages})) for v in vectors]
         return await self.query_points_batch(user_id, reqs)
 
     async def search_binary(self, user_id: str, dense_vector, limit: int = 10, oversampling: float = 4.0,
                             rescore: bool = True, filters: Optional[Dict] = None,
-                            filter_stages: str = "root") -> List[ScoredPoint]:
+                            filter_stages: str = "root", query_encoding: str = "binary") -> List[ScoredPoint]:
         """One query of search_binary_batch."""
-        res = await self.search_binary_batch(user_id, [dense_vector], limit, oversampling, rescore, filters, filter_stages)
+        res = await self.search_binary_batch(user_id, [dense_vector], limit, oversampling, rescore, filters, filter_stages,
+                                             query_encoding)
         return res[0] if res else []
 
     # ------------------------------------------------------------------------ term statistics

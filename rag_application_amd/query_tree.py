@@ -9,6 +9,8 @@ A request is a dict, or an object with attributes of the same names (qdrant_clie
                 only).  "binary"  takes a dense vector and ranks by the sign bits of a collection
                 created with binary_quantization=True: the leaf under a dense re-scoring node is Qdrant's
                 BinaryQuantization with oversampling and rescore (handler.search_binary builds exactly that).
+                "binary_scalar4bits" / "binary_scalar8bits"  are the same leaf with Qdrant's
+                query_encoding: the rows stay at one bit, the query keeps 4 or 8 bits per dimension.
   fusion node   query = {"fusion": "rrf" | "dbsf"} with optional "weights", "rrf_k", "rank_base"; 1 to 8 prefetches.
 A missing limit is 10, at the root too.  Everything else raises ValueError with the reason: nothing is answered with
 something else.
@@ -30,7 +32,11 @@ PREFETCH_DEFAULT_LIMIT = 10
 MAX_DEPTH = 8
 MAX_LIMIT = 2048                 # the largest list a stage keeps (hx.h)
 RESCORE_MAX = 8192               # the widest candidate list hx_rescore takes
-USINGS = ("dense", "quantized", "sparse", "binary")
+USINGS = ("dense", "quantized", "sparse", "binary", "binary_scalar4bits", "binary_scalar8bits")
+# the leaves over the 1-bit copy: using -> the query's bits per dimension (None: the sign alone, hx_search_bin)
+BINARY_USINGS = {"binary": None, "binary_scalar4bits": 4, "binary_scalar8bits": 8}
+# Qdrant's BinaryQuantization.query_encoding -> the leaf
+QUERY_ENCODINGS = {"binary": "binary", "scalar4bits": "binary_scalar4bits", "scalar8bits": "binary_scalar8bits"}
 NODE_KEYS = ("prefetch", "query", "using", "limit", "filter", "score_threshold", "params", "lookup_from")
 # what Qdrant's query interface also offers and a tree here does not
 FOREIGN_QUERIES = ("order_by", "recommend", "discover", "context", "formula", "mmr", "sample")
@@ -196,7 +202,7 @@ def parse(node, dim: int, msizes: Sequence[int], _depth: int = 1, _root: bool = 
         if using == "sparse":
             raise ValueError(f"{where}: using='sparse' needs a sparse query ({{'indices', 'values'}})")
         vec = _dense(q, using, prefix, dim, where)
-    if pre and using in ("quantized", "sparse", "binary"):
+    if pre and (using in ("quantized", "sparse") or using in BINARY_USINGS):
         raise ValueError(f"{where}: using={using!r} cannot re-score a prefetch (only 'dense' and 'matryoshka_<d>' can)")
     vecs.append(vec)
     children = tuple(parse(c, dim, msizes, _depth + 1, False, vecs, _notes)[0] for c in pre)
@@ -287,17 +293,22 @@ def push_to_leaves(shape):
 
 
 def uses_binary(shape) -> bool:
-    """whether some leaf of the shape is a using="binary" one (the collection must keep the 1-bit copy)"""
-    if shape[0] == "nearest" and shape[1] == "binary":
+    """whether some leaf of the shape ranks by the 1-bit copy, which the collection must then keep: using="binary" or
+    one of its query encodings"""
+    if shape[0] == "nearest" and shape[1] in BINARY_USINGS:
         return True
     return any(uses_binary(c) for c in shape[-1])
 
 
-def binary_request(vector, limit=10, oversampling=4.0, rescore=True, filters=None):
+def binary_request(vector, limit=10, oversampling=4.0, rescore=True, filters=None, query_encoding="binary"):
     """The request of handler.search_binary -- Qdrant's QuantizationSearchParams(oversampling, rescore) -- for one query
     vector: a using="binary" leaf of min(ceil(limit * oversampling), 2048) hits under a dense re-scoring node of `limit`,
-    or with rescore=False the leaf alone at `limit`.  `filters` becomes the root's.  ValueError for a limit outside
-    [1, 2048] and for an oversampling that is no finite number >= 1."""
+    or with rescore=False the leaf alone at `limit`.  `filters` becomes the root's.  query_encoding -- Qdrant's
+    BinaryQuantization.query_encoding: "binary" (the default: the request is what it was), "scalar4bits" or "scalar8bits"
+    -- names the leaf: using="binary_scalar4bits" / "binary_scalar8bits".  ValueError for a limit outside [1, 2048], for an
+    oversampling that is no finite number >= 1 and for an unknown query_encoding."""
+    if not isinstance(query_encoding, str) or query_encoding not in QUERY_ENCODINGS:
+        raise ValueError(f"search_binary: query_encoding must be one of {tuple(QUERY_ENCODINGS)}, got {query_encoding!r}")
     if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= int(limit) <= MAX_LIMIT:
         raise ValueError(f"search_binary: limit must be an integer in [1, {MAX_LIMIT}], got {limit!r}")
     if isinstance(oversampling, bool) or not isinstance(oversampling, (int, float, np.integer, np.floating)):
@@ -305,7 +316,7 @@ def binary_request(vector, limit=10, oversampling=4.0, rescore=True, filters=Non
     if not np.isfinite(oversampling) or oversampling < 1:
         raise ValueError(f"search_binary: oversampling must be finite and at least 1, got {oversampling!r}")
     limit = int(limit)
-    leaf = {"using": "binary", "query": vector}
+    leaf = {"using": QUERY_ENCODINGS[query_encoding], "query": vector}
     if rescore:
         wide = min(int(np.ceil(limit * float(oversampling))), MAX_LIMIT)
         req = {"using": "dense", "query": vector, "limit": limit, "prefetch": [dict(leaf, limit=max(wide, limit))]}
@@ -350,7 +361,8 @@ def batch_thresholds(threshold_lists: Sequence[Sequence[Any]]) -> List[np.ndarra
 def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None, thresholds: Sequence[Any] = ()):
     """Run one shape for the B queries whose vectors are `vectors` (batch_vectors).  `stages` offers the stage entries:
     dense(Q, limit, prefix), i8(Q, limit), sparse(pairs, limit), bin(Q, limit) (only a shape with a using="binary" leaf
-    calls it), rescore(Q, [(keys, counts)], limit, prefix) and
+    calls it), bin_asym(Q, limit, query_bits) (only one with a "binary_scalar4bits" / "binary_scalar8bits" leaf),
+    rescore(Q, [(keys, counts)], limit, prefix) and
     fuse([(keys, counts)], method, weights, limit, rrf_k, rank_base), each returning (keys [B, limit], counts [B]) in
     whatever array type it keeps lists in -- they stay where the stages put them between nodes.  root_limit overrides
     the root's limit (a filtered root runs at the width of its input).
@@ -378,6 +390,8 @@ def run(shape, vectors: Sequence[Any], stages, root_limit: Optional[int] = None,
             return stages.i8(q, limit, **mask)
         if using == "binary":
             return stages.bin(q, limit, **mask)
+        if using in BINARY_USINGS:
+            return stages.bin_asym(q, limit, BINARY_USINGS[using], **mask)
         return stages.dense(q, limit, prefix, **mask)
 
     def walk(s, limit=None, key=None, thr=None):
@@ -451,6 +465,9 @@ class DeviceStages:
 
     def bin(self, Q, limit, mask=None):
         return self.ix.search_bin(self._q(Q), limit, **self._kw(mask))
+
+    def bin_asym(self, Q, limit, query_bits, mask=None):
+        return self.ix.search_bin_asym(self._q(Q), limit, query_bits, **self._kw(mask))
 
     def keep(self, lists, mask, thresholds, limit):
         # several lists: side by side, every slot walked (a stage's slots past its count are 0, and hx_list_keep skips a 0)
